@@ -27,7 +27,13 @@ Extra objects on the JSON line:
   cpu_baseline -- oracle/cpu_ref.py (scipy.ndimage port of the same path) timed on the host
                   cores of this box on a bounded sample; rank 0 at N = 1 only (BASELINE.md section 4:
                   all host cores on independent positions, plus a single-core leg labelled
-                  extrapolated).
+                  extrapolated).  Only with ``--full``.
+
+A plain run (``--gpus N --steps K --warmup W``) does only what the headline needs: set up, W warm-ups,
+K timed steps, the JSON line.  ``--full`` adds what takes runs of its own (today: ``cpu_baseline``).
+``--dump-outputs DIR`` writes what the last timed step computed as ``DIR/<name>.npy`` (float32; a fixed,
+seeded sample of each large array, see ``dump_outputs``); the inputs are seeded, so two builds given the
+same arguments can be compared output for output.
 """
 
 from __future__ import annotations
@@ -127,7 +133,9 @@ def synthetic_raw(shape, seed, device):
     k = max(1, int(round(2e-5 * n)))
     idx = torch.randint(0, n, (k,), device=device, generator=g)
     amp = torch.empty(k, device=device).uniform_(200.0, 4000.0, generator=g) * 30.0
-    vol.view(-1)[idx] = amp
+    # a bead drawn twice keeps the brighter amplitude: a plain scatter would keep whichever write lands last, and the
+    # inputs must be the same from run to run (--dump-outputs compares builds output for output)
+    vol.view(-1).scatter_reduce_(0, idx, amp, reduce="amax")
     vol = correlate3d(vol, weight_factors=gaussian_factors())
     vol += 100.0
     return torch.poisson(vol, generator=g)
@@ -241,6 +249,38 @@ def library_stamp() -> dict:
 
     return {"path": str(_lib.LIB_PATH.relative_to(ROOT)) if _lib.LIB_PATH.is_relative_to(ROOT) else str(_lib.LIB_PATH),
             "source_sha16": _lib.library_source_sha16(), "checkout_sha16": _lib.kernel_source_sha16()}
+
+
+DUMP_SAMPLE = 1 << 21          # elements written per large output array (8 MB of float32)
+DUMP_SEED = 20240101
+DUMP_BUDGET_BYTES = 64 << 20   # everything --dump-outputs writes, indices included
+
+
+def dump_outputs(directory, arrays: dict) -> None:
+    """``--dump-outputs``: write each array as ``<directory>/<name>.npy`` in float32.  An array of more than
+    ``DUMP_SAMPLE`` elements is written as a fixed sample: ``DUMP_SAMPLE`` distinct flat positions drawn with
+    ``DUMP_SEED``, in increasing order, the same for every run with the same shape (``<name>_index.npy`` holds them,
+    as float64).  Called after the timed steps only."""
+    import numpy as np
+    import torch
+
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    files = {}
+    for name, t in arrays.items():
+        n = t.numel()
+        if n <= DUMP_SAMPLE:
+            files[name] = t.detach().to(torch.float32).cpu().numpy()
+            continue
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+        where = tuple(torch.as_tensor(c, device=t.device) for c in np.unravel_index(idx, tuple(t.shape)))
+        files[name] = t.detach()[where].to(torch.float32).cpu().numpy()
+        files[name + "_index"] = idx.astype(np.float64)
+    total = sum(a.nbytes for a in files.values())
+    if total > DUMP_BUDGET_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET_BYTES}-byte budget")
+    for name, a in files.items():
+        np.save(out / f"{name}.npy", np.ascontiguousarray(a))
 
 
 def device_state(device) -> dict:
@@ -444,6 +484,10 @@ def run_resident(args, rank, world, device, shared, backend, cpu):
     assert torch.isfinite(estimate).all(), "non-finite RL output"
     if rank != 0:
         return None
+    if args.dump_outputs:
+        # the last step's deconvolved volume, and the deskewed volume it started from
+        dump_outputs(args.dump_outputs, {"estimate": estimate,
+                                         "deskewed": deskewed if isinstance(deskewed, torch.Tensor) else deskewed.view})
 
     fused = bool(getattr(plan, "fused", False)) or bool(getattr(plan, "fused_ysep", False))
     ysep = plan.path.startswith("y-separable")
@@ -644,6 +688,8 @@ def run_plate(args, rank, world, device, shared, backend, cpu):
     rl_kernels_ms = sum(e[3].elapsed_time(e[4]) for e in events) / args.steps
     assert torch.isfinite(result["x"]).all(), "non-finite RL output"
     launch_s = rl_kernels_ms * 1e-3 / RL_ITERS
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"estimate": result["x"]})
     del result
 
     # ---- store to store: T x P units through cli.run_store (staged path) ----
@@ -781,6 +827,8 @@ def run_config1_cpu(args):
     for _ in range(args.steps):
         out = fast_deskew_zyx(raw_data=vol, **DESKEW)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"deskewed": out})
     t1 = time.perf_counter()
     want = o.deskew(raw, DESKEW["ls_angle_deg"], DESKEW["px_to_scan_ratio"], DESKEW["keep_overhang"], DESKEW["average_n_slices"])
     oracle_s = time.perf_counter() - t1
@@ -811,7 +859,12 @@ def main():
                          "same PSF with the plan free to split it (it separates along y: a (z, x) "
                          "stencil plus a y pass per correlation); measured = a dense 15x19x19 bead-patch PSF "
                          "(the RL iteration in the Fourier domain)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline (rank 0 at N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32; a fixed, "
+                         "seeded sample of each large array); bench_outputs/ in the repository is ignored by git")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--cpu-procs", type=int, default=None, help="cap the CPU baseline's worker count (default: all host cores)")
     ap.add_argument("--rl", default="fused", choices=["fused", "two-launch", "fused-ysep"],
                     help="one launch per RL iteration (default: rl_fused_sep / rl_fused_ysep kernels) or the ratio / "
@@ -836,9 +889,9 @@ def main():
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args.gpus))
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
-    # CPU baseline first (rank 0, N = 1 only), in spawned processes that never touch the GPU.
+    # --full: the CPU baseline first (rank 0, N = 1 only), in spawned processes that never touch the GPU.
     cpu = None
-    if world_env == 1 and args.gpus == 1 and not args.no_cpu_baseline:
+    if args.full and world_env == 1 and args.gpus == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(config_id=WORKLOADS[args.workload][0], max_procs=args.cpu_procs)
 
     rank, world, device, shared, backend = dist_setup(args)

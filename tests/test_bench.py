@@ -84,3 +84,64 @@ def test_config1_runs_on_the_cpu_through_the_product_path():
     assert line["n_gpus"] == 0 and line["dtype"] == "f32" and line["value"] > 0
     assert line["config"]["equals_oracle_bit_for_bit"] is True and line["config"]["raw_shape"] == [256, 64, 256]
     assert line["cpu_baseline"]["kind"] == "port" and line["cpu_baseline"]["cores"] == 1
+
+
+def test_a_plain_run_leaves_the_cpu_baseline_to_full(monkeypatch, capsys):
+    """``--gpus 1 --steps N --warmup W`` measures the headline only; ``--full`` adds the CPU baseline."""
+    import bench
+
+    calls = []
+    monkeypatch.setattr(bench, "cpu_baseline", lambda **kw: calls.append(kw) or {"kind": "port"})
+    monkeypatch.setattr(bench, "dist_setup", lambda args: (0, 1, "cuda:0", False, None))
+    monkeypatch.setattr(bench, "run_resident", lambda args, rank, world, device, shared, backend, cpu:
+                        {"metric": "m", "steps": args.steps, **({"cpu_baseline": cpu} if cpu is not None else {})})
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    for argv, want in ((["--gpus", "1", "--steps", "3", "--warmup", "1"], False),
+                       (["--gpus", "1", "--steps", "3", "--warmup", "1", "--full"], True),
+                       (["--gpus", "1", "--full", "--no-cpu-baseline"], False)):
+        calls.clear()
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        bench.main()
+        line = json.loads(capsys.readouterr().out)
+        assert bool(calls) is want and ("cpu_baseline" in line) is want, argv
+
+
+def test_dump_outputs_writes_float32_and_samples_large_arrays_at_fixed_positions(tmp_path):
+    import numpy as np
+    import torch
+
+    import bench
+
+    small = torch.arange(24, dtype=torch.float64).reshape(2, 3, 4)
+    big = torch.randn(40, 300, 310, generator=torch.Generator().manual_seed(1))[:, 5:295, 7:300]   # a strided window
+    bench.dump_outputs(tmp_path / "a", {"small": small, "big": big})
+    bench.dump_outputs(tmp_path / "b", {"big": big * 2})
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and s.shape == (2, 3, 4) and np.array_equal(s, small.numpy())
+    vals, idx = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "a" / "big_index.npy")
+    assert vals.dtype == np.float32 and vals.shape == (bench.DUMP_SAMPLE,) and idx.dtype == np.float64
+    i = idx.astype(np.int64)
+    assert np.all(np.diff(i) > 0) and i[-1] < big.numel()
+    assert np.array_equal(vals, big.contiguous().numpy().ravel()[i])
+    assert np.array_equal(np.load(tmp_path / "b" / "big_index.npy"), idx)     # same shape: same positions
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= bench.DUMP_BUDGET_BYTES
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_same_from_run_to_run(tmp_path):
+    """Seeded inputs: two runs with the same arguments write the same outputs, bit for bit."""
+    import numpy as np
+
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, "bench.py", "--workload", "small", "--steps", "2", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / run)], cwd=ROOT, env=_bare_env(), capture_output=True,
+                           text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and "cpu_baseline" not in line
+    names = sorted(f.name for f in (tmp_path / "a").iterdir())
+    assert names == ["deskewed.npy", "deskewed_index.npy", "estimate.npy", "estimate_index.npy"]
+    for name in names:
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+    assert np.isfinite(np.load(tmp_path / "a" / "estimate.npy")).all()

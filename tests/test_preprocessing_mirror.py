@@ -1,15 +1,10 @@
 """CPU tests of the preprocessor adapter; they read like the reference's
 ``shrimpy/tests/test_preprocessing.py`` (heavy steps monkeypatched, control flow exercised).
 
-The last test runs the REFERENCE's own ``shrimpy.preprocessing`` with this package standing in for
-``biahub`` (skipped where /root/reference is absent, e.g. on the GPU box): the drop-in claim,
-checked against the caller's real code.
+The last test replays what the REFERENCE's own ``shrimpy.preprocessing`` took from and called in ``biahub`` when it
+ran with this package standing in (captured by ``oracle/capture_dropin.py``): the drop-in claim, checked against the
+caller's real code.
 """
-
-import sys
-import types
-
-from pathlib import Path
 
 import numpy as np
 import pytest
@@ -168,33 +163,26 @@ def test_warm_up_resolves_deskewed_shape(monkeypatch):
     assert pre._zyx_shape == (171, 2048, 2270)
 
 
-REFERENCE = Path("/root/reference")
+def test_dropin_through_the_reference_preprocessor(monkeypatch, golden_dir):
+    """The reference's ``build_preprocessor`` / ``_LabelfreePreprocessor`` ran unmodified with this package bound as
+    ``biahub`` (``oracle/capture_dropin.py`` -> ``tests/golden/ref_dropin_preprocessor.npz``): the settings it
+    validated, the warm-up shape call and the deskew call it made, and what it kept of their answers.  Replayed here
+    on our modules: every name it took exists, the settings validate, each call got exactly the fields our function
+    accepts (the reference filters the dumped settings by signature), and the arithmetic -- the CPU tensor the
+    reference hands over runs the native host twin (a spy records the call and passes it on) -- equals the oracle."""
+    import importlib
+    import inspect
 
-
-@pytest.mark.skipif(not (REFERENCE / "shrimpy" / "preprocessing.py").exists(),
-                    reason="the reference is only mounted in the build container")
-def test_dropin_through_the_reference_preprocessor(monkeypatch):
-    """The reference's ``build_preprocessor`` / ``_LabelfreePreprocessor`` run unmodified with this
-    package bound as ``biahub``: settings validation, kwargs filtering by signature, warm-up shape
-    call and the deskew call all go through our modules -- and, since round 3, the arithmetic too: the CPU
-    tensor the reference hands over runs the native host twin (a spy records the call and passes it on)."""
     import torch
 
     import shrimpy_amd.deskew as our_deskew
-    import shrimpy_amd.settings as our_settings
 
     from oracle import cpu_ref as o
+    from tests.test_reference_suites_dropin import _dec, _load
 
-    biahub = types.ModuleType("biahub")
-    biahub.deskew = our_deskew
-    biahub.settings = our_settings
-    monkeypatch.setitem(sys.modules, "biahub", biahub)
-    monkeypatch.setitem(sys.modules, "biahub.deskew", our_deskew)
-    monkeypatch.setitem(sys.modules, "biahub.settings", our_settings)
-    monkeypatch.syspath_prepend(str(REFERENCE))
-    monkeypatch.setattr(sys, "dont_write_bytecode", True)
-    ref_pp = __import__("shrimpy.preprocessing", fromlist=["build_preprocessor"])
-
+    m, z = _load(golden_dir, "ref_dropin_preprocessor.npz")
+    for module, name in m["fetched"]:
+        assert hasattr(importlib.import_module(m["modules"][module]), name), f"{module}.{name}"
     calls = {}
 
     real_launch = our_deskew.deskew_with_matrix
@@ -207,22 +195,44 @@ def test_dropin_through_the_reference_preprocessor(monkeypatch):
         return res
 
     monkeypatch.setattr(our_deskew, "deskew_with_matrix", spy)
-    raw_shape = (48, 12, 20)
-    pre = ref_pp.build_preprocessor(raw_shape, ["deskew"], deskew=dict(DESKEW), output_channel="BF")
+    r = m["raw"]
+    raw_shape = tuple(r["shape"])
+    raw = np.random.default_rng(r["seed"]).integers(r["low"], r["high"], raw_shape).astype(np.uint16)
+    assert [run["deskew"] for run in m["runs"]] == [dict(DESKEW), dict(DESKEW, orientation="flip_z+rot90",
+                                                                        border="grid-constant")]
+    answers = []
+    for run in m["runs"]:
+        settings, results = None, []
+        for c in run["calls"]:
+            module, name = c["fn"].rsplit(".", 1)
+            fn = getattr(importlib.import_module(m["modules"][module]), name)
+            args, kwargs = _dec(c["args"], z), _dec(c["kwargs"], z)
+            if settings is None:
+                assert name == "DeskewSettings" and not args and kwargs == run["deskew"]
+                settings = fn(**kwargs)                    # our settings model validates the reference's dict
+                results.append(settings)
+                continue
+            params = list(inspect.signature(fn).parameters)
+            fields = {k: v for k, v in settings.model_dump().items() if k in params}
+            # the reference passes the volume (or its shape) plus the settings fields our function accepts
+            assert set(kwargs) == set(fields) | {params[0]} and all(kwargs[k] == fields[k] for k in fields), name
+            if params[0] == "raw_data":
+                np.testing.assert_array_equal(kwargs["raw_data"].numpy(), raw.astype(np.float32))
+            results.append(fn(*args, **kwargs))
+        shape = results[run["zyx_from_call"]][0]
+        assert tuple(shape) == tuple(run["zyx_shape"])     # the reference kept the first answer of OUR shape rule
+        answers.append((tuple(shape), results[run["bf_from_call"]], run["out_keys"], dict(calls)))
+
+    (shape, bf, keys, seen), (shape_rot, bf_rot, _, seen_rot) = answers
     expect_shape, _ = our_deskew.get_deskewed_data_shape(raw_shape, 30.0, 0.755, False, 3)
-    assert tuple(pre._zyx_shape) == expect_shape  # the reference's warm_up called OUR shape rule
-    raw = np.random.default_rng(0).integers(80, 600, raw_shape).astype(np.uint16)
-    out = pre(raw, label="A/1/0", return_intermediates=True)
-    assert set(out) == {"BF", "deskew"}
-    assert calls["args"] == (raw_shape, (12, 20, expect_shape[2]), 3)
-    np.testing.assert_array_equal(out["BF"].numpy(), o.deskew(raw.astype(np.float32), 30.0, 0.755, False, 3))
+    assert shape == expect_shape
+    assert keys == ["BF", "deskew"]
+    assert seen["args"] == (raw_shape, (12, 20, expect_shape[2]), 3)
+    np.testing.assert_array_equal(bf.numpy(), o.deskew(raw.astype(np.float32), 30.0, 0.755, False, 3))
 
     # the convention switches ride through the reference's signature filter like any other field
-    pre = ref_pp.build_preprocessor(raw_shape, ["deskew"], output_channel="BF",
-                                    deskew=dict(DESKEW, orientation="flip_z+rot90", border="grid-constant"))
     want = o.deskew(raw.astype(np.float32), 30.0, 0.755, False, 3, orientation="flip_z+rot90",
                     border="grid-constant")
-    assert tuple(pre._zyx_shape) == want.shape       # warm_up saw the rotated shape
-    out = pre(raw)
-    assert calls["border"] == "grid-constant"
-    np.testing.assert_array_equal(out["BF"].numpy(), want)
+    assert shape_rot == want.shape       # warm_up saw the rotated shape
+    assert seen_rot["border"] == "grid-constant"
+    np.testing.assert_array_equal(bf_rot.numpy(), want)
