@@ -639,7 +639,8 @@ int lsr_irfft_rows_peak(const float* spec, int64_t Z, int64_t Y, int64_t X, cons
  *     LSR_EPI_RATIO:  out = aux / (max(v, 0) + eps)    aux = y
  *     LSR_EPI_UPDATE: out = aux * v / H^T 1            aux = x; H^T 1 = norm_full inside, from norm_table ((pz+1)(py+1)
  *                     (px+1) prefix sums of the PSF, float64, device) within a PSF radius of the border; stats = 3 doubles
- *                     the launch ADDS the iteration's flux / change / total to (as lsr_correlate_*_stats_f32) or NULL.
+ *                     the launch ADDS the iteration's flux / change / total to (as lsr_correlate_*_stats_f32) or NULL;
+ *                     px <= 129 (LSR_E_UNSUPPORTED beyond: the border lookup covers a radius of 64 columns).
  *   out may be aux (in place).  The convolved volume is never written.
  * lsr_rl_rows_chain_f32: the same, CHAINED into the forward x leg of the iteration's next convolution: the epilogue's
  *   output row is zero-padded, transformed and stored back over its tile of `spec`, which afterwards holds what

@@ -605,3 +605,63 @@ def dt_compute_shift(ref, mov, method, scale_z, scale_yx, maximum=1.0, limits=No
     if dampening is not None:
         um = um * np.array(dampening, dtype=float)
     return float(um[2]), float(um[1]), float(um[0])
+
+
+# --------------------------------------------------------------------------------------
+# The LDS FFT kernels (csrc/rfft_rows.hip, csrc/zcorr.hip) restated in float64: each follows
+# the contract its entry's comment states, with numpy's transforms in double precision.
+# --------------------------------------------------------------------------------------
+
+
+def rows_rfft_t(src, grid, zero=False):
+    """``lsr_rfft_rows_t_c64`` (``zero=False``: the source reflect-padded / centre-cropped to ``grid`` as
+    :func:`dt_match_shape` does) or ``lsr_rfft_rows_zero_t_c64`` (``zero=True``: the source at the grid's origin,
+    zeros behind it): the unnormalised real-to-complex transform along x, laid out ``[Z][X/2+1][Y]``, complex128.
+    (The zero variant leaves planes ``z >= Zi`` unwritten; here they are the transform of zeros.)"""
+    src = np.asarray(src, np.float32)
+    if zero:
+        v = np.zeros(tuple(int(g) for g in grid), np.float64)
+        v[: src.shape[0], : src.shape[1], : src.shape[2]] = src
+    else:
+        v = dt_match_shape(src, tuple(int(g) for g in grid)).astype(np.float64)
+    return np.ascontiguousarray(np.fft.rfft(v, axis=-1).transpose(0, 2, 1))
+
+
+def rows_irfft_t(spec_t, x):
+    """The inverse row leg of ``lsr_irfft_rows_peak`` / ``lsr_irfft_rows_rl_f32`` before their epilogues: ``spec_t``
+    (``[Z][X/2+1][Y]``) back to a real ``(Z, Y, X)`` volume, unnormalised -- the inverse "carries a factor 2 X / 2 = X".
+    The imaginary parts of the DC and Nyquist coefficients are dropped (a real signal has none)."""
+    s = np.asarray(spec_t).astype(np.complex128).transpose(0, 2, 1)
+    return float(x) * np.fft.irfft(s, n=int(x), axis=-1)
+
+
+def z_leg(f1, g, mode, z_valid=None, z_keep=None):
+    """``lsr_cross_correlate_z_c64`` (mode 0: ``N IFFT_z(f1 conj(FFT_z(g)))``) and ``lsr_spectrum_multiply_z_c64``
+    (mode 1: ``N IFFT_z(f1 FFT_z(g))``, mode 2: ``N IFFT_z(conj(f1) FFT_z(g))``) in float64.  ``f1`` is ``[XC][Y][N]``,
+    ``g`` and the result ``[N][XC][Y]``.  Planes ``z >= z_valid`` of ``g`` are taken as zeros (never read); only the
+    planes ``z < z_keep`` of the result are returned."""
+    g = np.array(g, dtype=np.complex128)
+    n = g.shape[0]
+    z_valid = n if z_valid is None else int(z_valid)
+    z_keep = n if z_keep is None else int(z_keep)
+    g[z_valid:] = 0
+    G = np.fft.fft(g, axis=0)
+    F = np.asarray(f1).astype(np.complex128).transpose(2, 0, 1)           # [N][XC][Y]
+    prod = {0: F * np.conj(G), 1: F * G, 2: np.conj(F) * G}[int(mode)]
+    return (n * np.fft.ifft(prod, axis=0))[:z_keep]
+
+
+def rl_norm_direct(shape, psf):
+    """``H^T 1`` of the RL update by direct summation in float64: at every voxel the sum of the PSF taps that stay
+    inside the volume (``ndimage.correlate(ones, psf, mode="constant")``), tap by tap -- not from prefix sums."""
+    w = np.asarray(psf, np.float64)
+    zo, yo, xo = (int(v) for v in shape)
+    out = np.zeros((zo, yo, xo), np.float64)
+    c = [s // 2 for s in w.shape]
+    for (a, b, e), t in np.ndenumerate(w):
+        da, db, de = a - c[0], b - c[1], e - c[2]
+        # voxels whose tap lands inside: 0 <= v + d < n
+        lo_hi = [(max(0, -d), min(n, n - d)) for d, n in ((da, zo), (db, yo), (de, xo))]
+        if all(lo < hi for lo, hi in lo_hi):
+            out[tuple(slice(lo, hi) for lo, hi in lo_hi)] += t
+    return out

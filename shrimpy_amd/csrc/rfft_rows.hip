@@ -38,6 +38,9 @@ constexpr int kThreads = 512;
 constexpr int kRows = 8;                      // y rows per workgroup: 64-byte runs in the transposed layout
 constexpr int kPerRow = kThreads / kRows;     // 64 threads share a row's butterflies
 constexpr int kMaxM = 2048;                   // longest half-length: 8 * 2049 * 8 B + 8 KB of twiddles = 139 KB of LDS
+// widest PSF along x the UPDATE epilogue's border lookup covers: cx = px / 2 <= 64 = kPerRow, so the left border is a
+// lane's first m and the right one at most one m per lane (deconvolve_fft.py's MAX_FFT_TAPS)
+constexpr int kMaxTapsX = 2 * kPerRow + 1;
 
 struct RowsArgs {
   const float* in;        // forward: un-padded source [Zi][Yi][Xi]
@@ -606,6 +609,8 @@ extern "C" int lsr_irfft_rows_rl_f32(const float* spec, int64_t Z, int64_t Y, in
     LSR_REQUIRE(pz > 0 && py > 0 && px > 0 && pz % 2 == 1 && py % 2 == 1 && px % 2 == 1 && pz < 4096 && py < 4096 &&
                     px < 4096, LSR_E_ARG, "PSF extents (%d,%d,%d) must be odd and positive", pz, py, px);
     LSR_REQUIRE(norm_full > 0.0f, LSR_E_ARG, "norm_full must be positive");
+    LSR_REQUIRE(px <= kMaxTapsX, LSR_E_UNSUPPORTED, "PSF of %d taps along x: the border normalisation covers at most %d",
+                px, kMaxTapsX);
   }
   p.spec = const_cast<float2*>(reinterpret_cast<const float2*>(spec));
   p.aux = aux; p.out = out;
@@ -652,6 +657,8 @@ extern "C" int lsr_rl_rows_chain_f32(float* spec, int64_t Z, int64_t Y, int64_t 
     LSR_REQUIRE(pz > 0 && py > 0 && px > 0 && pz % 2 == 1 && py % 2 == 1 && px % 2 == 1 && pz < 4096 && py < 4096 &&
                     px < 4096, LSR_E_ARG, "PSF extents (%d,%d,%d) must be odd and positive", pz, py, px);
     LSR_REQUIRE(norm_full > 0.0f, LSR_E_ARG, "norm_full must be positive");
+    LSR_REQUIRE(px <= kMaxTapsX, LSR_E_UNSUPPORTED, "PSF of %d taps along x: the border normalisation covers at most %d",
+                px, kMaxTapsX);
   }
   p.spec = reinterpret_cast<float2*>(spec);
   p.aux = aux; p.out = out;

@@ -40,6 +40,7 @@ from . import _lib, fft3
 __all__ = ["FftRichardsonLucyPlan", "fft_grid", "fft_supported"]
 
 MAX_FFT_TAPS = 129     # per axis; beyond that the padding outgrows the volume for any stack this package sees
+                       # (and csrc/rfft_rows.hip: kMaxTapsX, the widest PSF along x its border lookup covers)
 
 
 def _next_smooth(n: int) -> int:

@@ -572,3 +572,24 @@ def test_fourier_domain_rl_grid_and_method_arguments():
         assert all(a >= n + p // 2 for a, n, p in zip(g, shape, psf)) and g[0] <= 256 and g[2] <= 4096 and g[2] % 4 == 0
     with pytest.raises(ValueError, match="method"):
         make_plan((8, 8, 8), np.ones((3, 3, 3), np.float32) / 27, "cpu", method="spectral")
+
+
+def test_fourier_rl_rows_refuse_a_psf_wider_than_their_border_lookup():
+    """The UPDATE epilogue of ``lsr_irfft_rows_rl_f32`` / ``lsr_rl_rows_chain_f32`` finds H^T 1 at the x borders for a PSF
+    radius of at most 64 columns (``MAX_FFT_TAPS`` = 129 taps): a wider PSF is LSR_E_UNSUPPORTED, not a wrong border.
+    Validation runs before any launch: safe with dummy pointers and no GPU."""
+    from shrimpy_amd.deconvolve_fft import MAX_FFT_TAPS
+
+    assert MAX_FFT_TAPS == 129
+    lib = _lib.load()
+    buf = np.zeros(4096, np.float32)
+    p, f = buf.ctypes.data, ctypes.c_float
+    for name in ("lsr_irfft_rows_rl_f32", "lsr_rl_rows_chain_f32"):
+        for px in (MAX_FFT_TAPS + 2, 4095):
+            rc = getattr(lib, name)(p, 4, 8, 16, p, p, _lib.EPI_UPDATE, p, p, 3, 5, 16, f(1.0 / 512), f(1e-6), 1, 1, px, p,
+                                    f(1.0), None, None)
+            assert rc == _lib.E_UNSUPPORTED, (name, px, rc, lib.lsr_last_error())
+            assert b"taps along x" in lib.lsr_last_error()
+        with pytest.raises(_lib.LsrUnsupported, match="at most 129"):
+            _lib.call(name, p, 4, 8, 16, p, p, _lib.EPI_UPDATE, p, p, 3, 5, 16, f(1.0 / 512), f(1e-6), 3, 5,
+                      MAX_FFT_TAPS + 2, p, f(1.0), None, None)

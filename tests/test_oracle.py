@@ -252,3 +252,93 @@ def test_dynatrack_dispatcher_oracle_matches_reference_capture(golden_dir):
                 continue  # (their estimators are covered by the PCC and mask fixtures)
             np.testing.assert_allclose(o.dt_compute_shift(g["a"], g["b"], method, **kw, **extra), want,
                                        rtol=0, atol=2e-4)
+
+
+# ---------------------------------------------------------------- float64 restatements of the LDS FFT kernels
+
+
+def _dft(n, sign=-1):
+    """The explicit O(n^2) DFT matrix, exp(sign 2 pi i j k / n)."""
+    j = np.arange(n)
+    return np.exp(sign * 2j * np.pi * np.outer(j, j) / n)
+
+
+@pytest.mark.parametrize("src_shape,grid", [((2, 3, 8), (2, 3, 8)), ((3, 5, 7), (4, 4, 12)), ((2, 6, 21), (3, 5, 20)),
+                                            ((1, 2, 9), (2, 3, 16))])
+def test_row_leg_restatements_against_the_dft_matrix(src_shape, grid):
+    rng = np.random.default_rng(11)
+    src = rng.standard_normal(src_shape).astype(np.float32)
+    x = grid[2]
+    dft = _dft(x)[: x // 2 + 1]                                           # rows k <= X / 2
+    for zero in (False, True):
+        if zero and any(s > g for s, g in zip(src_shape, grid)):
+            continue
+        if zero:
+            v = np.zeros(grid)
+            v[: src_shape[0], : src_shape[1], : src_shape[2]] = src
+        else:
+            v = o.dt_match_shape(src, grid).astype(np.float64)
+        want = np.einsum("kn,zyn->zky", dft, v)
+        got = o.rows_rfft_t(src, grid, zero=zero)
+        assert got.shape == (grid[0], x // 2 + 1, grid[1])
+        np.testing.assert_allclose(got, want, rtol=0, atol=1e-12 * np.abs(want).max())
+        # the inverse leg: X times the real inverse, i.e. the full Hermitian spectrum through exp(+2 pi i k n / X)
+        full = np.concatenate([want, np.conj(want[:, 1 : x // 2][:, ::-1])], axis=1)     # [Z][X][Y]
+        back = np.einsum("nk,zky->zyn", _dft(x, +1), full).real
+        np.testing.assert_allclose(o.rows_irfft_t(want, x), back, rtol=0, atol=1e-12 * np.abs(back).max())
+        np.testing.assert_allclose(back, x * v, rtol=0, atol=1e-10 * np.abs(v).max() * x)
+
+
+@pytest.mark.parametrize("n", [2, 3, 5, 6, 8])
+def test_z_leg_restatement_against_the_dft_matrix(n):
+    rng = np.random.default_rng(n)
+    xc, y = 2, 3
+    f1 = rng.standard_normal((xc, y, n)) + 1j * rng.standard_normal((xc, y, n))
+    g = rng.standard_normal((n, xc, y)) + 1j * rng.standard_normal((n, xc, y))
+    fwd, inv = _dft(n), _dft(n, +1)                                       # n IFFT = the unscaled +i transform
+    F = f1.transpose(2, 0, 1)
+    for z_valid, z_keep in ((n, n), (max(1, n - 1), max(1, n // 2)), (1, n)):
+        gv = g.copy()
+        gv[z_valid:] = np.nan                                             # never read
+        G = np.einsum("kz,zab->kab", fwd, np.where(np.isnan(gv), 0, gv))
+        for mode, prod in ((0, F * np.conj(G)), (1, F * G), (2, np.conj(F) * G)):
+            want = np.einsum("zk,kab->zab", inv, prod)[:z_keep]
+            got = o.z_leg(f1, gv, mode, z_valid, z_keep)
+            assert got.shape == (z_keep, xc, y)
+            np.testing.assert_allclose(got, want, rtol=0, atol=1e-12 * np.abs(want).max())
+
+
+@pytest.mark.parametrize("shape,psf_shape", [((4, 5, 6), (3, 3, 5)), ((2, 3, 9), (5, 1, 7)), ((3, 4, 2), (1, 3, 9))])
+def test_rl_norm_direct_sums_the_taps_inside(shape, psf_shape):
+    rng = np.random.default_rng(3)
+    w = rng.random(psf_shape)
+    got = o.rl_norm_direct(shape, w)
+    c = [s // 2 for s in psf_shape]
+    want = np.zeros(shape)
+    for z, yy, x in np.ndindex(*shape):
+        for a, b, e in np.ndindex(*psf_shape):
+            p = (z + a - c[0], yy + b - c[1], x + e - c[2])
+            if all(0 <= q < n for q, n in zip(p, shape)):
+                want[z, yy, x] += w[a, b, e]
+    np.testing.assert_allclose(got, want, rtol=1e-14)
+    np.testing.assert_allclose(got, o.rl_norm(shape, w), rtol=1e-6)
+
+
+@pytest.mark.parametrize("ref_shape,roll", [((8, 12, 16), (1, 2, -3)), ((9, 15, 20), (-2, 4, 5)), ((5, 7, 26), (2, -3, 6))])
+def test_restated_legs_compose_to_the_trackers_phase_cross_correlation(ref_shape, roll):
+    """x leg (rows_rfft_t), y transform, z leg (mode 0), y inverse, x inverse (rows_irfft_t): the peak of the
+    fftshift-ed modulus is the shift ``dt_phase_cross_corr`` returns, on odd and even grids."""
+    rng = np.random.default_rng(5)
+    ref = rng.random(ref_shape).astype(np.float32)
+    mov = np.roll(ref, roll, axis=(0, 1, 2)) + 0.05 * rng.random(ref_shape).astype(np.float32)
+    grid = tuple(o.dt_next_fast_len(s) for s in ref_shape)
+    f1 = np.fft.fft(np.fft.fft(o.rows_rfft_t(ref, grid), axis=2), axis=0).transpose(1, 2, 0)   # [XC][Y][Z]
+    g = np.fft.fft(o.rows_rfft_t(mov, grid), axis=2)                                           # [Z][XC][Y]
+    c = grid[1] * np.fft.ifft(o.z_leg(f1, g, 0), axis=2)
+    corr = o.rows_irfft_t(c, grid[2])
+    n = float(np.prod(grid))
+    a, b = (o.dt_match_shape(v, grid).astype(np.float64) for v in (ref, mov))
+    want = np.fft.irfftn(np.fft.rfftn(a) * np.conj(np.fft.rfftn(b)), s=grid, axes=(0, 1, 2))
+    np.testing.assert_allclose(corr, n * want, rtol=0, atol=1e-9 * n * np.abs(want).max())
+    peak = np.unravel_index(int(np.argmax(np.fft.fftshift(np.abs(corr)))), grid)
+    assert tuple(s // 2 - int(p) for s, p in zip(grid, peak)) == o.dt_phase_cross_corr(ref, mov)
