@@ -393,12 +393,19 @@ def test_device_decoder_reads_libzstd_frames_of_every_kind(device):
 # ---------------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("shards,streams", [("volume", "serial"), (None, "serial"), ("volume", "overlap")])
-def test_store_to_store_with_device_codecs_equals_the_host_codec_run(tmp_path, device, shards, streams, monkeypatch):
+@pytest.mark.parametrize("shards,streams,blocksize,zc", [
+    pytest.param("volume", "serial", 32768, 32, id="volume-serial"),
+    pytest.param(None, "serial", 32768, 32, id="None-serial"),
+    pytest.param("volume", "overlap", 32768, 32, id="volume-overlap"),
+    pytest.param("volume", "serial", 131072, 32, id="volume-serial-128K-blocks"),
+    pytest.param("volume", "serial", 1 << 20, 64, id="volume-serial-1M-blocks")])
+def test_store_to_store_with_device_codecs_equals_the_host_codec_run(tmp_path, device, shards, streams, blocksize, zc,
+                                                                      monkeypatch):
     """An input plate in the acquisition's format (Zarr v3, blosc-zstd chunks of 32 planes with 32 KB blocks, one shard per
     volume) -> deskew + RL -> blosc-zstd output.  With the device codecs the host neither decodes nor encodes a byte; the
     output store must hold the same volumes, bit for bit, as the run with the host codecs, and every chunk file of it must
-    decode with the system libzstd."""
+    decode with the system libzstd.  Also with the larger blocks of c-blosc's higher levels: 128 KB blocks (4 full ones
+    and a leftover per 32-plane chunk) and 1 MB blocks (64-plane chunks: one full block and a leftover)."""
     import torch
 
     import bench
@@ -417,7 +424,7 @@ def test_store_to_store_with_device_codecs_equals_the_host_codec_run(tmp_path, d
         for p, key in enumerate(keys):
             arr = plate.create_position(*key.split("/")).create_zeros(
                 "0", shape=(2, 1) + raw_shape, dtype="uint16", scale=(1, 1, 0.15, 0.1133, 0.1133), compress="blosc-zstd",
-                shards=shards, blocksize=32768)
+                shards=shards, blocksize=blocksize, chunks=(1, 1, zc) + raw_shape[1:])
             for t in range(2):
                 if (p, t) == (1, 1):
                     continue                                    # a volume that was never written: fill value
