@@ -665,3 +665,87 @@ def rl_norm_direct(shape, psf):
         if all(lo < hi for lo, hi in lo_hi):
             out[tuple(slice(lo, hi) for lo, hi in lo_hi)] += t
     return out
+
+
+# --------------------------------------------------------------------------------------
+# One Richardson-Lucy iteration in float64: what every spatial RL kernel and host twin is held to, voxel by voxel
+# (tests/test_rl_fp64_gpu.py, tests/test_host_twins.py).  Nothing below rounds to float32.
+# --------------------------------------------------------------------------------------
+
+
+def _axis_norm_direct(k, n, window=None):
+    """Per position of an axis of ``n`` samples, the sum of the taps of the 1-D correlation kernel ``k`` that land
+    inside it, added tap by tap in float64.  ``window = (first, total)``: the axis is the slice ``[first, first + n)``
+    of one of ``total`` samples, and the taps count as inside while they are inside that longer axis."""
+    k = np.asarray(k, np.float64)
+    first, total = (0, int(n)) if window is None else (int(window[0]), int(window[1]))
+    c = len(k) // 2
+    out = np.zeros(total, np.float64)
+    for j, t in enumerate(k):
+        lo, hi = max(0, c - j), min(total, total + c - j)
+        if lo < hi:
+            out[lo:hi] += t
+    return out[first:first + int(n)]
+
+
+def rl_iteration_f64(x, y, psf=None, factors=None, eps=1e-6, y_window=None):
+    """One iteration ``x_new = x * H^T(y / (H x + eps)) / H^T 1`` in float64; returns ``(blur, ratio, x_new)``.
+
+    ``x``, ``y`` and the taps are used as passed, promoted to float64 (hand in the float32 arrays the device gets);
+    ``eps`` is the float32 the entries receive.  ``H x`` is the convolution and ``H^T r`` the correlation with the PSF,
+    zero outside the volume; ``H^T 1`` is the sum of the taps that stay inside, tap by tap.  The PSF is either dense
+    (``psf``, even axes padded by a trailing zero plane as the product does), ``factors = (kz, ky, kx)`` (the PSF is
+    their exact outer product, three 1-D passes per correlation) or ``factors = (ky, kzx)`` with ``kzx`` 2-D (a y pass
+    and a (z, x) stencil).  ``y_window = (first, total)``: the volume is the row slab ``[first, first + Y)`` of a
+    volume of ``total`` rows, whose ``H^T 1`` it takes along y (rows outside the slab still read as zero)."""
+    x = np.asarray(x, np.float64)
+    y = np.asarray(y, np.float64)
+    if x.ndim != 3 or x.shape != y.shape:
+        raise ValueError("x and y must be (Z, Y, X) volumes of one shape")
+    if (psf is None) == (factors is None):
+        raise ValueError("pass psf or factors")
+    eps64 = np.float64(np.float32(eps))
+    nz_, ny_, nx_ = x.shape
+    kw = dict(mode="constant", cval=0.0)
+    if factors is not None:
+        ks = [np.asarray(k, np.float64) for k in factors]
+        if any(s % 2 == 0 for k in ks for s in k.shape):
+            raise ValueError("factors must have odd lengths")
+        if len(ks) == 3 and all(k.ndim == 1 for k in ks):
+
+            def corr(v, flip):
+                for axis, k in enumerate(ks):
+                    v = ndimage.correlate1d(v, k[::-1] if flip else k, axis=axis, **kw)
+                return v
+
+            norm = (_axis_norm_direct(ks[0], nz_)[:, None, None] * _axis_norm_direct(ks[1], ny_, y_window)[None, :, None]
+                    * _axis_norm_direct(ks[2], nx_)[None, None, :])
+        elif len(ks) == 2 and ks[0].ndim == 1 and ks[1].ndim == 2:
+            ky, kzx = ks
+
+            def corr(v, flip):
+                v = ndimage.correlate1d(v, ky[::-1] if flip else ky, axis=1, **kw)
+                return ndimage.correlate(v, (kzx[::-1, ::-1] if flip else kzx)[:, None, :], **kw)
+
+            nzx = rl_norm_direct((nz_, 1, nx_), kzx[:, None, :])
+            norm = nzx * _axis_norm_direct(ky, ny_, y_window)[None, :, None]
+        else:
+            raise ValueError("factors must be (kz, ky, kx) or (ky, kzx)")
+    else:
+        w = np.asarray(psf, np.float64)
+        if w.ndim != 3:
+            raise ValueError("psf must be 3-D")
+        w = np.pad(w, [(0, 1 - (s % 2)) for s in w.shape])
+
+        def corr(v, flip):
+            return ndimage.correlate(v, w[::-1, ::-1, ::-1] if flip else w, **kw)
+
+        if y_window is None:
+            norm = rl_norm_direct(x.shape, w)
+        else:
+            first, total = (int(v) for v in y_window)
+            norm = rl_norm_direct((nz_, total, nx_), w)[:, first:first + ny_, :]
+    blur = corr(x, True)
+    ratio = y / (blur + eps64)
+    x_new = x * corr(ratio, False) / norm
+    return blur, ratio, x_new

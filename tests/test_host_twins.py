@@ -464,3 +464,67 @@ def test_host_path_argument_errors_read_like_the_device_paths():
     t = torch.arange(8 * 4 * 6, dtype=torch.float64).reshape(6, 4, 8).permute(2, 1, 0)
     np.testing.assert_array_equal(fast_deskew_zyx(raw_data=t, ls_angle_deg=30, px_to_scan_ratio=0.755, keep_overhang=True).numpy(),
                                   o.deskew(t.numpy().astype(np.float32), 30.0, 0.755, True, 1))
+
+
+# ---------------------------------------------------------------- one RL iteration, voxel by voxel, against float64
+#
+# The inputs and the bound of tests/test_rl_fp64_gpu.py (tests/rl_fp64_cases.py) on the twins behind
+# ``host.richardson_lucy``: ref == 0 -> got == 0, else |got - ref| <= C u ref with C <= 2 T + 16 a priori.  The
+# constants are at most four times the worst ratio of THE TWINS over the cases below (measured on an x86-64 host; the
+# device's are recorded in tests/test_rl_fp64_gpu.py).
+
+C_HOST_SEP = 28.0            # separable twin: worst 7.23 u (31 x 7 x 3 taps); never above 2 T + 16
+C_HOST_DENSE = 140.0         # dense twin: worst 35.5 u (11 x 9 x 9 taps) ...
+F_HOST_DENSE = 0.38          # ... and at most this share of 2 T + 16: worst 0.0961 (3 x 3 x 3 taps, 6.73 u of 70)
+C_HOST_BLUR = 1.0            # correlate3d alone, in units of T u: at most one rounding of u / 2 per tap
+
+RL_F64_SEP = [((9, 7, 5), (20, 33, 130)), ((15, 9, 11), (37, 17, 129)), ((3, 15, 13), (5, 40, 257)),
+              ((1, 1, 1), (4, 9, 31)), ((3, 1, 3), (1, 33, 127)), ((5, 3, 1), (9, 1, 128)), ((31, 7, 3), (40, 12, 65)),
+              ((17, 15, 13), (16, 31, 40)), ((7, 5, 9), (6, 63, 3))]
+RL_F64_DENSE = [((3, 3, 3), (7, 33, 65)), ((5, 7, 3), (9, 31, 66)), ((9, 5, 7), (17, 20, 40)), ((11, 9, 9), (12, 17, 33)),
+                ((13, 11, 5), (14, 12, 30)), ((3, 5, 9), (1, 1, 70))]
+
+
+def _hold(name, got, ref, bound):
+    from tests import rl_fp64_cases as c
+
+    worst, idx, leak = c.worst_voxel(got, ref)
+    print(f"{name}: worst {worst:.3g} u at (z, y, x) = {idx}, bound {bound:.3g} u")
+    assert leak is None, f"{name}: non-zero at (z, y, x) = {leak} where the float64 iteration is exactly 0"
+    assert worst <= bound, f"{name}: {worst:.3g} u at (z, y, x) = {idx} (bound {bound:.3g} u)"
+
+
+@pytest.mark.parametrize("psf_shape,shape", RL_F64_SEP)
+def test_separable_twin_one_iteration_per_voxel_against_float64(psf_shape, shape):
+    """``lsr_correlate_sep_stats_f32_cpu`` (RATIO, then UPDATE) behind ``host.richardson_lucy(psf_factors=...)``; the
+    9 x 7 x 5 taps sum to 1.7, so ``H^T 1 != 1`` in the interior too; 17 and 31 z taps among them."""
+    from shrimpy_amd import host
+    from tests import rl_fp64_cases as c
+
+    rng = np.random.default_rng(sum(psf_shape))
+    ks = [c.taps_1d(n, rng, 1.7 if i == 0 and psf_shape[0] == 9 else 1.0) for i, n in enumerate(psf_shape)]
+    x, y = c.make_inputs(shape, psf_shape, sum(shape))
+    got = host.richardson_lucy(_t(y), psf_factors=ks, iterations=1, eps=c.EPS, x0=_t(x)).numpy()
+    blur, _, ref = o.rl_iteration_f64(x, y, factors=ks, eps=c.EPS)
+    _hold(f"separable twin {psf_shape} {shape}", got, ref, min(C_HOST_SEP, c.ceiling(sum(psf_shape))))
+    # lsr_correlate_sep_f32_cpu alone: H x = the correlation with the reversed factors
+    got_blur = host.correlate3d(_t(x), weight_factors=[k[::-1] for k in ks]).numpy()
+    _hold(f"separable correlate {psf_shape} {shape}", got_blur, blur, C_HOST_BLUR * sum(psf_shape))
+
+
+@pytest.mark.parametrize("psf_shape,shape", RL_F64_DENSE)
+def test_dense_twin_one_iteration_per_voxel_against_float64(psf_shape, shape):
+    """``lsr_rl_dense_stats_f32_cpu`` behind ``host.richardson_lucy(separable="never")`` and
+    ``lsr_correlate_dense_f32_cpu`` behind ``host.correlate3d``; 13 x 11 x 5 is past the tuned device kernel's range."""
+    from shrimpy_amd import host
+    from tests import rl_fp64_cases as c
+
+    rng = np.random.default_rng(sum(psf_shape))
+    w = c.taps_nd(psf_shape, rng)
+    x, y = c.make_inputs(shape, psf_shape, sum(shape))
+    got = host.richardson_lucy(_t(y), w, iterations=1, eps=c.EPS, x0=_t(x), separable="never").numpy()
+    blur, _, ref = o.rl_iteration_f64(x, y, psf=w, eps=c.EPS)
+    t = int(np.prod(psf_shape))
+    _hold(f"dense twin {psf_shape} {shape}", got, ref, min(C_HOST_DENSE, F_HOST_DENSE * c.ceiling(t)))
+    got_blur = host.correlate3d(_t(x), np.ascontiguousarray(w[::-1, ::-1, ::-1])).numpy()
+    _hold(f"dense correlate {psf_shape} {shape}", got_blur, blur, C_HOST_BLUR * t)

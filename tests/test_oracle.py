@@ -342,3 +342,91 @@ def test_restated_legs_compose_to_the_trackers_phase_cross_correlation(ref_shape
     np.testing.assert_allclose(corr, n * want, rtol=0, atol=1e-9 * n * np.abs(want).max())
     peak = np.unravel_index(int(np.argmax(np.fft.fftshift(np.abs(corr)))), grid)
     assert tuple(s // 2 - int(p) for s, p in zip(grid, peak)) == o.dt_phase_cross_corr(ref, mov)
+
+
+# ---------------------------------------------------------------- the float64 RL iteration (rl_iteration_f64)
+
+
+def _rl_loops(x, y, w, eps, total_rows=None, first=0):
+    """The iteration as literal loops over the taps of an odd PSF ``w`` (float64), voxel by voxel."""
+    z, yy, xx = x.shape
+    pz, py, px = w.shape
+    cz, cy, cx = pz // 2, py // 2, px // 2
+    total_rows = yy if total_rows is None else total_rows
+
+    def at(v, a, b, c):
+        return v[a, b, c] if 0 <= a < z and 0 <= b < yy and 0 <= c < xx else 0.0
+
+    blur, corr, norm = np.zeros(x.shape), np.zeros(x.shape), np.zeros(x.shape)
+    for i, j, k in np.ndindex(x.shape):
+        for a, b, c in np.ndindex(w.shape):
+            blur[i, j, k] += w[a, b, c] * at(x, i - (a - cz), j - (b - cy), k - (c - cx))       # convolution
+    ratio = y / (blur + np.float64(np.float32(eps)))
+    for i, j, k in np.ndindex(x.shape):
+        for a, b, c in np.ndindex(w.shape):
+            corr[i, j, k] += w[a, b, c] * at(ratio, i + a - cz, j + b - cy, k + c - cx)         # correlation
+            if 0 <= i + a - cz < z and 0 <= first + j + b - cy < total_rows and 0 <= k + c - cx < xx:
+                norm[i, j, k] += w[a, b, c]
+    return blur, ratio, x * corr / norm
+
+
+def _rl_case(shape, psf_shape, seed):
+    rng = np.random.default_rng(seed)
+    ks = [rng.uniform(0.2, 1.0, n).astype(np.float32) for n in psf_shape]           # asymmetric: a flipped stage shows
+    x = rng.uniform(0.5, 50.0, shape).astype(np.float32)
+    y = rng.uniform(0.5, 50.0, shape).astype(np.float32)
+    w = np.einsum("a,b,c->abc", *(k.astype(np.float64) for k in ks))
+    return x, y, ks, w
+
+
+@pytest.mark.parametrize("shape,psf_shape", [((4, 5, 6), (3, 5, 3)), ((3, 4, 7), (5, 3, 7)), ((2, 3, 2), (5, 7, 9)),
+                                             ((1, 1, 5), (1, 1, 3)), ((5, 4, 3), (3, 1, 5))])
+def test_rl_iteration_f64_equals_literal_loops_over_the_taps(shape, psf_shape):
+    """Dense, separable and ky (x) kzx formulations against a triple loop over the taps, to 1e-13 relative: asymmetric
+    taps (so convolution and correlation differ), PSFs larger than the volume on every axis among them."""
+    x, y, ks, w = _rl_case(shape, psf_shape, sum(shape) + sum(psf_shape))
+    want = _rl_loops(x.astype(np.float64), y.astype(np.float64), w, 1e-3)
+    kzx = np.einsum("a,c->ac", ks[0].astype(np.float64), ks[2].astype(np.float64))
+    for kw in (dict(psf=w), dict(factors=ks), dict(factors=(ks[1], kzx))):
+        got = o.rl_iteration_f64(x, y, eps=1e-3, **kw)
+        for g, r, name in zip(got, want, ("blur", "ratio", "x_new")):
+            assert g.dtype == np.float64
+            np.testing.assert_allclose(g, r, rtol=1e-13, atol=0, err_msg=f"{name} {sorted(kw)}")
+    # a flipped stage is a different result on these taps
+    flipped = o.rl_iteration_f64(x, y, psf=w[::-1, ::-1, ::-1], eps=1e-3)
+    if max(psf_shape) > 1 and min(shape) > 1:
+        assert np.abs(flipped[0] - want[0]).max() > 1e-3 * np.abs(want[0]).max()
+
+
+def test_rl_iteration_f64_takes_the_y_norm_of_the_taller_volume():
+    x, y, ks, w = _rl_case((3, 4, 5), (3, 5, 3), 77)
+    for first, total in ((0, 9), (3, 9), (5, 9), (0, 4)):
+        want = _rl_loops(x.astype(np.float64), y.astype(np.float64), w, 1e-6, total, first)
+        for kw in (dict(psf=w), dict(factors=ks)):
+            got = o.rl_iteration_f64(x, y, y_window=(first, total), **kw)
+            np.testing.assert_allclose(got[2], want[2], rtol=1e-13, atol=0)
+    # an interior slab has the full y sum everywhere; the first slab keeps the top border only
+    mid = o.rl_iteration_f64(x, y, factors=ks, y_window=(3, 10))[2]
+    assert not np.allclose(mid, o.rl_iteration_f64(x, y, factors=ks)[2], rtol=1e-6)
+
+
+def test_rl_iteration_f64_takes_eps_as_the_float32_the_entries_receive():
+    x, y, ks, w = _rl_case((3, 4, 5), (3, 3, 3), 5)
+    x[:] = 0                                                       # ratio = y / eps exactly
+    _, ratio, x_new = o.rl_iteration_f64(x, y, factors=ks, eps=1e-6)
+    np.testing.assert_array_equal(ratio, y.astype(np.float64) / np.float64(np.float32(1e-6)))
+    assert not x_new.any()
+
+
+def test_rl_iteration_f64_against_the_float32_oracle_loop():
+    """``richardson_lucy(..., iterations=1)`` rounds blur, ratio, correlation and norm to float32: it stays within a
+    few float32 roundings of the float64 iteration on positive data (and an even PSF axis is padded the same way)."""
+    rng = np.random.default_rng(9)
+    psf = rng.uniform(0.2, 1.0, (5, 4, 3)).astype(np.float32)
+    psf /= psf.sum()
+    x = rng.uniform(1.0, 100.0, (9, 12, 17)).astype(np.float32)
+    y = rng.uniform(1.0, 100.0, (9, 12, 17)).astype(np.float32)
+    want = o.rl_iteration_f64(x, y, psf=psf)[2]
+    got = o.richardson_lucy(y, psf, iterations=1, x0=x).astype(np.float64)
+    assert np.abs(got - want).max() > 0                                # (it does round)
+    assert (np.abs(got - want) <= 8 * 2.0 ** -24 * want).all()
