@@ -485,6 +485,26 @@ int lsr_correlate_z_f32(const float* in, int64_t in_pitch, int64_t in_plane, con
                         const float* nx, double* stats, lsr_stream_t stream);
 
 /*
+ * Total-variation factor of a regularised Richardson-Lucy iteration (RL-TV, Dey et al. 2006; csrc/rl_tv.hip):
+ *
+ *   out(r) = v(r) / (1 - lambda * div(r)),   div(r) = sum_a p_a(r) - p_a(r - e_a),   p_a = D_a u / n,
+ *   D_a u(r) = u(r + e_a) - u(r) (0 where r + e_a is outside),   n = sqrt(D_z^2 + D_y^2 + D_x^2 + tv_eps^2),
+ *   p_a(r - e_a) := 0 where r - e_a is outside
+ *
+ * with u = x_k (what the RL launches of the iteration read) and v = the plain RL update they wrote.  The borders are
+ * those of (Z, Y, X): nothing outside the logical volume is read, so u / v may be the logical origin of zero-haloed
+ * padded volumes and `out` a dense tensor.  Pitches and plane strides in elements (rows may be padded).  `out` may alias
+ * v (same pointer and strides) and must not overlap u.  lambda in [0, 1/6) (|div| <= 6: the denominator stays
+ * positive), tv_eps > 0 with tv_eps^2 a normal float32; anything else is LSR_E_ARG.  Where u is locally constant
+ * out == v bit for bit; v == 0 gives an exact 0.  stats2 (DEVICE memory, or NULL): the launch ADDS
+ * change = sum |out - u| and total = sum out to stats2[0], stats2[1] -- the reduction scheme of the RL epilogues (below),
+ * the caller zeroes them.  A z-marching LDS stencil, 12 algorithmic bytes per voxel.
+ */
+int lsr_rl_tv_scale_f32(const float* u, int64_t u_pitch, int64_t u_plane, const float* v, int64_t v_pitch,
+                        int64_t v_plane, float* out, int64_t o_pitch, int64_t o_plane, int64_t Z, int64_t Y, int64_t X,
+                        float lambda, float tv_eps, double* stats2, lsr_stream_t stream);
+
+/*
  * Richardson-Lucy reduction scalars (the north-star's "wavefront reductions for the ratio / normalisation").
  * Every entry that finishes an RL iteration has a `_stats` form with one more argument, `double* stats` (DEVICE memory;
  * host memory for the *_cpu twins); NULL = the plain entry, the same kernels, no cost.  Per iteration i three sums over
@@ -708,6 +728,10 @@ int lsr_rl_dense_stats_f32_cpu(const float* y, float* x, float* ratio, int64_t Z
                                const float* psf, const float* psf_flipped, int pz, int py, int px,
                                const double* norm_table, int iters, float eps, double* stats,
                                lsr_stream_t stream);
+/* ... of the RL-TV factor (csrc/rl_tv.hip: the same inline arithmetic, the kernel's bits; no stream; stats2 HOST memory) */
+int lsr_rl_tv_scale_f32_cpu(const float* u, int64_t u_pitch, int64_t u_plane, const float* v, int64_t v_pitch,
+                            int64_t v_plane, float* out, int64_t o_pitch, int64_t o_plane, int64_t Z, int64_t Y,
+                            int64_t X, float lambda, float tv_eps, double* stats2);
 int lsr_flatfield_pattern_f32_cpu(const float* in, int64_t Z, int64_t Y, int64_t X, float* pattern,
                                   float* mean_out, void* scratch /* unused */, lsr_stream_t stream);
 int lsr_flatfield_pattern_u16_cpu(const uint16_t* in, int64_t Z, int64_t Y, int64_t X, float* pattern,

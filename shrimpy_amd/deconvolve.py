@@ -14,6 +14,11 @@ per launch.  Rank-1 (separable) PSFs run ``pz+py+px`` FMAs per voxel and are HBM
 PSFs run ``pz*py*px`` FMAs per voxel and are fp32-VALU-bound.  float32 throughout; agreement
 with the float64-accumulating scipy loop is stated in ``tests/test_gpu_parity.py``.
 CPU tensors (no HIP device in play) run the native host twins of the same launches (``shrimpy_amd/host.py``).
+
+``tv_lambda > 0`` adds total-variation regularisation in the multiplicative form of Dey et al. 2006 (RL-TV): the
+iteration's result is divided voxel by voxel by ``1 - tv_lambda * div(grad x_k / |grad x_k|)`` (forward differences,
+backward divergence, the volume's own borders; ``csrc/rl_tv.hip``, one more streaming launch of 12 bytes per voxel per
+iteration behind the unchanged RL launches).  ``tv_lambda = 0`` (the default) is the plain iteration, launch for launch.
 """
 
 from __future__ import annotations
@@ -27,7 +32,21 @@ import numpy as np
 from . import _lib
 
 __all__ = ["richardson_lucy", "RichardsonLucyPlan", "RLStats", "factor_psf", "correlate3d", "prepare_psf",
-           "padded_shape", "PaddedVolume", "make_plan"]
+           "padded_shape", "PaddedVolume", "make_plan", "check_tv", "TV_LAMBDA_LIMIT"]
+
+TV_LAMBDA_LIMIT = 1.0 / 6.0     # |div(grad x / |grad x|)| <= 6: below this the RL-TV denominator is provably positive
+
+
+def check_tv(tv_lambda, tv_eps) -> tuple[float, float]:
+    """``(tv_lambda, tv_eps)`` as floats, or ``ValueError``: ``0 <= tv_lambda < 1/6`` (also as the float32 the kernels
+    take), ``tv_eps > 0`` and finite.  NaN fails both."""
+    lam, te = float(tv_lambda), float(tv_eps)
+    if not (0.0 <= lam < TV_LAMBDA_LIMIT and np.float32(lam) < np.float32(1.0) / np.float32(6.0)):
+        raise ValueError(f"tv_lambda must be in [0, 1/6), got {tv_lambda!r}")
+    if not (te > 0.0 and np.isfinite(te)):
+        raise ValueError(f"tv_eps must be a finite number > 0, got {tv_eps!r}")
+    return lam, te
+
 
 MAX_TAPS = 15
 MAX_Z_TAPS = 31     # separable PSFs only: the z factor runs as its own launch (csrc/correlate_z.hip)
@@ -179,7 +198,11 @@ class RLStats:
 
     ``flux[i]   = sum x_i * H^T(ratio_i) = sum x_{i+1} * H^T 1`` (what the update conserves; ``-> sum y`` as ``eps -> 0``),
     ``change[i] = sum |x_{i+1} - x_i|``, ``total[i] = sum x_{i+1}``; ``rel_change = change / total`` is what ``tol`` tests.
-    ``iterations`` = launches that ran (``< `` the requested count when ``tol`` stopped the loop)."""
+    ``iterations`` = launches that ran (``< `` the requested count when ``tol`` stopped the loop).
+
+    With ``tv_lambda > 0`` the iterate is the RL update divided by the total-variation factor: ``change`` and ``total``
+    are then summed by the TV launch over the iterate the caller gets (``lsr_rl_tv_scale_f32``), and ``tol`` tests
+    those.  ``flux`` has no counterpart there: it stays the RL launch's value, i.e. the flux BEFORE the TV factor."""
 
     flux: np.ndarray
     change: np.ndarray
@@ -353,6 +376,7 @@ class RichardsonLucyPlan:
         self._x_pad = None   # separable path: zero-haloed working volumes
         self._ratio_pad = None
         self._y_pad = None   # fused path: padded copy of a dense y
+        self._tv_prev = None  # RL-TV on the paths that update x in place: x_k, kept for the TV launch
         # one launch per iteration (rl_fused_sep.hip) where the PSF fits its specialisations
         self.fused = bool(self._psf.separable and not self._long_z and self._fused_mode in ("auto", "always")
                           and _lib.call_value("lsr_rl_sep_fused_supported", *self._psf.shape)
@@ -568,7 +592,7 @@ class RichardsonLucyPlan:
 
     def release(self) -> None:
         """Drop the scratch volumes."""
-        self._ratio = self._x_pad = self._ratio_pad = self._y_pad = self._t_pad = self._t_dense = None
+        self._ratio = self._x_pad = self._ratio_pad = self._y_pad = self._t_pad = self._t_dense = self._tv_prev = None
 
     # ------------------------------------------------------------------------------------------ the loop
     def _launch(self, st, it0: int, n: int, x_out, stats) -> None:
@@ -630,7 +654,7 @@ class RichardsonLucyPlan:
         return x_pad.view
 
     def __call__(self, y, iterations: int = 20, eps: float = 1e-6, x0=None, out=None, events=None, *,
-                 stats: bool = False, tol: float | None = None):
+                 stats: bool = False, tol: float | None = None, tv_lambda: float = 0.0, tv_eps: float = 1e-6):
         """Run RL.  ``events`` = optional ``(start, end)`` torch events recorded on the launch
         stream right around the kernel launches (``iterations`` fused launches, or
         ``2 * iterations`` ratio / update launches) -- what ``bench.py`` times.
@@ -640,9 +664,14 @@ class RichardsonLucyPlan:
         ``plan.stats_device``, one row per iteration).  ``tol``: stop as soon as the relative change
         ``sum|x_new - x| / sum x_new`` of an iteration falls below it.  The scalars of iteration i are read back while
         iteration i + 1 runs, so the GPU never waits for the host; the estimate returned is therefore the one
-        iteration past the first that met ``tol`` (``plan.last_stats.iterations`` says how many ran)."""
+        iteration past the first that met ``tol`` (``plan.last_stats.iterations`` says how many ran).
+
+        ``tv_lambda`` in ``(0, 1/6)``: RL-TV -- one RL iteration at a time, each followed by the total-variation launch
+        (``lsr_rl_tv_scale_f32``) on the same stream; ``change`` / ``total`` and ``tol`` then describe the regularised
+        iterate (:class:`RLStats`).  ``0`` (default): the plain run, launch for launch."""
         import torch
 
+        tv_lambda, tv_eps = check_tv(tv_lambda, tv_eps)
         y_padded = None
         if isinstance(y, PaddedVolume):  # e.g. written in place by the deskew kernel
             if not (self._psf.separable or self._psf.taps is not None or self._ysep is not None):
@@ -723,7 +752,16 @@ class RichardsonLucyPlan:
                 dev_stats = torch.zeros((iterations, 3), dtype=torch.float64, device=self.device)
             if events:
                 events[0].record()
-            if tol is None:
+            if tv_lambda > 0:
+                # x_0 as the first TV launch reads it: y itself (dense or padded) or the caller's x0 -- unless that is
+                # also the output tensor, which the launch may not read its neighbours from
+                u0 = None
+                if x0 is None:
+                    u0 = st["y"]
+                elif init.data_ptr() != x.data_ptr():
+                    u0 = (init.data_ptr(), self.shape[2], self.shape[1] * self.shape[2])
+                done, stopped, dev_stats = self._run_tv(st, iterations, tol, dev_stats, x, tv_lambda, tv_eps, u0)
+            elif tol is None:
                 self._launch(st, 0, iterations, None if st["kind"] == "generic" else x, dev_stats)
                 done, stopped = iterations, False
             else:
@@ -737,6 +775,78 @@ class RichardsonLucyPlan:
                 self.last_stats = RLStats.from_array(dev_stats.cpu().numpy(), done, stopped)
         _lib.mark_written(x)
         return x
+
+    def _tv_iteration(self, st, it: int, x_out, dev_stats, tv_stats, lam: float, tv_eps: float, u0) -> None:
+        """Iteration ``it`` of an RL-TV run: the plain iteration's launches, then ``lsr_rl_tv_scale_f32`` with ``u`` =
+        the estimate they read and ``v`` = the one they wrote, in place -- or into the dense ``x_out``.  The fused kinds
+        ping-pong between two volumes, so both are at hand; the kinds that update x in place get ``x_k`` copied into a
+        scratch volume first (``u0``, when not ``None``, is x_0 where the caller left it: no copy for iteration 0)."""
+        import torch
+
+        z, yy, xx = self.shape
+        dense = (xx, yy * xx)
+        kind = st["kind"]
+        if kind in ("fused", "fused-ysep"):
+            vols = self._scratch()
+            src, dst = vols[it & 1], vols[(it + 1) & 1]
+            u = u0 if (it == 0 and st["from_y"]) else (src.logical_ptr(), src.pitch, src.plane)
+            v = (dst.logical_ptr(), dst.pitch, dst.plane)
+        else:
+            if kind == "generic":
+                cur, v = st["x"], (st["x"].data_ptr(),) + dense
+            else:
+                x_pad = self._scratch()[0]
+                cur, v = x_pad.view, (x_pad.logical_ptr(), x_pad.pitch, x_pad.plane)
+            if it == 0 and u0 is not None:
+                u = u0
+            else:
+                if self._tv_prev is None:
+                    self._tv_prev = torch.empty(self.shape, dtype=torch.float32, device=self.device)
+                # (iteration 0 of the ysep / long-z kinds fills the working volume inside their own loop)
+                self._tv_prev.copy_(st["init"] if it == 0 else cur)
+                u = (self._tv_prev.data_ptr(),) + dense
+        self._launch(st, it, 1, None, dev_stats)
+        out = v if x_out is None else (x_out.data_ptr(),) + dense
+        _lib.call("lsr_rl_tv_scale_f32", *u, *v, *out, z, yy, xx, ctypes.c_float(lam), ctypes.c_float(tv_eps),
+                  None if tv_stats is None else tv_stats.data_ptr() + 16 * it, st["stream"])
+
+    def _run_tv(self, st, iterations: int, tol, dev_stats, x, lam: float, tv_eps: float, u0):
+        """The RL-TV loop.  Returns (iterations run, stopped early, the (iterations, 3) scalars the caller sees: flux
+        from the RL launches, change and total from the TV launches -- or ``None``).  ``tol`` reads the TV launch's
+        scalars one iteration late, as ``_run_to_tolerance`` does the RL launch's."""
+        import torch
+
+        tv_stats = None if dev_stats is None else torch.zeros((iterations, 2), dtype=torch.float64, device=self.device)
+        done, stopped = 0, False
+        if tol is None:
+            for it in range(iterations):
+                last = it + 1 == iterations and st["kind"] != "generic"
+                self._tv_iteration(st, it, x if last else None, dev_stats, tv_stats, lam, tv_eps, u0)
+            done = iterations
+        else:
+            host = torch.empty((iterations, 2), dtype=torch.float64).pin_memory()
+            arrived = [torch.cuda.Event() for _ in range(iterations)]
+
+            def met(i):
+                arrived[i].synchronize()
+                change, total = float(host[i, 0]), float(host[i, 1])
+                return total > 0 and change <= tol * total or total == 0
+
+            for it in range(iterations):
+                self._tv_iteration(st, it, None, dev_stats, tv_stats, lam, tv_eps, u0)
+                host[it].copy_(tv_stats[it], non_blocking=True)
+                arrived[it].record()
+                done = it + 1
+                if it >= 1 and met(it - 1):
+                    stopped = True
+                    break
+            if not stopped:
+                stopped = bool(met(iterations - 1))
+            if st["kind"] != "generic":
+                x.copy_(self._result_view(st, done))
+        if dev_stats is not None:
+            dev_stats = torch.cat((dev_stats[:, :1], tv_stats), dim=1)
+        return done, stopped, dev_stats
 
     def _run_to_tolerance(self, st, iterations: int, tol: float, dev_stats):
         """One launch group per iteration; iteration i's scalars travel to pinned host memory behind it and are looked at
@@ -808,7 +918,8 @@ def make_plan(shape_zyx, psf, device, *, separable: str = "auto", separable_rtol
 
 def richardson_lucy(y, psf=None, iterations: int = 20, eps: float = 1e-6, x0=None, *,
                     separable: str = "auto", separable_rtol: float = 1e-6, psf_factors=None,
-                    tol: float | None = None, return_stats: bool = False, method: str = "auto"):
+                    tol: float | None = None, return_stats: bool = False, method: str = "auto",
+                    tv_lambda: float = 0.0, tv_eps: float = 1e-6):
     """Richardson-Lucy deconvolution of a (Z, Y, X) float32 device tensor; returns a new tensor.
 
     ``psf`` is used as given (normalise it to sum 1 for flux conservation).  ``x0`` defaults to
@@ -822,8 +933,15 @@ def richardson_lucy(y, psf=None, iterations: int = 20, eps: float = 1e-6, x0=Non
     ``tol``: stop before ``iterations`` once an iteration's relative change ``sum|x_new - x| / sum x_new`` is below
     it (the kernels sum both in their epilogues; see :class:`RLStats`).  ``return_stats=True`` returns
     ``(estimate, RLStats)`` -- flux, change and total per iteration that ran.
+
+    ``tv_lambda`` in ``[0, 1/6)``: total-variation regularisation (RL-TV, Dey et al. 2006): every iteration's result is
+    divided by ``1 - tv_lambda * div(grad x / |grad x|)`` with the gradient norm floored by ``tv_eps``; typical values
+    are 0.001 .. 0.05.  ``0`` (default) is plain RL.
     """
     import torch
+
+    tv_lambda, tv_eps = check_tv(tv_lambda, tv_eps)
+    tv = dict(tv_lambda=tv_lambda, tv_eps=tv_eps) if tv_lambda > 0 else {}
 
     if not isinstance(y, torch.Tensor):
         raise TypeError(f"y must be a torch.Tensor, got {type(y).__name__}")
@@ -836,10 +954,10 @@ def richardson_lucy(y, psf=None, iterations: int = 20, eps: float = 1e-6, x0=Non
         from . import host
 
         return host.richardson_lucy(y, psf, iterations, eps, x0, separable=separable, separable_rtol=separable_rtol,
-                                    psf_factors=psf_factors, tol=tol, return_stats=return_stats)
+                                    psf_factors=psf_factors, tol=tol, return_stats=return_stats, **tv)
     plan = make_plan(tuple(y.shape), psf, y.device, separable=separable, separable_rtol=separable_rtol,
                      psf_factors=psf_factors, method=method)
-    x = plan(y, iterations=iterations, eps=eps, x0=x0, stats=return_stats, tol=tol)
+    x = plan(y, iterations=iterations, eps=eps, x0=x0, stats=return_stats, tol=tol, **tv)
     return (x, plan.last_stats) if return_stats else x
 
 

@@ -205,12 +205,15 @@ class FftRichardsonLucyPlan:
             self._iteration(x, y, eps, stats_row, first)
 
     def __call__(self, y, iterations: int = 20, eps: float = 1e-6, x0=None, out=None, events=None, *,
-                 stats: bool = False, tol: float | None = None):
+                 stats: bool = False, tol: float | None = None, tv_lambda: float = 0.0, tv_eps: float = 1e-6):
         """Run RL; arguments as :meth:`shrimpy_amd.deconvolve.RichardsonLucyPlan.__call__`.  ``events``: ``(start, end)``
-        torch events recorded right around the launches (ten per iteration)."""
+        torch events recorded right around the launches (ten per iteration).  ``tv_lambda > 0``: this route updates the
+        estimate in place, so x_k is copied aside before each iteration and the TV launch follows it."""
         import torch
 
-        from .deconvolve import RLStats
+        from .deconvolve import RLStats, check_tv
+
+        tv_lambda, tv_eps = check_tv(tv_lambda, tv_eps)
 
         y = _lib.require_device_f32(y, "y")
         if tuple(y.shape) != self.shape or y.device != self.device:
@@ -233,6 +236,12 @@ class FftRichardsonLucyPlan:
         if tuple(init.shape) != self.shape:
             raise ValueError(f"x0 must be {self.shape}, got {tuple(init.shape)}")
         want_stats = bool(stats) or tol is not None
+        self._tv = None
+        if tv_lambda > 0 and iterations > 0:
+            # x_0 where the caller left it (no copy for the first iteration) unless that is the output tensor itself
+            self._tv = dict(lam=tv_lambda, eps=tv_eps, u0=None if out.data_ptr() == init.data_ptr() else init,
+                            prev=torch.empty(self.shape, dtype=torch.float32, device=self.device),
+                            stats=torch.zeros((iterations, 2), dtype=torch.float64, device=self.device) if want_stats else None)
         with torch.cuda.device(self.device):
             if out.data_ptr() != init.data_ptr():
                 out.copy_(init)
@@ -242,16 +251,31 @@ class FftRichardsonLucyPlan:
             done, stopped = iterations, False
             if tol is None:
                 for it in range(iterations):
-                    self._step(out, y, float(eps), None if dev_stats is None else dev_stats[it], it == 0)
+                    self._step_tv(out, y, float(eps), None if dev_stats is None else dev_stats[it], it)
             else:
                 done, stopped = self._run_to_tolerance(out, y, float(eps), iterations, float(tol), dev_stats)
             if events:
                 events[1].record()
             if want_stats:
+                if self._tv is not None:     # flux from the RL epilogue, change and total from the TV launch
+                    dev_stats = torch.cat((dev_stats[:, :1], self._tv["stats"]), dim=1)
                 self.stats_device = dev_stats
                 self.last_stats = RLStats.from_array(dev_stats.cpu().numpy(), done, stopped)
+        self._tv = None
         _lib.mark_written(out)
         return out
+
+    def _step_tv(self, x, y, eps, stats_row, it: int) -> None:
+        """Iteration ``it``; with ``tv_lambda > 0`` followed by ``lsr_rl_tv_scale_f32`` (u = x_k, v = out = x in place)."""
+        tv = self._tv
+        if tv is None:
+            return self._step(x, y, eps, stats_row, it == 0)
+        z, yy, xx = self.shape
+        u = tv["u0"] if it == 0 and tv["u0"] is not None else tv["prev"].copy_(x)
+        self._step(x, y, eps, stats_row, it == 0)
+        _lib.call("lsr_rl_tv_scale_f32", u.data_ptr(), xx, yy * xx, x.data_ptr(), xx, yy * xx, x.data_ptr(), xx, yy * xx,
+                  z, yy, xx, ctypes.c_float(tv["lam"]), ctypes.c_float(tv["eps"]),
+                  None if tv["stats"] is None else tv["stats"].data_ptr() + 16 * it, _lib.stream_ptr(self.device))
 
     def _run_to_tolerance(self, x, y, eps, iterations, tol, dev_stats):
         """Iteration i's scalars travel to pinned host memory behind it and are looked at after iteration i + 1 has
@@ -270,8 +294,11 @@ class FftRichardsonLucyPlan:
 
         done = 0
         for it in range(iterations):
-            self._step(x, y, eps, dev_stats[it], it == 0)
-            host[it].copy_(dev_stats[it], non_blocking=True)
+            self._step_tv(x, y, eps, dev_stats[it], it)
+            if self._tv is None:
+                host[it].copy_(dev_stats[it], non_blocking=True)
+            else:      # RL-TV: the change and total that are tested are the TV launch's
+                host[it, 1:].copy_(self._tv["stats"][it], non_blocking=True)
             arrived[it].record()
             done = it + 1
             if it >= 1 and met(it - 1):

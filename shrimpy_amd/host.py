@@ -175,15 +175,18 @@ def correlate3d(volume, weights=None, weight_factors=None):
 
 def richardson_lucy(y, psf=None, iterations: int = 20, eps: float = 1e-6, x0=None, *, separable: str = "auto",
                     separable_rtol: float = 1e-6, psf_factors=None, tol: float | None = None,
-                    return_stats: bool = False):
+                    return_stats: bool = False, tv_lambda: float = 0.0, tv_eps: float = 1e-6):
     """``deconvolve.richardson_lucy`` for a CPU tensor: ``x <- x * H^T(y / (H x + eps)) / H^T 1`` with the two
     correlations and their epilogues as the host twins of the device launches (rank-1 PSFs run the
     separable form, others the dense one).  ``tol`` / ``return_stats``: the iteration scalars of
     ``deconvolve.RLStats``, summed by the twins' UPDATE pass; the loop stops after the first iteration whose relative
-    change is below ``tol``."""
+    change is below ``tol``.  ``tv_lambda > 0``: every iteration is followed by the twin of the total-variation launch
+    (``lsr_rl_tv_scale_f32_cpu``); ``change`` / ``total`` and ``tol`` are then those of the regularised iterate."""
     import torch
 
-    from .deconvolve import MAX_TAPS, RLStats, _axis_norm, _prefix_table, factor_psf, prepare_psf
+    from .deconvolve import MAX_TAPS, RLStats, _axis_norm, _prefix_table, check_tv, factor_psf, prepare_psf
+
+    tv_lambda, tv_eps = check_tv(tv_lambda, tv_eps)
 
     if tol is not None and not (tol >= 0 and np.isfinite(tol)):
         raise ValueError("tol must be a finite number >= 0")
@@ -221,10 +224,24 @@ def richardson_lucy(y, psf=None, iterations: int = 20, eps: float = 1e-6, x0=Non
     if iterations == 0:
         return (x, RLStats.from_array(np.zeros((0, 3)), 0)) if return_stats else x
     stats = np.zeros((iterations, 3), dtype=np.float64) if want else None
+    tv_stats = np.zeros((iterations, 2), dtype=np.float64) if want and tv_lambda > 0 else None
 
     def met(i):
+        if tv_stats is not None:
+            return tv_stats[i, 1] == 0 or tv_stats[i, 0] <= tol * tv_stats[i, 1]
         return stats[i, 2] == 0 or stats[i, 1] <= tol * stats[i, 2]
+
+    def report(done, stopped):
+        if tv_stats is not None:      # flux from the RL update, change and total from the TV pass
+            stats[:, 1:] = tv_stats
+        return RLStats.from_array(stats, done, stopped)
     z, yy, xx = (int(v) for v in y.shape)
+
+    def tv_scale(u, v, it):
+        """``v <- v / (1 - tv_lambda * div(grad u / |grad u|))`` in place."""
+        _lib.call("lsr_rl_tv_scale_f32_cpu", u.data_ptr(), xx, yy * xx, v.data_ptr(), xx, yy * xx, v.data_ptr(), xx, yy * xx,
+                  z, yy, xx, ctypes.c_float(tv_lambda), ctypes.c_float(tv_eps),
+                  None if tv_stats is None else tv_stats[it].ctypes.data)
     ratio, nxt = torch.empty_like(y), torch.empty_like(y)
     e = ctypes.c_float(eps)
     _threads()
@@ -246,22 +263,27 @@ def richardson_lucy(y, psf=None, iterations: int = 20, eps: float = 1e-6, x0=Non
         # are looked at after iteration i + 1 has run, so the estimate returned is the one iteration PAST the first that
         # met tol -- the same iterate, and the same RLStats.iterations, whichever device the tensor lives on
         done, stopped = 0, False
-        step = iterations if tol is None else 1
+        step = iterations if tol is None and tv_lambda == 0 else 1
         while done < iterations:
+            prev = x.clone() if tv_lambda > 0 else None
             _lib.call("lsr_rl_dense_stats_f32_cpu", y.data_ptr(), x.data_ptr(), ratio.data_ptr(), z, yy, xx, k.ctypes.data,
                       kf.ctypes.data, w.shape[0], w.shape[1], w.shape[2], table.ctypes.data, step, e,
                       None if stats is None else stats[done:].ctypes.data, None)
+            if tv_lambda > 0:
+                tv_scale(prev, x, done)
             done += step
             if tol is not None and done >= 2 and met(done - 2):
                 stopped = True
                 break
         if tol is not None and not stopped:
             stopped = bool(met(done - 1))
-        return (x, RLStats.from_array(stats, done, stopped)) if return_stats else x
+        return (x, report(done, stopped)) if return_stats else x
     done, stopped = 0, False
     for it in range(iterations):
         corr(x, ratio, y, kf, _lib.EPI_RATIO)       # ratio = y / (H x + eps): H = correlation with the flipped taps
         corr(ratio, nxt, x, k, _lib.EPI_UPDATE, None if stats is None else stats[it])     # x <- x * H^T ratio / H^T 1
+        if tv_lambda > 0:
+            tv_scale(x, nxt, it)
         x, nxt = nxt, x
         done = it + 1
         if tol is not None and it >= 1 and met(it - 1):     # (one iteration past the first that met tol: see above)
@@ -269,4 +291,4 @@ def richardson_lucy(y, psf=None, iterations: int = 20, eps: float = 1e-6, x0=Non
             break
     if tol is not None and not stopped:
         stopped = bool(met(done - 1))
-    return (x, RLStats.from_array(stats, done, stopped)) if return_stats else x
+    return (x, report(done, stopped)) if return_stats else x

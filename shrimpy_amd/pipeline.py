@@ -202,12 +202,14 @@ class VolumeReconstructor:
                                              mode=r.mode, cval=r.cval, out=target)
         if self._plan is not None:
             dec = self.settings.deconvolution
-            vol = self._plan(vol, iterations=dec.iterations, eps=dec.eps, events=rl_events)
+            tv = dict(tv_lambda=dec.tv_lambda, tv_eps=dec.tv_eps) if dec.tv_lambda > 0 else {}
+            vol = self._plan(vol, iterations=dec.iterations, eps=dec.eps, events=rl_events, **tv)
         elif self._host_rl is not None:
             from .deconvolve import richardson_lucy
 
             dec = self.settings.deconvolution
-            vol = richardson_lucy(vol, iterations=dec.iterations, eps=dec.eps, **self._host_rl)
+            tv = dict(tv_lambda=dec.tv_lambda, tv_eps=dec.tv_eps) if dec.tv_lambda > 0 else {}
+            vol = richardson_lucy(vol, iterations=dec.iterations, eps=dec.eps, **self._host_rl, **tv)
         return vol
 
 

@@ -25,6 +25,7 @@ import yaml
 from pydantic import (
     BaseModel,
     ConfigDict,
+    NonNegativeFloat,
     NonNegativeInt,
     PositiveFloat,
     PositiveInt,
@@ -186,10 +187,16 @@ class DeconvolveSettings(_StrictModel):
     the PSF to ``separable_rtol`` of its peak: the default only admits PSFs that factor exactly; a
     measured PSF can be run in a factored form by raising it (the PSF used is then the factored
     one).  ``"force"`` insists on three 1-D kernels, ``"never"`` on the dense stencil.
+
+    ``tv_lambda`` in ``[0, 1/6)`` turns on total-variation regularisation (RL-TV, Dey et al. 2006: every iteration's
+    result divided by ``1 - tv_lambda * div(grad x / |grad x|)``, the gradient norm floored by ``tv_eps``); typical
+    values are 0.001 .. 0.05, ``0`` (the default) is plain Richardson-Lucy.
     """
 
     iterations: NonNegativeInt = 20
     eps: PositiveFloat = 1e-6
+    tv_lambda: NonNegativeFloat = 0.0
+    tv_eps: PositiveFloat = 1e-6
     psf_path: Optional[str] = None
     psf_shape_zyx: Optional[tuple[PositiveInt, PositiveInt, PositiveInt]] = None
     gaussian_sigma_zyx: tuple[PositiveFloat, PositiveFloat, PositiveFloat] = (2.0, 1.2, 1.2)
@@ -199,6 +206,13 @@ class DeconvolveSettings(_StrictModel):
     # "auto": stencil kernels where a tuned one takes the PSF, the Fourier-domain iteration for dense PSFs beyond
     # them (deconvolve.make_plan); "direct" / "fft" insist on one
     method: Literal["auto", "direct", "fft"] = "auto"
+
+    @field_validator("tv_lambda")
+    @classmethod
+    def _tv_lambda_below_a_sixth(cls, v):
+        from .deconvolve import check_tv
+
+        return check_tv(v, 1.0)[0]
 
     @field_validator("gaussian_shape_zyx")
     @classmethod

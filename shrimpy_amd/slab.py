@@ -103,10 +103,18 @@ def _neighbour_halo(slab: Slab, direction: int) -> int:
     return slab.own0 - slab.ext0 if direction < 0 else slab.ext1 - slab.own1
 
 
-def run_slabs_in_process(slab_rls: "list[SlabRichardsonLucy]", iterations: int = 20, eps: float = 1e-6):
+def _refuse_tv(tv_lambda) -> None:
+    if tv_lambda:
+        raise ValueError("tv_lambda > 0 is not available on the slab split: the TV factor needs one more halo row of x_k "
+                         "per side than the RL exchange provides")
+
+
+def run_slabs_in_process(slab_rls: "list[SlabRichardsonLucy]", iterations: int = 20, eps: float = 1e-6, *,
+                         tv_lambda: float = 0.0):
     """All ranks of a split in ONE process, in lockstep, halos copied directly between the slabs --
     the reference behaviour of the distributed run (used by the parity tests, which have one GPU).
-    Returns the owned rows of every slab, in rank order."""
+    Returns the owned rows of every slab, in rank order.  ``tv_lambda > 0`` (RL-TV) is refused here."""
+    _refuse_tv(tv_lambda)
     src = [s._x[0] for s in slab_rls]
     dst = [s._x[1] for s in slab_rls]
     for s, v in zip(slab_rls, src):
@@ -145,11 +153,12 @@ class SlabRichardsonLucy:
         self.y_pad = self.plan.new_padded_input()      # the caller (or deskew_slab) fills .view
         self._x = [PaddedVolume(self.plan.shape, self.plan._psf.shape, device) for _ in range(2)]
 
-    def run(self, iterations: int = 20, eps: float = 1e-6, exchange=None):
+    def run(self, iterations: int = 20, eps: float = 1e-6, exchange=None, *, tv_lambda: float = 0.0):
         """RL from ``x0 = y`` on the extended slab; returns the OWNED rows ``(Z, own rows, X)`` (a view).
 
         ``exchange(view, slab)`` refreshes halo rows after each iteration (default:
-        :func:`exchange_halos` over the default process group)."""
+        :func:`exchange_halos` over the default process group).  ``tv_lambda > 0`` (RL-TV) is refused here."""
+        _refuse_tv(tv_lambda)
         if exchange is None:
             exchange = exchange_halos
         src, dst = self._x

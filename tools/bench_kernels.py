@@ -42,6 +42,8 @@ def main():
     ap.add_argument("--psf-sweep", action="store_true", help="only: ms per RL iteration over separable PSF sizes")
     ap.add_argument("--rl-fft", action="store_true", help="only: ms per RL iteration in the Fourier domain (dense PSFs "
                     "beyond the stencil kernels) next to the generic / dense stencils where they exist")
+    ap.add_argument("--rl-tv", action="store_true", help="only: ms per total-variation launch and per RL-TV iteration (fused "
+                    "separable 9x7x7) beside the plain fused iteration, on --rl-grid")
     ap.add_argument("--psf-sweep-wide", action="store_true", help="with --psf-sweep: every pz for in-plane extents 9-15")
     args = ap.parse_args()
 
@@ -58,6 +60,9 @@ def main():
 
     if args.rl_fft:
         _rl_fft(args, torch, dev, g, tuple(int(v) for v in args.rl_grid.split(",")))
+        return
+    if args.rl_tv:
+        _rl_tv(args, torch, dev, g, bench, RichardsonLucyPlan, tuple(int(v) for v in args.rl_grid.split(",")))
         return
     if args.psf_sweep:
         _psf_sweep(args, torch, dev, g, RichardsonLucyPlan, tuple(int(v) for v in args.rl_grid.split(",")))
@@ -279,6 +284,43 @@ def _psf_sweep(args, torch, dev, g, RichardsonLucyPlan, oshape):
                               "frac_of_8TBps": 12.0 * y.numel() / ms / 1e6 / 8000}), flush=True)
             if fused == "auto" and path != "fused":
                 break      # (the two-launch form was what ran)
+
+
+def _rl_tv(args, torch, dev, g, bench, RichardsonLucyPlan, oshape):
+    """The total-variation launch of RL-TV (csrc/rl_tv.hip) alone -- between the plan's padded working volumes, in place,
+    as an iteration runs it -- and an RL-TV iteration beside the plain fused one, all in this run (12 algorithmic bytes per
+    voxel for the TV launch and for the fused RL launch alike)."""
+    import ctypes
+
+    from shrimpy_amd import _lib
+    from shrimpy_amd.pipeline import gaussian_psf_factors
+
+    y = torch.poisson(torch.full(oshape, 100.0, device=dev), generator=g)
+    plan = RichardsonLucyPlan(oshape, None, dev, psf_factors=gaussian_psf_factors((9, 7, 7), (2.0, 1.2, 1.2)))
+    out = torch.empty_like(y)
+    plan(y, iterations=2, out=out)                                   # fills both working volumes
+    a, b = plan._scratch()
+    z, yy, xx = oshape
+    n = y.numel()
+    for label, stats in (("TV launch", None), ("TV launch with the reduction scalars", torch.zeros(2, dtype=torch.float64, device=dev))):
+        def launch():
+            _lib.call("lsr_rl_tv_scale_f32", a.logical_ptr(), a.pitch, a.plane, b.logical_ptr(), b.pitch, b.plane,
+                      b.logical_ptr(), b.pitch, b.plane, z, yy, xx, ctypes.c_float(0.01), ctypes.c_float(1e-6),
+                      None if stats is None else stats.data_ptr(), _lib.stream_ptr(dev))
+        ms = timed(launch, args.reps)
+        print(json.dumps({"kernel": label, "path": plan.path, "grid": oshape, "ms": ms,
+                          "algorithmic_GBps": 12.0 * n / ms / 1e6, "frac_of_8TBps": 12.0 * n / ms / 1e6 / 8000}), flush=True)
+    for label, kw in (("RL iteration, fused separable 9x7x7", {}), ("RL-TV iteration, fused separable 9x7x7", dict(tv_lambda=0.01)),
+                      ("RL iteration, fused separable 9x7x7 (again)", {})):
+        ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        plan(y, iterations=1, out=out, **kw)
+        torch.cuda.synchronize()
+        iters = max(4, args.reps)
+        plan(y, iterations=iters, out=out, events=ev, **kw)
+        torch.cuda.synchronize()
+        print(json.dumps({"kernel": label, "path": plan.path, "grid": oshape, "iterations": iters,
+                          "ms_per_iteration": ev[0].elapsed_time(ev[1]) / iters}), flush=True)
+    plan.release()
 
 
 def _rl_fft(args, torch, dev, g, oshape):
