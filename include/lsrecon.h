@@ -505,6 +505,37 @@ int lsr_rl_tv_scale_f32(const float* u, int64_t u_pitch, int64_t u_plane, const 
                         float lambda, float tv_eps, double* stats2, lsr_stream_t stream);
 
 /*
+ * Accelerated Richardson-Lucy: the vector extrapolation of Biggs & Andrews (Appl. Opt. 36, 1997) around the unchanged
+ * RL launches (csrc/rl_accel.hip).  With RL(.) one plain iteration and p_0 = x_0, iteration k runs x_{k+1} = RL(p_k) and,
+ * unless it is the last one, the two launches below on the same stream:
+ *
+ *   g_k     = x_{k+1} - p_k                                                     (float32)
+ *   a_{k+1} = 0 for k = 0, else clamp(<g_k, g_{k-1}> / <g_{k-1}, g_{k-1}>, 0, 1); 0 for a zero denominator
+ *   p_{k+1} = max(fma(a_{k+1}, x_{k+1} - x_k, x_{k+1}), 0)                      (float32; a_{k+1} rounded to float32 once)
+ *
+ * lsr_rl_accel_dots_f32: reads x1 = x_{k+1} and p = p_k (strided: pointer, row pitch and plane stride in elements, so the
+ * logical origin of a padded working volume goes in directly), reads the dense g = g_{k-1} (Z*Y*X floats) and writes g_k
+ * over it; `first` != 0 (k = 0): g is only written and <g_0, g_{-1}> := 0.  Leaves dots2[0] = <g_k, g_{k-1}> and
+ * dots2[1] = <g_k, g_k> (DEVICE memory): float64 sums of float64 products, bit-reproducible from run to run -- every
+ * workgroup stores its partial sums into `workspace` (lsr_rl_accel_workspace_bytes(Z, Y, X) bytes of DEVICE memory, 8-byte
+ * aligned; a function of the shape alone) and a second kernel adds them in index order; no floating-point atomics.  g must
+ * not overlap x1 or p.  16 algorithmic bytes per voxel.
+ *
+ * lsr_rl_accel_predict_f32: reads x1 = x_{k+1}, reads x0 = x_k and writes p_{k+1} over it (strided; only the logical
+ * volume is touched).  a_{k+1} is formed on the device from *num = <g_k, g_{k-1}> and *den = <g_{k-1}, g_{k-1}> (DEVICE
+ * memory: dots2[0] of this iteration's dots launch and dots2[1] of the one before); den == NULL is the first step:
+ * a_1 = 0, p_1 = max(x_1, 0), x0 is not read.  alpha_out (DEVICE memory, or NULL) receives a_{k+1} as a double.  x0 must
+ * not overlap x1.  12 algorithmic bytes per voxel.
+ */
+int lsr_rl_accel_workspace_bytes(int64_t Z, int64_t Y, int64_t X);
+int lsr_rl_accel_dots_f32(const float* x1, int64_t x1_pitch, int64_t x1_plane, const float* p, int64_t p_pitch,
+                          int64_t p_plane, float* g, int64_t Z, int64_t Y, int64_t X, int first, double* dots2,
+                          void* workspace, lsr_stream_t stream);
+int lsr_rl_accel_predict_f32(const float* x1, int64_t x1_pitch, int64_t x1_plane, float* x0, int64_t x0_pitch,
+                             int64_t x0_plane, int64_t Z, int64_t Y, int64_t X, const double* num, const double* den,
+                             double* alpha_out, lsr_stream_t stream);
+
+/*
  * Richardson-Lucy reduction scalars (the north-star's "wavefront reductions for the ratio / normalisation").
  * Every entry that finishes an RL iteration has a `_stats` form with one more argument, `double* stats` (DEVICE memory;
  * host memory for the *_cpu twins); NULL = the plain entry, the same kernels, no cost.  Per iteration i three sums over
@@ -732,6 +763,15 @@ int lsr_rl_dense_stats_f32_cpu(const float* y, float* x, float* ratio, int64_t Z
 int lsr_rl_tv_scale_f32_cpu(const float* u, int64_t u_pitch, int64_t u_plane, const float* v, int64_t v_pitch,
                             int64_t v_plane, float* out, int64_t o_pitch, int64_t o_plane, int64_t Z, int64_t Y,
                             int64_t X, float lambda, float tv_eps, double* stats2);
+/* ... of the accelerated RL launches (csrc/host_twins.hip: the same inline arithmetic, g and p are the kernels' bits; the
+ * inner products are summed over fixed row chunks in a fixed order, the same bits at every lsr_set_host_threads value; no
+ * stream; dots2, num, den and alpha_out HOST memory) */
+int lsr_rl_accel_dots_f32_cpu(const float* x1, int64_t x1_pitch, int64_t x1_plane, const float* p, int64_t p_pitch,
+                              int64_t p_plane, float* g, int64_t Z, int64_t Y, int64_t X, int first, double* dots2,
+                              void* workspace /* unused */);
+int lsr_rl_accel_predict_f32_cpu(const float* x1, int64_t x1_pitch, int64_t x1_plane, float* x0, int64_t x0_pitch,
+                                 int64_t x0_plane, int64_t Z, int64_t Y, int64_t X, const double* num, const double* den,
+                                 double* alpha_out);
 int lsr_flatfield_pattern_f32_cpu(const float* in, int64_t Z, int64_t Y, int64_t X, float* pattern,
                                   float* mean_out, void* scratch /* unused */, lsr_stream_t stream);
 int lsr_flatfield_pattern_u16_cpu(const uint16_t* in, int64_t Z, int64_t Y, int64_t X, float* pattern,

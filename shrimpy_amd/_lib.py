@@ -117,6 +117,11 @@ SIGNATURES: dict[str, list] = {
                             _int, _f32, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p, _stream],
     "lsr_rl_tv_scale_f32": [_c_f32p, _i64, _i64, _c_f32p, _i64, _i64, _c_f32p, _i64, _i64, _i64, _i64, _i64, _f32, _f32,
                             ctypes.c_void_p, _stream],
+    "lsr_rl_accel_workspace_bytes": [_i64, _i64, _i64],
+    "lsr_rl_accel_dots_f32": [_c_f32p, _i64, _i64, _c_f32p, _i64, _i64, _c_f32p, _i64, _i64, _i64, _int, ctypes.c_void_p,
+                              ctypes.c_void_p, _stream],
+    "lsr_rl_accel_predict_f32": [_c_f32p, _i64, _i64, _c_f32p, _i64, _i64, _i64, _i64, _i64, ctypes.c_void_p, ctypes.c_void_p,
+                                 ctypes.c_void_p, _stream],
     "lsr_crc32c_host": [ctypes.c_void_p, _i64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)],
     "lsr_crc32c_host_portable": [ctypes.c_void_p, _i64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)],
     "lsr_average_slices_f32": [_c_f32p, _i64, _i64, _i64, _c_f32p, _i64, _int, _stream],
@@ -193,6 +198,8 @@ for _name in ("lsr_deskew_f32", "lsr_deskew_u16", "lsr_deskew_cval", "lsr_affine
               "lsr_blosc_encode_device", "lsr_blosc_decode_device"):
     SIGNATURES[_name + "_cpu"] = SIGNATURES[_name]
 SIGNATURES["lsr_rl_tv_scale_f32_cpu"] = SIGNATURES["lsr_rl_tv_scale_f32"][:-1]     # (this twin takes no stream)
+for _name in ("lsr_rl_accel_dots_f32", "lsr_rl_accel_predict_f32"):                    # (nor do these)
+    SIGNATURES[_name + "_cpu"] = SIGNATURES[_name][:-1]
 
 
 def kernel_source_sha16() -> str:

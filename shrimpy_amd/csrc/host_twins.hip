@@ -13,6 +13,7 @@
 //   lsr_rl_dense_f32_cpu                      <->  lsr_rl_dense_f32                    (correlate.hip)
 //   lsr_flatfield_pattern_f32_cpu / _u16_cpu  <->  lsr_flatfield_pattern_f32 / _u16    (flatfield.hip)
 //   lsr_flatfield_apply_f32_cpu / _u16_cpu    <->  lsr_flatfield_apply_f32 / _u16      (flatfield.hip)
+//   lsr_rl_accel_dots_f32_cpu / _predict_f32_cpu  <->  lsr_rl_accel_dots_f32 / _predict_f32  (rl_accel.hip)
 //
 // Arithmetic (what "the same" means):
 //   resamplers -- coordinates ((zo*m0 + yo*m1) + xo*m2) + shift, weights w0 = 1 - f, w1 = 1 - w0 and the
@@ -38,6 +39,7 @@
 #include "common.hpp"
 #include "correlate_common.hpp"
 #include "host_parallel.hpp"
+#include "rl_accel.hpp"
 
 namespace {
 
@@ -657,4 +659,68 @@ extern "C" int lsr_flatfield_apply_u16_cpu(const uint16_t* in, const float* patt
                                            int64_t Z, int64_t Y, int64_t X, lsr_stream_t) {
   LSR_REQUIRE_HOST_FMA();
   return flat_apply_cpu(in, pattern, mean_dev, out, Z, Y, X);
+}
+
+// ---- accelerated Richardson-Lucy (rl_accel.hip): the same inline functions, so g and p are the kernels' bits.  The inner
+// products are float64 from the first add, summed over fixed chunks of rows (their number depends on the shape alone,
+// rl_accel.hpp: parts_of) and the chunks added in index order: the same bits at every lsr_set_host_threads value.
+// `workspace` is unused (may be NULL); dots2, num, den and alpha_out are HOST memory.
+extern "C" int lsr_rl_accel_dots_f32_cpu(const float* x1, int64_t x1_pitch, int64_t x1_plane, const float* p, int64_t p_pitch,
+                                         int64_t p_plane, float* g, int64_t Z, int64_t Y, int64_t X, int first, double* dots2,
+                                         void*) {
+  namespace ac = lsr::accel;
+  LSR_REQUIRE_HOST_FMA();
+  if (int rc = ac::check_dots(ac::Vol{x1, x1_pitch, x1_plane}, ac::Vol{p, p_pitch, p_plane}, g, dots2, Z, Y, X)) return rc;
+  const int64_t rows = Z * Y, parts = ac::parts_of(rows), per = lsr::ceil_div(rows, parts);
+  double part[2 * ac::kMaxParts];
+  parallel_ranges(parts, [&](int64_t c_first, int64_t c_last) {
+    for (int64_t c = c_first; c < c_last; ++c) {
+      double s_gh = 0.0, s_gg = 0.0;
+      const int64_t r_last = (c + 1) * per < rows ? (c + 1) * per : rows;
+      for (int64_t r = c * per; r < r_last; ++r) {
+        const int64_t z = r / Y, y = r - z * Y;
+        const float* a = x1 + z * x1_plane + y * x1_pitch;
+        const float* b = p + z * p_plane + y * p_pitch;
+        float* gr = g + r * X;
+        for (int64_t x = 0; x < X; ++x) {
+          const float gk = ac::change_of(a[x], b[x]);
+          if (!first) s_gh += static_cast<double>(gk) * static_cast<double>(gr[x]);
+          s_gg += static_cast<double>(gk) * static_cast<double>(gk);
+          gr[x] = gk;
+        }
+      }
+      part[2 * c] = s_gh;
+      part[2 * c + 1] = s_gg;
+    }
+  });
+  double s_gh = 0.0, s_gg = 0.0;
+  for (int64_t c = 0; c < parts; ++c) {
+    s_gh += part[2 * c];
+    s_gg += part[2 * c + 1];
+  }
+  dots2[0] = s_gh;
+  dots2[1] = s_gg;
+  return LSR_OK;
+}
+
+extern "C" int lsr_rl_accel_predict_f32_cpu(const float* x1, int64_t x1_pitch, int64_t x1_plane, float* x0, int64_t x0_pitch,
+                                            int64_t x0_plane, int64_t Z, int64_t Y, int64_t X, const double* num,
+                                            const double* den, double* alpha_out) {
+  namespace ac = lsr::accel;
+  LSR_REQUIRE_HOST_FMA();
+  if (int rc = ac::check_predict(ac::Vol{x1, x1_pitch, x1_plane}, ac::Vol{x0, x0_pitch, x0_plane}, Z, Y, X)) return rc;
+  LSR_REQUIRE(den == nullptr || num != nullptr, LSR_E_NULL, "num is NULL although den is not (den == NULL: the first step)");
+  const bool first = den == nullptr;
+  const float alpha = first ? 0.0f : ac::step_length(*num, *den);
+  if (alpha_out != nullptr) *alpha_out = static_cast<double>(alpha);
+  parallel_ranges(Z * Y, [&](int64_t r_first, int64_t r_last) {
+    for (int64_t r = r_first; r < r_last; ++r) {
+      const int64_t z = r / Y, y = r - z * Y;
+      const float* a = x1 + z * x1_plane + y * x1_pitch;
+      float* b = x0 + z * x0_plane + y * x0_pitch;
+      if (first) for (int64_t x = 0; x < X; ++x) b[x] = ac::predict_first(a[x]);
+      else for (int64_t x = 0; x < X; ++x) b[x] = ac::predict_of(alpha, a[x], b[x]);
+    }
+  });
+  return LSR_OK;
 }

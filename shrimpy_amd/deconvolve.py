@@ -19,6 +19,11 @@ CPU tensors (no HIP device in play) run the native host twins of the same launch
 iteration's result is divided voxel by voxel by ``1 - tv_lambda * div(grad x_k / |grad x_k|)`` (forward differences,
 backward divergence, the volume's own borders; ``csrc/rl_tv.hip``, one more streaming launch of 12 bytes per voxel per
 iteration behind the unchanged RL launches).  ``tv_lambda = 0`` (the default) is the plain iteration, launch for launch.
+
+``acceleration="biggs-andrews"`` starts every iteration from a point extrapolated along the last change (Biggs & Andrews
+1997; ``csrc/rl_accel.hip``: two more streaming launches per iteration, 16 + 12 bytes per voxel, no tuning parameter, no
+host round trip) and reaches the likelihood of a plain run in a third to a half of its iterations.  ``"none"`` (the
+default) is the plain run, launch for launch.
 """
 
 from __future__ import annotations
@@ -32,7 +37,8 @@ import numpy as np
 from . import _lib
 
 __all__ = ["richardson_lucy", "RichardsonLucyPlan", "RLStats", "factor_psf", "correlate3d", "prepare_psf",
-           "padded_shape", "PaddedVolume", "make_plan", "check_tv", "TV_LAMBDA_LIMIT"]
+           "padded_shape", "PaddedVolume", "make_plan", "check_tv", "TV_LAMBDA_LIMIT", "check_acceleration",
+           "ACCELERATIONS"]
 
 TV_LAMBDA_LIMIT = 1.0 / 6.0     # |div(grad x / |grad x|)| <= 6: below this the RL-TV denominator is provably positive
 
@@ -46,6 +52,51 @@ def check_tv(tv_lambda, tv_eps) -> tuple[float, float]:
     if not (te > 0.0 and np.isfinite(te)):
         raise ValueError(f"tv_eps must be a finite number > 0, got {tv_eps!r}")
     return lam, te
+
+
+ACCELERATIONS = ("none", "biggs-andrews")
+
+
+def check_acceleration(acceleration, tv_lambda: float = 0.0) -> bool:
+    """Whether the Biggs-Andrews extrapolation is on, or ``ValueError``: an unknown name, or acceleration together with
+    ``tv_lambda > 0`` (the TV factor changes the map whose fixed point the extrapolation heads for)."""
+    if acceleration not in ACCELERATIONS:
+        raise ValueError(f"acceleration must be one of {ACCELERATIONS}, got {acceleration!r}")
+    on = acceleration == "biggs-andrews"
+    if on and tv_lambda > 0:
+        raise ValueError("acceleration='biggs-andrews' cannot be combined with tv_lambda > 0: the total-variation factor "
+                         "breaks the fixed-point map the extrapolation assumes")
+    return on
+
+
+class AccelState:
+    """What one accelerated run keeps on the device beside its volumes: the inner products of every iteration
+    (``dots[k] = <g_k, g_{k-1}>, <g_k, g_k>``), the step lengths ``alphas[k] = a_{k+1}`` and the workspace of the dots
+    launch; ``step`` issues the two launches that follow ``x_{k+1} = RL(p_k)``.  ``g`` is the caller's dense volume."""
+
+    def __init__(self, shape, device, iterations: int, g):
+        import torch
+
+        self.shape = tuple(int(v) for v in shape)
+        self.g = g
+        n = max(int(iterations) - 1, 1)
+        self.dots = torch.zeros((n, 2), dtype=torch.float64, device=device)
+        self.alphas = torch.zeros(n, dtype=torch.float64, device=device)
+        self.work = torch.empty(_lib.call_value("lsr_rl_accel_workspace_bytes", *self.shape) // 8, dtype=torch.float64,
+                                device=device)
+
+    def step(self, k: int, x1, p, x0, stream) -> None:
+        """``x1``, ``p``, ``x0``: (pointer, pitch, plane) of x_{k+1}, p_k and x_k; p_{k+1} is written over x_k (which is
+        not read when ``k == 0``: a_1 = 0)."""
+        d = self.dots.data_ptr()
+        _lib.call("lsr_rl_accel_dots_f32", *x1, *p, self.g.data_ptr(), *self.shape, int(k == 0), d + 16 * k,
+                  self.work.data_ptr(), stream)
+        _lib.call("lsr_rl_accel_predict_f32", *x1, *x0, *self.shape, None if k == 0 else d + 16 * k,
+                  None if k == 0 else d + 16 * (k - 1) + 8, self.alphas.data_ptr() + 8 * k, stream)
+
+    def used(self, done: int) -> np.ndarray:
+        """a_1 .. a_{done-1}: the step lengths the ``done`` iterations that ran started from."""
+        return self.alphas[:max(int(done) - 1, 0)].cpu().numpy().copy()
 
 
 MAX_TAPS = 15
@@ -202,13 +253,18 @@ class RLStats:
 
     With ``tv_lambda > 0`` the iterate is the RL update divided by the total-variation factor: ``change`` and ``total``
     are then summed by the TV launch over the iterate the caller gets (``lsr_rl_tv_scale_f32``), and ``tol`` tests
-    those.  ``flux`` has no counterpart there: it stays the RL launch's value, i.e. the flux BEFORE the TV factor."""
+    those.  ``flux`` has no counterpart there: it stays the RL launch's value, i.e. the flux BEFORE the TV factor.
+
+    With ``acceleration="biggs-andrews"`` the scalars keep the RL launch's meaning, and that launch reads the
+    extrapolated point ``p_i``: ``change[i] = sum |x_{i+1} - p_i|`` (``p_0 = x_0``), ``flux`` and ``total`` describe
+    ``x_{i+1}``.  ``alphas`` (host route; the plans keep ``plan.last_alphas``) are the step lengths a_1 .. used."""
 
     flux: np.ndarray
     change: np.ndarray
     total: np.ndarray
     iterations: int
     stopped_by_tol: bool = False
+    alphas: np.ndarray | None = None
 
     @property
     def rel_change(self) -> np.ndarray:
@@ -377,6 +433,10 @@ class RichardsonLucyPlan:
         self._ratio_pad = None
         self._y_pad = None   # fused path: padded copy of a dense y
         self._tv_prev = None  # RL-TV on the paths that update x in place: x_k, kept for the TV launch
+        self._accel_g = None     # accelerated runs: the dense g_k ...
+        self._accel_pad = None   # ... the third padded volume the fused kinds rotate through ...
+        self._accel_prev = None  # ... or, on the paths that update x in place, two dense volumes (p_k and x_k)
+        self.last_alphas = None
         # one launch per iteration (rl_fused_sep.hip) where the PSF fits its specialisations
         self.fused = bool(self._psf.separable and not self._long_z and self._fused_mode in ("auto", "always")
                           and _lib.call_value("lsr_rl_sep_fused_supported", *self._psf.shape)
@@ -593,12 +653,15 @@ class RichardsonLucyPlan:
     def release(self) -> None:
         """Drop the scratch volumes."""
         self._ratio = self._x_pad = self._ratio_pad = self._y_pad = self._t_pad = self._t_dense = self._tv_prev = None
+        self._accel_g = self._accel_pad = self._accel_prev = None
 
     # ------------------------------------------------------------------------------------------ the loop
-    def _launch(self, st, it0: int, n: int, x_out, stats) -> None:
+    def _launch(self, st, it0: int, n: int, x_out, stats, ab=None) -> None:
         """Iterations ``it0 .. it0 + n - 1`` of the run described by ``st`` (set up by ``__call__``); the last one
         writes the dense ``x_out`` when that is not ``None``, otherwise the estimate stays in the working volume
-        ``_result_view(it0 + n)`` names.  ``stats``: float64 device tensor (iterations, 3), zero where not yet run."""
+        ``_result_view(it0 + n)`` names.  ``stats``: float64 device tensor (iterations, 3), zero where not yet run.
+        ``ab`` (fused kinds): the padded allocations the first iteration reads and writes, instead of the two of
+        ``_scratch()`` by the parity of ``it0`` (an accelerated run rotates three)."""
         z, yy, xx = self.shape
         ps = self._psf
         stream, eps = st["stream"], ctypes.c_float(st["eps"])
@@ -610,7 +673,7 @@ class RichardsonLucyPlan:
         if kind in ("fused", "fused-ysep"):
             x_pad, ratio_pad = self._scratch()
             bufs = (x_pad.full.data_ptr(), ratio_pad.full.data_ptr())   # iteration i reads bufs[i & 1], writes the other
-            a, b = bufs[it0 & 1], bufs[(it0 + 1) & 1]
+            a, b = (bufs[it0 & 1], bufs[(it0 + 1) & 1]) if ab is None else ab
             if kind == "fused":
                 nz, ny, nx = self._norm
                 _lib.call("lsr_rl_sep_fused_stats_f32", y_ptr, y_pitch, y_plane, from_y, a, b, xo, z, yy, xx,
@@ -654,7 +717,8 @@ class RichardsonLucyPlan:
         return x_pad.view
 
     def __call__(self, y, iterations: int = 20, eps: float = 1e-6, x0=None, out=None, events=None, *,
-                 stats: bool = False, tol: float | None = None, tv_lambda: float = 0.0, tv_eps: float = 1e-6):
+                 stats: bool = False, tol: float | None = None, tv_lambda: float = 0.0, tv_eps: float = 1e-6,
+                 acceleration: str = "none"):
         """Run RL.  ``events`` = optional ``(start, end)`` torch events recorded on the launch
         stream right around the kernel launches (``iterations`` fused launches, or
         ``2 * iterations`` ratio / update launches) -- what ``bench.py`` times.
@@ -668,10 +732,18 @@ class RichardsonLucyPlan:
 
         ``tv_lambda`` in ``(0, 1/6)``: RL-TV -- one RL iteration at a time, each followed by the total-variation launch
         (``lsr_rl_tv_scale_f32``) on the same stream; ``change`` / ``total`` and ``tol`` then describe the regularised
-        iterate (:class:`RLStats`).  ``0`` (default): the plain run, launch for launch."""
+        iterate (:class:`RLStats`).  ``0`` (default): the plain run, launch for launch.
+
+        ``acceleration="biggs-andrews"``: one RL iteration at a time, each but the last followed by the two launches of
+        ``csrc/rl_accel.hip`` on the same stream; the next iteration starts from the extrapolated point they leave.  The
+        fused kinds rotate three padded volumes (no copy); the kinds that update x in place keep p_k and x_k in two dense
+        volumes (two copies per iteration).  ``plan.last_alphas``: the step lengths used (float64, a_1 = 0 first).
+        ``stats`` / ``tol`` keep the RL launch's meaning (:class:`RLStats`).  ``"none"`` (default): the plain run."""
         import torch
 
         tv_lambda, tv_eps = check_tv(tv_lambda, tv_eps)
+        accelerate = check_acceleration(acceleration, tv_lambda)
+        self.last_alphas = None
         y_padded = None
         if isinstance(y, PaddedVolume):  # e.g. written in place by the deskew kernel
             if not (self._psf.separable or self._psf.taps is not None or self._ysep is not None):
@@ -711,6 +783,8 @@ class RichardsonLucyPlan:
             x.copy_(init)
             if stats or tol is not None:
                 self.last_stats = RLStats.from_array(np.zeros((0, 3)), 0)
+            if accelerate:
+                self.last_alphas = np.zeros(0)
             return x
         ps = self._psf
         want_stats = bool(stats) or tol is not None
@@ -752,14 +826,17 @@ class RichardsonLucyPlan:
                 dev_stats = torch.zeros((iterations, 3), dtype=torch.float64, device=self.device)
             if events:
                 events[0].record()
-            if tv_lambda > 0:
-                # x_0 as the first TV launch reads it: y itself (dense or padded) or the caller's x0 -- unless that is
-                # also the output tensor, which the launch may not read its neighbours from
+            if tv_lambda > 0 or accelerate:
+                # x_0 as the first TV (dots) launch reads it: y itself (dense or padded) or the caller's x0 -- unless that
+                # is also the output tensor, which the RL launches write
                 u0 = None
                 if x0 is None:
                     u0 = st["y"]
                 elif init.data_ptr() != x.data_ptr():
                     u0 = (init.data_ptr(), self.shape[2], self.shape[1] * self.shape[2])
+            if accelerate:
+                done, stopped = self._run_accel(st, iterations, tol, dev_stats, x, u0)
+            elif tv_lambda > 0:
                 done, stopped, dev_stats = self._run_tv(st, iterations, tol, dev_stats, x, tv_lambda, tv_eps, u0)
             elif tol is None:
                 self._launch(st, 0, iterations, None if st["kind"] == "generic" else x, dev_stats)
@@ -848,6 +925,87 @@ class RichardsonLucyPlan:
             dev_stats = torch.cat((dev_stats[:, :1], tv_stats), dim=1)
         return done, stopped, dev_stats
 
+    def _run_accel(self, st, iterations: int, tol, dev_stats, x, u0):
+        """The accelerated loop (``csrc/rl_accel.hip`` states it).  Returns (iterations run, stopped early); the dense ``x``
+        holds x_done.  Fused kinds: ``rd`` holds p_k, ``wr`` receives x_{k+1}, ``hold`` holds x_k and receives p_{k+1};
+        then ``rd, wr, hold = hold, rd, wr``.  The other kinds run RL in place in the working volume ``cur``: ``b`` is a
+        copy of p_k, ``c`` holds x_k and receives p_{k+1}; before the next RL launch x_{k+1} is saved from ``cur`` into
+        the free ``b`` and p_{k+1} copied into ``cur``, and ``b`` and ``c`` trade places.  ``tol`` reads the RL launch's
+        scalars one iteration late, as ``_run_to_tolerance`` does."""
+        import torch
+
+        z, yy, xx = self.shape
+        dense = (xx, yy * xx)
+        kind, stream = st["kind"], st["stream"]
+        if self._accel_g is None:
+            self._accel_g = torch.empty(self.shape, dtype=torch.float32, device=self.device)
+        acc = AccelState(self.shape, self.device, iterations, self._accel_g)
+
+        def tri(v):
+            return (v.logical_ptr(), v.pitch, v.plane)
+
+        rotate = kind in ("fused", "fused-ysep")
+        if rotate:
+            if self._accel_pad is None:
+                self._accel_pad = PaddedVolume(self.shape, self._pad_psf_shape(), self.device)
+            rd, wr = self._scratch()
+            hold = self._accel_pad
+        else:
+            if self._accel_prev is None:
+                self._accel_prev = [torch.empty(self.shape, dtype=torch.float32, device=self.device) for _ in range(2)]
+            b, c = self._accel_prev
+            if kind == "generic":
+                cur, cur3 = st["x"], (st["x"].data_ptr(),) + dense
+            else:
+                x_pad = self._scratch()[0]
+                cur, cur3 = x_pad.view, tri(x_pad)
+        if tol is not None:
+            host = torch.empty((iterations, 3), dtype=torch.float64).pin_memory()
+            arrived = [torch.cuda.Event() for _ in range(iterations)]
+
+        def met(i):
+            arrived[i].synchronize()
+            change, total = float(host[i, 1]), float(host[i, 2])
+            return total > 0 and change <= tol * total or total == 0
+
+        done, stopped, result = 0, False, None
+        for it in range(iterations):
+            last = it + 1 == iterations
+            x_out = x if (last and tol is None and kind != "generic") else None
+            if rotate:
+                self._launch(st, it, 1, x_out, dev_stats, ab=(rd.full.data_ptr(), wr.full.data_ptr()))
+                result = wr.view
+                if not last:
+                    acc.step(it, tri(wr), st["y"] if (it == 0 and st["from_y"]) else tri(rd), tri(hold), stream)
+                    rd, wr, hold = hold, rd, wr
+            else:
+                if it == 0:
+                    # (iteration 0 of the ysep / long-z kinds fills the working volume inside their own loop)
+                    p3 = u0 if u0 is not None else (b.copy_(st["init"]).data_ptr(),) + dense
+                else:
+                    b.copy_(cur)
+                    cur.copy_(c)
+                    b, c = c, b
+                    p3 = (b.data_ptr(),) + dense
+                self._launch(st, it, 1, x_out, dev_stats)
+                result = cur
+                if not last:
+                    acc.step(it, cur3, p3, (c.data_ptr(),) + dense, stream)
+            done = it + 1
+            if tol is not None:
+                host[it].copy_(dev_stats[it], non_blocking=True)
+                arrived[it].record()
+                if it >= 1 and met(it - 1):
+                    stopped = True
+                    break
+        if tol is not None:
+            if not stopped:
+                stopped = bool(met(done - 1))
+            if kind != "generic":
+                x.copy_(result)
+        self.last_alphas = acc.used(done)
+        return done, stopped
+
     def _run_to_tolerance(self, st, iterations: int, tol: float, dev_stats):
         """One launch group per iteration; iteration i's scalars travel to pinned host memory behind it and are looked at
         after iteration i + 1 has been queued.  Returns (iterations run, stopped early)."""
@@ -919,7 +1077,7 @@ def make_plan(shape_zyx, psf, device, *, separable: str = "auto", separable_rtol
 def richardson_lucy(y, psf=None, iterations: int = 20, eps: float = 1e-6, x0=None, *,
                     separable: str = "auto", separable_rtol: float = 1e-6, psf_factors=None,
                     tol: float | None = None, return_stats: bool = False, method: str = "auto",
-                    tv_lambda: float = 0.0, tv_eps: float = 1e-6):
+                    tv_lambda: float = 0.0, tv_eps: float = 1e-6, acceleration: str = "none"):
     """Richardson-Lucy deconvolution of a (Z, Y, X) float32 device tensor; returns a new tensor.
 
     ``psf`` is used as given (normalise it to sum 1 for flux conservation).  ``x0`` defaults to
@@ -937,11 +1095,18 @@ def richardson_lucy(y, psf=None, iterations: int = 20, eps: float = 1e-6, x0=Non
     ``tv_lambda`` in ``[0, 1/6)``: total-variation regularisation (RL-TV, Dey et al. 2006): every iteration's result is
     divided by ``1 - tv_lambda * div(grad x / |grad x|)`` with the gradient norm floored by ``tv_eps``; typical values
     are 0.001 .. 0.05.  ``0`` (default) is plain RL.
+
+    ``acceleration="biggs-andrews"``: the vector extrapolation of Biggs & Andrews (1997) -- every iteration starts from a
+    point extrapolated along the last change, with a step length taken from the last two changes; about 10 iterations
+    reach the likelihood of 20 plain ones.  A different path up the same likelihood, not the plain run's numbers; not
+    together with ``tv_lambda > 0``.  With ``return_stats=True`` the step lengths are ``RLStats.alphas``.
     """
     import torch
 
     tv_lambda, tv_eps = check_tv(tv_lambda, tv_eps)
     tv = dict(tv_lambda=tv_lambda, tv_eps=tv_eps) if tv_lambda > 0 else {}
+    if check_acceleration(acceleration, tv_lambda):
+        tv["acceleration"] = acceleration
 
     if not isinstance(y, torch.Tensor):
         raise TypeError(f"y must be a torch.Tensor, got {type(y).__name__}")
@@ -958,6 +1123,8 @@ def richardson_lucy(y, psf=None, iterations: int = 20, eps: float = 1e-6, x0=Non
     plan = make_plan(tuple(y.shape), psf, y.device, separable=separable, separable_rtol=separable_rtol,
                      psf_factors=psf_factors, method=method)
     x = plan(y, iterations=iterations, eps=eps, x0=x0, stats=return_stats, tol=tol, **tv)
+    if return_stats and plan.last_alphas is not None:
+        plan.last_stats.alphas = plan.last_alphas
     return (x, plan.last_stats) if return_stats else x
 
 

@@ -125,11 +125,13 @@ class FftRichardsonLucyPlan:
         self._scale = 1.0 / (float(gz) * float(gy) * float(gx))
         self._b = None         # [Z][XC][Y] complex64: the one spectrum in flight
         self._ratio = None
+        self._accel = None     # accelerated runs: the dense g_k and two dense volumes (p_k and x_k)
         self.last_stats = None
         self.stats_device = None
+        self.last_alphas = None
 
     def release(self) -> None:
-        self._b = self._ratio = None
+        self._b = self._ratio = self._accel = None
 
     def _scratch(self):
         import torch
@@ -205,15 +207,20 @@ class FftRichardsonLucyPlan:
             self._iteration(x, y, eps, stats_row, first)
 
     def __call__(self, y, iterations: int = 20, eps: float = 1e-6, x0=None, out=None, events=None, *,
-                 stats: bool = False, tol: float | None = None, tv_lambda: float = 0.0, tv_eps: float = 1e-6):
+                 stats: bool = False, tol: float | None = None, tv_lambda: float = 0.0, tv_eps: float = 1e-6,
+                 acceleration: str = "none"):
         """Run RL; arguments as :meth:`shrimpy_amd.deconvolve.RichardsonLucyPlan.__call__`.  ``events``: ``(start, end)``
         torch events recorded right around the launches (ten per iteration).  ``tv_lambda > 0``: this route updates the
-        estimate in place, so x_k is copied aside before each iteration and the TV launch follows it."""
+        estimate in place, so x_k is copied aside before each iteration and the TV launch follows it.
+        ``acceleration="biggs-andrews"``: likewise in place -- p_k and x_k live in two dense volumes, two copies and the
+        two launches of ``csrc/rl_accel.hip`` per iteration beside the ten of the iteration itself."""
         import torch
 
-        from .deconvolve import RLStats, check_tv
+        from .deconvolve import RLStats, check_acceleration, check_tv
 
         tv_lambda, tv_eps = check_tv(tv_lambda, tv_eps)
+        accelerate = check_acceleration(acceleration, tv_lambda)
+        self.last_alphas = None
 
         y = _lib.require_device_f32(y, "y")
         if tuple(y.shape) != self.shape or y.device != self.device:
@@ -249,7 +256,9 @@ class FftRichardsonLucyPlan:
             if events:
                 events[0].record()
             done, stopped = iterations, False
-            if tol is None:
+            if accelerate:
+                done, stopped = self._run_accel(out, y, float(eps), iterations, tol, dev_stats, init)
+            elif tol is None:
                 for it in range(iterations):
                     self._step_tv(out, y, float(eps), None if dev_stats is None else dev_stats[it], it)
             else:
@@ -276,6 +285,59 @@ class FftRichardsonLucyPlan:
         _lib.call("lsr_rl_tv_scale_f32", u.data_ptr(), xx, yy * xx, x.data_ptr(), xx, yy * xx, x.data_ptr(), xx, yy * xx,
                   z, yy, xx, ctypes.c_float(tv["lam"]), ctypes.c_float(tv["eps"]),
                   None if tv["stats"] is None else tv["stats"].data_ptr() + 16 * it, _lib.stream_ptr(self.device))
+
+    def _run_accel(self, x, y, eps, iterations, tol, dev_stats, init):
+        """The accelerated loop (``csrc/rl_accel.hip`` states it) on this route, which runs RL in place in ``x``: ``b`` is a
+        copy of p_k (x_0 itself where the caller left it), ``c`` holds x_k and receives p_{k+1}; before the next iteration
+        x_{k+1} is saved from ``x`` into the free ``b`` and p_{k+1} copied into ``x``, and ``b`` and ``c`` trade places.
+        Returns (iterations run, stopped early); ``tol`` as in ``_run_to_tolerance``."""
+        import torch
+
+        from .deconvolve import AccelState
+
+        if iterations == 0:
+            self.last_alphas = np.zeros(0)
+            return 0, False
+        z, yy, xx = self.shape
+        dense = (xx, yy * xx)
+        if self._accel is None:
+            self._accel = [torch.empty(self.shape, dtype=torch.float32, device=self.device) for _ in range(3)]
+        g, b, c = self._accel
+        acc = AccelState(self.shape, self.device, iterations, g)
+        stream = _lib.stream_ptr(self.device)
+        if tol is not None:
+            host = torch.empty((iterations, 3), dtype=torch.float64).pin_memory()
+            arrived = [torch.cuda.Event() for _ in range(iterations)]
+
+        def met(i):
+            arrived[i].synchronize()
+            change, total = float(host[i, 1]), float(host[i, 2])
+            return total > 0 and change <= tol * total or total == 0
+
+        done, stopped = 0, False
+        for it in range(iterations):
+            if it == 0:
+                p = init if init.data_ptr() != x.data_ptr() else b.copy_(x)
+            else:
+                b.copy_(x)
+                x.copy_(c)
+                b, c = c, b
+                p = b
+            # (first=True: the chained form's carried-over spectrum would be x_{k}'s, not p_k's)
+            self._step(x, y, eps, None if dev_stats is None else dev_stats[it], True)
+            if it + 1 < iterations:
+                acc.step(it, (x.data_ptr(),) + dense, (p.data_ptr(),) + dense, (c.data_ptr(),) + dense, stream)
+            done = it + 1
+            if tol is not None:
+                host[it].copy_(dev_stats[it], non_blocking=True)
+                arrived[it].record()
+                if it >= 1 and met(it - 1):
+                    stopped = True
+                    break
+        if tol is not None and not stopped:
+            stopped = bool(met(done - 1))
+        self.last_alphas = acc.used(done)
+        return done, stopped
 
     def _run_to_tolerance(self, x, y, eps, iterations, tol, dev_stats):
         """Iteration i's scalars travel to pinned host memory behind it and are looked at after iteration i + 1 has

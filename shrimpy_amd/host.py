@@ -175,18 +175,23 @@ def correlate3d(volume, weights=None, weight_factors=None):
 
 def richardson_lucy(y, psf=None, iterations: int = 20, eps: float = 1e-6, x0=None, *, separable: str = "auto",
                     separable_rtol: float = 1e-6, psf_factors=None, tol: float | None = None,
-                    return_stats: bool = False, tv_lambda: float = 0.0, tv_eps: float = 1e-6):
+                    return_stats: bool = False, tv_lambda: float = 0.0, tv_eps: float = 1e-6,
+                    acceleration: str = "none"):
     """``deconvolve.richardson_lucy`` for a CPU tensor: ``x <- x * H^T(y / (H x + eps)) / H^T 1`` with the two
     correlations and their epilogues as the host twins of the device launches (rank-1 PSFs run the
     separable form, others the dense one).  ``tol`` / ``return_stats``: the iteration scalars of
     ``deconvolve.RLStats``, summed by the twins' UPDATE pass; the loop stops after the first iteration whose relative
     change is below ``tol``.  ``tv_lambda > 0``: every iteration is followed by the twin of the total-variation launch
-    (``lsr_rl_tv_scale_f32_cpu``); ``change`` / ``total`` and ``tol`` are then those of the regularised iterate."""
+    (``lsr_rl_tv_scale_f32_cpu``); ``change`` / ``total`` and ``tol`` are then those of the regularised iterate.
+    ``acceleration="biggs-andrews"``: every iteration but the last is followed by the twins of the two launches of
+    ``csrc/rl_accel.hip`` and the next one starts from the extrapolated point (``RLStats.alphas``: the step lengths)."""
     import torch
 
-    from .deconvolve import MAX_TAPS, RLStats, _axis_norm, _prefix_table, check_tv, factor_psf, prepare_psf
+    from .deconvolve import (MAX_TAPS, RLStats, _axis_norm, _prefix_table, check_acceleration, check_tv, factor_psf,
+                             prepare_psf)
 
     tv_lambda, tv_eps = check_tv(tv_lambda, tv_eps)
+    accelerate = check_acceleration(acceleration, tv_lambda)
 
     if tol is not None and not (tol >= 0 and np.isfinite(tol)):
         raise ValueError("tol must be a finite number >= 0")
@@ -222,7 +227,10 @@ def richardson_lucy(y, psf=None, iterations: int = 20, eps: float = 1e-6, x0=Non
         raise ValueError(f"x0 must be {tuple(y.shape)}")
     x = init.clone()
     if iterations == 0:
-        return (x, RLStats.from_array(np.zeros((0, 3)), 0)) if return_stats else x
+        empty = RLStats.from_array(np.zeros((0, 3)), 0)
+        if accelerate:
+            empty.alphas = np.zeros(0)
+        return (x, empty) if return_stats else x
     stats = np.zeros((iterations, 3), dtype=np.float64) if want else None
     tv_stats = np.zeros((iterations, 2), dtype=np.float64) if want and tv_lambda > 0 else None
 
@@ -234,8 +242,24 @@ def richardson_lucy(y, psf=None, iterations: int = 20, eps: float = 1e-6, x0=Non
     def report(done, stopped):
         if tv_stats is not None:      # flux from the RL update, change and total from the TV pass
             stats[:, 1:] = tv_stats
-        return RLStats.from_array(stats, done, stopped)
+        out = RLStats.from_array(stats, done, stopped)
+        if accelerate:
+            out.alphas = alphas[:max(done - 1, 0)].copy()
+        return out
     z, yy, xx = (int(v) for v in y.shape)
+    if accelerate:
+        g = torch.empty_like(y)
+        dots = np.zeros((max(iterations - 1, 1), 2), dtype=np.float64)
+        alphas = np.zeros(max(iterations - 1, 1), dtype=np.float64)
+
+    def extrapolate(k, x1, p, x0):
+        """The two launches behind ``x1 = RL(p)`` of iteration ``k``: p_{k+1} is written over ``x0`` = x_k (not read when
+        ``k == 0``)."""
+        _lib.call("lsr_rl_accel_dots_f32_cpu", x1.data_ptr(), xx, yy * xx, p.data_ptr(), xx, yy * xx, g.data_ptr(), z, yy, xx,
+                  int(k == 0), dots[k].ctypes.data, None)
+        _lib.call("lsr_rl_accel_predict_f32_cpu", x1.data_ptr(), xx, yy * xx, x0.data_ptr(), xx, yy * xx, z, yy, xx,
+                  None if k == 0 else dots[k, 0:].ctypes.data, None if k == 0 else dots[k - 1, 1:].ctypes.data,
+                  alphas[k:].ctypes.data)
 
     def tv_scale(u, v, it):
         """``v <- v / (1 - tv_lambda * div(grad u / |grad u|))`` in place."""
@@ -263,32 +287,46 @@ def richardson_lucy(y, psf=None, iterations: int = 20, eps: float = 1e-6, x0=Non
         # are looked at after iteration i + 1 has run, so the estimate returned is the one iteration PAST the first that
         # met tol -- the same iterate, and the same RLStats.iterations, whichever device the tensor lives on
         done, stopped = 0, False
-        step = iterations if tol is None and tv_lambda == 0 else 1
+        step = iterations if tol is None and tv_lambda == 0 and not accelerate else 1
+        held = torch.empty_like(x) if accelerate else None      # x_k, then p_{k+1}
+        result = x
         while done < iterations:
-            prev = x.clone() if tv_lambda > 0 else None
+            prev = x.clone() if tv_lambda > 0 or accelerate else None     # (accelerated: p_k, which x holds here)
             _lib.call("lsr_rl_dense_stats_f32_cpu", y.data_ptr(), x.data_ptr(), ratio.data_ptr(), z, yy, xx, k.ctypes.data,
                       kf.ctypes.data, w.shape[0], w.shape[1], w.shape[2], table.ctypes.data, step, e,
                       None if stats is None else stats[done:].ctypes.data, None)
             if tv_lambda > 0:
                 tv_scale(prev, x, done)
+            result = x
+            if accelerate and done + 1 < iterations:
+                # x = x_{k+1}; p_{k+1} goes over x_k in `held`, then the two trade places: x = p_{k+1}, held = x_{k+1}
+                extrapolate(done, x, prev, held)
+                x, held = held, x
             done += step
             if tol is not None and done >= 2 and met(done - 2):
                 stopped = True
                 break
         if tol is not None and not stopped:
             stopped = bool(met(done - 1))
-        return (x, report(done, stopped)) if return_stats else x
+        return (result, report(done, stopped)) if return_stats else result
     done, stopped = 0, False
+    held = torch.empty_like(x) if accelerate else None          # x_k, then p_{k+1}
     for it in range(iterations):
         corr(x, ratio, y, kf, _lib.EPI_RATIO)       # ratio = y / (H x + eps): H = correlation with the flipped taps
         corr(ratio, nxt, x, k, _lib.EPI_UPDATE, None if stats is None else stats[it])     # x <- x * H^T ratio / H^T 1
         if tv_lambda > 0:
             tv_scale(x, nxt, it)
-        x, nxt = nxt, x
+        result = nxt
+        if accelerate and it + 1 < iterations:
+            # x = p_k, nxt = x_{k+1}; p_{k+1} goes over x_k in `held`: three volumes rotate, nothing is copied
+            extrapolate(it, nxt, x, held)
+            x, nxt, held = held, x, nxt
+        else:
+            x, nxt = nxt, x
         done = it + 1
         if tol is not None and it >= 1 and met(it - 1):     # (one iteration past the first that met tol: see above)
             stopped = True
             break
     if tol is not None and not stopped:
         stopped = bool(met(done - 1))
-    return (x, report(done, stopped)) if return_stats else x
+    return (result, report(done, stopped)) if return_stats else result

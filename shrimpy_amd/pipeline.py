@@ -203,12 +203,16 @@ class VolumeReconstructor:
         if self._plan is not None:
             dec = self.settings.deconvolution
             tv = dict(tv_lambda=dec.tv_lambda, tv_eps=dec.tv_eps) if dec.tv_lambda > 0 else {}
+            if dec.acceleration != "none":
+                tv["acceleration"] = dec.acceleration
             vol = self._plan(vol, iterations=dec.iterations, eps=dec.eps, events=rl_events, **tv)
         elif self._host_rl is not None:
             from .deconvolve import richardson_lucy
 
             dec = self.settings.deconvolution
             tv = dict(tv_lambda=dec.tv_lambda, tv_eps=dec.tv_eps) if dec.tv_lambda > 0 else {}
+            if dec.acceleration != "none":
+                tv["acceleration"] = dec.acceleration
             vol = richardson_lucy(vol, iterations=dec.iterations, eps=dec.eps, **self._host_rl, **tv)
         return vol
 

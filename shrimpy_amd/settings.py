@@ -191,12 +191,17 @@ class DeconvolveSettings(_StrictModel):
     ``tv_lambda`` in ``[0, 1/6)`` turns on total-variation regularisation (RL-TV, Dey et al. 2006: every iteration's
     result divided by ``1 - tv_lambda * div(grad x / |grad x|)``, the gradient norm floored by ``tv_eps``); typical
     values are 0.001 .. 0.05, ``0`` (the default) is plain Richardson-Lucy.
+
+    ``acceleration="biggs-andrews"`` starts every iteration from a point extrapolated along the last change (Biggs &
+    Andrews 1997; no tuning parameter): about 10 iterations then reach the likelihood of 20 plain ones, so lower
+    ``iterations`` with it.  Not together with ``tv_lambda > 0``.  ``"none"`` (the default) is plain Richardson-Lucy.
     """
 
     iterations: NonNegativeInt = 20
     eps: PositiveFloat = 1e-6
     tv_lambda: NonNegativeFloat = 0.0
     tv_eps: PositiveFloat = 1e-6
+    acceleration: Literal["none", "biggs-andrews"] = "none"
     psf_path: Optional[str] = None
     psf_shape_zyx: Optional[tuple[PositiveInt, PositiveInt, PositiveInt]] = None
     gaussian_sigma_zyx: tuple[PositiveFloat, PositiveFloat, PositiveFloat] = (2.0, 1.2, 1.2)
@@ -213,6 +218,13 @@ class DeconvolveSettings(_StrictModel):
         from .deconvolve import check_tv
 
         return check_tv(v, 1.0)[0]
+
+    @model_validator(mode="after")
+    def _acceleration_without_tv(self):
+        from .deconvolve import check_acceleration
+
+        check_acceleration(self.acceleration, self.tv_lambda)
+        return self
 
     @field_validator("gaussian_shape_zyx")
     @classmethod

@@ -109,12 +109,22 @@ def _refuse_tv(tv_lambda) -> None:
                          "per side than the RL exchange provides")
 
 
+def _refuse_acceleration(acceleration) -> None:
+    from .deconvolve import check_acceleration
+
+    if check_acceleration(acceleration):
+        raise ValueError("acceleration is not available on the slab split: the step length is an inner product over the "
+                         "whole volume, which the ranks would have to reduce every iteration")
+
+
 def run_slabs_in_process(slab_rls: "list[SlabRichardsonLucy]", iterations: int = 20, eps: float = 1e-6, *,
-                         tv_lambda: float = 0.0):
+                         tv_lambda: float = 0.0, acceleration: str = "none"):
     """All ranks of a split in ONE process, in lockstep, halos copied directly between the slabs --
     the reference behaviour of the distributed run (used by the parity tests, which have one GPU).
-    Returns the owned rows of every slab, in rank order.  ``tv_lambda > 0`` (RL-TV) is refused here."""
+    Returns the owned rows of every slab, in rank order.  ``tv_lambda > 0`` (RL-TV) and ``acceleration`` other than
+    ``"none"`` are refused here."""
     _refuse_tv(tv_lambda)
+    _refuse_acceleration(acceleration)
     src = [s._x[0] for s in slab_rls]
     dst = [s._x[1] for s in slab_rls]
     for s, v in zip(slab_rls, src):
@@ -153,12 +163,15 @@ class SlabRichardsonLucy:
         self.y_pad = self.plan.new_padded_input()      # the caller (or deskew_slab) fills .view
         self._x = [PaddedVolume(self.plan.shape, self.plan._psf.shape, device) for _ in range(2)]
 
-    def run(self, iterations: int = 20, eps: float = 1e-6, exchange=None, *, tv_lambda: float = 0.0):
+    def run(self, iterations: int = 20, eps: float = 1e-6, exchange=None, *, tv_lambda: float = 0.0,
+            acceleration: str = "none"):
         """RL from ``x0 = y`` on the extended slab; returns the OWNED rows ``(Z, own rows, X)`` (a view).
 
         ``exchange(view, slab)`` refreshes halo rows after each iteration (default:
-        :func:`exchange_halos` over the default process group).  ``tv_lambda > 0`` (RL-TV) is refused here."""
+        :func:`exchange_halos` over the default process group).  ``tv_lambda > 0`` (RL-TV) and ``acceleration`` other than
+        ``"none"`` are refused here."""
         _refuse_tv(tv_lambda)
+        _refuse_acceleration(acceleration)
         if exchange is None:
             exchange = exchange_halos
         src, dst = self._x

@@ -44,6 +44,9 @@ def main():
                     "beyond the stencil kernels) next to the generic / dense stencils where they exist")
     ap.add_argument("--rl-tv", action="store_true", help="only: ms per total-variation launch and per RL-TV iteration (fused "
                     "separable 9x7x7) beside the plain fused iteration, on --rl-grid")
+    ap.add_argument("--rl-accel", action="store_true", help="only: ms per launch of the Biggs-Andrews extrapolation, per "
+                    "accelerated iteration and the wall time of 9 / 10 / 15 accelerated beside 20 plain iterations on the "
+                    "fused separable, ky (x) kzx and Fourier routes, on --rl-grid")
     ap.add_argument("--psf-sweep-wide", action="store_true", help="with --psf-sweep: every pz for in-plane extents 9-15")
     args = ap.parse_args()
 
@@ -63,6 +66,9 @@ def main():
         return
     if args.rl_tv:
         _rl_tv(args, torch, dev, g, bench, RichardsonLucyPlan, tuple(int(v) for v in args.rl_grid.split(",")))
+        return
+    if args.rl_accel:
+        _rl_accel(args, torch, dev, g, tuple(int(v) for v in args.rl_grid.split(",")))
         return
     if args.psf_sweep:
         _psf_sweep(args, torch, dev, g, RichardsonLucyPlan, tuple(int(v) for v in args.rl_grid.split(",")))
@@ -321,6 +327,77 @@ def _rl_tv(args, torch, dev, g, bench, RichardsonLucyPlan, oshape):
         print(json.dumps({"kernel": label, "path": plan.path, "grid": oshape, "iterations": iters,
                           "ms_per_iteration": ev[0].elapsed_time(ev[1]) / iters}), flush=True)
     plan.release()
+
+
+def _rl_accel(args, torch, dev, g, oshape):
+    """Accelerated RL (csrc/rl_accel.hip): the two launches alone, between the fused plan's padded working volumes as an
+    iteration runs them (16 and 12 algorithmic bytes per voxel), then per route -- fused separable 9x7x7, ky (x) kzx
+    9x7x7 (a Gaussian turned 30 degrees in (z, x)), Fourier 15x19x19 -- the wall time of 20 plain iterations and of 9, 10
+    and 15 accelerated ones, all in this run."""
+    from shrimpy_amd import _lib
+    from shrimpy_amd.deconvolve import AccelState, PaddedVolume, make_plan
+    from shrimpy_amd.pipeline import gaussian_psf_factors
+
+    y = torch.poisson(torch.full(oshape, 100.0, device=dev), generator=g)
+    ks = gaussian_psf_factors((9, 7, 7), (2.0, 1.2, 1.2))
+    n = y.numel()
+    out = torch.empty_like(y)
+
+    def grid_psf(size, tilt):
+        zz, yy, xx = np.meshgrid(*[np.arange(m) - m // 2 for m in size], indexing="ij")
+        c, s = np.cos(np.deg2rad(tilt)), np.sin(np.deg2rad(tilt))
+        zr, xr = c * zz + s * xx, -s * zz + c * xx
+        w = np.exp(-0.5 * ((zr / (size[0] / 4.5)) ** 2 + (yy / (size[1] / 5.8)) ** 2 + (xr / (size[2] / 5.8)) ** 2))
+        return (w / w.sum()).astype(np.float32)
+
+    routes = (("fused separable 9x7x7", dict(psf=None, psf_factors=ks)),
+              ("ky (x) kzx 9x7x7", dict(psf=grid_psf((9, 7, 7), 30.0))),
+              ("Fourier 15x19x19", dict(psf=grid_psf((15, 19, 19), 30.0), method="fft")))
+    for route, kw in routes:
+        plan = make_plan(oshape, kw.pop("psf"), dev, **kw)
+        if route.startswith("fused"):
+            plan(y, iterations=2, out=out)                               # fills both working volumes
+            a, b = plan._scratch()
+            third = PaddedVolume(oshape, plan._pad_psf_shape(), dev)
+            acc = AccelState(oshape, dev, 3, torch.zeros_like(y))
+            tri = lambda v: (v.logical_ptr(), v.pitch, v.plane)         # noqa: E731
+            z, yy, xx = oshape
+            d = acc.dots.data_ptr()
+            launches = (
+                ("accel dots launch", 16.0, lambda: _lib.call(
+                    "lsr_rl_accel_dots_f32", *tri(b), *tri(a), acc.g.data_ptr(), z, yy, xx, 0, d + 16, acc.work.data_ptr(),
+                    _lib.stream_ptr(dev))),
+                ("accel dots launch (first: g not read)", 12.0, lambda: _lib.call(
+                    "lsr_rl_accel_dots_f32", *tri(b), *tri(a), acc.g.data_ptr(), z, yy, xx, 1, d, acc.work.data_ptr(),
+                    _lib.stream_ptr(dev))),
+                ("accel predict launch", 12.0, lambda: _lib.call(
+                    "lsr_rl_accel_predict_f32", *tri(b), *tri(third), z, yy, xx, d + 16, d + 8, None, _lib.stream_ptr(dev))))
+            for label, nbytes, launch in launches:
+                ms = timed(launch, args.reps)
+                print(json.dumps({"kernel": label, "grid": oshape, "ms": ms, "bytes_per_voxel": nbytes,
+                                  "ns_per_GB": ms * 1e6 / (nbytes * n / 1e9), "algorithmic_GBps": nbytes * n / ms / 1e6,
+                                  "frac_of_8TBps": nbytes * n / ms / 1e6 / 8000}), flush=True)
+            del third, acc
+        walls = {}
+        for label, iters, kw2 in (("plain", 20, {}), ("accelerated", 9, dict(acceleration="biggs-andrews")),
+                                  ("accelerated", 10, dict(acceleration="biggs-andrews")),
+                                  ("accelerated", 15, dict(acceleration="biggs-andrews")), ("plain", 20, {})):
+            ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            plan(y, iterations=2, out=out, **kw2)                        # allocations and first-use costs
+            torch.cuda.synchronize()
+            plan(y, iterations=iters, out=out, events=ev, **kw2)
+            torch.cuda.synchronize()
+            ms = ev[0].elapsed_time(ev[1])
+            walls.setdefault((label, iters), []).append(ms)
+            print(json.dumps({"kernel": f"{iters} {label} RL iterations, {route}", "path": plan.path, "grid": oshape,
+                              "iterations": iters, "ms": ms, "ms_per_iteration": ms / iters}), flush=True)
+        plain = min(walls[("plain", 20)])
+        print(json.dumps({"kernel": f"accelerated against 20 plain iterations, {route}", "path": plan.path, "grid": oshape,
+                          "ms_20_plain": plain,
+                          **{f"ratio_{k}_accelerated": walls[("accelerated", k)][0] / plain for k in (9, 10, 15)}}), flush=True)
+        plan.release()
+        del plan
+        torch.cuda.empty_cache()
 
 
 def _rl_fft(args, torch, dev, g, oshape):
