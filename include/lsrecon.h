@@ -717,6 +717,38 @@ int lsr_peak_abs_shifted_f32(const float* in, int64_t Z, int64_t Y, int64_t X, l
                              void* scratch, lsr_stream_t stream);
 
 /*
+ * Bead detection and PSF averaging (csrc/peaks.hip, shrimpy_amd/psf.py): what scripts/measure_psf.py hands to biahub's
+ * _characterize_psf, which is not vendored -- PARITY UNPINNED, the rule is defined here (tests/psf_ref.py restates it).
+ * lsr_box_smooth_f32: the smoothing in front of the detection: `taps` (odd, <= 129, taps / 2 < every extent) equal weights
+ *   `tap` per axis, mirrored borders (index -k -> k: scipy.ndimage.correlate1d(mode="mirror")), one launch per axis with
+ *   float64 sums in tap order and float64 results between the passes, rounded to float32 once -- within one unit of 2^-24
+ *   of the float64 filter per voxel (three chained float32 passes reach 3 and can reach 4.5).  `scratch`:
+ *   lsr_box_smooth_scratch_bytes(Z, Y, X, &bytes) bytes of device memory, 8-byte aligned.  out must not be in.
+ * lsr_local_max_candidates_f32: the peaks of the (smoothed) volume s under a box window of half-widths (rz, ry, rx) <= 64
+ *   (LSR_E_UNSUPPORTED beyond).  Voxel p is a peak iff s(p) >= threshold, s(p) >= s(q) for every in-volume q of its window
+ *   and s(p) > s(q) for every such q of smaller linear index (ties: the first in C order); NaNs are never peaks and leave
+ *   no peak within their reach.  Every peak is appended, in no particular order, as (linear index, value) to cand_index /
+ *   cand_value (`capacity` entries each, device) through *count (one device counter, zeroed by the call); the counter
+ *   keeps counting past the capacity while nothing is stored there, so *count > capacity afterwards means the buffers were
+ *   too small.  `scratch`: lsr_local_max_scratch_bytes(Z, Y, X, &bytes) bytes of device memory (two volumes: the separable
+ *   box maximum's partial results).  Three launches, no host synchronisation.
+ * lsr_psf_accumulate_f32: psf (pz * py * px float32, odd extents <= 129) = the mean over the contributing beads of
+ *   (patch - B) / S, patches centred on the linear indices `centres` (n_beads, device), B = the float64 mean of the patch's
+ *   outer shell (its six faces), S = sum(patch - B) in float64 in a fixed order; bead_stats (n_beads x {B, S}, float64,
+ *   device) is written for the caller.  A bead with S <= 0 (or whose patch does not fit the volume: B = S = 0) contributes
+ *   nothing; with no contributing bead the result is zeros.  Float64 accumulation in list order: reproducible bits.
+ */
+int lsr_box_smooth_scratch_bytes(int64_t Z, int64_t Y, int64_t X, int64_t* bytes);
+int lsr_box_smooth_f32(const float* in, float* out, int64_t Z, int64_t Y, int64_t X, int taps, float tap, void* scratch,
+                       lsr_stream_t stream);
+int lsr_local_max_scratch_bytes(int64_t Z, int64_t Y, int64_t X, int64_t* bytes);
+int lsr_local_max_candidates_f32(const float* s, int64_t Z, int64_t Y, int64_t X, int rz, int ry, int rx, float threshold,
+                                 long long* cand_index, float* cand_value, int64_t capacity, unsigned long long* count,
+                                 void* scratch, lsr_stream_t stream);
+int lsr_psf_accumulate_f32(const float* vol, int64_t Z, int64_t Y, int64_t X, const long long* centres, int64_t n_beads,
+                           int pz, int py, int px, double* bead_stats, float* psf, lsr_stream_t stream);
+
+/*
  * Host twins (csrc/host_twins.hip): the same signatures with HOST pointers, the same argument checks and the
  * same arithmetic in the same order, so the results equal the device entry points' bit for bit.  They serve
  * the boxes where the reference itself resolves to the CPU (shrimpy/preprocessing.py:78-82 -- its CI has no
@@ -802,6 +834,17 @@ int lsr_cross_power_c64_cpu(float* a, const float* b, int64_t n, lsr_stream_t st
 int lsr_cross_power_into_c64_cpu(const float* a, float* b, int64_t n, lsr_stream_t stream);
 int lsr_peak_abs_shifted_f32_cpu(const float* in, int64_t Z, int64_t Y, int64_t X, long long* out_index,
                                  void* scratch, lsr_stream_t stream);
+
+/* ... of the bead detection and the PSF average (csrc/peaks.hip): the same peaks (callers sort them) and the same bits of
+ * bead_stats and psf; every pointer HOST memory, `scratch` unused (the twin allocates its three volumes itself) */
+int lsr_box_smooth_f32_cpu(const float* in, float* out, int64_t Z, int64_t Y, int64_t X, int taps, float tap, void* scratch,
+                           lsr_stream_t stream);
+int lsr_local_max_candidates_f32_cpu(const float* s, int64_t Z, int64_t Y, int64_t X, int rz, int ry, int rx,
+                                     float threshold, long long* cand_index, float* cand_value, int64_t capacity,
+                                     unsigned long long* count, void* scratch, lsr_stream_t stream);
+int lsr_psf_accumulate_f32_cpu(const float* vol, int64_t Z, int64_t Y, int64_t X, const long long* centres,
+                               int64_t n_beads, int pz, int py, int px, double* bead_stats, float* psf,
+                               lsr_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -10,6 +10,7 @@ CPU path (biahub's; the reference's own CLI has only ``acquire`` and ``gui``,
     python -m shrimpy_amd.cli deconvolve  -i in.zarr  -c deconvolve.yml  -o deconvolved.zarr
     python -m shrimpy_amd.cli reconstruct -i raw.zarr -c recon.yml       -o recon.zarr
     python -m shrimpy_amd.cli estimate-registration -s moving.zarr -t target.zarr -o register.yml
+    python -m shrimpy_amd.cli characterize-psf -i beads.zarr -c psf.yml -o psf.zarr
 
 Every (position, timepoint, channel) volume is an independent unit.  Launched under
 ``python -m torch.distributed.run --nproc-per-node N`` each rank takes the units
@@ -769,6 +770,91 @@ def run_estimate(source_path, target_path, output_path, source_channel=None, tar
         return {"output": str(output_path), "rms": est.rms, "gain": est.gain, "offset": est.offset,
                 "iterations": est.iterations, "converged": est.converged,
                 "affine_transform_zyx": doc["affine_transform_zyx"]}
+    finally:
+        if created:
+            import torch.distributed as dist
+
+            dist.destroy_process_group()
+
+
+@cli.command("characterize-psf")
+@click.option("-i", "--input-position-dirpaths", "input_path", required=True, type=click.Path(exists=True, path_type=Path),
+              help="Store holding the bead volume (deskewed, for a PSF that `deconvolve` applies to deskewed data).")
+@click.option("-c", "--config-filepath", "config", required=True, type=click.Path(exists=True, dir_okay=False, path_type=Path),
+              help="CharacterizeSettings YAML (the keys of scripts/measure_psf.py:20-50, plus axis_labels and patch_size).")
+@click.option("-o", "--output-dirpath", "output_path", required=True, type=click.Path(path_type=Path),
+              help="OME-Zarr store to write the averaged PSF to (what `deconvolve --psf-dirpath` reads); peaks.csv and "
+                   "report.json are written inside it.")
+@click.option("-p", "--position", default=None, help='Position key ("row/col/fov") (default: the first).')
+@click.option("--timepoint", type=int, default=0, show_default=True)
+@click.option("--channel", default=None, help="Channel name (default: the first).")
+@click.option("--io", "io_backend", type=click.Choice(["auto", "native", "iohub"]), default="auto", show_default=True)
+def characterize_psf(input_path, config, output_path, position, timepoint, channel, io_backend):
+    """Detect the beads of a volume and average them into a PSF (PARITY UNPINNED: the rule is this package's own)."""
+    click.echo(run_characterize(input_path, config, output_path, position, timepoint, channel, io_backend))
+
+
+def run_characterize(input_path, config, output_path, position=None, timepoint: int = 0, channel=None,
+                     io_backend: str = "auto") -> dict:
+    """Read one bead volume, characterise it (:func:`psf.characterize_psf`), write the PSF store -- HCS, position
+    ``0/0/0``, array ``"0"``, T = C = 1, the input's scale: the layout ``DeconvolveSettings.load_psf`` reads -- with
+    ``peaks.csv`` (z, y, x, value, isolated, fwhm_z, fwhm_y, fwhm_x; widths in voxels) and ``report.json`` inside it."""
+    import csv
+    import json
+
+    import torch
+
+    from .io.omezarr import as_volume_array, open_ome_zarr, position_scale
+    from .psf import characterize_psf as characterize
+    from .settings import CharacterizeSettings
+
+    settings = CharacterizeSettings.from_yaml(config)
+    output_path = Path(output_path)
+    if output_path.exists() and any(output_path.iterdir()):
+        raise click.ClickException(f"-o: {output_path} exists and is not empty")
+    _, _, device, created = _distributed()
+    try:
+        _, positions = _open_source(Path(input_path), io_backend)
+        key = position or next(iter(positions))
+        if key not in positions:
+            raise click.ClickException(f"position {key!r} not in {input_path} (it has {list(positions)})")
+        pos = positions[key]
+        names = list(pos.channel_names)
+        if channel is None:
+            c = 0
+        elif channel in names:
+            c = names.index(channel)
+        else:
+            raise click.ClickException(f"channel {channel!r} not in {input_path} (it has {names})")
+        arr = as_volume_array(pos["0"])
+        if not 0 <= timepoint < arr.shape[0]:
+            raise click.ClickException(f"timepoint {timepoint} out of range for {input_path} (T = {arr.shape[0]})")
+        scale = tuple(float(v) for v in position_scale(pos)[-3:])
+        volume = torch.as_tensor(np.ascontiguousarray(arr.read_volume(timepoint, c), dtype=np.float32), device=device)
+        try:
+            res = characterize(volume, settings, scale)
+        except ValueError as exc:
+            raise click.ClickException(str(exc)) from exc
+        psf = res.psf.cpu().numpy()
+        with open_ome_zarr(output_path, layout="hcs", mode="w", channel_names=[names[c] if names else "PSF"],
+                           version="0.5", prefer_iohub=False) as store:
+            out = store.create_position("0", "0", "0").create_zeros("0", shape=(1, 1) + psf.shape, dtype="float32",
+                                                                      scale=(1.0, 1.0) + scale)
+            out.write_volume(0, 0, psf)
+        with open(output_path / "peaks.csv", "w", newline="") as f:
+            w = csv.writer(f)
+            w.writerow(["z", "y", "x", "value", "isolated", "fwhm_z", "fwhm_y", "fwhm_x"])
+            for (z, y, x), v, iso, fw in zip(res.peaks, res.values, res.isolated, res.fwhm_vox_zyx):
+                w.writerow([int(z), int(y), int(x), repr(float(v)), int(iso)] + [repr(float(q)) for q in fw])
+        report = dict(res.report(), input=str(input_path), position=key, timepoint=int(timepoint),
+                      channel=names[c] if names else str(c), volume_shape_zyx=[int(n) for n in volume.shape],
+                      skipped=[int(i) for i in res.skipped], settings=settings.model_dump(mode="json"),
+                      parity="UNPINNED: the detection rule is shrimpy_amd's own (biahub's _characterize_psf is not vendored)")
+        with open(output_path / "report.json", "w") as f:
+            json.dump(report, f, indent=1)
+        return {"output": str(output_path), "n_peaks": report["n_peaks"], "n_isolated": report["n_isolated"],
+                "n_averaged": report["n_averaged"], "patch_shape_zyx": report["patch_shape_zyx"],
+                "psf_fwhm_vox_zyx": report["psf_fwhm_vox_zyx"], "psf_fwhm_zyx": report["psf_fwhm_zyx"]}
     finally:
         if created:
             import torch.distributed as dist

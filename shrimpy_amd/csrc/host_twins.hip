@@ -30,6 +30,8 @@
 #include <atomic>
 #include <cmath>
 #include <cstring>
+#include <limits>
+#include <type_traits>
 #include <mutex>
 #include <new>
 #include <system_error>
@@ -720,6 +722,187 @@ extern "C" int lsr_rl_accel_predict_f32_cpu(const float* x1, int64_t x1_pitch, i
       float* b = x0 + z * x0_plane + y * x0_pitch;
       if (first) for (int64_t x = 0; x < X; ++x) b[x] = ac::predict_first(a[x]);
       else for (int64_t x = 0; x < X; ++x) b[x] = ac::predict_of(alpha, a[x], b[x]);
+    }
+  });
+  return LSR_OK;
+}
+
+// ---- bead detection and PSF averaging (peaks.hip): the same rule, the same sums in the same order ----
+#include "peaks.hpp"
+
+namespace {
+
+// out(i) = max of in over [i - r, i + r] within [0, L) along one line (van Herk / Gil-Werman on the -inf padded line);
+// `pad`, `g`, `h` are the worker's buffers of at least L + 4 r + 1 floats
+void line_max(const float* in, float* out, int64_t L, int64_t stride, int r, float* pad, float* g, float* h) {
+  using lsr::peaks::nmax;
+  const float ninf = -std::numeric_limits<float>::infinity();
+  const int64_t w = 2 * r + 1, total = lsr::ceil_div(L + 2 * r, w) * w;
+  for (int64_t j = 0; j < total; ++j) pad[j] = (j >= r && j < L + r) ? in[(j - r) * stride] : ninf;
+  for (int64_t b = 0; b < total; b += w) {
+    g[b] = pad[b];
+    for (int64_t t = 1; t < w; ++t) g[b + t] = nmax(g[b + t - 1], pad[b + t]);
+    h[b + w - 1] = pad[b + w - 1];
+    for (int64_t t = w - 2; t >= 0; --t) h[b + t] = nmax(h[b + t + 1], pad[b + t]);
+  }
+  for (int64_t i = 0; i < L; ++i) out[i * stride] = nmax(h[i], g[i + w - 1]);
+}
+
+struct Candidate {
+  long long index;
+  float value;
+};
+
+}  // namespace
+
+extern "C" int lsr_box_smooth_f32_cpu(const float* in, float* out, int64_t Z, int64_t Y, int64_t X, int taps, float tap,
+                                      void* /* scratch: unused */, lsr_stream_t) {
+  if (int rc = lsr::peaks::check_box_smooth(in, out, Z, Y, X, taps, tap)) return rc;
+  const int64_t n = Z * Y * X;
+  std::vector<double> a, b;
+  try {
+    a.resize(static_cast<size_t>(n));
+    b.resize(static_cast<size_t>(n));
+  } catch (const std::bad_alloc&) {
+    return lsr::fail(LSR_E_ARG, "lsr_box_smooth_f32_cpu: out of memory for two float64 volumes of %lld voxels", (long long)n);
+  }
+  const double t = static_cast<double>(tap);
+  const int r = taps / 2;
+  auto pass = [&](auto* src, auto* dst, int64_t L, int64_t inner) {
+    using TOut = std::remove_reference_t<decltype(*dst)>;
+    parallel_ranges(n, [&](int64_t first, int64_t last) {
+      for (int64_t e = first; e < last; ++e) {
+        const int64_t i = (e / inner) % L;
+        const auto* line = src + (e - i * inner);
+        double acc = 0.0;
+        for (int k = 0; k < taps; ++k) acc += t * static_cast<double>(line[lsr::peaks::mirror(i - r + k, L) * inner]);
+        dst[e] = static_cast<TOut>(acc);
+      }
+    });
+  };
+  pass(in, a.data(), X, int64_t(1));
+  pass(a.data(), b.data(), Y, X);
+  pass(b.data(), out, Z, Y * X);
+  return LSR_OK;
+}
+
+extern "C" int lsr_local_max_candidates_f32_cpu(const float* s, int64_t Z, int64_t Y, int64_t X, int rz, int ry, int rx,
+                                                float threshold, long long* cand_index, float* cand_value,
+                                                int64_t capacity, unsigned long long* count, void* /* scratch: unused */,
+                                                lsr_stream_t) {
+  if (int rc = lsr::peaks::check_local_max(s, Z, Y, X, rz, ry, rx, threshold, cand_index, cand_value, capacity, count))
+    return rc;
+  const int64_t n = Z * Y * X, plane = Y * X;
+  std::atomic<bool> failed{false};
+  std::vector<float> a, b, m;
+  try {
+    a.resize(static_cast<size_t>(n));
+    b.resize(static_cast<size_t>(n));
+    m.resize(static_cast<size_t>(n));
+  } catch (const std::bad_alloc&) {
+    return lsr::fail(LSR_E_ARG, "lsr_local_max_candidates_f32_cpu: out of memory for three volumes of %lld voxels", (long long)n);
+  }
+  const int64_t longest = std::max(Z, std::max(Y, X)) + 4 * lsr::peaks::kMaxHalfWidth + 1;
+  auto pass = [&](const float* in, float* out, int64_t lines, int64_t L, int64_t stride, int r, auto&& base_of) {
+    parallel_ranges(lines, [&](int64_t first, int64_t last) {
+      std::vector<float> buf(static_cast<size_t>(3 * longest));
+      for (int64_t ln = first; ln < last; ++ln) {
+        const int64_t base = base_of(ln);
+        line_max(in + base, out + base, L, stride, r, buf.data(), buf.data() + longest, buf.data() + 2 * longest);
+      }
+    }, failed);
+  };
+  pass(s, a.data(), Z * Y, X, 1, rx, [&](int64_t ln) { return ln * X; });
+  pass(a.data(), b.data(), Z * X, Y, X, ry, [&](int64_t ln) { return (ln / X) * plane + ln % X; });
+  pass(b.data(), m.data(), plane, Z, plane, rz, [&](int64_t ln) { return ln; });
+  std::vector<std::vector<Candidate>> found(1024);
+  const int used = lsr::parallel_ranges_indexed(Z * Y, [&](int rank, int64_t first, int64_t last) {
+    std::vector<Candidate>& mine = found[rank];
+    for (int64_t row = first; row < last; ++row) {
+      const int64_t z = row / Y, y = row - z * Y;
+      for (int64_t x = 0; x < X; ++x) {
+        const int64_t lin = row * X + x;
+        const float sv = s[lin];
+        if (!(sv == m[lin] && sv >= threshold)) continue;
+        bool tie = false;
+        for (int64_t d = std::min<int64_t>(rx, x); d > 0 && !tie; --d) tie = s[lin - d] >= sv;
+        for (int64_t d = std::min<int64_t>(ry, y); d > 0 && !tie; --d) tie = a[lin - d * X] >= sv;
+        for (int64_t d = std::min<int64_t>(rz, z); d > 0 && !tie; --d) tie = b[lin - d * plane] >= sv;
+        if (!tie) mine.push_back(Candidate{static_cast<long long>(lin), sv});
+      }
+    }
+  }, failed);
+  LSR_REQUIRE(!failed.load(), LSR_E_ARG, "lsr_local_max_candidates_f32_cpu: out of memory in a worker");
+  unsigned long long total = 0;
+  for (int k = 0; k < used; ++k)
+    for (const Candidate& c : found[k]) {
+      if (total < static_cast<unsigned long long>(capacity)) {
+        cand_index[total] = c.index;
+        cand_value[total] = c.value;
+      }
+      ++total;
+    }
+  *count = total;
+  return LSR_OK;
+}
+
+extern "C" int lsr_psf_accumulate_f32_cpu(const float* vol, int64_t Z, int64_t Y, int64_t X, const long long* centres,
+                                          int64_t n_beads, int pz, int py, int px, double* bead_stats, float* psf,
+                                          lsr_stream_t) {
+  namespace pk = lsr::peaks;
+  if (int rc = pk::check_psf_accumulate(vol, Z, Y, X, centres, n_beads, pz, py, px, bead_stats, psf)) return rc;
+  const int n = pz * py * px;
+  constexpr int kTree = pk::kTreeThreads;
+  // the kernel's tree: partial sum t takes elements t, t + 256, ... in order, then red[t] += red[t + w], w = 128 .. 1
+  auto tree = [](double* red) {
+    for (int w = kTree / 2; w > 0; w >>= 1)
+      for (int t = 0; t < w; ++t) red[t] += red[t + w];
+    return red[0];
+  };
+  parallel_ranges(n_beads, [&](int64_t first, int64_t last) {
+    double red[kTree];
+    for (int64_t b = first; b < last; ++b) {
+      int64_t z0 = 0, y0 = 0, x0 = 0;
+      if (!pk::patch_origin(centres[b], Z, Y, X, pz, py, px, z0, y0, x0)) {
+        bead_stats[2 * b] = bead_stats[2 * b + 1] = 0.0;
+        continue;
+      }
+      const float* corner = vol + (z0 * Y + y0) * X + x0;
+      auto at = [&](int e) {
+        const int iz = e / (py * px), rem = e - iz * (py * px), iy = rem / px, ix = rem - iy * px;
+        return corner[(iz * Y + iy) * X + ix];
+      };
+      for (int t = 0; t < kTree; ++t) {
+        double acc = 0.0;
+        for (int e = t; e < n; e += kTree) {
+          const int iz = e / (py * px), rem = e - iz * (py * px), iy = rem / px, ix = rem - iy * px;
+          if (pk::on_shell(iz, iy, ix, pz, py, px)) acc += static_cast<double>(at(e));
+        }
+        red[t] = acc;
+      }
+      const double bg = tree(red) / static_cast<double>(pk::shell_count(pz, py, px));
+      for (int t = 0; t < kTree; ++t) {
+        double acc = 0.0;
+        for (int e = t; e < n; e += kTree) acc += static_cast<double>(at(e)) - bg;
+        red[t] = acc;
+      }
+      bead_stats[2 * b] = bg;
+      bead_stats[2 * b + 1] = tree(red);
+    }
+  });
+  parallel_ranges(n, [&](int64_t first, int64_t last) {
+    for (int64_t e = first; e < last; ++e) {
+      const int64_t iz = e / (py * px), rem = e - iz * (py * px), iy = rem / px, ix = rem - iy * px;
+      double acc = 0.0;
+      int used = 0;
+      for (int64_t b = 0; b < n_beads; ++b) {
+        const double bg = bead_stats[2 * b], total = bead_stats[2 * b + 1];
+        int64_t z0 = 0, y0 = 0, x0 = 0;
+        if (!(total > 0.0) || !pk::patch_origin(centres[b], Z, Y, X, pz, py, px, z0, y0, x0)) continue;
+        acc += (static_cast<double>(vol[((z0 + iz) * Y + y0 + iy) * X + x0 + ix]) - bg) / total;
+        ++used;
+      }
+      psf[e] = used > 0 ? static_cast<float>(acc / static_cast<double>(used)) : 0.0f;
     }
   });
   return LSR_OK;

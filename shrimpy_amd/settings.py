@@ -10,6 +10,8 @@ Field names are evidenced at ``shrimpy/dynatrack/tracking.py:200-204``,
 ``scripts/measure_psf.py:225``.  The strict-validation idiom is the reference's own
 (``shrimpy/config.py:82-127``).
 
+``CharacterizeSettings`` takes the keyword arguments of the reference's PSF script (``scripts/measure_psf.py:20-50``).
+
 ``RegisterSettings`` and ``DeconvolveSettings`` have no reference counterpart (registration and
 deconvolution are "being developed", ``docs/data_structure.md:58-62``); they follow the same idiom.
 """
@@ -284,6 +286,69 @@ class DeconvolveSettings(_StrictModel):
                                 else "129 taps per axis")
                              + "; give psf_shape_zyx (odd) to cut it around its peak")
         return np.ascontiguousarray(psf, dtype=np.float32)
+
+
+class CharacterizeSettings(_StrictModel):
+    """Bead detection and PSF characterisation (``shrimpy_amd/psf.py``, the ``characterize-psf`` command).
+
+    The field names are those of the reference's call sites (``scripts/measure_psf.py:20-50, 194-203, 253-263``:
+    ``CharacterizeSettings(**bead_detection_settings, axis_labels=..., patch_size=...)``); the arithmetic behind them is
+    biahub's and not vendored -- PARITY UNPINNED, the detection rule is this package's own (an exact sliding-window
+    maximum, see ``shrimpy_amd/psf.py``).
+
+    ``blur_kernel_size`` (odd): equal-tap box smoothing before detection; ``min_distance``: the window half-widths in
+    voxels (one integer or ``(z, y, x)``, each <= 64); ``threshold_abs``: the least smoothed value of a peak;
+    ``exclude_border``: peaks closer than this many voxels to a face are dropped; ``max_num_peaks``: keep the N brightest;
+    ``patch_size``: the PSF patch ``(z, y, x)`` in the store's physical units, converted with the store's scale and
+    rounded up to odd voxel counts (default: 15 x 18 x 18 voxels, ``scripts/measure_psf.py:187``, i.e. 15 x 19 x 19).
+    ``block_size``, ``nms_distance`` and ``device`` are accepted for call-site compatibility and **unused**: they
+    parametrise biahub's block-pooling detector, detection here is an exact sliding window and runs where the volume is.
+    ``axis_labels`` is recorded in the report only.
+    """
+
+    block_size: tuple[PositiveInt, PositiveInt, PositiveInt] = (8, 8, 8)
+    blur_kernel_size: PositiveInt = 3
+    nms_distance: Optional[NonNegativeInt] = None
+    min_distance: Union[NonNegativeInt, tuple[NonNegativeInt, NonNegativeInt, NonNegativeInt]] = 20
+    threshold_abs: float = 200.0
+    max_num_peaks: Optional[PositiveInt] = 500
+    exclude_border: tuple[NonNegativeInt, NonNegativeInt, NonNegativeInt] = (5, 5, 5)
+    device: str = "cuda"
+    axis_labels: tuple[str, str, str] = ("Z", "Y", "X")
+    patch_size: Optional[tuple[PositiveFloat, PositiveFloat, PositiveFloat]] = None
+
+    @field_validator("blur_kernel_size")
+    @classmethod
+    def _odd_blur(cls, v):
+        if v % 2 == 0 or v > 129:
+            raise ValueError("blur_kernel_size must be odd (and <= 129)")
+        return v
+
+    @field_validator("min_distance")
+    @classmethod
+    def _window_limit(cls, v):
+        if max((v,) if isinstance(v, int) else v) > 64:
+            raise ValueError("min_distance: the window half-widths are limited to 64 voxels per axis")
+        return v
+
+    @field_validator("threshold_abs")
+    @classmethod
+    def _finite_threshold(cls, v):
+        if not np.isfinite(v):
+            raise ValueError("threshold_abs must be finite")
+        return v
+
+    def patch_shape_zyx(self, zyx_scale=(1.0, 1.0, 1.0)) -> tuple[int, int, int]:
+        """``patch_size`` in voxels of a store with ``zyx_scale``: ``ceil(size / scale)`` rounded up to odd."""
+        scale = tuple(float(s) for s in zyx_scale)
+        if len(scale) != 3 or not all(s > 0 and np.isfinite(s) for s in scale):
+            raise ValueError(f"zyx_scale must be three positive numbers, got {zyx_scale!r}")
+        size = self.patch_size if self.patch_size is not None else (15 * scale[0], 18 * scale[1], 18 * scale[2])
+        out = []
+        for length, s in zip(size, scale):
+            n = max(1, int(np.ceil(length / s - 1e-6)))       # (15 * s / s may come out as 15.000000000000002)
+            out.append(n if n % 2 else n + 1)
+        return tuple(out)
 
 
 class ReconstructSettings(_StrictModel):

@@ -47,6 +47,10 @@ def main():
     ap.add_argument("--rl-accel", action="store_true", help="only: ms per launch of the Biggs-Andrews extrapolation, per "
                     "accelerated iteration and the wall time of 9 / 10 / 15 accelerated beside 20 plain iterations on the "
                     "fused separable, ky (x) kzx and Fourier routes, on --rl-grid")
+    ap.add_argument("--peaks", action="store_true", help="only: ms of the bead-detection launches (csrc/peaks.hip) at "
+                    "min_distance 10 and 50 and of the box smoothing in front of them, on --rl-grid")
+    ap.add_argument("--peaks-host", action="store_true", help="with --peaks: also time scipy.ndimage.maximum_filter for "
+                    "the same windows on this box's host cores")
     ap.add_argument("--psf-sweep-wide", action="store_true", help="with --psf-sweep: every pz for in-plane extents 9-15")
     args = ap.parse_args()
 
@@ -61,6 +65,9 @@ def main():
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(3)
 
+    if args.peaks:
+        _peaks(args, torch, dev, g, tuple(int(v) for v in args.rl_grid.split(",")))
+        return
     if args.rl_fft:
         _rl_fft(args, torch, dev, g, tuple(int(v) for v in args.rl_grid.split(",")))
         return
@@ -327,6 +334,56 @@ def _rl_tv(args, torch, dev, g, bench, RichardsonLucyPlan, oshape):
         print(json.dumps({"kernel": label, "path": plan.path, "grid": oshape, "iterations": iters,
                           "ms_per_iteration": ev[0].elapsed_time(ev[1]) / iters}), flush=True)
     plan.release()
+
+
+def _peaks(args, torch, dev, g, oshape):
+    """Bead detection (csrc/peaks.hip): the three launches of lsr_local_max_candidates_f32 -- x, y and the fused z pass
+    of the separable box maximum -- on a smoothed Poisson volume with a few hundred beads, per min_distance; 24 algorithmic
+    bytes per voxel (s, A and B each written or read once per pass; the marching passes read every input twice, the
+    second time from cache).  --peaks-host: scipy's maximum_filter over the same window on the host, the step a user
+    without this kernel would run."""
+    import ctypes
+    import time
+
+    from shrimpy_amd import _lib, psf
+
+    z, y, x = oshape
+    vol = torch.poisson(torch.full(oshape, 100.0, device=dev), generator=g)
+    n = vol.numel()
+    beads = torch.randint(0, n, (400,), device=dev, generator=g)
+    vol.view(-1)[beads] += 30000.0
+    ms = timed(lambda: psf.smooth(vol, 3), args.reps)
+    print(json.dumps({"kernel": "lsr_box_smooth_f32, 3 taps per axis (3 launches, float64 between them)", "grid": oshape, "ms": ms,
+                      "algorithmic_GBps": 40.0 * n / ms / 1e6}), flush=True)
+    s = psf.smooth(vol, 3)
+    del vol
+    nbytes = ctypes.c_int64(0)
+    _lib.call("lsr_local_max_scratch_bytes", z, y, x, ctypes.byref(nbytes))
+    scratch = torch.empty(nbytes.value // 4, dtype=torch.float32, device=dev)
+    capacity = 1 << 20
+    index = torch.empty(capacity, dtype=torch.int64, device=dev)
+    value = torch.empty(capacity, dtype=torch.float32, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    for r in (10, 50):
+        def launch():
+            _lib.call("lsr_local_max_candidates_f32", s.data_ptr(), z, y, x, r, r, r, ctypes.c_float(200.0), index.data_ptr(),
+                      value.data_ptr(), capacity, count.data_ptr(), scratch.data_ptr(), _lib.stream_ptr(dev))
+        ms = timed(launch, args.reps)
+        print(json.dumps({"kernel": "lsr_local_max_candidates_f32 (3 launches)", "grid": oshape, "min_distance": r,
+                          "threshold_abs": 200.0, "peaks": int(count.item()), "ms": ms, "Mvox_per_s": n / ms / 1e3,
+                          "algorithmic_GBps": 24.0 * n / ms / 1e6, "frac_of_8TBps": 24.0 * n / ms / 1e6 / 8000}), flush=True)
+    if args.peaks_host:
+        from scipy import ndimage
+
+        host = s.cpu().numpy()
+        del s, scratch
+        for r in (10, 50):
+            t0 = time.perf_counter()
+            m = ndimage.maximum_filter(host, size=2 * r + 1, mode="constant", cval=-np.inf)
+            found = int(np.count_nonzero((host == m) & (host >= 200.0)))
+            sec = time.perf_counter() - t0
+            print(json.dumps({"kernel": "scipy.ndimage.maximum_filter + compare (host)", "grid": oshape, "min_distance": r,
+                              "maxima": found, "ms": sec * 1e3, "Mvox_per_s": n / sec / 1e6}), flush=True)
 
 
 def _rl_accel(args, torch, dev, g, oshape):
