@@ -710,6 +710,25 @@ int lsr_rl_rows_chain_f32(float* spec, int64_t Z, int64_t Y, int64_t X, const fl
                           int epilogue, const float* aux, float* out, int64_t Zo, int64_t Yo, int64_t Xo, float scale,
                           float eps, int pz, int py, int px, const double* norm_table, float norm_full, double* stats,
                           lsr_stream_t stream);
+/*
+ * Label-free 3-D phase reconstruction (csrc/phase.hip, shrimpy_amd/phase.py): the x legs of a Tikhonov inverse filter
+ * applied in the Fourier domain to a volume that is periodically MIRROR-extended onto the transform grid (Z, Y, X); the
+ * y leg is hipFFT, the z leg lsr_spectrum_multiply_z_c64 with the filter in [XC][Y][Z] (conj_f1 = 0, z_valid = Z).
+ * Mirror rule per axis (n samples, grid g, index i): i < n is sample i; otherwise, with a = i - n and b = g - 1 - i,
+ * sample n - 1 - min(a, n - 1) if a <= b, else sample min(b, n - 1).  Row lengths, tw_half and tw_x as lsr_rfft_rows_t_c64.
+ * lsr_phase_rows_forward_c64: spec[z][k][y] = sum_n v(z, y, n) exp(-2 pi i k n / X) for EVERY row of the grid, v = `in`
+ *   ((Zi, Yi, Xi) <= grid, float32) extended by the rule on all three axes (never written).  mean[0] <- the float64 mean
+ *   of `in`, mean[1] <- its sum: one partial per workgroup in `partial` (lsr_phase_rows_scratch_bytes(Z, Y) bytes, device,
+ *   8-byte aligned), reduced in a fixed order by a second launch (the same bits on every call).
+ * lsr_phase_rows_inverse_f32: out ((Zo, Yo, Xo) float32) = the complex-to-real inverse of spec along x on the grid's first
+ *   (Zo, Yo, Xo) points, times 1 / (Z Y X mean[0]), mean read on the device (no host synchronisation in between).
+ */
+int64_t lsr_phase_rows_scratch_bytes(int64_t Z, int64_t Y);
+int lsr_phase_rows_forward_c64(const float* in, int64_t Zi, int64_t Yi, int64_t Xi, float* spec, int64_t Z, int64_t Y,
+                               int64_t X, const float* tw_half, const float* tw_x, double* partial, double* mean,
+                               lsr_stream_t stream);
+int lsr_phase_rows_inverse_f32(const float* spec, int64_t Z, int64_t Y, int64_t X, const float* tw_half, const float* tw_x,
+                               const double* mean, float* out, int64_t Zo, int64_t Yo, int64_t Xo, lsr_stream_t stream);
 /* b <- a * conj(b): the same product written over the second operand, so that `a` (the spectrum of
  * a reference volume that is compared against many timepoints) can be kept. */
 int lsr_cross_power_into_c64(const float* a, float* b, int64_t n, lsr_stream_t stream);

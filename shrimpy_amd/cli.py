@@ -11,6 +11,7 @@ CPU path (biahub's; the reference's own CLI has only ``acquire`` and ``gui``,
     python -m shrimpy_amd.cli reconstruct -i raw.zarr -c recon.yml       -o recon.zarr
     python -m shrimpy_amd.cli estimate-registration -s moving.zarr -t target.zarr -o register.yml
     python -m shrimpy_amd.cli characterize-psf -i beads.zarr -c psf.yml -o psf.zarr
+    python -m shrimpy_amd.cli phase       -i deskewed.zarr -c phase.yml  -o phase.zarr
 
 Every (position, timepoint, channel) volume is an independent unit.  Launched under
 ``python -m torch.distributed.run --nproc-per-node N`` each rank takes the units
@@ -289,12 +290,14 @@ def _channel_plan(settings: ReconstructSettings, names: list[str], nc: int) -> l
     return [known[c] in reg.source_channel_names for c in range(nc)]
 
 
-def _fingerprint(input_path: Path, settings: ReconstructSettings, shape, dtype, keys) -> str:
+def _fingerprint(input_path: Path, settings: ReconstructSettings, shape, dtype, keys, extra=None) -> str:
     import hashlib
     import json
 
     doc = {"input": str(Path(input_path).resolve()), "settings": settings.model_dump(mode="json"),
            "shape": list(shape), "dtype": str(dtype), "positions": list(keys)}
+    if extra is not None:     # settings of a step that is not part of ReconstructSettings (the phase command)
+        doc["extra"] = extra
     return hashlib.sha256(json.dumps(doc, sort_keys=True).encode()).hexdigest()
 
 
@@ -373,8 +376,12 @@ class _FailLedger:
 def run_store(input_path: Path, output_path: Path, settings: ReconstructSettings, positions=(),
               zarr_version: str = "0.4", reconstructor_factory=None, stage_through_pinned: bool = True,
               resume: bool = False, io_backend: str = "auto", compression: str | None = None,
-              device_codec: bool | None = None, on_error: str = "raise") -> dict:
+              device_codec: bool | None = None, on_error: str = "raise", output_channel_names=None,
+              fingerprint_extra=None) -> dict:
     """Apply ``settings`` to every (position, t, c) volume of ``input_path`` -> ``output_path``.
+
+    ``output_channel_names(names) -> names``: the output store's channel names from the input's (default: the same);
+    ``fingerprint_extra``: JSON-able settings of a ``reconstructor_factory`` step, part of the ``--resume`` fingerprint.
 
     ``device_codec`` (default: on, ``LSR_DEVICE_CODEC=0`` turns it off): with a blosc-zstd output on a GPU the chunk
     frames are written by the device (``io/device_codec.py``) and the host stores them as they are; an input stored as
@@ -400,7 +407,7 @@ def run_store(input_path: Path, output_path: Path, settings: ReconstructSettings
             min_blocks = int(os.environ.get("LSR_DEVICE_DECODE_MIN_BLOCKS", "8192") or 0)
         return _run_store(input_path, output_path, settings, positions, zarr_version, reconstructor_factory,
                           stage_through_pinned, resume, io_backend, compression, rank, world, device, device_codec,
-                          on_error, min_blocks)
+                          on_error, min_blocks, output_channel_names, fingerprint_extra)
     finally:
         if created:
             import torch.distributed as dist
@@ -410,7 +417,7 @@ def run_store(input_path: Path, output_path: Path, settings: ReconstructSettings
 
 def _run_store(input_path, output_path, settings, positions, zarr_version, reconstructor_factory,
                stage_through_pinned, resume, io_backend, compression, rank, world, device, device_codec=True,
-               on_error="raise", min_decode_blocks=0) -> dict:
+               on_error="raise", min_decode_blocks=0, output_channel_names=None, fingerprint_extra=None) -> dict:
     import torch
 
     from .io.omezarr import as_volume_array, create_level, open_ome_zarr, position_scale
@@ -466,7 +473,9 @@ def _run_store(input_path, output_path, settings, positions, zarr_version, recon
     # where output index 0 sits in the target's physical frame: non-zero only when keep_overhang grew the grid below zero
     origin = tuple(getattr(rec, "register_origin", (0, 0, 0)))
     out_translation = [0.0, 0.0] + [float(o) * float(sc) for o, sc in zip(origin, out_scale[2:])] if any(origin) else None
-    ledger = _DoneLedger(output_path, _fingerprint(input_path, settings, shape5, raw_dtype, keys))
+    ledger = _DoneLedger(output_path, _fingerprint(input_path, settings, shape5, raw_dtype, keys, fingerprint_extra))
+    if output_channel_names is not None:
+        channel_names = list(output_channel_names(channel_names or [str(c) for c in range(nc)]))
     fail_ledger = _FailLedger(output_path)
     out_shape5 = (nt, nc, oz, oy, ox)
 
@@ -701,6 +710,39 @@ def reconstruct(input_path, config, output_path, positions, zarr_version, resume
         raise click.ClickException("the config enables no step")
     _finish(run_store(input_path, output_path, s, positions, zarr_version, resume=resume,
                       io_backend=io_backend, compression=compression, on_error=on_error))
+
+
+class _PhaseReconstructor:
+    """``run_store``'s per-volume step of the ``phase`` command: one :class:`shrimpy_amd.phase.PhasePlan` for the store's
+    volume shape; the volume keeps its shape."""
+
+    def __init__(self, phase_settings, raw_shape, _settings, device):
+        from .phase import PhasePlan
+
+        self.device = device
+        self.output_shape = tuple(int(n) for n in raw_shape)
+        self._plan = PhasePlan(self.output_shape, phase_settings, device)
+        logger.info("phase: filter for %s on grid %s ready in %.1f s", self.output_shape, self._plan.grid, self._plan.seconds)
+
+    def __call__(self, raw):
+        import torch
+
+        return self._plan(torch.as_tensor(raw, device=self.device).to(torch.float32).contiguous())
+
+
+@cli.command(cls=_eat_all_command("-i", "--input-position-dirpaths"))
+@_common
+def phase(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error):
+    """Label-free 3-D phase reconstruction of (deskewed) bright-field volumes (config: PhaseSettings YAML)."""
+    from .settings import PhaseSettings
+
+    input_path, positions = _inputs(input_path, positions)
+    s = PhaseSettings.from_yaml(config)
+    _finish(run_store(input_path, output_path, ReconstructSettings(), positions, zarr_version,
+                      reconstructor_factory=functools.partial(_PhaseReconstructor, s), resume=resume, io_backend=io_backend,
+                      compression=compression, on_error=on_error,
+                      output_channel_names=lambda names: ["Phase3D"] if len(names) == 1 else [f"Phase3D_{n}" for n in names],
+                      fingerprint_extra={"phase": s.model_dump(mode="json")}))
 
 
 @cli.command("estimate-registration")

@@ -6,8 +6,8 @@ INTEGRATION.md binds this package underneath THAT code (as ``biahub.deskew``), s
 own module stays the caller; this file is for users who want the same call shape without the
 reference installed.  It is deliberately small:
 
-* which stages run is decided once, at construction (``flatfield`` and/or ``deskew``; ``phase`` and
-  ``vs`` are outside SURVEY.md section 8 and are refused up front);
+* which stages run is decided once, at construction (``flatfield``, ``deskew`` and -- given its ``phase`` block --
+  ``phase``, :mod:`shrimpy_amd.phase`; ``vs``, and ``phase`` without its block, are refused up front);
 * the stack is uploaded once -- camera ``uint16`` stays ``uint16`` over PCIe and in HBM, the kernels
   widen it exactly;
 * when both stages are on, the flat-field median is its own launch and the division happens while
@@ -20,8 +20,9 @@ reference installed.  It is deliberately small:
 
 Contract kept from the reference (names are its API): ``build_preprocessor``'s signature, the
 ``RECON_STEPS`` tuple (``:41``), the returned dict keyed by ``output_channel`` with the optional
-``"deskew"`` intermediate (``:347-355``), ``warm_up`` replacing the working shape by the deskewed
-one (``:224-244``), and errors propagating to the caller after being logged (``:376-383``).
+``"deskew"`` and ``"phase"`` intermediates (``:347-355``), ``warm_up`` replacing the working shape by the deskewed
+one and computing the phase filter for it (``:224-247``), and errors propagating to the caller after being logged
+(``:376-383``).
 """
 
 from __future__ import annotations
@@ -67,13 +68,15 @@ def build_preprocessor(zyx_shape, preprocessing, deskew=None, phase=None, virtua
     otherwise a warmed-up :class:`HotPathPreprocessor`.
 
     ``deskew`` is the plain dict the reference passes (pixel size and scan step already injected by
-    its caller, ``shrimpy/dynatrack/manager.py:297-299``); ``phase`` / ``virtual_staining`` are
-    accepted for signature compatibility and must stay unused.
+    its caller, ``shrimpy/dynatrack/manager.py:297-299``); ``virtual_staining`` is accepted for signature
+    compatibility and must stay unused;
+    ``phase`` is the reference's ``phase:`` block (``transfer_function`` with the pixel sizes injected, ``apply_inverse``):
+    with it, ``'phase'`` in ``preprocessing`` adds the phase stage; without it the step is refused, as ``'vs'`` always is.
     """
     wanted = [s for s in (preprocessing or ()) if s in RECON_STEPS]
     if not wanted:
         return None
-    foreign = [s for s in wanted if s not in _HOT_PATH_STEPS]
+    foreign = [s for s in wanted if s not in _HOT_PATH_STEPS and not (s == "phase" and phase)]
     if foreign:
         raise NotImplementedError(
             f"{foreign}: phase reconstruction (waveorder) and virtual staining (cytoland) are not part "
@@ -83,8 +86,14 @@ def build_preprocessor(zyx_shape, preprocessing, deskew=None, phase=None, virtua
         from .settings import DeskewSettings
 
         settings = DeskewSettings(**deskew)
+    phase_settings = None
+    if "phase" in wanted:
+        from .settings import PhaseSettings
+
+        phase_settings = PhaseSettings(**phase)
     pre = HotPathPreprocessor(zyx_shape, deskew_settings=settings, output_channel=output_channel,
-                              apply_flatfield="flatfield" in wanted, require_gpu=require_gpu)
+                              apply_flatfield="flatfield" in wanted, require_gpu=require_gpu,
+                              phase_settings=phase_settings)
     pre.warm_up()
     return pre
 
@@ -94,8 +103,10 @@ class HotPathPreprocessor:
 
     def __init__(self, zyx_shape, deskew_settings=None, output_channel="phase", apply_flatfield=False,
                  require_gpu=False, phase_settings=None, vs_config=None):
-        if phase_settings is not None or vs_config is not None:
-            raise NotImplementedError("phase / virtual staining settings given to the hot-path adapter")
+        if vs_config is not None:
+            raise NotImplementedError("virtual staining settings given to the hot-path adapter")
+        self._phase_settings = phase_settings
+        self._phase_plan = None
         self._zyx_shape = tuple(int(n) for n in zyx_shape)
         self._deskew_settings = deskew_settings
         self._apply_flatfield = bool(apply_flatfield)
@@ -121,6 +132,13 @@ class HotPathPreprocessor:
             log.info("deskew geometry: raw %s -> %s, voxel %s um (ratio %s)", raw_shape, self._zyx_shape,
                      tuple(round(v, 4) for v in voxel),
                      getattr(self._deskew_settings, "px_to_scan_ratio", None))
+        if self._phase_settings is not None:
+            from .phase import PhasePlan
+
+            log.info("computing the phase transfer function for %s ...", self._zyx_shape)
+            self._phase_plan = PhasePlan(self._zyx_shape, self._phase_settings, self._device)
+            log.info("phase filter ready on %s (grid %s, %.1f s, computed on the host)", self._device,
+                     self._phase_plan.grid, self._phase_plan.seconds)
 
     # ------------------------------------------------------------------ per volume
     def __call__(self, volume_bf, label="", return_intermediates=False) -> dict:
@@ -136,11 +154,15 @@ class HotPathPreprocessor:
             deskewed = None
             if self._deskew_settings is not None:
                 volume = deskewed = self._step(tag, "deskew", self._deskew, volume)
+            if self._phase_settings is not None:
+                volume = self._step(tag, "phase", self._reconstruct_phase, volume)
         finally:
             self._pending_flat_field = None
         out = {self._output_channel: volume}
         if return_intermediates and deskewed is not None and "deskew" not in out:
             out["deskew"] = deskewed
+        if return_intermediates and self._phase_settings is not None:
+            out.setdefault("phase", volume)
         if self._require_gpu:
             on_host = sorted(k for k, v in out.items() if v.device.type != "cuda")
             if on_host:
@@ -204,6 +226,14 @@ class HotPathPreprocessor:
         out = deskew_with_matrix(volume, geo.matrix_3x4, geo.pre_average_shape, avg, flat_field=pattern,
                                  border=kw.get("border", "constant"))
         return orient_volume(out, kw.get("orientation", "identity"))
+
+    def _reconstruct_phase(self, volume):
+        """The Tikhonov inverse filter ``warm_up`` made (``shrimpy_amd/phase.py``: five launches on a HIP device)."""
+        import torch
+
+        if self._phase_plan is None:
+            raise RuntimeError("warm_up() computes the phase filter: call it before the first volume")
+        return self._phase_plan(volume.to(torch.float32))
 
 
 _LabelfreePreprocessor = HotPathPreprocessor   # the reference's class name, for callers that use it

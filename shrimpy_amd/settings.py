@@ -351,6 +351,54 @@ class CharacterizeSettings(_StrictModel):
         return tuple(out)
 
 
+class PhaseTransferFunctionSettings(_StrictModel):
+    """Optics of the 3-D phase transfer function; lengths in micrometres.  Field names as the reference's ``phase:`` block
+    (``config/mda/mantis/dynatrack_demo.yaml:171-178``; ``yx_pixel_size`` / ``z_pixel_size`` are injected by its caller)."""
+
+    wavelength_illumination: PositiveFloat
+    yx_pixel_size: PositiveFloat
+    z_pixel_size: PositiveFloat
+    z_padding: NonNegativeInt = 0
+    index_of_refraction_media: PositiveFloat
+    numerical_aperture_detection: PositiveFloat
+    numerical_aperture_illumination: PositiveFloat
+    invert_phase_contrast: bool = False
+
+    @model_validator(mode="after")
+    def _check_optics(self):
+        na_ill, na_det, n = (self.numerical_aperture_illumination, self.numerical_aperture_detection,
+                             self.index_of_refraction_media)
+        if not na_ill <= na_det < n:
+            raise ValueError(f"need numerical_aperture_illumination <= numerical_aperture_detection < "
+                             f"index_of_refraction_media, got {na_ill}, {na_det}, {n}")
+        if (na_ill + na_det) / self.wavelength_illumination > 1.0 / (2.0 * self.yx_pixel_size):
+            raise ValueError(f"the transfer function's support (NA_ill + NA_det) / wavelength = "
+                             f"{(na_ill + na_det) / self.wavelength_illumination:.4g} / um aliases at yx_pixel_size "
+                             f"{self.yx_pixel_size} um (Nyquist {1.0 / (2.0 * self.yx_pixel_size):.4g} / um)")
+        return self
+
+
+class PhaseInverseSettings(_StrictModel):
+    """``apply_inverse`` of the reference's ``phase:`` block (``dynatrack_demo.yaml:179-181``)."""
+
+    reconstruction_algorithm: Literal["Tikhonov"] = "Tikhonov"
+    regularization_strength: PositiveFloat = 1e-3
+
+    @field_validator("reconstruction_algorithm", mode="before")
+    @classmethod
+    def _tv_is_not_built(cls, v):
+        if v == "TV":
+            raise ValueError("reconstruction_algorithm 'TV' (total-variation regularised phase) is not built: use 'Tikhonov'")
+        return v
+
+
+class PhaseSettings(_StrictModel):
+    """Label-free 3-D phase reconstruction (``shrimpy_amd/phase.py``, the ``phase`` command): the reference's ``phase:`` block."""
+
+    transfer_function: PhaseTransferFunctionSettings
+    apply_inverse: PhaseInverseSettings = PhaseInverseSettings()
+
+
 class ReconstructSettings(_StrictModel):
     """Whole per-volume pipeline: (flat-field) -> deskew -> (register) -> (deconvolve)."""
 

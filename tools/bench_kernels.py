@@ -51,6 +51,9 @@ def main():
                     "min_distance 10 and 50 and of the box smoothing in front of them, on --rl-grid")
     ap.add_argument("--peaks-host", action="store_true", help="with --peaks: also time scipy.ndimage.maximum_filter for "
                     "the same windows on this box's host cores")
+    ap.add_argument("--phase", action="store_true", help="only: one application of the phase reconstruction (yaml optics) on "
+                    "--rl-grid, per launch and in total, the warm-up (host transfer function) time, and one Fourier-domain RL "
+                    "convolution on the same volume as the yardstick; appended to profiles/phase_config2.jsonl")
     ap.add_argument("--psf-sweep-wide", action="store_true", help="with --psf-sweep: every pz for in-plane extents 9-15")
     args = ap.parse_args()
 
@@ -65,6 +68,9 @@ def main():
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(3)
 
+    if args.phase:
+        _phase(args, torch, dev, g, tuple(int(v) for v in args.rl_grid.split(",")))
+        return
     if args.peaks:
         _peaks(args, torch, dev, g, tuple(int(v) for v in args.rl_grid.split(",")))
         return
@@ -489,6 +495,72 @@ def _rl_fft(args, torch, dev, g, oshape):
             del plan
             torch.cuda.empty_cache()
             print(json.dumps(row), flush=True)
+
+
+def _phase(args, torch, dev, g, oshape):
+    """One application of the phase reconstruction (shrimpy_amd/phase.py) on a deskewed volume of ``oshape`` with the optics
+    of the reference's dynatrack_demo.yaml: ms per launch and in total (HIP events), the warm-up seconds; beside it one
+    convolution of the Fourier-domain Richardson-Lucy (forward rows, y, z leg, y back, ratio epilogue) on the same volume
+    with a measured-PSF-sized kernel -- the yardstick: the same legs on a grid without the mirror padding."""
+    import logging
+
+    from shrimpy_amd import _lib, fft3
+    from shrimpy_amd.deconvolve_fft import FftRichardsonLucyPlan
+    from shrimpy_amd.phase import PhasePlan
+
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s %(message)s")
+    settings = dict(transfer_function=dict(wavelength_illumination=0.450, z_padding=5, index_of_refraction_media=1.4,
+                                           numerical_aperture_detection=1.35, numerical_aperture_illumination=0.52,
+                                           invert_phase_contrast=False, yx_pixel_size=0.1133, z_pixel_size=0.17),
+                    apply_inverse=dict(reconstruction_algorithm="Tikhonov", regularization_strength=0.01))
+    y = torch.poisson(torch.full(oshape, 300.0, device=dev), generator=g)
+    out = torch.empty_like(y)
+
+    # the yardstick first (its scratch is released before the phase plan's is made)
+    psf = np.random.default_rng(4).random((15, 19, 19)).astype(np.float32)
+    rl = FftRichardsonLucyPlan(oshape, psf / psf.sum(), dev)
+    rl._scratch()
+
+    def rl_convolution():
+        rl._forward(y)
+        rl._middle(0)
+        rl._epilogue("lsr_irfft_rows_rl_f32", _lib.EPI_RATIO, y, out, 1e-6, None)
+
+    rl_ms = timed(rl_convolution, args.reps)
+    rl_grid = list(rl.grid)
+    rl.release()
+    del rl
+    torch.cuda.empty_cache()
+
+    plan = PhasePlan(oshape, settings, dev)
+    plan(y, out=out)
+    gz, gy, gx = plan.grid
+    z, yy, x = oshape
+    xc, stream = plan._xc, _lib.stream_ptr(dev)
+    b = plan._b
+    launches = {
+        "rows forward": lambda: _lib.call("lsr_phase_rows_forward_c64", y.data_ptr(), z, yy, x, b.data_ptr(), gz, gy, gx,
+                                          plan._half.data_ptr(), plan._full.data_ptr(), plan._partial.data_ptr(),
+                                          plan._mean.data_ptr(), stream),
+        "y forward (hipFFT)": lambda: fft3._exec(dev, fft3._HIPFFT_C2C, gy, gz * xc, b.data_ptr(), b.data_ptr(), fft3._FORWARD),
+        "z leg x filter": lambda: _lib.call("lsr_spectrum_multiply_z_c64", plan._filter.data_ptr(), b.data_ptr(),
+                                            plan._tw_z.data_ptr(), gz, gy, xc, 0, gz, z, stream),
+        "y back (hipFFT)": lambda: fft3._exec(dev, fft3._HIPFFT_C2C, gy, z * xc, b.data_ptr(), b.data_ptr(), fft3._BACKWARD),
+        "rows inverse": lambda: _lib.call("lsr_phase_rows_inverse_f32", b.data_ptr(), gz, gy, gx, plan._half.data_ptr(),
+                                          plan._full.data_ptr(), plan._mean.data_ptr(), out.data_ptr(), z, yy, x, stream),
+    }
+    # (each launch alone, on whatever the spectrum buffer holds: the kernels' time does not depend on the values)
+    per_launch = {name: timed(fn, args.reps) for name, fn in launches.items()}
+    total = timed(lambda: plan(y, out=out), args.reps)       # the whole call, its one wait for the mean included
+    row = {"kernel": "phase reconstruction, one application", "shape": list(oshape), "grid": list(plan.grid),
+           "ms_per_launch": per_launch, "ms_launches_sum": sum(per_launch.values()), "ms_total": total,
+           "warm_up_seconds": plan.seconds, "rl_fft_convolution_ms": rl_ms, "rl_fft_grid": rl_grid,
+           "ratio_to_rl_convolution": total / rl_ms, "device": torch.cuda.get_device_name(dev),
+           "kernel_sources": _lib.kernel_source_sha16()}
+    print(json.dumps(row), flush=True)
+    if list(oshape) == [171, 2048, 2270]:
+        with open(ROOT / "profiles" / "phase_config2.jsonl", "a") as f:
+            f.write(json.dumps(row) + "\n")
 
 
 if __name__ == "__main__":
