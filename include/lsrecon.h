@@ -729,6 +729,38 @@ int lsr_phase_rows_forward_c64(const float* in, int64_t Zi, int64_t Yi, int64_t 
                                lsr_stream_t stream);
 int lsr_phase_rows_inverse_f32(const float* spec, int64_t Z, int64_t Y, int64_t X, const float* tw_half, const float* tw_x,
                                const double* mean, float* out, int64_t Zo, int64_t Yo, int64_t Xo, lsr_stream_t stream);
+/*
+ * Mid-band spectral power of every z plane (csrc/focus.hip, shrimpy_amd/focus.py): the focus measure of the time-lapse
+ * stabilization, waveorder's focus_from_transverse_band -- not vendored, PARITY UNPINNED, the rule is defined here
+ * (tests/focus_ref.py restates it).  The window (Yc, Xc) at (y0, x0) of every plane of `in` ((Z, Y, X) float32) is
+ * transformed, F = fft2(window) unnormalised, and
+ *   out_power[z] = sum of |F(ky, kx)| over the bins with band_lo < r < band_hi,
+ *   r = sqrt((min(ky, Yc - ky) / (Yc pixel_size))^2 + (min(kx, Xc - kx) / (Xc pixel_size))^2)   (float64, both strict).
+ * Lengths (lsr_band_power_supported, LSR_E_UNSUPPORTED otherwise): Xc as lsr_rfft_rows_supported, Yc 5-smooth in [2, 2048].
+ * lsr_band_power_plan (host only): decides the inequalities in float64.  table (host, 2 * (Xc / 2 + 1) int32): for every
+ *   column kx <= Xc / 2 of the half spectrum the closed interval [table[2 kx], table[2 kx + 1]] of min(ky, Yc - ky) inside
+ *   the band (a > b: none).  *k_hi <- the last column that holds a bin (-1: the band is empty), *weighted_bins (may be
+ *   NULL) <- the number of bins of the full spectrum inside the band.
+ * lsr_band_power_scratch_bytes: *spec_bytes, *partial_bytes <- the sizes of spec_scratch and partial (device, 8-byte aligned).
+ * lsr_band_power_f32: table = the first 2 * (k_hi + 1) entries of the plan, in device memory; tw_half, tw_x as
+ *   lsr_rfft_rows_t_c64 for the length Xc; tw_y = exp(-2 pi i k / Yc), k < Yc, complex64.  Three launches: the x leg keeps
+ *   only the columns kx <= k_hi (spec_scratch[z][kx][y], complex64), the y leg transforms eight columns per workgroup in LDS
+ *   and adds |F| over each column's interval and its mirror rows, columns 0 < kx < Xc / 2 twice, in float64 -- one partial
+ *   per workgroup; out_power (Z float64, device) <- the partials of each plane added in a fixed order: the same bits on every
+ *   call, no atomics.  The cropped volume and the y-transformed spectrum are never written.
+ * lsr_band_power_f32_cpu: the same arguments as host pointers (tw_*, spec_scratch and partial are unused and may be NULL),
+ *   float64 transforms: a host route for machines without a GPU, close to but not bit-equal with the kernels.
+ */
+int lsr_band_power_supported(int64_t Yc, int64_t Xc);
+int lsr_band_power_plan(int64_t Yc, int64_t Xc, double pixel_size, double band_lo, double band_hi, int32_t* table,
+                        int64_t* k_hi, int64_t* weighted_bins);
+int lsr_band_power_scratch_bytes(int64_t Z, int64_t Yc, int64_t k_hi, int64_t* spec_bytes, int64_t* partial_bytes);
+int lsr_band_power_f32(const float* in, int64_t Z, int64_t Y, int64_t X, int64_t y0, int64_t x0, int64_t Yc, int64_t Xc,
+                       const float* tw_half, const float* tw_x, const float* tw_y, const int32_t* table, int64_t k_hi,
+                       float* spec_scratch, double* partial, double* out_power, lsr_stream_t stream);
+int lsr_band_power_f32_cpu(const float* in, int64_t Z, int64_t Y, int64_t X, int64_t y0, int64_t x0, int64_t Yc, int64_t Xc,
+                           const float* tw_half, const float* tw_x, const float* tw_y, const int32_t* table, int64_t k_hi,
+                           float* spec_scratch, double* partial, double* out_power, lsr_stream_t stream);
 /* b <- a * conj(b): the same product written over the second operand, so that `a` (the spectrum of
  * a reference volume that is compared against many timepoints) can be kept. */
 int lsr_cross_power_into_c64(const float* a, float* b, int64_t n, lsr_stream_t stream);

@@ -87,6 +87,12 @@ SIGNATURES: dict[str, list] = {
                                    ctypes.c_void_p, _stream],
     "lsr_phase_rows_inverse_f32": [_c_f32p, _i64, _i64, _i64, _c_f32p, _c_f32p, ctypes.c_void_p, _c_f32p, _i64, _i64, _i64,
                                    _stream],
+    "lsr_band_power_supported": [_i64, _i64],
+    "lsr_band_power_plan": [_i64, _i64, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p,
+                            ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)],
+    "lsr_band_power_scratch_bytes": [_i64, _i64, _i64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64)],
+    "lsr_band_power_f32": [_c_f32p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _c_f32p, _c_f32p, _c_f32p, ctypes.c_void_p, _i64,
+                           _c_f32p, ctypes.c_void_p, ctypes.c_void_p, _stream],
     "lsr_cross_correlate_z_supported": [_i64],
     "lsr_cross_correlate_z_c64": [_c_f32p, _c_f32p, _c_f32p, _i64, _i64, _i64, _stream],
     "lsr_transpose_last2_c64": [_c_f32p, _c_f32p, _i64, _i64, _i64, _stream],
@@ -209,7 +215,9 @@ for _name in ("lsr_deskew_f32", "lsr_deskew_u16", "lsr_deskew_cval", "lsr_affine
               # ... and of the device-side chunk codecs (csrc/blosc_encode.hip)
               "lsr_blosc_encode_device", "lsr_blosc_decode_device",
               # ... and of the bead detection and the PSF average (csrc/peaks.hip)
-              "lsr_box_smooth_f32", "lsr_local_max_candidates_f32", "lsr_psf_accumulate_f32"):
+              "lsr_box_smooth_f32", "lsr_local_max_candidates_f32", "lsr_psf_accumulate_f32",
+              # ... and of the focus measure (csrc/focus.hip)
+              "lsr_band_power_f32"):
     SIGNATURES[_name + "_cpu"] = SIGNATURES[_name]
 SIGNATURES["lsr_rl_tv_scale_f32_cpu"] = SIGNATURES["lsr_rl_tv_scale_f32"][:-1]     # (this twin takes no stream)
 for _name in ("lsr_rl_accel_dots_f32", "lsr_rl_accel_predict_f32"):                    # (nor do these)

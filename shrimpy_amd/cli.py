@@ -12,6 +12,8 @@ CPU path (biahub's; the reference's own CLI has only ``acquire`` and ``gui``,
     python -m shrimpy_amd.cli estimate-registration -s moving.zarr -t target.zarr -o register.yml
     python -m shrimpy_amd.cli characterize-psf -i beads.zarr -c psf.yml -o psf.zarr
     python -m shrimpy_amd.cli phase       -i deskewed.zarr -c phase.yml  -o phase.zarr
+    python -m shrimpy_amd.cli estimate-stabilization -i series.zarr -c estimate.yml -o stabilization/
+    python -m shrimpy_amd.cli stabilize   -i series.zarr -c stabilization/ -o stabilized.zarr
 
 Every (position, timepoint, channel) volume is an independent unit.  Launched under
 ``python -m torch.distributed.run --nproc-per-node N`` each rank takes the units
@@ -546,7 +548,10 @@ def _run_store(input_path, output_path, settings, positions, zarr_version, recon
         fail_ledger.clear(u)
 
     def process(data, unit: Unit):
-        return (rec if warp[unit.c] else rec_unwarped)(data)
+        step = rec if warp[unit.c] else rec_unwarped
+        # a step that works differently from unit to unit (stabilize: one matrix per timepoint) hands out its callable
+        for_unit = getattr(step, "for_unit", None)
+        return (step if for_unit is None else for_unit(unit))(data)
 
     stager = None
     if (stage_through_pinned and torch.device(device).type == "cuda"
@@ -902,6 +907,181 @@ def run_characterize(input_path, config, output_path, position=None, timepoint: 
             import torch.distributed as dist
 
             dist.destroy_process_group()
+
+
+def _position_file(key: str) -> str:
+    return key.replace("/", "_") + ".yml"
+
+
+@cli.command("estimate-stabilization", cls=_eat_all_command("-i", "--input-position-dirpaths"))
+@click.option("-i", "--input-position-dirpaths", "input_path", required=True, multiple=True, type=click.UNPROCESSED,
+              help="Time-lapse store (HCS plate or single FOV), or position directories of one plate.")
+@click.option("-c", "--config-filepath", "config", required=True, type=click.Path(exists=True, dir_okay=False, path_type=Path),
+              help="EstimateStabilizationSettings YAML.")
+@click.option("-o", "--output-dirpath", "output_path", required=True, type=click.Path(file_okay=False, path_type=Path),
+              help="Directory for one StabilizationSettings YAML per position, <row>_<col>_<fov>.yml.")
+@click.option("-p", "--position", "positions", multiple=True, help='Restrict to these position keys ("row/col/fov").')
+@click.option("--io", "io_backend", type=click.Choice(["auto", "native", "iohub"]), default="auto", show_default=True)
+def estimate_stabilization_cmd(input_path, config, output_path, positions, io_backend):
+    """Estimate the per-timepoint drift of every position (config: EstimateStabilizationSettings YAML)."""
+    input_path, positions = _inputs(input_path, positions)
+    click.echo(run_estimate_stabilization(input_path, config, output_path, positions, io_backend))
+
+
+def run_estimate_stabilization(input_path, config, output_path, positions=(), io_backend: str = "auto") -> dict:
+    """One ``StabilizationSettings`` YAML per position under ``output_path``; rank ``r`` of ``W`` takes the positions
+    ``r, r + W, ...`` (``pipeline.shard_units``).  The pixel size is the store's x scale."""
+    import torch
+
+    from .io.omezarr import as_volume_array, position_scale
+    from .pipeline import shard_units
+    from .settings import EstimateStabilizationSettings, StabilizationSettings
+    from .stabilize import estimate_stabilization
+
+    settings = EstimateStabilizationSettings.from_yaml(config)
+    rank, world, device, created = _distributed()
+    try:
+        src, src_positions = _open_source(Path(input_path), io_backend)
+        keys = [k for k in src_positions if not positions or k in positions]
+        missing = [p for p in positions if p not in src_positions]
+        if missing:
+            raise click.ClickException(f"positions {missing} not found; available: {list(src_positions)}")
+        if not keys:
+            raise click.ClickException("no positions to process")
+        output_path = Path(output_path)
+        output_path.mkdir(parents=True, exist_ok=True)
+        written = []
+        for key in shard_units(keys, rank, world):
+            pos = src_positions[key]
+            names = list(pos.channel_names)
+            wanted = [settings.stabilization_estimation_channel] + list(settings.stabilization_channels)
+            unknown = [n for n in wanted if n not in names]
+            if unknown:
+                raise click.ClickException(f"position {key}: channels {unknown} not in the store (it has {names})")
+            c = names.index(settings.stabilization_estimation_channel)
+            arr = as_volume_array(pos["0"])
+            if len(arr.shape) != 5:
+                raise click.ClickException(f"position {key}: expected 5-D TCZYX data, got shape {tuple(arr.shape)}")
+            pixel_size = float(position_scale(pos)[-1])
+
+            def series(arr=arr, c=c):
+                for t in range(int(arr.shape[0])):
+                    yield torch.as_tensor(np.ascontiguousarray(arr.read_volume(t, c), dtype=np.float32), device=device)
+
+            try:
+                matrices = estimate_stabilization(series(), settings, pixel_size)
+            except ValueError as exc:
+                raise click.ClickException(f"position {key}: {exc}") from exc
+            doc = StabilizationSettings(stabilization_estimation_channel=settings.stabilization_estimation_channel,
+                                        stabilization_type=settings.stabilization_type,
+                                        stabilization_channels=list(settings.stabilization_channels),
+                                        affine_transform_zyx_list=[m.tolist() for m in matrices])
+            doc.to_yaml(output_path / _position_file(key))
+            written.append(_position_file(key))
+            logger.info("position %s: drift of %d timepoints estimated (last shift %s)", key, len(matrices),
+                        matrices[-1][:3, 3].tolist())
+        close = getattr(src, "close", None)
+        if close:
+            close()
+        return {"rank": rank, "world_size": world, "output": str(output_path), "written": written}
+    finally:
+        if created:
+            import torch.distributed as dist
+
+            dist.destroy_process_group()
+
+
+class _StabilizeStep:
+    """``run_store``'s step of the ``stabilize`` command: ``for_unit`` hands out the translation of the unit's position and
+    timepoint (``warp`` channels) or a plain copy (every other channel); the volume keeps its shape."""
+
+    def __init__(self, matrices_of, warp: bool, raw_shape, _settings, device):
+        self.device = device
+        self.output_shape = tuple(int(n) for n in raw_shape)
+        self._matrices_of, self._warp = matrices_of, warp
+
+    def for_unit(self, unit):
+        import torch
+
+        from .stabilize import apply_stabilization
+
+        matrix = self._matrices_of(unit.position)[unit.t] if self._warp else None
+
+        def step(raw):
+            vol = torch.as_tensor(raw, device=self.device).to(torch.float32).contiguous()
+            return vol if matrix is None else apply_stabilization(vol, matrix)
+
+        return step
+
+
+@cli.command(cls=_eat_all_command("-i", "--input-position-dirpaths"))
+@_common
+def stabilize(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error):
+    """Apply per-timepoint translations (config: a StabilizationSettings YAML, or the directory estimate-stabilization wrote)."""
+    input_path, positions = _inputs(input_path, positions)
+    _finish(run_stabilize(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error))
+
+
+# (`-c` of this command may be a directory)
+for _p in stabilize.params:
+    if _p.name == "config":
+        _p.type = click.Path(exists=True, path_type=Path)
+
+
+def run_stabilize(input_path, config, output_path, positions=(), zarr_version: str = "0.5", resume: bool = False,
+                  io_backend: str = "auto", compression=None, on_error: str = "raise") -> dict:
+    """``stabilize``: every ``(position, t, c)`` volume of a stabilized channel is moved by its timepoint's matrix, the other
+    channels are copied.  ``config``: one ``StabilizationSettings`` file for every position, or a directory that holds
+    ``<row>_<col>_<fov>.yml`` per position.  Everything is checked before the output store is created."""
+    from .io.omezarr import as_volume_array
+    from .settings import StabilizationSettings
+
+    config = Path(config)
+    src, src_positions = _open_source(Path(input_path), io_backend)
+    try:
+        keys = [k for k in src_positions if not positions or k in positions]
+        if not keys:
+            raise click.ClickException("no positions to process")
+        per_position = {}
+        for key in keys:
+            path = config / _position_file(key) if config.is_dir() else config
+            if not path.exists():
+                raise click.ClickException(f"-c: {config} holds no {_position_file(key)} for position {key}")
+            try:
+                per_position[key] = StabilizationSettings.from_yaml(path)
+            except (ValueError, TypeError) as exc:
+                raise click.ClickException(f"{path}: {exc}") from exc
+            n_t = int(as_volume_array(src_positions[key]["0"]).shape[0])
+            n = len(per_position[key].affine_transform_zyx_list)
+            if n != n_t:
+                raise click.ClickException(f"{path}: {n} matrices for position {key}, whose store has T = {n_t}")
+        first = per_position[keys[0]]
+        channels = list(first.stabilization_channels)
+        if not channels:
+            raise click.ClickException("stabilization_channels is empty: nothing to stabilize")
+        odd = [k for k, s in per_position.items() if list(s.stabilization_channels) != channels]
+        if odd:
+            raise click.ClickException(f"positions {odd} name other stabilization_channels than {keys[0]} ({channels})")
+        names = list(src_positions[keys[0]].channel_names)
+        unknown = [n for n in channels if n not in names]
+        if unknown:
+            raise click.ClickException(f"stabilization_channels {unknown} not in the store (it has {names})")
+    finally:
+        close = getattr(src, "close", None)
+        if close:
+            close()
+    matrices = {k: [np.asarray(m, dtype=np.float64) for m in s.affine_transform_zyx_list] for k, s in per_position.items()}
+    # run_store's channel plan: the named channels take the first step, the others the second
+    plan = ReconstructSettings(registration=RegisterSettings(source_channel_names=channels,
+                                                             affine_transform_zyx=np.eye(4).tolist()))
+
+    def factory(raw_shape, settings, device):
+        return _StabilizeStep(matrices.__getitem__, settings.registration is not None, raw_shape, settings, device)
+
+    return run_store(input_path, output_path, plan, tuple(keys) if positions else (), zarr_version,
+                     reconstructor_factory=factory, resume=resume, io_backend=io_backend, compression=compression,
+                     on_error=on_error,
+                     fingerprint_extra={"stabilize": {k: s.model_dump(mode="json") for k, s in per_position.items()}})
 
 
 def main():

@@ -907,3 +907,87 @@ extern "C" int lsr_psf_accumulate_f32_cpu(const float* vol, int64_t Z, int64_t Y
   });
   return LSR_OK;
 }
+
+// ---- mid-band spectral power of every plane (focus.hip): the same table of intervals, float64 transforms ----
+#include <complex>
+
+#include "focus.hpp"
+
+namespace {
+
+using cplx = std::complex<double>;
+
+struct HostFft {
+  int n;
+  std::vector<int> radix;
+  std::vector<cplx> w;      // exp(-2 pi i k / n)
+  explicit HostFft(int n_) : n(n_), w(static_cast<size_t>(n_)) {
+    int m = n_;
+    for (int r : {2, 3, 5})
+      while (m % r == 0) { radix.push_back(r); m /= r; }
+    const double step = -2.0 * 3.14159265358979323846 / n_;
+    for (int k = 0; k < n_; ++k) w[static_cast<size_t>(k)] = cplx(std::cos(step * k), std::sin(step * k));
+  }
+  // Stockham autosort passes between x and y (each n long); returns the buffer that holds the result
+  cplx* run(cplx* x, cplx* y) const {
+    int len = n, s = 1;
+    for (int r : radix) {
+      const int m = len / r;
+      for (int p = 0; p < m; ++p)
+        for (int q = 0; q < s; ++q)
+          for (int j = 0; j < r; ++j) {
+            cplx acc(0.0, 0.0);
+            for (int k = 0; k < r; ++k) acc += x[q + s * (p + m * k)] * w[static_cast<size_t>(((j * k) % r) * (n / r))];
+            y[q + s * (r * p + j)] = acc * w[static_cast<size_t>(p) * s * j];
+          }
+      std::swap(x, y);
+      len = m;
+      s *= r;
+    }
+    return x;
+  }
+};
+
+}  // namespace
+
+// The twin of lsr_band_power_f32: host pointers; the twiddle tables and the scratch buffers are not used (may be NULL).
+extern "C" int lsr_band_power_f32_cpu(const float* in, int64_t Z, int64_t Y, int64_t X, int64_t y0, int64_t x0, int64_t Yc,
+                                      int64_t Xc, const float* /* tw_half */, const float* /* tw_x */, const float* /* tw_y */,
+                                      const int32_t* table, int64_t k_hi, float* /* spec_scratch */, double* /* partial */,
+                                      double* out_power, lsr_stream_t) {
+  if (int rc = lsr::focus::check(in, Z, Y, X, y0, x0, Yc, Xc, table, k_hi, out_power)) return rc;
+  LSR_REQUIRE(lsr::focus::lengths_ok(Yc, Xc), LSR_E_UNSUPPORTED,
+              "window (%lld,%lld): Xc a multiple of 4 whose half is 5-smooth and at most 2048, Yc 5-smooth in [2, %d]",
+              (long long)Yc, (long long)Xc, lsr::focus::kMaxY);
+  const int ny = static_cast<int>(Yc), nx = static_cast<int>(Xc), kc = static_cast<int>(k_hi) + 1;
+  std::atomic<bool> failed{false};
+  parallel_ranges(Z, [&](int64_t first, int64_t last) {
+    const HostFft fx(nx), fy(ny);
+    const size_t longest = static_cast<size_t>(std::max(nx, ny));
+    std::vector<cplx> a(longest), b(longest), spec(static_cast<size_t>(kc) * ny);
+    for (int64_t z = first; z < last; ++z) {
+      for (int y = 0; y < ny; ++y) {
+        const float* src = in + (z * Y + y0 + y) * X + x0;
+        for (int x = 0; x < nx; ++x) a[static_cast<size_t>(x)] = cplx(static_cast<double>(src[x]), 0.0);
+        const cplx* f = fx.run(a.data(), b.data());
+        for (int k = 0; k < kc; ++k) spec[static_cast<size_t>(k) * ny + y] = f[k];
+      }
+      double total = 0.0;
+      for (int k = 0; k < kc; ++k) {
+        const int lo = std::max(table[2 * k], 0), hi = std::min(table[2 * k + 1], ny / 2);
+        if (lo > hi) continue;
+        std::copy(spec.begin() + static_cast<size_t>(k) * ny, spec.begin() + static_cast<size_t>(k + 1) * ny, a.begin());
+        const cplx* f = fy.run(a.data(), b.data());
+        double acc = 0.0;
+        for (int m = lo; m <= hi; ++m) {
+          acc += std::abs(f[m]);
+          if (m != 0 && 2 * m != ny) acc += std::abs(f[ny - m]);
+        }
+        total += (k == 0 || 2 * k == nx) ? acc : 2.0 * acc;
+      }
+      out_power[z] = total;
+    }
+  }, failed);
+  LSR_REQUIRE(!failed.load(), LSR_E_ARG, "lsr_band_power_f32_cpu: out of memory for the plane buffers");
+  return LSR_OK;
+}

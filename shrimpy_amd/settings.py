@@ -399,6 +399,85 @@ class PhaseSettings(_StrictModel):
     apply_inverse: PhaseInverseSettings = PhaseInverseSettings()
 
 
+def _check_matrix_4x4(v, name="affine_transform_zyx"):
+    m = np.asarray(v, dtype=np.float64)
+    if m.shape != (4, 4):
+        raise ValueError(f"{name} must be 4x4, got {m.shape}")
+    if not np.all(np.isfinite(m)):
+        raise ValueError(f"{name} contains non-finite entries")
+    if not np.allclose(m[3], [0, 0, 0, 1]):
+        raise ValueError(f"last row of {name} must be [0, 0, 0, 1]")
+    return m.tolist()
+
+
+class FocusFindingSettings(_StrictModel):
+    """``focus_finding_settings`` of :class:`EstimateStabilizationSettings` (``shrimpy_amd/focus.py``); lengths in the
+    store's units (micrometres)."""
+
+    center_crop_xy: tuple[PositiveInt, PositiveInt] = (800, 800)
+    NA_det: PositiveFloat = 1.35
+    lambda_ill: PositiveFloat = 0.5
+    midband_fractions: tuple[NonNegativeFloat, PositiveFloat] = (0.125, 0.25)
+    threshold_FWHM: NonNegativeFloat = 0.0
+
+    @field_validator("midband_fractions")
+    @classmethod
+    def _ordered(cls, v):
+        if not v[0] < v[1]:
+            raise ValueError("midband_fractions must be increasing")
+        return v
+
+
+class PhaseCrossCorrSettings(_StrictModel):
+    """``phase_cross_corr_settings`` of :class:`EstimateStabilizationSettings` (``dynatrack._phase_cross_corr``)."""
+
+    t_reference: Literal["first", "previous"] = "first"
+    center_crop_xy: tuple[PositiveInt, PositiveInt] = (800, 800)
+    maximum_shift: PositiveFloat = 1.0
+
+
+class EstimateStabilizationSettings(_StrictModel):
+    """Drift estimation of a time-lapse (``shrimpy_amd/stabilize.py``, the ``estimate-stabilization`` command).  Field
+    names are biahub's [RECALLED]; bead-based estimation, averaging across wells and sub-pixel shifts are not built.
+
+    ``stabilization_method`` ``"focus-finding"`` estimates z from the mid-band spectral power of every plane and takes
+    ``stabilization_type`` ``"z"`` or ``"xyz"`` (y and x then come from the phase cross-correlation);
+    ``"phase-cross-corr"`` takes ``"xy"`` or ``"xyz"``."""
+
+    stabilization_estimation_channel: str
+    stabilization_channels: list[str]
+    stabilization_type: Literal["z", "xy", "xyz"]
+    stabilization_method: Literal["focus-finding", "phase-cross-corr"] = "focus-finding"
+    focus_finding_settings: FocusFindingSettings = FocusFindingSettings()
+    phase_cross_corr_settings: PhaseCrossCorrSettings = PhaseCrossCorrSettings()
+
+    @model_validator(mode="after")
+    def _check_pair(self):
+        allowed = {"focus-finding": ("z", "xyz"), "phase-cross-corr": ("xy", "xyz")}[self.stabilization_method]
+        if self.stabilization_type not in allowed:
+            raise ValueError(f"stabilization_method {self.stabilization_method!r} estimates stabilization_type "
+                             f"{' or '.join(repr(a) for a in allowed)}, not {self.stabilization_type!r}")
+        return self
+
+
+class StabilizationSettings(_StrictModel):
+    """What ``estimate-stabilization`` writes and ``stabilize`` applies: one 4x4 matrix per timepoint, ZYX voxel units,
+    output index -> input coordinate (the ``scipy.ndimage.affine_transform`` convention, as :class:`RegisterSettings`)."""
+
+    stabilization_estimation_channel: str
+    stabilization_type: Literal["z", "xy", "xyz"]
+    stabilization_channels: list[str]
+    affine_transform_zyx_list: list[list[list[float]]]
+    time_indices: Literal["all"] = "all"
+
+    @field_validator("affine_transform_zyx_list")
+    @classmethod
+    def _check_list(cls, v):
+        if not v:
+            raise ValueError("affine_transform_zyx_list is empty")
+        return [_check_matrix_4x4(m, f"affine_transform_zyx_list[{i}]") for i, m in enumerate(v)]
+
+
 class ReconstructSettings(_StrictModel):
     """Whole per-volume pipeline: (flat-field) -> deskew -> (register) -> (deconvolve)."""
 

@@ -1,0 +1,150 @@
+"""The focus measure on the host: the float64 interval table against the model's mask, the host twin
+(``lsr_band_power_f32_cpu``) against ``tests/focus_ref.py``, the focus index, the width restatement and the window rule.
+
+waveorder is not installed: PARITY IS UNPINNED and ``focus_ref`` (float64 NumPy) is the oracle.  The cases' bands hold 54 to
+5902 bins of the full spectrum (5904 with ``r`` from ``np.fft.fftfreq``, whose products round two boundary bins the other
+way); every case peaks at its ``z0`` with a gap to the second-largest power of at least 0.36 of the peak, and a complex64
+pocketfft evaluation of the rule differs from float64 by at most 4e-8 of the peak.
+"""
+
+import numpy as np
+import pytest
+import torch
+
+from shrimpy_amd import focus as F
+from tests import focus_ref as R
+
+
+def _all_cases():
+    out = [(f"case{i}", c, {}) for i, c in enumerate(R.CASES)]
+    out += [(name, a, kw) for name, (a, kw) in R.extra_cases().items()]
+    return out
+
+
+ALL = _all_cases()
+IDS = [a[0] for a in ALL]
+
+
+@pytest.fixture(scope="module")
+def data():
+    out = {}
+    for name, args, kw in ALL:
+        vol = R.stack(*args)
+        out[name] = (vol, kw, R.power(vol, **R.OPTICS, **kw), R.bound(vol, **R.OPTICS, **kw))
+    return out
+
+
+@pytest.mark.parametrize("name,args,kw", ALL, ids=IDS)
+def test_band_table_is_the_models_mask(name, args, kw):
+    yc, xc, _, _ = F.focus_grid(args[:3], kw.get("center_crop_xy", (800, 800)))
+    fractions = kw.get("midband_fractions", R.FRACTIONS)
+    lo, hi = F.band_limits(R.OPTICS["NA_det"], R.OPTICS["lambda_ill"], fractions)
+    table, k_hi, weighted = F.band_table(yc, xc, R.OPTICS["pixel_size"], lo, hi)
+    mask = R.band_mask(yc, xc, midband_fractions=fractions, **R.OPTICS)
+    got = np.zeros((yc, xc), dtype=bool)
+    for kx in range(xc // 2 + 1):
+        a, b = table[kx]
+        for m in range(a, b + 1):
+            for ky in {m, (yc - m) % yc}:
+                got[ky, kx] = got[ky, (xc - kx) % xc] = True
+    assert np.array_equal(got, mask)
+    assert weighted == int(mask.sum())
+    assert k_hi == max(kx for kx in range(xc // 2 + 1) if mask[:, kx].any())
+    assert 54 <= weighted <= 5904
+
+
+def test_nyquist_case_reaches_the_last_column():
+    args, kw = R.extra_cases()["nyquist"]
+    yc, xc, _, _ = F.focus_grid(args[:3])
+    lo, hi = F.band_limits(R.OPTICS["NA_det"], R.OPTICS["lambda_ill"], kw["midband_fractions"])
+    assert hi * R.OPTICS["pixel_size"] > 0.5
+    assert F.band_table(yc, xc, R.OPTICS["pixel_size"], lo, hi)[1] == xc // 2
+
+
+@pytest.mark.parametrize("name", IDS)
+def test_host_twin_against_the_model(name, data):
+    vol, kw, ref, bound = data[name]
+    got = F.midband_power(torch.from_numpy(vol), **R.OPTICS, **kw)
+    assert got.dtype == torch.float64 and tuple(got.shape) == (vol.shape[0],)
+    ratio = np.abs(got.numpy() - ref) / bound
+    print(f"{name}: worst |P - P_ref| / bound = {ratio.max():.3g}")
+    assert np.all(ratio <= 1.0)
+    assert np.array_equal(F.midband_power(vol, **R.OPTICS, **kw), got.numpy())      # arrays take the same route
+
+
+def test_uint16_is_widened():
+    vol = R.stack(*R.CASES[0])
+    assert np.array_equal(F.midband_power(torch.from_numpy(vol.astype(np.uint16)), **R.OPTICS).numpy(),
+                          F.midband_power(torch.from_numpy(vol), **R.OPTICS).numpy())
+
+
+@pytest.mark.parametrize("i", range(len(R.CASES)))
+def test_model_properties(i, data):
+    z, y, x, z0 = R.CASES[i]
+    vol, _, ref, _ = data[f"case{i}"]
+    assert int(np.argmax(ref)) == z0
+    top = np.sort(ref)[::-1]
+    assert (top[0] - top[1]) / top[0] >= 0.36
+    single = R.power(vol, **R.OPTICS, dtype=np.float32)
+    assert np.max(np.abs(single - ref)) <= 4e-8 * ref.max()
+
+
+@pytest.mark.parametrize("name", IDS)
+def test_focus_index(name, data):
+    vol, kw, ref, _ = data[name]
+    t = torch.from_numpy(vol)
+    assert F.focus_from_transverse_band(t, **R.OPTICS, **kw) == R.focus_index(ref)
+    assert F.focus_from_transverse_band(t, **R.OPTICS, mode="min", **kw) == R.focus_index(ref, mode="min")
+    wide = R.width(ref, int(np.argmax(ref))) + 0.5
+    assert R.focus_index(ref, threshold_FWHM=wide) is None
+    assert F.focus_from_transverse_band(t, **R.OPTICS, threshold_FWHM=wide, **kw) is None
+    index, stats = F.focus_from_transverse_band(t, **R.OPTICS, return_statistics=True, **kw)
+    assert index == stats["peak_index"] == int(np.argmax(ref))
+    assert abs(stats["peak_FWHM"] - R.width(ref, index)) <= 1e-9
+    assert set(stats) == {"peak_index", "peak_FWHM", "midband_power"} and stats["midband_power"].shape == ref.shape
+
+
+@pytest.mark.parametrize("name", IDS)
+def test_width_restatement(name, data):
+    ref = data[name][2]
+    for curve in (ref, ref[::-1].copy(), -ref, np.concatenate([ref, ref[:-1] * 0.5])):
+        for peak in range(curve.size):
+            assert abs(F.peak_width(curve, peak) - R.width(curve, peak)) <= 1e-12
+
+
+def test_single_plane_and_refusals():
+    vol = torch.from_numpy(R.stack(*R.CASES[0]))
+    assert F.focus_from_transverse_band(vol[:1], **R.OPTICS) == 0
+    for kw in (dict(polynomial_fit_order=4), dict(enable_subpixel_precision=True), dict(plot_path="curve.pdf")):
+        with pytest.raises(NotImplementedError):
+            F.focus_from_transverse_band(vol, **R.OPTICS, **kw)
+    with pytest.raises(ValueError):
+        F.focus_from_transverse_band(vol, **R.OPTICS, mode="median")
+
+
+def test_empty_band_is_an_error():
+    args, kw = R.EMPTY_BAND
+    with pytest.raises(ValueError, match="cycles per pixel.*window"):
+        F.midband_power(torch.from_numpy(R.stack(*args)), **R.OPTICS, **kw)
+    with pytest.raises(ValueError):
+        R.power(R.stack(*args), **R.OPTICS, **kw)
+
+
+def test_focus_grid():
+    from shrimpy_amd import _lib
+
+    assert F.focus_grid((5, 12, 16)) == (12, 16, 0, 0)
+    assert F.focus_grid((6, 50, 100), (32, 48)) == (32, 48, 9, 26)
+    assert F.focus_grid((5, 46, 62)) == (45, 60, 0, 1)
+    assert F.focus_grid((171, 2048, 2270)) == (800, 800, 624, 735)
+    assert F.focus_grid((3, 5000, 5000), (5000, 5000)) == (2048, 4096, 1476, 452)
+    for y in range(2, 140, 7):
+        for x in range(8, 300, 13):
+            yc, xc, y0, x0 = F.focus_grid((1, y, x), (100, 200))
+            assert yc <= min(y, 100) and xc <= min(x, 200) and (y0, x0) == ((y - yc) // 2, (x - xc) // 2)
+            assert _lib.call_value("lsr_band_power_supported", yc, xc) == 1
+            # the largest: nothing between the window and the limit is taken
+            assert not any(_lib.call_value("lsr_band_power_supported", n, xc) for n in range(yc + 1, min(y, 100) + 1))
+            assert not any(_lib.call_value("lsr_rfft_rows_supported", n) for n in range(xc + 1, min(x, 200) + 1))
+    with pytest.raises(ValueError):
+        F.focus_grid((1, 1, 7))
