@@ -34,7 +34,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from . import _lib
+from . import _lib, rl_loop
 
 __all__ = ["richardson_lucy", "RichardsonLucyPlan", "RLStats", "factor_psf", "correlate3d", "prepare_psf",
            "padded_shape", "PaddedVolume", "make_plan", "check_tv", "TV_LAMBDA_LIMIT", "check_acceleration",
@@ -67,36 +67,6 @@ def check_acceleration(acceleration, tv_lambda: float = 0.0) -> bool:
         raise ValueError("acceleration='biggs-andrews' cannot be combined with tv_lambda > 0: the total-variation factor "
                          "breaks the fixed-point map the extrapolation assumes")
     return on
-
-
-class AccelState:
-    """What one accelerated run keeps on the device beside its volumes: the inner products of every iteration
-    (``dots[k] = <g_k, g_{k-1}>, <g_k, g_k>``), the step lengths ``alphas[k] = a_{k+1}`` and the workspace of the dots
-    launch; ``step`` issues the two launches that follow ``x_{k+1} = RL(p_k)``.  ``g`` is the caller's dense volume."""
-
-    def __init__(self, shape, device, iterations: int, g):
-        import torch
-
-        self.shape = tuple(int(v) for v in shape)
-        self.g = g
-        n = max(int(iterations) - 1, 1)
-        self.dots = torch.zeros((n, 2), dtype=torch.float64, device=device)
-        self.alphas = torch.zeros(n, dtype=torch.float64, device=device)
-        self.work = torch.empty(_lib.call_value("lsr_rl_accel_workspace_bytes", *self.shape) // 8, dtype=torch.float64,
-                                device=device)
-
-    def step(self, k: int, x1, p, x0, stream) -> None:
-        """``x1``, ``p``, ``x0``: (pointer, pitch, plane) of x_{k+1}, p_k and x_k; p_{k+1} is written over x_k (which is
-        not read when ``k == 0``: a_1 = 0)."""
-        d = self.dots.data_ptr()
-        _lib.call("lsr_rl_accel_dots_f32", *x1, *p, self.g.data_ptr(), *self.shape, int(k == 0), d + 16 * k,
-                  self.work.data_ptr(), stream)
-        _lib.call("lsr_rl_accel_predict_f32", *x1, *x0, *self.shape, None if k == 0 else d + 16 * k,
-                  None if k == 0 else d + 16 * (k - 1) + 8, self.alphas.data_ptr() + 8 * k, stream)
-
-    def used(self, done: int) -> np.ndarray:
-        """a_1 .. a_{done-1}: the step lengths the ``done`` iterations that ran started from."""
-        return self.alphas[:max(int(done) - 1, 0)].cpu().numpy().copy()
 
 
 MAX_TAPS = 15
@@ -278,21 +248,6 @@ class RLStats:
                    stopped_by_tol=bool(stopped))
 
 
-@dataclass
-class _DevicePsf:
-    separable: bool
-    shape: tuple[int, int, int]
-    # separable
-    k: tuple | None = None
-    k_flipped: tuple | None = None
-    # dense
-    w: object | None = None
-    w_flipped: object | None = None
-    norm_table: object | None = None
-    taps: object | None = None          # tuned dense kernel: host-prepared tap arrays (device)
-    taps_flipped: object | None = None
-    norm_full: float = 1.0
-
 
 def fused_pays(pz: int, py: int, px: int) -> bool:
     """Whether the one-launch iteration beats the ratio / update pair for a separable PSF of this extent.
@@ -302,6 +257,296 @@ def fused_pays(pz: int, py: int, px: int) -> bool:
     by 20-40 % (config-2 grid, ``tools/bench_kernels.py --psf-sweep --psf-sweep-wide``,
     ``profiles/r03_rl_psf_sweep.jsonl``: e.g. 5x13x13 4.79 vs 4.28 ms, 11x13x13 5.14 vs 5.34, 9x7x7 2.50 vs 4.31)."""
     return max(py, px) <= 11 or pz >= 11
+
+
+def _dev(a, device, dtype=np.float32):
+    import torch
+
+    # (np.array copies: a reversed 1-element view keeps its negative stride otherwise)
+    return torch.as_tensor(np.array(a, dtype=dtype, order="C"), device=device)
+
+
+class _Path(rl_loop.InPlace):
+    """One way of running RL iterations on the device -- the stepper ``rl_loop.run`` drives: its tap and normalisation
+    tensors, its scratch and its launches.  Working volumes carry a zero halo (the kernels never bounds-check a load);
+    unless the path ``rotates`` between the two, the estimate lives in the first and the second takes the ratio."""
+
+    name = ""
+    separable = False          # three 1-D factors
+    padded = True              # works in padded volumes and takes a padded y
+    needs_padded_y = False     # ... and reads y on the tile grown by the PSF radius: a dense y is copied into one
+    reads_y = True             # iteration 0 can take x_0 = y from a padded y (no copy into the working volume)
+    dense_out = True           # the last launch can write a dense volume
+
+    def __init__(self, shape, psf_shape, device):
+        super().__init__(shape, device)
+        self.psf_shape = tuple(int(v) for v in psf_shape)
+        self.pad_psf_shape = self.psf_shape     # the PSF extents the padded volumes are laid out for
+        self._vols = None
+
+    def volumes(self):
+        if self._vols is None:
+            self._vols = [PaddedVolume(self.shape, self.pad_psf_shape, self.device) for _ in range(2)]
+        return self._vols
+
+    @property
+    def cur(self):
+        return self.volumes()[0]
+
+    def release(self) -> None:
+        self._vols = None
+        self.drop_sides()
+
+    def begin(self, y, from_y: bool, eps: float, stream) -> None:
+        """The run that follows: ``y`` as (pointer, pitch, plane); ``from_y``: iteration 0 reads it as x_0."""
+        self.y, self.from_y, self.eps, self.stream = y, from_y, ctypes.c_float(eps), stream
+        self.restart()
+
+    def load(self, init, out) -> None:
+        self.cur.view.copy_(init)
+
+    def _target(self, x_out):
+        return rl_loop.tri(self.cur if x_out is None else x_out)
+
+
+class _Rotating(_Path):
+    """One launch per iteration, from one padded volume into the other (and a third in an accelerated run)."""
+
+    rotates = True
+    needs_padded_y = True
+
+    def third(self):
+        if "third" not in self._sides:
+            self._sides["third"] = PaddedVolume(self.shape, self.pad_psf_shape, self.device)
+        return self._sides["third"]
+
+    def run(self, it0, n, x_out, rows, ab=None) -> None:
+        rd, wr = ab or self.volumes()
+        self.launch(self.y, int(self.from_y and it0 == 0), rd, wr, x_out, n, self.eps, rl_loop.row_ptr(rows, it0),
+                    self.stream)
+
+
+class _Fused(_Rotating):
+    name = "fused"
+    separable = True
+
+    def __init__(self, shape, device, factors, norm):
+        super().__init__(shape, [len(k) for k in factors], device)
+        kz, ky, kx = (np.ascontiguousarray(k, dtype=np.float32) for k in factors)
+        block = np.zeros(_lib.call_value("lsr_rl_sep_fused_taps_count"), np.float32)
+        _lib.call("lsr_rl_sep_fused_prepare_taps", kz.ctypes.data, len(kz), ky.ctypes.data, len(ky),
+                  kx.ctypes.data, len(kx), block.ctypes.data)
+        self.taps, self.norm = _dev(block, device), norm
+
+    def launch(self, y, from_y, rd, wr, x_out, n, eps, sp, stream) -> None:
+        """Iteration i reads ``rd`` when i is even and ``wr`` when odd, and writes the other."""
+        nz, ny, nx = self.norm
+        _lib.call("lsr_rl_sep_fused_stats_f32", *y, from_y, rd.full.data_ptr(), wr.full.data_ptr(),
+                  None if x_out is None else x_out.data_ptr(), *self.shape, self.taps.data_ptr(), *self.psf_shape,
+                  nz.data_ptr(), ny.data_ptr(), nx.data_ptr(), n, eps, sp, stream)
+
+
+class _FusedYsep(_Rotating):
+    name = "y-separable (fused)"
+
+    def __init__(self, shape, device, ky, kzx, norm_table, norm_full):
+        super().__init__(shape, (kzx.shape[0], len(ky), kzx.shape[1]), device)
+        ky_c, kzx_c = np.ascontiguousarray(ky, dtype=np.float32), np.ascontiguousarray(kzx, dtype=np.float32)
+        block = np.zeros(_lib.call_value("lsr_rl_ysep_fused_taps_count"), np.float32)
+        _lib.call("lsr_rl_ysep_fused_prepare_taps", ky_c.ctypes.data, len(ky_c), kzx_c.ctypes.data,
+                  kzx_c.shape[0], kzx_c.shape[1], block.ctypes.data)
+        self.taps, self.norm_table, self.norm_full = _dev(block, device), norm_table, norm_full
+
+    def launch(self, y, from_y, rd, wr, x_out, n, eps, sp, stream) -> None:
+        _lib.call("lsr_rl_ysep_fused_stats_f32", *y, from_y, rd.full.data_ptr(), wr.full.data_ptr(),
+                  None if x_out is None else x_out.data_ptr(), *self.shape, self.taps.data_ptr(), *self.psf_shape,
+                  self.norm_table.data_ptr(), ctypes.c_float(self.norm_full), n, eps, sp, stream)
+
+
+class _SeparablePair(_Path):
+    """The ratio / update pair of the tiled separable kernel."""
+
+    name = "separable"
+    separable = True
+
+    def __init__(self, shape, device, factors, norm):
+        super().__init__(shape, [len(k) for k in factors], device)
+        self.k = tuple(_dev(k, device) for k in factors)
+        self.k_flipped = tuple(_dev(k[::-1], device) for k in factors)
+        self.norm = norm
+
+    def run(self, it0, n, x_out, rows, ab=None) -> None:
+        x_pad, ratio_pad = self.volumes()
+        (kz, ky, kx), (fz, fy, fx) = self.k, self.k_flipped
+        nz, ny, nx = self.norm
+        pz, py, px = self.psf_shape
+        _lib.call("lsr_rl_sep_stats_f32", *self.y, int(self.from_y and it0 == 0), x_pad.full.data_ptr(),
+                  ratio_pad.full.data_ptr(), None if x_out is None else x_out.data_ptr(), *self.shape, kz.data_ptr(),
+                  fz.data_ptr(), pz, ky.data_ptr(), fy.data_ptr(), py, kx.data_ptr(), fx.data_ptr(), px,
+                  nz.data_ptr(), ny.data_ptr(), nx.data_ptr(), n, self.eps, rl_loop.row_ptr(rows, it0), self.stream)
+
+
+class _LongZ(_SeparablePair):
+    """A separable PSF with 17 .. 31 z taps: H x = Cz(Cyx(x)) -- the in-plane factors through the tiled separable kernel
+    with a single z tap, the z factor through ``lsr_correlate_z_f32`` (a register march, no halo), which also carries
+    the epilogues.  Four launches and 48 algorithmic bytes per voxel and iteration."""
+
+    name = "separable (long z, 4 launches)"
+    reads_y = False
+
+    def __init__(self, shape, device, factors, norm):
+        super().__init__(shape, device, factors, norm)
+        # (the z extent is not the tiled kernels' business: they run with one z tap)
+        self.pad_psf_shape = (1,) + self.psf_shape[1:]
+        self.one = _dev(np.ones(1, np.float32), device)
+
+    def run(self, it0, n, x_out, rows, ab=None) -> None:
+        x_pad, ratio_pad = self.volumes()
+        t = self.side("t")
+        z, yy, xx = self.shape
+        (kz, ky, kx), (fz, fy, fx) = self.k, self.k_flipped
+        nz, ny, nx = self.norm
+        pz, py, px = self.psf_shape
+        x3, r3, t3, f0 = rl_loop.tri(x_pad), rl_loop.tri(ratio_pad), rl_loop.tri(t), ctypes.c_float(0.0)
+        for it in range(it0, it0 + n):
+            out3 = self._target(x_out if it + 1 == it0 + n else None)
+            for src3, wy, wx, wz, epi, aux3, dst3 in ((x3, fy, fx, fz, _lib.EPI_RATIO, self.y, r3),
+                                                      (r3, ky, kx, kz, _lib.EPI_UPDATE, x3, out3)):
+                _lib.call("lsr_correlate_sep_strided_f32", *src3, None, 0, 0, *t3, z, yy, xx, self.one.data_ptr(), 1,
+                          wy.data_ptr(), py, wx.data_ptr(), px, _lib.EPI_NONE, f0, None, None, None, self.stream)
+                _lib.call("lsr_correlate_z_f32", *t3, *aux3, *dst3, z, yy, xx, wz.data_ptr(), pz, epi, self.eps,
+                          nz.data_ptr(), ny.data_ptr(), nx.data_ptr(),
+                          rl_loop.row_ptr(rows, it) if epi == _lib.EPI_UPDATE else None, self.stream)
+
+
+class _Dense(_Path):
+    """The tuned dense stencil (pz <= 11, py, px <= 9) on padded volumes."""
+
+    name = "dense"
+
+    def __init__(self, shape, device, w, taps):
+        super().__init__(shape, w.shape, device)
+        self.taps, self.taps_flipped = _dev(taps[0], device), _dev(taps[1], device)
+        self.norm_table = _dev(_prefix_table(w).ravel(), device, np.float64)
+        self.norm_full = float(w.astype(np.float64).sum())
+
+    def run(self, it0, n, x_out, rows, ab=None) -> None:
+        x_pad, ratio_pad = self.volumes()
+        _lib.call("lsr_rl_dense_padded_stats_f32", *self.y, int(self.from_y and it0 == 0), x_pad.full.data_ptr(),
+                  ratio_pad.full.data_ptr(), None if x_out is None else x_out.data_ptr(), *self.shape,
+                  self.taps.data_ptr(), self.taps_flipped.data_ptr(), *self.psf_shape, self.norm_table.data_ptr(),
+                  ctypes.c_float(self.norm_full), n, self.eps, rl_loop.row_ptr(rows, it0), self.stream)
+
+
+class _Generic(_Path):
+    """The bounds-checked dense stencil: dense volumes, x updated in place in the output tensor."""
+
+    name = "generic"
+    padded = reads_y = dense_out = False
+    cur = None
+
+    def __init__(self, shape, device, w):
+        super().__init__(shape, w.shape, device)
+        self.w, self.w_flipped = _dev(w.ravel(), device), _dev(w[::-1, ::-1, ::-1].ravel(), device)
+        self.norm_table = _dev(_prefix_table(w).ravel(), device, np.float64)
+
+    def volumes(self):
+        return self.cur, self.side("ratio")
+
+    def load(self, init, out) -> None:
+        self.cur = out
+        out.copy_(init)
+
+    def run(self, it0, n, x_out, rows, ab=None) -> None:
+        _lib.call("lsr_rl_dense_stats_f32", self.y[0], self.cur.data_ptr(), self.side("ratio").data_ptr(), *self.shape,
+                  self.w.data_ptr(), self.w_flipped.data_ptr(), *self.psf_shape, self.norm_table.data_ptr(), n,
+                  self.eps, rl_loop.row_ptr(rows, it0), self.stream)
+
+
+class _YsepPair(_Path):
+    """``psf = ky (x) kzx``: each correlation is the dense (z, x) stencil (PZ * PX FMAs per voxel instead of
+    PZ * PY * PX) and the y pass that carries the epilogue -- ``H x = Y~(ZX~(x))`` with ``ratio = y / (. + eps)`` in the
+    y pass; ``H^T r = Y(ZX(r))`` with the (z, x) border normalisation in the stencil launch (``LSR_EPI_SCALE``) and
+    ``x * . / ny`` in the y pass.  Two launches per iteration where both factors fit one kernel
+    (``lsr_correlate_zxy_padded_f32``: the y pass runs inside the stencil kernel, wave by wave, on the staged plane),
+    otherwise four."""
+
+    reads_y = False
+
+    def __init__(self, shape, device, psf, ky, kzx, zx_taps, both):
+        super().__init__(shape, psf.shape, device)
+        self.name = "y-separable" if both is not None else "y-separable (4 launches)"
+        self.both = both      # (taps, flipped taps, norm table, norm_full) of the two-launch form, or None
+        self.ky, self.ky_flipped = _dev(ky, device), _dev(ky[::-1], device)
+        if both is None:
+            z, y, x = self.shape
+            zx = np.ascontiguousarray(kzx[:, None, :])                     # a (pz, 1, px) PSF
+            self.kzx = psf.astype(np.float64).sum(axis=1)                  # ky sums to 1: the (z, x) stencil
+            self.taps, self.taps_flipped = _dev(zx_taps[0], device), _dev(zx_taps[1], device)
+            self.norm_table = _dev(_prefix_table(zx).ravel(), device, np.float64)
+            self.norm_full = float(zx.astype(np.float64).sum())
+            self.one = _dev(np.ones(1, np.float32), device)
+            self.ny = _dev(_axis_norm(ky, y), device)
+            self.ones_z, self.ones_x = _dev(np.ones(z, np.float32), device), _dev(np.ones(x, np.float32), device)
+            self._nzx = None
+
+    def release(self) -> None:
+        super().release()
+        self._nzx = None
+
+    def nzx(self):
+        """(Z, X) table of the (z, x) stencil's border normalisation (sum of the kzx taps that land inside), float64 on
+        the device -- only the four-launch form's flux needs it (its last launch divides by ny alone)."""
+        import torch
+
+        if self._nzx is None:
+            z, _, x = self.shape
+            pz, px = self.kzx.shape
+            cs = np.zeros((pz + 1, px + 1))
+            cs[1:, 1:] = self.kzx.cumsum(0).cumsum(1)
+            zi, xi = np.arange(z), np.arange(x)
+            a0, a1 = np.maximum(0, pz // 2 - zi), np.minimum(pz, z - zi + pz // 2)
+            c0, c1 = np.maximum(0, px // 2 - xi), np.minimum(px, x - xi + px // 2)
+            t = cs[a1][:, c1] - cs[a0][:, c1] - cs[a1][:, c0] + cs[a0][:, c0]
+            self._nzx = torch.as_tensor(t, device=self.device)
+        return self._nzx
+
+    def run(self, it0, n, x_out, rows, ab=None) -> None:
+        import torch
+
+        x_pad, ratio_pad = self.volumes()
+        z, yy, xx = self.shape
+        pz, py, px = self.psf_shape
+        x3, r3, eps, stream = rl_loop.tri(x_pad), rl_loop.tri(ratio_pad), self.eps, self.stream
+        for it in range(it0, it0 + n):
+            last = x_out if it + 1 == it0 + n else None
+            out3, sp = self._target(last), rl_loop.row_ptr(rows, it)
+            if self.both is not None:
+                taps, taps_flipped, norm_table, norm_full = self.both
+                _lib.call("lsr_correlate_zxy_padded_f32", *x3, *self.y, *r3, z, yy, xx, taps_flipped.data_ptr(),
+                          self.ky_flipped.data_ptr(), pz, py, px, _lib.EPI_RATIO, eps, None, ctypes.c_float(1.0), stream)
+                _lib.call("lsr_correlate_zxy_padded_stats_f32", *r3, *x3, *out3, z, yy, xx, taps.data_ptr(),
+                          self.ky.data_ptr(), pz, py, px, _lib.EPI_UPDATE, eps, norm_table.data_ptr(),
+                          ctypes.c_float(norm_full), sp, stream)
+                continue
+            if "t" not in self._sides:
+                self._sides["t"] = PaddedVolume(self.shape, self.psf_shape, self.device)
+            t3, one, f0 = rl_loop.tri(self._sides["t"]), self.one.data_ptr(), ctypes.c_float(0.0)
+            _lib.call("lsr_correlate_dense_padded_f32", *x3, None, 0, 0, *t3, z, yy, xx, self.taps_flipped.data_ptr(),
+                      pz, 1, px, _lib.EPI_NONE, f0, None, ctypes.c_float(1.0), stream)
+            _lib.call("lsr_correlate_sep_strided_f32", *t3, *self.y, *r3, z, yy, xx, one, 1,
+                      self.ky_flipped.data_ptr(), py, one, 1, _lib.EPI_RATIO, eps, None, None, None, stream)
+            _lib.call("lsr_correlate_dense_padded_f32", *r3, None, 0, 0, *t3, z, yy, xx, self.taps.data_ptr(), pz, 1, px,
+                      _lib.EPI_SCALE, f0, self.norm_table.data_ptr(), ctypes.c_float(self.norm_full), stream)
+            _lib.call("lsr_correlate_sep_strided_stats_f32", *t3, *x3, *out3, z, yy, xx, one, 1, self.ky.data_ptr(), py,
+                      one, 1, _lib.EPI_UPDATE, eps, self.ones_z.data_ptr(), self.ny.data_ptr(), self.ones_x.data_ptr(),
+                      sp, stream)
+            if rows is not None:
+                # this launch's x * u is x * H^T(ratio) / nzx (the (z, x) normalisation went into the stencil launch): the
+                # flux of the full update, sum x_new * nzx * ny, is formed here from the new estimate -- this path is the
+                # fallback for y extents beyond the one-launch kernels, an extra reduction does not matter to it
+                x_new = x_pad.view if last is None else last
+                rows[it, 0] = (torch.einsum("zyx,y->zx", x_new, self.ny).double() * self.nzx()).sum()
 
 
 class RichardsonLucyPlan:
@@ -320,7 +565,6 @@ class RichardsonLucyPlan:
 
         if fused not in ("auto", "never", "always"):
             raise ValueError("fused must be 'auto', 'never' or 'always'")
-        self._fused_mode = fused
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.LsrError("RichardsonLucyPlan", -1,
@@ -349,186 +593,99 @@ class RichardsonLucyPlan:
             if factors is None and self.psf.shape[0] > MAX_TAPS:
                 raise ValueError(f"a PSF with {self.psf.shape[0]} z taps must be separable (kz x ky x kx within "
                                  f"separable_rtol): the dense and ky (x) kzx stencils hold <= {MAX_TAPS} taps per axis")
-
-        def dev(a, dtype=torch.float32):
-            # (np.array copies: a reversed 1-element view keeps its negative stride otherwise)
-            return torch.as_tensor(np.array(a, order="C"), device=self.device).to(dtype)
-
-        z, y, x = self.shape
-        # an axial factor beyond the tiled kernels' 15 taps: every correlation = in-plane launch + z launch
-        self._long_z = factors is not None and len(factors[0]) > MAX_TAPS
-        self._t_dense = None
+        self.psf_shape = tuple(int(v) for v in self.psf.shape) if factors is None else tuple(len(k) for k in factors)
+        self._y_pad = None   # the paths that need a padded y: padded copy of a dense one
+        self.last_stats = self.stats_device = self.last_alphas = None
         if factors is not None:
-            kz, ky, kx = factors
-            self._psf = _DevicePsf(
-                separable=True,
-                shape=(len(kz), len(ky), len(kx)),
-                k=(dev(kz), dev(ky), dev(kx)),
-                k_flipped=(dev(kz[::-1]), dev(ky[::-1]), dev(kx[::-1])),
-            )
-            ny = _axis_norm(ky, y)
-            if y_window is not None:
-                first, total = (int(v) for v in y_window)
-                if first < 0 or first + y > total:
-                    raise ValueError(f"y_window {y_window} does not contain {y} rows")
-                ny = _axis_norm(ky, total)[first:first + y]
-            self._norm = (dev(_axis_norm(kz, z)), dev(ny), dev(_axis_norm(kx, x)))
-            self._one = dev(np.ones(1, np.float32))
+            self._path = self._separable_path(factors, fused, y_window)
         else:
-            w = self.psf
-            ysep = factor_psf_y(w, separable_rtol) if separable == "auto" and y_window is None else None
-            self._ysep = None
-            if ysep is not None and len(ysep[0]) <= MAX_TAPS:
-                ky, kzx = ysep
-                zx = np.ascontiguousarray(kzx[:, None, :])                     # a (pz, 1, px) PSF
-                zx_taps = prepared_dense_taps(zx)
-                if zx_taps is not None:                                        # pz <= 11, px <= 9
-                    one = dev(np.ones(1, np.float32))
-                    emb = np.zeros(w.shape, np.float32)                        # kzx in the centre y row
-                    emb[:, w.shape[1] // 2, :] = kzx
-                    fused_taps = prepared_dense_taps(emb)                      # also needs py <= 9
-                    self._ysep = dict(
-                        fused=None if fused_taps is None else dict(
-                            taps=dev(fused_taps[0]), taps_flipped=dev(fused_taps[1]),
-                            norm_table=dev(_prefix_table(ky[None, :, None] * kzx[:, None, :]).ravel(), torch.float64),
-                            norm_full=float((ky.astype(np.float64)[None, :, None]
-                                             * kzx.astype(np.float64)[:, None, :]).sum())),
-                        ky=dev(ky), ky_flipped=dev(ky[::-1]), one=one, py=len(ky), zx_shape=zx.shape,
-                        taps=dev(zx_taps[0]), taps_flipped=dev(zx_taps[1]),
-                        norm_table=dev(_prefix_table(zx).ravel(), torch.float64),
-                        norm_full=float(zx.astype(np.float64).sum()),
-                        ny=dev(_axis_norm(ky, y)), ones_z=dev(np.ones(z, np.float32)),
-                        ones_x=dev(np.ones(x, np.float32)))
-            self._psf = _DevicePsf(
-                separable=False,
-                shape=tuple(w.shape),
-                w=dev(w.ravel()),
-                w_flipped=dev(w[::-1, ::-1, ::-1].ravel()),
-                norm_table=dev(_prefix_table(w).ravel(), torch.float64),
-                norm_full=float(w.astype(np.float64).sum()),
-            )
-            taps = prepared_dense_taps(w) if self._ysep is None else None
-            if taps is not None:  # PSF small enough for the tuned dense kernel
-                self._psf.taps, self._psf.taps_flipped = dev(taps[0]), dev(taps[1])
-            self._norm = None
-        if factors is not None:
-            self._ysep = None
-        # ky (x) kzx with both factors inside the kernels' range: one launch per ITERATION (rl_fused_ysep.hip; results
-        # bit-identical to the pair) -- since round 4 the faster form at every compiled extent (config-2 grid, ms per
-        # iteration, one launch / pair: 3x3x3 2.27 / 4.71, 5x5x5 2.82 / 4.57, 9x7x7 4.37 / 5.02, 9x9x9 5.14 / 5.46,
-        # 11x9x9 6.19 / 6.95; profiles/r04_ysep_sweep.jsonl).  fused="never" keeps one launch per correlation.
-        self.fused_ysep = False
-        if (self._ysep is not None and self._ysep["fused"] is not None and self._fused_mode in ("auto", "always")
-                and _lib.call_value("lsr_rl_ysep_fused_supported", *self._psf.shape)):
-            ky, kzx = ysep
-            ky_c, kzx_c = np.ascontiguousarray(ky, dtype=np.float32), np.ascontiguousarray(kzx, dtype=np.float32)
-            block = np.zeros(_lib.call_value("lsr_rl_ysep_fused_taps_count"), np.float32)
-            _lib.call("lsr_rl_ysep_fused_prepare_taps", ky_c.ctypes.data, len(ky_c), kzx_c.ctypes.data,
-                      kzx_c.shape[0], kzx_c.shape[1], block.ctypes.data)
-            self._ysep["iter_taps"] = dev(block)
-            self.fused_ysep = True
-        self._t_pad = None   # y-separable path: the intermediate between the (z, x) and the y pass
-        self._ratio = None   # dense path: ratio scratch
-        self._x_pad = None   # separable path: zero-haloed working volumes
-        self._ratio_pad = None
-        self._y_pad = None   # fused path: padded copy of a dense y
-        self._tv_prev = None  # RL-TV on the paths that update x in place: x_k, kept for the TV launch
-        self._accel_g = None     # accelerated runs: the dense g_k ...
-        self._accel_pad = None   # ... the third padded volume the fused kinds rotate through ...
-        self._accel_prev = None  # ... or, on the paths that update x in place, two dense volumes (p_k and x_k)
-        self.last_alphas = None
+            ysep = factor_psf_y(self.psf, separable_rtol) if separable == "auto" and y_window is None else None
+            self._path = self._dense_path(ysep, fused)
+
+    def _separable_path(self, factors, fused: str, y_window):
+        z, y, x = self.shape
+        kz, ky, kx = factors
+        ny = _axis_norm(ky, y)
+        if y_window is not None:
+            first, total = (int(v) for v in y_window)
+            if first < 0 or first + y > total:
+                raise ValueError(f"y_window {y_window} does not contain {y} rows")
+            ny = _axis_norm(ky, total)[first:first + y]
+        norm = tuple(_dev(n, self.device) for n in (_axis_norm(kz, z), ny, _axis_norm(kx, x)))
+        # an axial factor beyond the tiled kernels' 15 taps: every correlation = in-plane launch + z launch
+        if len(kz) > MAX_TAPS:
+            return _LongZ(self.shape, self.device, factors, norm)
         # one launch per iteration (rl_fused_sep.hip) where the PSF fits its specialisations
-        self.fused = bool(self._psf.separable and not self._long_z and self._fused_mode in ("auto", "always")
-                          and _lib.call_value("lsr_rl_sep_fused_supported", *self._psf.shape)
-                          and (self._fused_mode == "always" or fused_pays(*self._psf.shape)))
-        if self.fused:
-            kz, ky, kx = (np.ascontiguousarray(k, dtype=np.float32) for k in factors)
-            block = np.zeros(_lib.call_value("lsr_rl_sep_fused_taps_count"), np.float32)
-            _lib.call("lsr_rl_sep_fused_prepare_taps", kz.ctypes.data, len(kz), ky.ctypes.data, len(ky),
-                      kx.ctypes.data, len(kx), block.ctypes.data)
-            self._fused_taps = dev(block)
+        if (fused in ("auto", "always") and _lib.call_value("lsr_rl_sep_fused_supported", *self.psf_shape)
+                and (fused == "always" or fused_pays(*self.psf_shape))):
+            return _Fused(self.shape, self.device, factors, norm)
+        return _SeparablePair(self.shape, self.device, factors, norm)
+
+    def _dense_path(self, ysep, fused: str):
+        w, device = self.psf, self.device
+        if ysep is not None and len(ysep[0]) <= MAX_TAPS:
+            ky, kzx = ysep
+            zx_taps = prepared_dense_taps(np.ascontiguousarray(kzx[:, None, :]))      # a (pz, 1, px) PSF
+            if zx_taps is not None:                                        # pz <= 11, px <= 9
+                emb = np.zeros(w.shape, np.float32)                        # kzx in the centre y row
+                emb[:, w.shape[1] // 2, :] = kzx
+                both_taps = prepared_dense_taps(emb)                       # also needs py <= 9
+                both = None
+                if both_taps is not None:
+                    full = ky.astype(np.float64)[None, :, None] * kzx.astype(np.float64)[:, None, :]
+                    both = (_dev(both_taps[0], device), _dev(both_taps[1], device),
+                            _dev(_prefix_table(ky[None, :, None] * kzx[:, None, :]).ravel(), device, np.float64),
+                            float(full.sum()))
+                # ky (x) kzx with both factors inside the kernels' range: one launch per ITERATION (rl_fused_ysep.hip;
+                # results bit-identical to the pair) -- since round 4 the faster form at every compiled extent (config-2
+                # grid, ms per iteration, one launch / pair: 3x3x3 2.27 / 4.71, 5x5x5 2.82 / 4.57, 9x7x7 4.37 / 5.02,
+                # 9x9x9 5.14 / 5.46, 11x9x9 6.19 / 6.95; profiles/r04_ysep_sweep.jsonl).  fused="never" keeps one launch
+                # per correlation.
+                if (both is not None and fused in ("auto", "always")
+                        and _lib.call_value("lsr_rl_ysep_fused_supported", *self.psf_shape)):
+                    return _FusedYsep(self.shape, device, ky, kzx, both[2], both[3])
+                return _YsepPair(self.shape, device, w, ky, kzx, zx_taps, both)
+        taps = prepared_dense_taps(w)
+        if taps is not None:  # PSF small enough for the tuned dense kernel
+            return _Dense(self.shape, device, w, taps)
+        return _Generic(self.shape, device, w)
 
     @property
     def separable(self) -> bool:
-        return self._psf.separable
+        return self._path.separable
+
+    @property
+    def fused(self) -> bool:
+        return isinstance(self._path, _Fused)
+
+    @property
+    def fused_ysep(self) -> bool:
+        return isinstance(self._path, _FusedYsep)
 
     @property
     def padded_input(self) -> bool:
         """``plan(y)`` can take a zero-haloed :class:`PaddedVolume` written in place by the producer of ``y``."""
-        return self.path != "generic"
+        return self._path.padded
 
     @property
     def path(self) -> str:
         """Which kernels an iteration runs: ``fused`` (one launch), ``separable`` (ratio / update
         pair), ``y-separable`` ((z, x) stencil + y pass, twice), ``dense`` or ``generic``."""
-        if self._psf.separable:
-            if self._long_z:
-                return "separable (long z, 4 launches)"
-            return "fused" if self.fused else "separable"
-        if self._ysep is not None:
-            if self.fused_ysep:
-                return "y-separable (fused)"
-            return "y-separable" if self._ysep["fused"] is not None else "y-separable (4 launches)"
-        return "dense" if self._psf.taps is not None else "generic"
+        return self._path.name
 
     def _scratch(self):
-        import torch
-
-        if self._psf.separable or self._psf.taps is not None or self._ysep is not None:
-            if self._x_pad is None:
-                self._x_pad = PaddedVolume(self.shape, self._pad_psf_shape(), self.device)
-                self._ratio_pad = PaddedVolume(self.shape, self._pad_psf_shape(), self.device)
-            return self._x_pad, self._ratio_pad
-        if self._ratio is None:
-            self._ratio = torch.empty(self.shape, dtype=torch.float32, device=self.device)
-        return self._ratio
+        """The two working volumes of the path."""
+        return tuple(self._path.volumes())
 
     def padded_geometry(self):
         """(pitch, plane, rows, origin_row, origin_col) of this plan's padded working volumes."""
-        rows, pitch, oy, ox = padded_shape(self.shape, self._pad_psf_shape())
+        rows, pitch, oy, ox = padded_shape(self.shape, self._path.pad_psf_shape)
         return pitch, rows * pitch, rows, oy, ox
 
     def new_padded_input(self) -> "PaddedVolume":
         """A zero-haloed volume in this plan's geometry, for a producer (the deskew kernel) to write
         ``y`` into; pass it to ``plan(...)`` to skip both the pad copy and the ``x0 = y`` copy."""
-        return PaddedVolume(self.shape, self._pad_psf_shape(), self.device)
-
-    def _pad_psf_shape(self):
-        """The PSF extents the padded working volumes are laid out for (the z extent of a long-z PSF is not the tiled
-        kernels' business: they run with one z tap)."""
-        return (1,) + tuple(self._psf.shape[1:]) if self._long_z else tuple(self._psf.shape)
-
-    def _iterate_long_z(self, y_ptr, y_pitch, y_plane, init, x_out, it0, n, eps, stream, stats):
-        """RL for a separable PSF with 17 .. 31 z taps: H x = Cz(Cyx(x)) -- the in-plane factors through the tiled
-        separable kernel with a single z tap, the z factor through ``lsr_correlate_z_f32`` (a register march, no halo),
-        which also carries the epilogues.  Four launches and 48 algorithmic bytes per voxel and iteration."""
-        import torch
-
-        x_pad, ratio_pad = self._scratch()
-        if it0 == 0:
-            x_pad.view.copy_(init)
-        if self._t_dense is None:
-            self._t_dense = torch.empty(self.shape, dtype=torch.float32, device=self.device)
-        t = self._t_dense
-        z, yy, xx = self.shape
-        pitch, plane = x_pad.pitch, x_pad.plane
-        (kz, ky, kx), (fz, fy, fx) = self._psf.k, self._psf.k_flipped
-        nz, ny, nx = self._norm
-        pz, py, px = self._psf.shape
-        one = self._one
-        ceps, f0 = ctypes.c_float(eps), ctypes.c_float(0.0)
-        for it in range(it0, it0 + n):
-            last = x_out is not None and it + 1 == it0 + n
-            for src, wy, wx, wz, epi, aux, out in (
-                    (x_pad, fy, fx, fz, _lib.EPI_RATIO, (y_ptr, y_pitch, y_plane), (ratio_pad.logical_ptr(), pitch, plane)),
-                    (ratio_pad, ky, kx, kz, _lib.EPI_UPDATE, (x_pad.logical_ptr(), pitch, plane),
-                     (x_out.data_ptr(), xx, yy * xx) if last else (x_pad.logical_ptr(), pitch, plane))):
-                _lib.call("lsr_correlate_sep_strided_f32", src.logical_ptr(), pitch, plane, None, 0, 0, t.data_ptr(), xx,
-                          yy * xx, z, yy, xx, one.data_ptr(), 1, wy.data_ptr(), py, wx.data_ptr(), px, _lib.EPI_NONE, f0,
-                          None, None, None, stream)
-                _lib.call("lsr_correlate_z_f32", t.data_ptr(), xx, yy * xx, aux[0], aux[1], aux[2], out[0], out[1], out[2],
-                          z, yy, xx, wz.data_ptr(), pz, epi, ceps, nz.data_ptr(), ny.data_ptr(), nx.data_ptr(),
-                          None if (stats is None or epi != _lib.EPI_UPDATE) else stats.data_ptr() + 24 * it, stream)
+        return PaddedVolume(self.shape, self._path.pad_psf_shape, self.device)
 
     def iterate_padded(self, y_pad: "PaddedVolume", src: "PaddedVolume", dst: "PaddedVolume",
                        eps: float = 1e-6, stats=None) -> None:
@@ -548,173 +705,16 @@ class RichardsonLucyPlan:
                 raise ValueError(f"{name} does not have this plan's padded geometry")
         if src is dst:
             raise ValueError("src and dst must be different volumes")
-        z, yy, xx = self.shape
-        ps = self._psf
-        nz, ny, nx = self._norm
         with torch.cuda.device(self.device):
-            # x_a = src (iteration 0 reads it), x_b = dst (iteration 0 writes it)
             if stats is not None and (stats.dtype != torch.float64 or stats.numel() < 3 or stats.device != self.device):
                 raise ValueError("stats must be a float64 tensor of >= 3 elements on the plan's device")
-            _lib.call(
-                "lsr_rl_sep_fused_stats_f32", y_pad.logical_ptr(), y_pad.pitch, y_pad.plane, 0,
-                src.full.data_ptr(), dst.full.data_ptr(), None, z, yy, xx, self._fused_taps.data_ptr(),
-                ps.shape[0], ps.shape[1], ps.shape[2], nz.data_ptr(), ny.data_ptr(), nx.data_ptr(), 1,
-                ctypes.c_float(eps), None if stats is None else stats.data_ptr(), _lib.stream_ptr(self.device),
-            )
-
-    def _ysep_nzx(self):
-        """(Z, X) table of the (z, x) stencil's border normalisation (sum of the kzx taps that land inside), float64 on
-        the device -- only the four-launch path's flux needs it (its last launch divides by ny alone)."""
-        import torch
-
-        q = self._ysep
-        if "nzx" not in q:
-            z, _, x = self.shape
-            kzx = self.psf.astype(np.float64).sum(axis=1)          # ky sums to 1: the (z, x) stencil
-            pz, px = kzx.shape
-            cs = np.zeros((pz + 1, px + 1))
-            cs[1:, 1:] = kzx.cumsum(0).cumsum(1)
-            zi, xi = np.arange(z), np.arange(x)
-            a0, a1 = np.maximum(0, pz // 2 - zi), np.minimum(pz, z - zi + pz // 2)
-            c0, c1 = np.maximum(0, px // 2 - xi), np.minimum(px, x - xi + px // 2)
-            t = cs[a1][:, c1] - cs[a0][:, c1] - cs[a1][:, c0] + cs[a0][:, c0]
-            q["nzx"] = torch.as_tensor(t, device=self.device)
-        return q["nzx"]
-
-    def _iterate_ysep(self, y_ptr, y_pitch, y_plane, init, x_out, it0, n, eps, stream, stats):
-        """RL with ``psf = ky (x) kzx``, iterations ``it0 .. it0 + n - 1`` (the estimate lives in ``x_pad`` between
-        calls; ``init`` is copied in when ``it0 == 0``): each correlation is the dense (z, x) stencil (PZ * PX FMAs per
-        voxel instead of PZ * PY * PX) followed by the y pass that carries the epilogue --
-        ``H x = Y~(ZX~(x))`` with ``ratio = y / (. + eps)`` in the y pass; ``H^T r = Y(ZX(r))`` with the
-        (z, x) border normalisation in the stencil launch (``LSR_EPI_SCALE``) and ``x * . / ny`` in
-        the y pass.  Four launches per iteration (two where both factors fit one kernel), all on zero-haloed padded
-        volumes.  ``stats``: float64 device tensor (iterations, 3), zeroed by the caller, or ``None``."""
-        import torch
-
-        q = self._ysep
-        x_pad, ratio_pad = self._scratch()
-        if it0 == 0:
-            x_pad.view.copy_(init)
-        z, yy, xx = self.shape
-        pitch, plane = x_pad.pitch, x_pad.plane
-        ceps = ctypes.c_float(eps)
-
-        def sptr(it):
-            return None if stats is None else stats.data_ptr() + 24 * it
-
-        if q["fused"] is not None:
-            # both factors in one launch per correlation (lsr_correlate_zxy_padded_f32): the y pass
-            # runs inside the stencil kernel, wave by wave, on the staged plane
-            f = q["fused"]
-            pz, py, px = self._psf.shape
-            for it in range(it0, it0 + n):
-                last = x_out is not None and it + 1 == it0 + n
-                _lib.call("lsr_correlate_zxy_padded_f32", x_pad.logical_ptr(), pitch, plane, y_ptr, y_pitch, y_plane,
-                          ratio_pad.logical_ptr(), pitch, plane, z, yy, xx, f["taps_flipped"].data_ptr(),
-                          q["ky_flipped"].data_ptr(), pz, py, px, _lib.EPI_RATIO, ceps, None,
-                          ctypes.c_float(1.0), stream)
-                out_ptr, out_pitch, out_plane = ((x_out.data_ptr(), xx, yy * xx) if last
-                                                 else (x_pad.logical_ptr(), pitch, plane))
-                _lib.call("lsr_correlate_zxy_padded_stats_f32", ratio_pad.logical_ptr(), pitch, plane, x_pad.logical_ptr(),
-                          pitch, plane, out_ptr, out_pitch, out_plane, z, yy, xx, f["taps"].data_ptr(),
-                          q["ky"].data_ptr(), pz, py, px, _lib.EPI_UPDATE, ceps, f["norm_table"].data_ptr(),
-                          ctypes.c_float(f["norm_full"]), sptr(it), stream)
-            return
-        if self._t_pad is None:
-            self._t_pad = PaddedVolume(self.shape, self._psf.shape, self.device)
-        t_pad = self._t_pad
-        pz, _, px = q["zx_shape"]
-        one, f0 = q["one"].data_ptr(), ctypes.c_float(0.0)
-        for it in range(it0, it0 + n):
-            last = x_out is not None and it + 1 == it0 + n
-            _lib.call("lsr_correlate_dense_padded_f32", x_pad.logical_ptr(), pitch, plane, None, 0, 0,
-                      t_pad.logical_ptr(), pitch, plane, z, yy, xx, q["taps_flipped"].data_ptr(), pz, 1, px,
-                      _lib.EPI_NONE, f0, None, ctypes.c_float(1.0), stream)
-            _lib.call("lsr_correlate_sep_strided_f32", t_pad.logical_ptr(), pitch, plane, y_ptr, y_pitch, y_plane,
-                      ratio_pad.logical_ptr(), pitch, plane, z, yy, xx, one, 1, q["ky_flipped"].data_ptr(), q["py"],
-                      one, 1, _lib.EPI_RATIO, ceps, None, None, None, stream)
-            _lib.call("lsr_correlate_dense_padded_f32", ratio_pad.logical_ptr(), pitch, plane, None, 0, 0,
-                      t_pad.logical_ptr(), pitch, plane, z, yy, xx, q["taps"].data_ptr(), pz, 1, px,
-                      _lib.EPI_SCALE, f0, q["norm_table"].data_ptr(), ctypes.c_float(q["norm_full"]), stream)
-            out_ptr, out_pitch, out_plane = ((x_out.data_ptr(), xx, yy * xx) if last
-                                             else (x_pad.logical_ptr(), pitch, plane))
-            _lib.call("lsr_correlate_sep_strided_stats_f32", t_pad.logical_ptr(), pitch, plane, x_pad.logical_ptr(), pitch,
-                      plane, out_ptr, out_pitch, out_plane, z, yy, xx, one, 1, q["ky"].data_ptr(), q["py"], one, 1,
-                      _lib.EPI_UPDATE, ceps, q["ones_z"].data_ptr(), q["ny"].data_ptr(), q["ones_x"].data_ptr(),
-                      sptr(it), stream)
-            if stats is not None:
-                # this launch's x * u is x * H^T(ratio) / nzx (the (z, x) normalisation went into the stencil launch): the
-                # flux of the full update, sum x_new * nzx * ny, is formed here from the new estimate -- this path is the
-                # fallback for y extents beyond the one-launch kernels, an extra reduction does not matter to it
-                x_new = x_out if last else x_pad.view
-                rows = torch.einsum("zyx,y->zx", x_new, q["ny"])
-                stats[it, 0] = (rows.double() * self._ysep_nzx()).sum()
+            self._path.launch(rl_loop.tri(y_pad), 0, src, dst, None, 1, ctypes.c_float(eps),
+                              None if stats is None else stats.data_ptr(), _lib.stream_ptr(self.device))
 
     def release(self) -> None:
         """Drop the scratch volumes."""
-        self._ratio = self._x_pad = self._ratio_pad = self._y_pad = self._t_pad = self._t_dense = self._tv_prev = None
-        self._accel_g = self._accel_pad = self._accel_prev = None
-
-    # ------------------------------------------------------------------------------------------ the loop
-    def _launch(self, st, it0: int, n: int, x_out, stats, ab=None) -> None:
-        """Iterations ``it0 .. it0 + n - 1`` of the run described by ``st`` (set up by ``__call__``); the last one
-        writes the dense ``x_out`` when that is not ``None``, otherwise the estimate stays in the working volume
-        ``_result_view(it0 + n)`` names.  ``stats``: float64 device tensor (iterations, 3), zero where not yet run.
-        ``ab`` (fused kinds): the padded allocations the first iteration reads and writes, instead of the two of
-        ``_scratch()`` by the parity of ``it0`` (an accelerated run rotates three)."""
-        z, yy, xx = self.shape
-        ps = self._psf
-        stream, eps = st["stream"], ctypes.c_float(st["eps"])
-        y_ptr, y_pitch, y_plane = st["y"]
-        from_y = int(st["from_y"] and it0 == 0)
-        xo = None if x_out is None else x_out.data_ptr()
-        sp = None if stats is None else stats.data_ptr() + 24 * it0
-        kind = st["kind"]
-        if kind in ("fused", "fused-ysep"):
-            x_pad, ratio_pad = self._scratch()
-            bufs = (x_pad.full.data_ptr(), ratio_pad.full.data_ptr())   # iteration i reads bufs[i & 1], writes the other
-            a, b = (bufs[it0 & 1], bufs[(it0 + 1) & 1]) if ab is None else ab
-            if kind == "fused":
-                nz, ny, nx = self._norm
-                _lib.call("lsr_rl_sep_fused_stats_f32", y_ptr, y_pitch, y_plane, from_y, a, b, xo, z, yy, xx,
-                          self._fused_taps.data_ptr(), ps.shape[0], ps.shape[1], ps.shape[2], nz.data_ptr(),
-                          ny.data_ptr(), nx.data_ptr(), n, eps, sp, stream)
-            else:
-                f = self._ysep["fused"]
-                _lib.call("lsr_rl_ysep_fused_stats_f32", y_ptr, y_pitch, y_plane, from_y, a, b, xo, z, yy, xx,
-                          self._ysep["iter_taps"].data_ptr(), ps.shape[0], ps.shape[1], ps.shape[2],
-                          f["norm_table"].data_ptr(), ctypes.c_float(f["norm_full"]), n, eps, sp, stream)
-        elif kind == "separable":
-            x_pad, ratio_pad = self._scratch()
-            (kz, ky, kx), (fz, fy, fx) = ps.k, ps.k_flipped
-            nz, ny, nx = self._norm
-            _lib.call("lsr_rl_sep_stats_f32", y_ptr, y_pitch, y_plane, from_y, x_pad.full.data_ptr(),
-                      ratio_pad.full.data_ptr(), xo, z, yy, xx, kz.data_ptr(), fz.data_ptr(), ps.shape[0],
-                      ky.data_ptr(), fy.data_ptr(), ps.shape[1], kx.data_ptr(), fx.data_ptr(), ps.shape[2],
-                      nz.data_ptr(), ny.data_ptr(), nx.data_ptr(), n, eps, sp, stream)
-        elif kind == "ysep":
-            self._iterate_ysep(y_ptr, y_pitch, y_plane, st["init"], x_out, it0, n, st["eps"], stream, stats)
-        elif kind == "longz":
-            self._iterate_long_z(y_ptr, y_pitch, y_plane, st["init"], x_out, it0, n, st["eps"], stream, stats)
-        elif kind == "dense":
-            x_pad, ratio_pad = self._scratch()
-            _lib.call("lsr_rl_dense_padded_stats_f32", y_ptr, y_pitch, y_plane, from_y, x_pad.full.data_ptr(),
-                      ratio_pad.full.data_ptr(), xo, z, yy, xx, ps.taps.data_ptr(), ps.taps_flipped.data_ptr(),
-                      ps.shape[0], ps.shape[1], ps.shape[2], ps.norm_table.data_ptr(), ctypes.c_float(ps.norm_full),
-                      n, eps, sp, stream)
-        else:   # generic: dense volumes, x updated in place
-            _lib.call("lsr_rl_dense_stats_f32", st["y_dense"].data_ptr(), st["x"].data_ptr(), self._scratch().data_ptr(),
-                      z, yy, xx, ps.w.data_ptr(), ps.w_flipped.data_ptr(), ps.shape[0], ps.shape[1], ps.shape[2],
-                      ps.norm_table.data_ptr(), n, eps, sp, stream)
-
-    def _result_view(self, st, done: int):
-        """Where the estimate is after ``done`` iterations that did not write the dense output."""
-        if st["kind"] == "generic":
-            return st["x"]
-        x_pad, ratio_pad = self._scratch()
-        if st["kind"] in ("fused", "fused-ysep"):
-            return (x_pad, ratio_pad)[done & 1].view
-        return x_pad.view
+        self._y_pad = None
+        self._path.release()
 
     def __call__(self, y, iterations: int = 20, eps: float = 1e-6, x0=None, out=None, events=None, *,
                  stats: bool = False, tol: float | None = None, tv_lambda: float = 0.0, tv_eps: float = 1e-6,
@@ -738,15 +738,15 @@ class RichardsonLucyPlan:
         ``csrc/rl_accel.hip`` on the same stream; the next iteration starts from the extrapolated point they leave.  The
         fused kinds rotate three padded volumes (no copy); the kinds that update x in place keep p_k and x_k in two dense
         volumes (two copies per iteration).  ``plan.last_alphas``: the step lengths used (float64, a_1 = 0 first).
-        ``stats`` / ``tol`` keep the RL launch's meaning (:class:`RLStats`).  ``"none"`` (default): the plain run."""
+        ``stats`` / ``tol`` keep the RL launch's meaning (:class:`RLStats`).  ``"none"`` (default): the plain run.
+
+        The loop itself is ``shrimpy_amd.rl_loop.run``; the launches are the path's."""
         import torch
 
-        tv_lambda, tv_eps = check_tv(tv_lambda, tv_eps)
-        accelerate = check_acceleration(acceleration, tv_lambda)
-        self.last_alphas = None
+        path = self._path
         y_padded = None
         if isinstance(y, PaddedVolume):  # e.g. written in place by the deskew kernel
-            if not (self._psf.separable or self._psf.taps is not None or self._ysep is not None):
+            if not path.padded:
                 y = y.view.contiguous()
             else:
                 y_padded, y = y, y.view
@@ -756,278 +756,39 @@ class RichardsonLucyPlan:
             raise ValueError(f"y must be {self.shape} on {self.device}, got {tuple(y.shape)} on {y.device}")
         if y_padded is not None and (y_padded.pitch, y_padded.plane) != self.padded_geometry()[:2]:
             raise ValueError("the padded y does not have this plan's padded geometry")
-        iterations = int(iterations)
-        if iterations < 0:
-            raise ValueError("iterations must be >= 0")
-        if not eps > 0:
-            raise ValueError("eps must be > 0")
-        if tol is not None and not (tol >= 0 and np.isfinite(tol)):
-            raise ValueError("tol must be a finite number >= 0")
-        # x0 = y with a padded y needs no initial copy: the first iteration reads y directly
-        from_y = y_padded is not None and x0 is None and iterations > 0
-        y_ptr, y_pitch, y_plane = ((y_padded.logical_ptr(), y_padded.pitch, y_padded.plane)
-                                   if y_padded is not None else (y.data_ptr(), self.shape[2],
-                                                                 self.shape[1] * self.shape[2]))
-        init = y if x0 is None else _lib.require_device_f32(x0, "x0")
-        if tuple(init.shape) != self.shape:
-            raise ValueError(f"x0 must be {self.shape}")
-        if out is None:
-            x = torch.empty(self.shape, dtype=torch.float32, device=self.device)
-        else:
-            x = _lib.require_device_f32(out, "out")
-            if tuple(x.shape) != self.shape or x.data_ptr() == y.data_ptr():
-                raise ValueError("out must have the volume shape and must not alias y")
-        self.last_stats = None
-        self.stats_device = None
-        if iterations == 0:
-            x.copy_(init)
-            if stats or tol is not None:
-                self.last_stats = RLStats.from_array(np.zeros((0, 3)), 0)
-            if accelerate:
-                self.last_alphas = np.zeros(0)
-            return x
-        ps = self._psf
-        want_stats = bool(stats) or tol is not None
+        req = rl_loop.check_run(y, iterations, eps, x0, out, stats, tol, tv_lambda, tv_eps, acceleration,
+                                _lib.require_device_f32)
+        if req.out is None:
+            req.out = torch.empty(self.shape, dtype=torch.float32, device=self.device)
+        self.last_stats = self.stats_device = self.last_alphas = None
+
+        def begin():
+            y_vol = y if y_padded is None else y_padded
+            if path.needs_padded_y and y_padded is None:
+                if self._y_pad is None:
+                    self._y_pad = PaddedVolume(self.shape, path.pad_psf_shape, self.device)
+                self._y_pad.view.copy_(y)
+                y_vol = self._y_pad
+            # x0 = y with a padded y needs no initial copy: the first iteration reads y directly
+            from_y = path.reads_y and x0 is None and y_vol is not y
+            path.begin(rl_loop.tri(y_vol), from_y, req.eps, _lib.stream_ptr(self.device))
+            if not from_y:
+                path.load(req.init, req.out)
+            # x_0 as the first TV (dots) launch reads it: y itself (dense or padded) or the caller's x0 -- unless that is
+            # also the output tensor, which the RL launches write; a path that rotates has it in the volume it reads
+            if path.rotates:
+                u0 = y_vol if from_y else None
+            elif x0 is None:
+                u0 = y_vol
+            else:
+                u0 = None if req.init.data_ptr() == req.out.data_ptr() else req.init
+            return path, rl_loop.DeviceBackend(self.shape, self.device), u0, lambda: path.side("g")
+
         with torch.cuda.device(self.device):
-            st = dict(stream=_lib.stream_ptr(self.device), eps=float(eps), init=init)
-            padded_y_kinds = {"fused": ps.separable and self.fused,
-                              "fused-ysep": (not ps.separable) and self._ysep is not None and self.fused_ysep}
-            if padded_y_kinds["fused"] or padded_y_kinds["fused-ysep"]:
-                # one launch per iteration; y must be a zero-haloed padded volume (the kernel
-                # reads it on the tile grown by the PSF radius)
-                st["kind"] = "fused" if padded_y_kinds["fused"] else "fused-ysep"
-                x_pad, _ = self._scratch()
-                if y_padded is None:
-                    if self._y_pad is None:
-                        self._y_pad = PaddedVolume(self.shape, ps.shape, self.device)
-                    self._y_pad.view.copy_(y)
-                    y_padded = self._y_pad
-                    y_ptr, y_pitch, y_plane = y_padded.logical_ptr(), y_padded.pitch, y_padded.plane
-                    from_y = x0 is None
-                if not from_y:
-                    x_pad.view.copy_(init)
-            elif self._long_z:
-                st["kind"] = "longz"
-            elif ps.separable or ps.taps is not None and self._ysep is None:
-                # working volumes carry a zero halo: the kernels never bounds-check a load
-                st["kind"] = "separable" if ps.separable else "dense"
-                x_pad, _ = self._scratch()
-                if not from_y:
-                    x_pad.view.copy_(init)
-            elif self._ysep is not None:
-                st["kind"] = "ysep"
-            else:
-                st["kind"] = "generic"
-                x.copy_(init)
-                st["x"], st["y_dense"] = x, y
-            st["y"], st["from_y"] = (y_ptr, y_pitch, y_plane), from_y
-            dev_stats = None
-            if want_stats:
-                dev_stats = torch.zeros((iterations, 3), dtype=torch.float64, device=self.device)
-            if events:
-                events[0].record()
-            if tv_lambda > 0 or accelerate:
-                # x_0 as the first TV (dots) launch reads it: y itself (dense or padded) or the caller's x0 -- unless that
-                # is also the output tensor, which the RL launches write
-                u0 = None
-                if x0 is None:
-                    u0 = st["y"]
-                elif init.data_ptr() != x.data_ptr():
-                    u0 = (init.data_ptr(), self.shape[2], self.shape[1] * self.shape[2])
-            if accelerate:
-                done, stopped = self._run_accel(st, iterations, tol, dev_stats, x, u0)
-            elif tv_lambda > 0:
-                done, stopped, dev_stats = self._run_tv(st, iterations, tol, dev_stats, x, tv_lambda, tv_eps, u0)
-            elif tol is None:
-                self._launch(st, 0, iterations, None if st["kind"] == "generic" else x, dev_stats)
-                done, stopped = iterations, False
-            else:
-                done, stopped = self._run_to_tolerance(st, iterations, float(tol), dev_stats)
-                if st["kind"] != "generic":
-                    x.copy_(self._result_view(st, done))
-            if events:
-                events[1].record()
-            if want_stats:
-                self.stats_device = dev_stats
-                self.last_stats = RLStats.from_array(dev_stats.cpu().numpy(), done, stopped)
-        _lib.mark_written(x)
-        return x
-
-    def _tv_iteration(self, st, it: int, x_out, dev_stats, tv_stats, lam: float, tv_eps: float, u0) -> None:
-        """Iteration ``it`` of an RL-TV run: the plain iteration's launches, then ``lsr_rl_tv_scale_f32`` with ``u`` =
-        the estimate they read and ``v`` = the one they wrote, in place -- or into the dense ``x_out``.  The fused kinds
-        ping-pong between two volumes, so both are at hand; the kinds that update x in place get ``x_k`` copied into a
-        scratch volume first (``u0``, when not ``None``, is x_0 where the caller left it: no copy for iteration 0)."""
-        import torch
-
-        z, yy, xx = self.shape
-        dense = (xx, yy * xx)
-        kind = st["kind"]
-        if kind in ("fused", "fused-ysep"):
-            vols = self._scratch()
-            src, dst = vols[it & 1], vols[(it + 1) & 1]
-            u = u0 if (it == 0 and st["from_y"]) else (src.logical_ptr(), src.pitch, src.plane)
-            v = (dst.logical_ptr(), dst.pitch, dst.plane)
-        else:
-            if kind == "generic":
-                cur, v = st["x"], (st["x"].data_ptr(),) + dense
-            else:
-                x_pad = self._scratch()[0]
-                cur, v = x_pad.view, (x_pad.logical_ptr(), x_pad.pitch, x_pad.plane)
-            if it == 0 and u0 is not None:
-                u = u0
-            else:
-                if self._tv_prev is None:
-                    self._tv_prev = torch.empty(self.shape, dtype=torch.float32, device=self.device)
-                # (iteration 0 of the ysep / long-z kinds fills the working volume inside their own loop)
-                self._tv_prev.copy_(st["init"] if it == 0 else cur)
-                u = (self._tv_prev.data_ptr(),) + dense
-        self._launch(st, it, 1, None, dev_stats)
-        out = v if x_out is None else (x_out.data_ptr(),) + dense
-        _lib.call("lsr_rl_tv_scale_f32", *u, *v, *out, z, yy, xx, ctypes.c_float(lam), ctypes.c_float(tv_eps),
-                  None if tv_stats is None else tv_stats.data_ptr() + 16 * it, st["stream"])
-
-    def _run_tv(self, st, iterations: int, tol, dev_stats, x, lam: float, tv_eps: float, u0):
-        """The RL-TV loop.  Returns (iterations run, stopped early, the (iterations, 3) scalars the caller sees: flux
-        from the RL launches, change and total from the TV launches -- or ``None``).  ``tol`` reads the TV launch's
-        scalars one iteration late, as ``_run_to_tolerance`` does the RL launch's."""
-        import torch
-
-        tv_stats = None if dev_stats is None else torch.zeros((iterations, 2), dtype=torch.float64, device=self.device)
-        done, stopped = 0, False
-        if tol is None:
-            for it in range(iterations):
-                last = it + 1 == iterations and st["kind"] != "generic"
-                self._tv_iteration(st, it, x if last else None, dev_stats, tv_stats, lam, tv_eps, u0)
-            done = iterations
-        else:
-            host = torch.empty((iterations, 2), dtype=torch.float64).pin_memory()
-            arrived = [torch.cuda.Event() for _ in range(iterations)]
-
-            def met(i):
-                arrived[i].synchronize()
-                change, total = float(host[i, 0]), float(host[i, 1])
-                return total > 0 and change <= tol * total or total == 0
-
-            for it in range(iterations):
-                self._tv_iteration(st, it, None, dev_stats, tv_stats, lam, tv_eps, u0)
-                host[it].copy_(tv_stats[it], non_blocking=True)
-                arrived[it].record()
-                done = it + 1
-                if it >= 1 and met(it - 1):
-                    stopped = True
-                    break
-            if not stopped:
-                stopped = bool(met(iterations - 1))
-            if st["kind"] != "generic":
-                x.copy_(self._result_view(st, done))
-        if dev_stats is not None:
-            dev_stats = torch.cat((dev_stats[:, :1], tv_stats), dim=1)
-        return done, stopped, dev_stats
-
-    def _run_accel(self, st, iterations: int, tol, dev_stats, x, u0):
-        """The accelerated loop (``csrc/rl_accel.hip`` states it).  Returns (iterations run, stopped early); the dense ``x``
-        holds x_done.  Fused kinds: ``rd`` holds p_k, ``wr`` receives x_{k+1}, ``hold`` holds x_k and receives p_{k+1};
-        then ``rd, wr, hold = hold, rd, wr``.  The other kinds run RL in place in the working volume ``cur``: ``b`` is a
-        copy of p_k, ``c`` holds x_k and receives p_{k+1}; before the next RL launch x_{k+1} is saved from ``cur`` into
-        the free ``b`` and p_{k+1} copied into ``cur``, and ``b`` and ``c`` trade places.  ``tol`` reads the RL launch's
-        scalars one iteration late, as ``_run_to_tolerance`` does."""
-        import torch
-
-        z, yy, xx = self.shape
-        dense = (xx, yy * xx)
-        kind, stream = st["kind"], st["stream"]
-        if self._accel_g is None:
-            self._accel_g = torch.empty(self.shape, dtype=torch.float32, device=self.device)
-        acc = AccelState(self.shape, self.device, iterations, self._accel_g)
-
-        def tri(v):
-            return (v.logical_ptr(), v.pitch, v.plane)
-
-        rotate = kind in ("fused", "fused-ysep")
-        if rotate:
-            if self._accel_pad is None:
-                self._accel_pad = PaddedVolume(self.shape, self._pad_psf_shape(), self.device)
-            rd, wr = self._scratch()
-            hold = self._accel_pad
-        else:
-            if self._accel_prev is None:
-                self._accel_prev = [torch.empty(self.shape, dtype=torch.float32, device=self.device) for _ in range(2)]
-            b, c = self._accel_prev
-            if kind == "generic":
-                cur, cur3 = st["x"], (st["x"].data_ptr(),) + dense
-            else:
-                x_pad = self._scratch()[0]
-                cur, cur3 = x_pad.view, tri(x_pad)
-        if tol is not None:
-            host = torch.empty((iterations, 3), dtype=torch.float64).pin_memory()
-            arrived = [torch.cuda.Event() for _ in range(iterations)]
-
-        def met(i):
-            arrived[i].synchronize()
-            change, total = float(host[i, 1]), float(host[i, 2])
-            return total > 0 and change <= tol * total or total == 0
-
-        done, stopped, result = 0, False, None
-        for it in range(iterations):
-            last = it + 1 == iterations
-            x_out = x if (last and tol is None and kind != "generic") else None
-            if rotate:
-                self._launch(st, it, 1, x_out, dev_stats, ab=(rd.full.data_ptr(), wr.full.data_ptr()))
-                result = wr.view
-                if not last:
-                    acc.step(it, tri(wr), st["y"] if (it == 0 and st["from_y"]) else tri(rd), tri(hold), stream)
-                    rd, wr, hold = hold, rd, wr
-            else:
-                if it == 0:
-                    # (iteration 0 of the ysep / long-z kinds fills the working volume inside their own loop)
-                    p3 = u0 if u0 is not None else (b.copy_(st["init"]).data_ptr(),) + dense
-                else:
-                    b.copy_(cur)
-                    cur.copy_(c)
-                    b, c = c, b
-                    p3 = (b.data_ptr(),) + dense
-                self._launch(st, it, 1, x_out, dev_stats)
-                result = cur
-                if not last:
-                    acc.step(it, cur3, p3, (c.data_ptr(),) + dense, stream)
-            done = it + 1
-            if tol is not None:
-                host[it].copy_(dev_stats[it], non_blocking=True)
-                arrived[it].record()
-                if it >= 1 and met(it - 1):
-                    stopped = True
-                    break
-        if tol is not None:
-            if not stopped:
-                stopped = bool(met(done - 1))
-            if kind != "generic":
-                x.copy_(result)
-        self.last_alphas = acc.used(done)
-        return done, stopped
-
-    def _run_to_tolerance(self, st, iterations: int, tol: float, dev_stats):
-        """One launch group per iteration; iteration i's scalars travel to pinned host memory behind it and are looked at
-        after iteration i + 1 has been queued.  Returns (iterations run, stopped early)."""
-        import torch
-
-        host = torch.empty((iterations, 3), dtype=torch.float64).pin_memory()
-        arrived = [torch.cuda.Event() for _ in range(iterations)]
-
-        def met(i):
-            arrived[i].synchronize()
-            change, total = float(host[i, 1]), float(host[i, 2])
-            return total > 0 and change <= tol * total or total == 0
-
-        done = 0
-        for it in range(iterations):
-            self._launch(st, it, 1, None, dev_stats)
-            host[it].copy_(dev_stats[it], non_blocking=True)
-            arrived[it].record()
-            done = it + 1
-            if it >= 1 and met(it - 1):
-                return done, True
-        return done, bool(met(iterations - 1))
+            res = rl_loop.run(req, begin, events)
+        self.last_stats, self.stats_device, self.last_alphas = res.stats, res.rows, res.alphas
+        _lib.mark_written(res.x)
+        return res.x
 
 
 def make_plan(shape_zyx, psf, device, *, separable: str = "auto", separable_rtol: float = 1e-6, psf_factors=None,

@@ -35,7 +35,7 @@ import ctypes
 
 import numpy as np
 
-from . import _lib, fft3
+from . import _lib, fft3, rl_loop
 
 __all__ = ["FftRichardsonLucyPlan", "fft_grid", "fft_supported"]
 
@@ -74,7 +74,7 @@ def fft_supported(shape_zyx, psf_shape) -> bool:
     return fft3.rows_supported((gz, 8, gx))
 
 
-class FftRichardsonLucyPlan:
+class FftRichardsonLucyPlan(rl_loop.InPlace):
     """Spectrum of the PSF, border normalisation and scratch for one (volume shape, PSF, device).
 
     Same call contract as :class:`shrimpy_amd.deconvolve.RichardsonLucyPlan`: ``plan(y)`` runs the iterations and
@@ -83,6 +83,7 @@ class FftRichardsonLucyPlan:
     reaching 0 at a fixed point, so a ``tol`` below ~1e-6 never stops this route early.)"""
 
     padded_input = False     # y is a plain dense volume (the stencil plans take zero-haloed ones)
+    dense_out = False        # the iterations run in the output tensor itself
     path = "fft"
     separable = False
     fused = False
@@ -92,11 +93,10 @@ class FftRichardsonLucyPlan:
 
         from .deconvolve import _prefix_table, prepare_psf
 
-        self.device = torch.device(device)
+        rl_loop.InPlace.__init__(self, shape_zyx, torch.device(device))
         if self.device.type != "cuda":
             raise _lib.LsrError("FftRichardsonLucyPlan", -1, f"device {self.device} is not a GPU: CPU tensors run the host "
                                 "twins of the stencil path through richardson_lucy()")
-        self.shape = tuple(int(v) for v in shape_zyx)
         if len(self.shape) != 3 or min(self.shape) <= 0:
             raise ValueError(f"shape_zyx must be three positive ints, got {self.shape}")
         self.psf = prepare_psf(psf, MAX_FFT_TAPS, MAX_FFT_TAPS)
@@ -125,13 +125,11 @@ class FftRichardsonLucyPlan:
         self._scale = 1.0 / (float(gz) * float(gy) * float(gx))
         self._b = None         # [Z][XC][Y] complex64: the one spectrum in flight
         self._ratio = None
-        self._accel = None     # accelerated runs: the dense g_k and two dense volumes (p_k and x_k)
-        self.last_stats = None
-        self.stats_device = None
-        self.last_alphas = None
+        self.last_stats = self.stats_device = self.last_alphas = None
 
     def release(self) -> None:
-        self._b = self._ratio = self._accel = None
+        self._b = self._ratio = None
+        self.drop_sides()       # RL-TV and accelerated runs: the dense x_k / p_k copies and g_k
 
     def _scratch(self):
         import torch
@@ -206,163 +204,44 @@ class FftRichardsonLucyPlan:
         else:
             self._iteration(x, y, eps, stats_row, first)
 
+    def run(self, it0, n, x_out, rows, ab=None) -> None:
+        """The stepper of ``rl_loop.run``: iterations in place in ``cur`` (the output tensor).  An accelerated run passes
+        ``first=True`` to every step: the chained form's carried-over spectrum would be x_k's, not p_k's."""
+        for it in range(it0, it0 + n):
+            self._step(self.cur, self._y, self._eps, None if rows is None else rows[it], it == 0 or self._accelerated)
+
     def __call__(self, y, iterations: int = 20, eps: float = 1e-6, x0=None, out=None, events=None, *,
                  stats: bool = False, tol: float | None = None, tv_lambda: float = 0.0, tv_eps: float = 1e-6,
                  acceleration: str = "none"):
         """Run RL; arguments as :meth:`shrimpy_amd.deconvolve.RichardsonLucyPlan.__call__`.  ``events``: ``(start, end)``
-        torch events recorded right around the launches (ten per iteration).  ``tv_lambda > 0``: this route updates the
-        estimate in place, so x_k is copied aside before each iteration and the TV launch follows it.
-        ``acceleration="biggs-andrews"``: likewise in place -- p_k and x_k live in two dense volumes, two copies and the
-        two launches of ``csrc/rl_accel.hip`` per iteration beside the ten of the iteration itself."""
+        torch events recorded right around the launches (ten per iteration).  This route updates the estimate in place
+        in the output tensor: with ``tv_lambda > 0`` x_k is copied aside before each iteration and the TV launch follows
+        it; with ``acceleration="biggs-andrews"`` p_k and x_k live in two dense volumes, two copies and the two launches
+        of ``csrc/rl_accel.hip`` per iteration beside the ten of the iteration itself (``shrimpy_amd.rl_loop.run``)."""
         import torch
-
-        from .deconvolve import RLStats, check_acceleration, check_tv
-
-        tv_lambda, tv_eps = check_tv(tv_lambda, tv_eps)
-        accelerate = check_acceleration(acceleration, tv_lambda)
-        self.last_alphas = None
 
         y = _lib.require_device_f32(y, "y")
         if tuple(y.shape) != self.shape or y.device != self.device:
             raise ValueError(f"y must be {self.shape} on {self.device}, got {tuple(y.shape)} on {y.device}")
-        iterations = int(iterations)
-        if iterations < 0:
-            raise ValueError("iterations must be >= 0")
-        if not eps > 0:
-            raise ValueError("eps must be > 0")
-        if tol is not None and not (tol >= 0 and np.isfinite(tol)):
-            raise ValueError("tol must be a finite number >= 0")
-        if out is None:
-            out = torch.empty(self.shape, dtype=torch.float32, device=self.device)
-        elif (tuple(out.shape) != self.shape or out.dtype != torch.float32 or out.device != self.device
-              or not out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous float32 {self.shape} tensor on {self.device}")
-        if out.data_ptr() == y.data_ptr():
-            raise ValueError("out must not alias y (y is read by every iteration)")
-        init = y if x0 is None else _lib.require_device_f32(x0, "x0")
-        if tuple(init.shape) != self.shape:
-            raise ValueError(f"x0 must be {self.shape}, got {tuple(init.shape)}")
-        want_stats = bool(stats) or tol is not None
-        self._tv = None
-        if tv_lambda > 0 and iterations > 0:
+        req = rl_loop.check_run(y, iterations, eps, x0, out, stats, tol, tv_lambda, tv_eps, acceleration,
+                                _lib.require_device_f32)
+        if req.out is None:
+            req.out = torch.empty(self.shape, dtype=torch.float32, device=self.device)
+        self.last_stats = self.stats_device = self.last_alphas = None
+
+        def begin():
             # x_0 where the caller left it (no copy for the first iteration) unless that is the output tensor itself
-            self._tv = dict(lam=tv_lambda, eps=tv_eps, u0=None if out.data_ptr() == init.data_ptr() else init,
-                            prev=torch.empty(self.shape, dtype=torch.float32, device=self.device),
-                            stats=torch.zeros((iterations, 2), dtype=torch.float64, device=self.device) if want_stats else None)
+            aliased = req.out.data_ptr() == req.init.data_ptr()
+            if not aliased:
+                req.out.copy_(req.init)
+            self.cur, self._y, self._eps, self._accelerated = req.out, y, req.eps, req.accelerate
+            self.restart()
+            return (self, rl_loop.DeviceBackend(self.shape, self.device), None if aliased else req.init,
+                    lambda: self.side("g"))
+
         with torch.cuda.device(self.device):
-            if out.data_ptr() != init.data_ptr():
-                out.copy_(init)
-            dev_stats = torch.zeros((iterations, 3), dtype=torch.float64, device=self.device) if want_stats else None
-            if events:
-                events[0].record()
-            done, stopped = iterations, False
-            if accelerate:
-                done, stopped = self._run_accel(out, y, float(eps), iterations, tol, dev_stats, init)
-            elif tol is None:
-                for it in range(iterations):
-                    self._step_tv(out, y, float(eps), None if dev_stats is None else dev_stats[it], it)
-            else:
-                done, stopped = self._run_to_tolerance(out, y, float(eps), iterations, float(tol), dev_stats)
-            if events:
-                events[1].record()
-            if want_stats:
-                if self._tv is not None:     # flux from the RL epilogue, change and total from the TV launch
-                    dev_stats = torch.cat((dev_stats[:, :1], self._tv["stats"]), dim=1)
-                self.stats_device = dev_stats
-                self.last_stats = RLStats.from_array(dev_stats.cpu().numpy(), done, stopped)
-        self._tv = None
-        _lib.mark_written(out)
-        return out
-
-    def _step_tv(self, x, y, eps, stats_row, it: int) -> None:
-        """Iteration ``it``; with ``tv_lambda > 0`` followed by ``lsr_rl_tv_scale_f32`` (u = x_k, v = out = x in place)."""
-        tv = self._tv
-        if tv is None:
-            return self._step(x, y, eps, stats_row, it == 0)
-        z, yy, xx = self.shape
-        u = tv["u0"] if it == 0 and tv["u0"] is not None else tv["prev"].copy_(x)
-        self._step(x, y, eps, stats_row, it == 0)
-        _lib.call("lsr_rl_tv_scale_f32", u.data_ptr(), xx, yy * xx, x.data_ptr(), xx, yy * xx, x.data_ptr(), xx, yy * xx,
-                  z, yy, xx, ctypes.c_float(tv["lam"]), ctypes.c_float(tv["eps"]),
-                  None if tv["stats"] is None else tv["stats"].data_ptr() + 16 * it, _lib.stream_ptr(self.device))
-
-    def _run_accel(self, x, y, eps, iterations, tol, dev_stats, init):
-        """The accelerated loop (``csrc/rl_accel.hip`` states it) on this route, which runs RL in place in ``x``: ``b`` is a
-        copy of p_k (x_0 itself where the caller left it), ``c`` holds x_k and receives p_{k+1}; before the next iteration
-        x_{k+1} is saved from ``x`` into the free ``b`` and p_{k+1} copied into ``x``, and ``b`` and ``c`` trade places.
-        Returns (iterations run, stopped early); ``tol`` as in ``_run_to_tolerance``."""
-        import torch
-
-        from .deconvolve import AccelState
-
-        if iterations == 0:
-            self.last_alphas = np.zeros(0)
-            return 0, False
-        z, yy, xx = self.shape
-        dense = (xx, yy * xx)
-        if self._accel is None:
-            self._accel = [torch.empty(self.shape, dtype=torch.float32, device=self.device) for _ in range(3)]
-        g, b, c = self._accel
-        acc = AccelState(self.shape, self.device, iterations, g)
-        stream = _lib.stream_ptr(self.device)
-        if tol is not None:
-            host = torch.empty((iterations, 3), dtype=torch.float64).pin_memory()
-            arrived = [torch.cuda.Event() for _ in range(iterations)]
-
-        def met(i):
-            arrived[i].synchronize()
-            change, total = float(host[i, 1]), float(host[i, 2])
-            return total > 0 and change <= tol * total or total == 0
-
-        done, stopped = 0, False
-        for it in range(iterations):
-            if it == 0:
-                p = init if init.data_ptr() != x.data_ptr() else b.copy_(x)
-            else:
-                b.copy_(x)
-                x.copy_(c)
-                b, c = c, b
-                p = b
-            # (first=True: the chained form's carried-over spectrum would be x_{k}'s, not p_k's)
-            self._step(x, y, eps, None if dev_stats is None else dev_stats[it], True)
-            if it + 1 < iterations:
-                acc.step(it, (x.data_ptr(),) + dense, (p.data_ptr(),) + dense, (c.data_ptr(),) + dense, stream)
-            done = it + 1
-            if tol is not None:
-                host[it].copy_(dev_stats[it], non_blocking=True)
-                arrived[it].record()
-                if it >= 1 and met(it - 1):
-                    stopped = True
-                    break
-        if tol is not None and not stopped:
-            stopped = bool(met(done - 1))
-        self.last_alphas = acc.used(done)
-        return done, stopped
-
-    def _run_to_tolerance(self, x, y, eps, iterations, tol, dev_stats):
-        """Iteration i's scalars travel to pinned host memory behind it and are looked at after iteration i + 1 has
-        been queued (as the stencil plans do): the estimate returned is the one past the first that met ``tol``."""
-        import torch
-
-        if iterations == 0:
-            return 0, False
-        host = torch.empty((iterations, 3), dtype=torch.float64).pin_memory()
-        arrived = [torch.cuda.Event() for _ in range(iterations)]
-
-        def met(i):
-            arrived[i].synchronize()
-            change, total = float(host[i, 1]), float(host[i, 2])
-            return total > 0 and change <= tol * total or total == 0
-
-        done = 0
-        for it in range(iterations):
-            self._step_tv(x, y, eps, dev_stats[it], it)
-            if self._tv is None:
-                host[it].copy_(dev_stats[it], non_blocking=True)
-            else:      # RL-TV: the change and total that are tested are the TV launch's
-                host[it, 1:].copy_(self._tv["stats"][it], non_blocking=True)
-            arrived[it].record()
-            done = it + 1
-            if it >= 1 and met(it - 1):
-                return done, True
-        return done, bool(met(iterations - 1))
+            res = rl_loop.run(req, begin, events)
+        self.cur = None
+        self.last_stats, self.stats_device, self.last_alphas = res.stats, res.rows, res.alphas
+        _lib.mark_written(res.x)
+        return res.x

@@ -19,7 +19,7 @@ import ctypes
 
 import numpy as np
 
-from . import _lib
+from . import _lib, rl_loop
 
 __all__ = ["is_host", "deskew_with_matrix", "average_n_slices", "apply_affine", "correlate3d", "richardson_lucy"]
 
@@ -173,6 +173,79 @@ def correlate3d(volume, weights=None, weight_factors=None):
     return out
 
 
+class _SeparableStepper:
+    """The separable form, between rotating volumes: ``ratio = y / (H x + eps)`` (H = correlation with the flipped taps),
+    then ``x * H^T ratio / H^T 1`` into the other volume."""
+
+    rotates, dense_out = True, False
+
+    def __init__(self, y, x, factors, eps: float):
+        import torch
+
+        from .deconvolve import _axis_norm
+
+        self.y, self.eps, self.ratio, self._vols = y, ctypes.c_float(eps), torch.empty_like(y), (x, torch.empty_like(y))
+        self.k, self.kf = [_taps(f) for f in factors], [_taps(f[::-1]) for f in factors]
+        self.norm = [_axis_norm(f, n) for f, n in zip(factors, y.shape)]
+
+    def volumes(self):
+        return self._vols
+
+    def third(self):
+        import torch
+
+        return torch.empty_like(self.y)
+
+    def _correlate(self, src, dst, aux, taps, epilogue, sp=None) -> None:
+        _lib.call("lsr_correlate_sep_stats_f32_cpu", src.data_ptr(), dst.data_ptr(), aux.data_ptr(), *self.y.shape,
+                  taps[0].ctypes.data, len(taps[0]), taps[1].ctypes.data, len(taps[1]), taps[2].ctypes.data, len(taps[2]),
+                  epilogue, self.eps, self.norm[0].ctypes.data, self.norm[1].ctypes.data, self.norm[2].ctypes.data, sp, None)
+
+    def run(self, it0, n, x_out, rows, ab=None) -> None:
+        rd, wr = ab or self._vols
+        for it in range(it0, it0 + n):
+            self._correlate(rd, self.ratio, self.y, self.kf, _lib.EPI_RATIO)
+            self._correlate(self.ratio, wr, rd, self.k, _lib.EPI_UPDATE, rl_loop.row_ptr(rows, it))
+            rd, wr = wr, rd
+
+
+class _DenseStepper:
+    """The dense form, in place in ``cur``: one native call for ``n`` iterations (the twin of ``lsr_rl_dense_f32``).
+    What the launches behind an iteration need is cloned aside; an accelerated run lets ``cur`` and ``held`` trade
+    places instead of copying p_{k+1} back."""
+
+    rotates = dense_out = False
+
+    def __init__(self, y, x, w, eps: float):
+        import torch
+
+        from .deconvolve import _prefix_table
+
+        self.y, self.cur, self.eps, self.ratio, self._held = y, x, ctypes.c_float(eps), torch.empty_like(y), None
+        self.w, self.k, self.kf = w, _taps(w), _taps(w[::-1, ::-1, ::-1])
+        self.table = np.ascontiguousarray(_prefix_table(w).ravel(), dtype=np.float64)
+
+    def run(self, it0, n, x_out, rows, ab=None) -> None:
+        _lib.call("lsr_rl_dense_stats_f32_cpu", self.y.data_ptr(), self.cur.data_ptr(), self.ratio.data_ptr(),
+                  *self.y.shape, self.k.ctypes.data, self.kf.ctypes.data, *self.w.shape, self.table.ctypes.data, n,
+                  self.eps, rl_loop.row_ptr(rows, it0), None)
+
+    def keep(self):
+        return self.cur.clone()
+
+    @property
+    def held(self):
+        import torch
+
+        if self._held is None:
+            self._held = torch.empty_like(self.cur)
+        return self._held
+
+    def turn(self):
+        self.cur, self._held = self._held, self.cur
+        return self.cur.clone()
+
+
 def richardson_lucy(y, psf=None, iterations: int = 20, eps: float = 1e-6, x0=None, *, separable: str = "auto",
                     separable_rtol: float = 1e-6, psf_factors=None, tol: float | None = None,
                     return_stats: bool = False, tv_lambda: float = 0.0, tv_eps: float = 1e-6,
@@ -180,41 +253,30 @@ def richardson_lucy(y, psf=None, iterations: int = 20, eps: float = 1e-6, x0=Non
     """``deconvolve.richardson_lucy`` for a CPU tensor: ``x <- x * H^T(y / (H x + eps)) / H^T 1`` with the two
     correlations and their epilogues as the host twins of the device launches (rank-1 PSFs run the
     separable form, others the dense one).  ``tol`` / ``return_stats``: the iteration scalars of
-    ``deconvolve.RLStats``, summed by the twins' UPDATE pass; the loop stops after the first iteration whose relative
-    change is below ``tol``.  ``tv_lambda > 0``: every iteration is followed by the twin of the total-variation launch
-    (``lsr_rl_tv_scale_f32_cpu``); ``change`` / ``total`` and ``tol`` are then those of the regularised iterate.
-    ``acceleration="biggs-andrews"``: every iteration but the last is followed by the twins of the two launches of
-    ``csrc/rl_accel.hip`` and the next one starts from the extrapolated point (``RLStats.alphas``: the step lengths)."""
+    ``deconvolve.RLStats``, summed by the twins' UPDATE pass.  ``tol`` as the device plans read it
+    (``shrimpy_amd.rl_loop.run``): the scalars of iteration i are looked at after iteration i + 1 has run, so the estimate
+    returned is the one iteration PAST the first that met ``tol`` -- the same iterate, and the same
+    ``RLStats.iterations``, whichever device the tensor lives on.  ``tv_lambda > 0``: every iteration is followed by the
+    twin of the total-variation launch (``lsr_rl_tv_scale_f32_cpu``); ``change`` / ``total`` and ``tol`` are then those of
+    the regularised iterate.  ``acceleration="biggs-andrews"``: every iteration but the last is followed by the twins of
+    the two launches of ``csrc/rl_accel.hip`` and the next one starts from the extrapolated point (``RLStats.alphas``:
+    the step lengths)."""
     import torch
 
-    from .deconvolve import (MAX_TAPS, RLStats, _axis_norm, _prefix_table, check_acceleration, check_tv, factor_psf,
-                             prepare_psf)
-
-    tv_lambda, tv_eps = check_tv(tv_lambda, tv_eps)
-    accelerate = check_acceleration(acceleration, tv_lambda)
-
-    if tol is not None and not (tol >= 0 and np.isfinite(tol)):
-        raise ValueError("tol must be a finite number >= 0")
-    want = bool(return_stats) or tol is not None
+    from .deconvolve import MAX_TAPS, MAX_Z_TAPS, factor_psf, prepare_psf
 
     y = _f32(y, "y")
     if separable not in ("auto", "force", "never"):
         raise ValueError("separable must be 'auto', 'force' or 'never'")
-    iterations = int(iterations)
-    if iterations < 0:
-        raise ValueError("iterations must be >= 0")
-    if not eps > 0:
-        raise ValueError("eps must be > 0")
+    req = rl_loop.check_run(y, iterations, eps, x0, None, return_stats, tol, tv_lambda, tv_eps, acceleration, _f32)
     factors = None
     if psf_factors is not None:
         factors = tuple(_taps(np.asarray(k).ravel()) for k in psf_factors)
-        from .deconvolve import MAX_Z_TAPS
-
         if (len(factors) != 3 or any(len(k) % 2 == 0 for k in factors) or len(factors[0]) > MAX_Z_TAPS
                 or max(len(factors[1]), len(factors[2])) > MAX_TAPS):
             raise ValueError("psf_factors must be three odd-length 1-D kernels (<= 31 taps along z, <= 15 in plane)")
     else:
-        # (up to the extents the device takes through the Fourier domain: the loops below take any count)
+        # (up to the extents the device takes through the Fourier domain: the steppers take any count)
         from .deconvolve_fft import MAX_FFT_TAPS
 
         w = prepare_psf(psf, MAX_FFT_TAPS, MAX_FFT_TAPS)
@@ -222,111 +284,14 @@ def richardson_lucy(y, psf=None, iterations: int = 20, eps: float = 1e-6, x0=Non
             factors = factor_psf(w, separable_rtol)
             if factors is None and separable == "force":
                 raise ValueError("psf is not rank-1 within separable_rtol")
-    init = y if x0 is None else _f32(x0, "x0")
-    if tuple(init.shape) != tuple(y.shape):
-        raise ValueError(f"x0 must be {tuple(y.shape)}")
-    x = init.clone()
-    if iterations == 0:
-        empty = RLStats.from_array(np.zeros((0, 3)), 0)
-        if accelerate:
-            empty.alphas = np.zeros(0)
-        return (x, empty) if return_stats else x
-    stats = np.zeros((iterations, 3), dtype=np.float64) if want else None
-    tv_stats = np.zeros((iterations, 2), dtype=np.float64) if want and tv_lambda > 0 else None
 
-    def met(i):
-        if tv_stats is not None:
-            return tv_stats[i, 1] == 0 or tv_stats[i, 0] <= tol * tv_stats[i, 1]
-        return stats[i, 2] == 0 or stats[i, 1] <= tol * stats[i, 2]
+    def begin():
+        _threads()
+        x = req.init.clone()
+        step = _SeparableStepper(y, x, factors, req.eps) if factors is not None else _DenseStepper(y, x, w, req.eps)
+        return step, rl_loop.HostBackend(y.shape), None, lambda: torch.empty_like(y)
 
-    def report(done, stopped):
-        if tv_stats is not None:      # flux from the RL update, change and total from the TV pass
-            stats[:, 1:] = tv_stats
-        out = RLStats.from_array(stats, done, stopped)
-        if accelerate:
-            out.alphas = alphas[:max(done - 1, 0)].copy()
-        return out
-    z, yy, xx = (int(v) for v in y.shape)
-    if accelerate:
-        g = torch.empty_like(y)
-        dots = np.zeros((max(iterations - 1, 1), 2), dtype=np.float64)
-        alphas = np.zeros(max(iterations - 1, 1), dtype=np.float64)
-
-    def extrapolate(k, x1, p, x0):
-        """The two launches behind ``x1 = RL(p)`` of iteration ``k``: p_{k+1} is written over ``x0`` = x_k (not read when
-        ``k == 0``)."""
-        _lib.call("lsr_rl_accel_dots_f32_cpu", x1.data_ptr(), xx, yy * xx, p.data_ptr(), xx, yy * xx, g.data_ptr(), z, yy, xx,
-                  int(k == 0), dots[k].ctypes.data, None)
-        _lib.call("lsr_rl_accel_predict_f32_cpu", x1.data_ptr(), xx, yy * xx, x0.data_ptr(), xx, yy * xx, z, yy, xx,
-                  None if k == 0 else dots[k, 0:].ctypes.data, None if k == 0 else dots[k - 1, 1:].ctypes.data,
-                  alphas[k:].ctypes.data)
-
-    def tv_scale(u, v, it):
-        """``v <- v / (1 - tv_lambda * div(grad u / |grad u|))`` in place."""
-        _lib.call("lsr_rl_tv_scale_f32_cpu", u.data_ptr(), xx, yy * xx, v.data_ptr(), xx, yy * xx, v.data_ptr(), xx, yy * xx,
-                  z, yy, xx, ctypes.c_float(tv_lambda), ctypes.c_float(tv_eps),
-                  None if tv_stats is None else tv_stats[it].ctypes.data)
-    ratio, nxt = torch.empty_like(y), torch.empty_like(y)
-    e = ctypes.c_float(eps)
-    _threads()
-    if factors is not None:
-        k = [_taps(f) for f in factors]
-        kf = [_taps(f[::-1]) for f in factors]
-        norm = [_axis_norm(f, n) for f, n in zip(factors, (z, yy, xx))]
-        sizes = [len(f) for f in k]
-
-        def corr(src, dst, aux, taps, epi, srow=None):
-            _lib.call("lsr_correlate_sep_stats_f32_cpu", src.data_ptr(), dst.data_ptr(), aux.data_ptr(), z, yy, xx,
-                      taps[0].ctypes.data, sizes[0], taps[1].ctypes.data, sizes[1], taps[2].ctypes.data, sizes[2], epi, e,
-                      norm[0].ctypes.data, norm[1].ctypes.data, norm[2].ctypes.data,
-                      None if srow is None else srow.ctypes.data, None)
-    else:    # the dense loop is one native call per chunk (the twin of lsr_rl_dense_f32: x updated in place)
-        k, kf = _taps(w), _taps(w[::-1, ::-1, ::-1])
-        table = np.ascontiguousarray(_prefix_table(w).ravel(), dtype=np.float64)
-        # ``tol`` as the device plans read it (deconvolve.RichardsonLucyPlan._run_to_tolerance): the scalars of iteration i
-        # are looked at after iteration i + 1 has run, so the estimate returned is the one iteration PAST the first that
-        # met tol -- the same iterate, and the same RLStats.iterations, whichever device the tensor lives on
-        done, stopped = 0, False
-        step = iterations if tol is None and tv_lambda == 0 and not accelerate else 1
-        held = torch.empty_like(x) if accelerate else None      # x_k, then p_{k+1}
-        result = x
-        while done < iterations:
-            prev = x.clone() if tv_lambda > 0 or accelerate else None     # (accelerated: p_k, which x holds here)
-            _lib.call("lsr_rl_dense_stats_f32_cpu", y.data_ptr(), x.data_ptr(), ratio.data_ptr(), z, yy, xx, k.ctypes.data,
-                      kf.ctypes.data, w.shape[0], w.shape[1], w.shape[2], table.ctypes.data, step, e,
-                      None if stats is None else stats[done:].ctypes.data, None)
-            if tv_lambda > 0:
-                tv_scale(prev, x, done)
-            result = x
-            if accelerate and done + 1 < iterations:
-                # x = x_{k+1}; p_{k+1} goes over x_k in `held`, then the two trade places: x = p_{k+1}, held = x_{k+1}
-                extrapolate(done, x, prev, held)
-                x, held = held, x
-            done += step
-            if tol is not None and done >= 2 and met(done - 2):
-                stopped = True
-                break
-        if tol is not None and not stopped:
-            stopped = bool(met(done - 1))
-        return (result, report(done, stopped)) if return_stats else result
-    done, stopped = 0, False
-    held = torch.empty_like(x) if accelerate else None          # x_k, then p_{k+1}
-    for it in range(iterations):
-        corr(x, ratio, y, kf, _lib.EPI_RATIO)       # ratio = y / (H x + eps): H = correlation with the flipped taps
-        corr(ratio, nxt, x, k, _lib.EPI_UPDATE, None if stats is None else stats[it])     # x <- x * H^T ratio / H^T 1
-        if tv_lambda > 0:
-            tv_scale(x, nxt, it)
-        result = nxt
-        if accelerate and it + 1 < iterations:
-            # x = p_k, nxt = x_{k+1}; p_{k+1} goes over x_k in `held`: three volumes rotate, nothing is copied
-            extrapolate(it, nxt, x, held)
-            x, nxt, held = held, x, nxt
-        else:
-            x, nxt = nxt, x
-        done = it + 1
-        if tol is not None and it >= 1 and met(it - 1):     # (one iteration past the first that met tol: see above)
-            stopped = True
-            break
-    if tol is not None and not stopped:
-        stopped = bool(met(done - 1))
-    return (result, report(done, stopped)) if return_stats else result
+    res = rl_loop.run(req, begin)
+    if res.stats is not None:
+        res.stats.alphas = res.alphas
+    return (res.x, res.stats) if return_stats else res.x

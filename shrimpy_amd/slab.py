@@ -161,7 +161,7 @@ class SlabRichardsonLucy:
         if not self.plan.fused:
             raise ValueError("the slab split runs the fused separable kernel; this PSF has no specialisation")
         self.y_pad = self.plan.new_padded_input()      # the caller (or deskew_slab) fills .view
-        self._x = [PaddedVolume(self.plan.shape, self.plan._psf.shape, device) for _ in range(2)]
+        self._x = [PaddedVolume(self.plan.shape, self.plan.psf_shape, device) for _ in range(2)]
 
     def run(self, iterations: int = 20, eps: float = 1e-6, exchange=None, *, tv_lambda: float = 0.0,
             acceleration: str = "none"):

@@ -91,7 +91,7 @@ def test_rl_full_size_is_finite_non_negative_and_conserves_weighted_flux(scene, 
     _, deskewed = scene
     plan, _, x = deconvolved
     assert bool(torch.isfinite(x).all()) and float(x.min()) >= 0
-    nz, ny, nx = (n.double() for n in plan._norm)
+    nz, ny, nx = (n.double() for n in plan._path.norm)
     flux = torch.einsum("zyx,z,y,x->", x.double(), nz, ny, nx)
     total = deskewed.double().sum()
     assert abs(float(flux / total) - 1.0) < 1e-4

@@ -182,7 +182,7 @@ def test_richardson_lucy_and_make_plan_take_the_keyword(device):
     assert torch.equal(richardson_lucy(y, psf_factors=ks, iterations=5, acceleration="none"),
                        richardson_lucy(y, psf_factors=ks, iterations=5))
     plan.release()
-    assert plan._accel_g is None and plan._accel_pad is None
+    assert not plan._path._sides      # g_k, the third padded volume, the dense copies: all dropped
 
 
 # ---------------------------------------------------------------- against float64, and that it accelerates

@@ -398,7 +398,8 @@ def _rl_accel(args, torch, dev, g, oshape):
     9x7x7 (a Gaussian turned 30 degrees in (z, x)), Fourier 15x19x19 -- the wall time of 20 plain iterations and of 9, 10
     and 15 accelerated ones, all in this run."""
     from shrimpy_amd import _lib
-    from shrimpy_amd.deconvolve import AccelState, PaddedVolume, make_plan
+    from shrimpy_amd.deconvolve import PaddedVolume, make_plan
+    from shrimpy_amd.rl_loop import AccelState, DeviceBackend
     from shrimpy_amd.pipeline import gaussian_psf_factors
 
     y = torch.poisson(torch.full(oshape, 100.0, device=dev), generator=g)
@@ -421,8 +422,8 @@ def _rl_accel(args, torch, dev, g, oshape):
         if route.startswith("fused"):
             plan(y, iterations=2, out=out)                               # fills both working volumes
             a, b = plan._scratch()
-            third = PaddedVolume(oshape, plan._pad_psf_shape(), dev)
-            acc = AccelState(oshape, dev, 3, torch.zeros_like(y))
+            third = PaddedVolume(oshape, plan._path.pad_psf_shape, dev)
+            acc = AccelState(DeviceBackend(oshape, dev), 3, torch.zeros_like(y))
             tri = lambda v: (v.logical_ptr(), v.pitch, v.plane)         # noqa: E731
             z, yy, xx = oshape
             d = acc.dots.data_ptr()
