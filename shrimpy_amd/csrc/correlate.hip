@@ -236,20 +236,47 @@ int launch_correlate(const CorrArgs& p, hipStream_t s) {
   return lsr::launch_status(SEP ? "lsr_correlate_sep_f32" : "lsr_correlate_dense_f32");
 }
 
-int check_common(const float* in, float* out, const float* aux, int64_t Z, int64_t Y, int64_t X,
-                 int pz, int py, int px, int epilogue) {
-  LSR_REQUIRE_PTR(in);
-  LSR_REQUIRE_PTR(out);
+int check_volume(int64_t Z, int64_t Y, int64_t X) {
   LSR_REQUIRE(Z > 0 && Y > 0 && X > 0, LSR_E_SHAPE, "shape (%lld,%lld,%lld) must be positive",
               (long long)Z, (long long)Y, (long long)X);
   LSR_REQUIRE_VOLUME(Z, Y, X);
+  return LSR_OK;
+}
+
+int check_taps(int pz, int py, int px) {
   LSR_REQUIRE(pz >= 1 && py >= 1 && px >= 1 && (pz & 1) && (py & 1) && (px & 1) &&
                   pz <= kMaxTaps && py <= kMaxTaps && px <= kMaxTaps,
               LSR_E_UNSUPPORTED, "PSF taps (%d,%d,%d) must be odd and <= %d per axis", pz, py, px,
               kMaxTaps);
-  LSR_REQUIRE(epilogue == LSR_EPI_NONE || epilogue == LSR_EPI_RATIO || epilogue == LSR_EPI_UPDATE,
+  return LSR_OK;
+}
+
+// The LSR_EPI_* argument (LSR_EPI_SCALE: the tuned dense kernel only) and the volume the RL epilogues read.
+int check_epilogue(int epilogue, bool with_scale, const float* aux) {
+  LSR_REQUIRE(epilogue == LSR_EPI_NONE || epilogue == LSR_EPI_RATIO || epilogue == LSR_EPI_UPDATE ||
+                  (with_scale && epilogue == LSR_EPI_SCALE),
               LSR_E_ARG, "unknown epilogue %d", epilogue);
-  if (epilogue != LSR_EPI_NONE) LSR_REQUIRE_PTR(aux);
+  if (epilogue == LSR_EPI_RATIO || epilogue == LSR_EPI_UPDATE) LSR_REQUIRE_PTR(aux);
+  return LSR_OK;
+}
+
+// The factors of H^T 1 that the separable LSR_EPI_UPDATE divides by.
+int check_sep_norms(int epilogue, const float* nz, const float* ny, const float* nx) {
+  if (epilogue == LSR_EPI_UPDATE) {
+    LSR_REQUIRE_PTR(nz);
+    LSR_REQUIRE_PTR(ny);
+    LSR_REQUIRE_PTR(nx);
+  }
+  return LSR_OK;
+}
+
+int check_common(const float* in, float* out, const float* aux, int64_t Z, int64_t Y, int64_t X,
+                 int pz, int py, int px, int epilogue) {
+  LSR_REQUIRE_PTR(in);
+  LSR_REQUIRE_PTR(out);
+  if (int rc = check_volume(Z, Y, X)) return rc;
+  if (int rc = check_taps(pz, py, px)) return rc;
+  if (int rc = check_epilogue(epilogue, false, aux)) return rc;
   LSR_REQUIRE(in != out, LSR_E_ARG, "out must not alias in");
   return LSR_OK;
 }
@@ -274,11 +301,7 @@ extern "C" int lsr_correlate_sep_stats_f32(const float* in, float* out, const fl
   LSR_REQUIRE_PTR(wz);
   LSR_REQUIRE_PTR(wy);
   LSR_REQUIRE_PTR(wx);
-  if (epilogue == LSR_EPI_UPDATE) {
-    LSR_REQUIRE_PTR(nz);
-    LSR_REQUIRE_PTR(ny);
-    LSR_REQUIRE_PTR(nx);
-  }
+  if (int rc = check_sep_norms(epilogue, nz, ny, nx)) return rc;
   CorrArgs p{};
   p.in = in; p.out = out; p.aux = aux;
   p.Z = Z; p.Y = Y; p.X = X;
@@ -314,12 +337,112 @@ int zero_stats(double* stats, int iters, lsr_stream_t stream) {
   return LSR_OK;
 }
 
-int check_taps(int pz, int py, int px) {
-  LSR_REQUIRE(pz >= 1 && py >= 1 && px >= 1 && (pz & 1) && (py & 1) && (px & 1) &&
-                  pz <= kMaxTaps && py <= kMaxTaps && px <= kMaxTaps,
-              LSR_E_UNSUPPORTED, "PSF taps (%d,%d,%d) must be odd and <= %d per axis", pz, py, px,
-              kMaxTaps);
+// `name` (in, y) is a strided volume with a zero halo: its strides are in range, at least the padded shape `need` that
+// lsr_sep_padded_shape asks for, and multiples of 16 bytes; its plane stride, the other two plane strides the kernel
+// multiplies by a z index, and Z stay below `lim`, so that in-plane offsets fit 32 bits.
+int check_padded_input(const char* name, int64_t pitch, int64_t plane, const int64_t need[4], int64_t lim,
+                       int64_t plane_b, int64_t plane_c, int64_t Z) {
+  LSR_REQUIRE_STRIDES(pitch, plane);
+  LSR_REQUIRE(pitch >= need[1] && plane >= need[0] * pitch, LSR_E_SHAPE,
+              "%s strides (%lld,%lld) are smaller than the padded shape (%lld rows x %lld) that lsr_sep_padded_shape asks "
+              "for: %s must be a zero-haloed padded volume",
+              name, (long long)pitch, (long long)plane, (long long)need[0], (long long)need[1], name);
+  LSR_REQUIRE(pitch % 4 == 0 && plane % 4 == 0, LSR_E_ARG,
+              "pitch and plane stride (%lld,%lld) of the padded %s must be multiples of 4 floats", (long long)pitch,
+              (long long)plane, name);
+  LSR_REQUIRE(plane < lim && plane_b < lim && plane_c < lim && Z < lim, LSR_E_UNSUPPORTED,
+              "plane strides (%lld,%lld,%lld) or Z = %lld exceed the kernel's 32-bit in-plane offsets (limit %lld)",
+              (long long)plane, (long long)plane_b, (long long)plane_c, (long long)Z, (long long)lim);
   return LSR_OK;
+}
+
+// The working volumes of the RL loops: what lsr_sep_padded_shape asks for, as strides and the offset of logical (0,0,0).
+struct PaddedGeometry {
+  int64_t shape[4];
+  int64_t pitch, plane, origin;
+};
+int padded_geometry(int64_t Y, int64_t X, int pz, int py, int px, PaddedGeometry* g) {
+  if (int rc = lsr_sep_padded_shape(Y, X, pz, py, px, g->shape)) return rc;
+  g->pitch = g->shape[1];
+  g->plane = g->shape[0] * g->shape[1];
+  g->origin = g->shape[2] * g->pitch + g->shape[3];
+  return LSR_OK;
+}
+
+int check_grid(int64_t blocks) {
+  LSR_REQUIRE(blocks < (int64_t(1) << 31), LSR_E_SHAPE, "grid of %lld workgroups is too large", (long long)blocks);
+  return LSR_OK;
+}
+
+// Richardson-Lucy as two launches per iteration on padded working volumes (x_pad, ratio_pad):
+//   ratio(x, x_pitch, x_plane, ratio)                          ratio = y / (H x + eps)
+//   update(ratio, x, x_pitch, x_plane, out, out_pitch, out_plane, stats)   out = x * H^T ratio / H^T 1
+// With init_from_y the first iteration reads x = y straight from the (padded) y volume; the last update may go straight
+// to the dense result x_out.
+template <typename Ratio, typename Update>
+int run_two_launch_rl(const float* y, int64_t y_pitch, int64_t y_plane, int init_from_y, float* x_pad, float* ratio_pad,
+                      float* x_out, int64_t Y, int64_t X, int pz, int py, int px, int iters, double* stats,
+                      lsr_stream_t stream, Ratio ratio, Update update) {
+  LSR_REQUIRE_PTR(y);
+  LSR_REQUIRE_PTR(x_pad);
+  LSR_REQUIRE_PTR(ratio_pad);
+  LSR_REQUIRE(iters >= 1, LSR_E_ARG, "iters %d must be >= 1", iters);
+  LSR_REQUIRE(ratio_pad != x_pad, LSR_E_ARG, "x_pad and ratio_pad must be distinct");
+  PaddedGeometry g;
+  if (int rc = padded_geometry(Y, X, pz, py, px, &g)) return rc;
+  float* xl = x_pad + g.origin;        // logical (0,0,0) inside the padded volumes
+  float* rl = ratio_pad + g.origin;
+  if (int rc = zero_stats(stats, iters, stream)) return rc;
+  for (int it = 0; it < iters; ++it) {
+    const bool from_y = init_from_y && it == 0;
+    const float* xin = from_y ? y : xl;
+    const int64_t xin_pitch = from_y ? y_pitch : g.pitch, xin_plane = from_y ? y_plane : g.plane;
+    if (int rc = ratio(xin, xin_pitch, xin_plane, rl, g.pitch, g.plane)) return rc;
+    const bool last = it + 1 == iters && x_out != nullptr;
+    if (int rc = update(rl, g.pitch, g.plane, xin, xin_pitch, xin_plane, last ? x_out : xl, last ? X : g.pitch,
+                        last ? Y * X : g.plane, stats ? stats + lsr::kRlStats * it : nullptr))
+      return rc;
+  }
+  return LSR_OK;
+}
+
+// The iterations of a one-launch (fused) entry: x ping-pongs between the working volumes x_a and x_b; with init_from_y
+// the first launch reads x = y, the last may write the dense x_out.  `p` arrives with everything else filled in;
+// launch(p, last) starts one iteration and says whether there was a kernel for it.
+template <typename Args, typename Launch>
+int run_fused_rl(Args& p, const char* what, const char* family, const float* y, int64_t y_pitch, int64_t y_plane,
+                 int init_from_y, float* x_a, float* x_b, float* x_out, const PaddedGeometry& g, int64_t Y, int64_t X,
+                 int pz, int py, int px, int iters, double* stats, lsr_stream_t stream, Launch launch) {
+  float* bufs[2] = {x_a + g.origin, x_b + g.origin};  // logical (0,0,0) of the two working volumes
+  if (int rc = zero_stats(stats, iters, stream)) return rc;
+  for (int it = 0; it < iters; ++it) {
+    const bool from_y = init_from_y && it == 0;
+    const bool last = it + 1 == iters && x_out != nullptr;
+    p.x = from_y ? y : bufs[it & 1];
+    p.pitch = static_cast<int>(from_y ? y_pitch : g.pitch);
+    p.plane = from_y ? y_plane : g.plane;
+    p.out = last ? x_out : bufs[(it + 1) & 1];
+    p.out_pitch = static_cast<int>(last ? X : g.pitch);
+    p.out_plane = last ? Y * X : g.plane;
+    p.stats = stats ? stats + lsr::kRlStats * it : nullptr;
+    LSR_REQUIRE(launch(p, last), LSR_E_UNSUPPORTED, "no %s specialisation for taps (%d,%d,%d)", family, pz, py, px);
+    if (int rc = lsr::launch_status(what)) return rc;
+  }
+  return LSR_OK;
+}
+
+// What lsr_rl_*_fused_supported said no to.
+int fused_unsupported(int pz, int py, int px) {
+  return lsr::fail(LSR_E_UNSUPPORTED,
+                   "no fused RL specialisation for taps (%d,%d,%d) (up to %d x %d x %d, not 15 z taps with 11+ in-plane "
+                   "taps): use lsr_rl_sep_f32",
+                   pz, py, px, lsr::kFusedMaxPZ, lsr::kFusedMaxPYX, lsr::kFusedMaxPYX);
+}
+int ysep_unsupported(int pz, int py, int px) {
+  return lsr::fail(LSR_E_UNSUPPORTED,
+                   "no fused ky (x) kzx specialisation for taps (%d,%d,%d) (up to %d z taps, %d in-plane): use "
+                   "lsr_correlate_zxy_padded_f32",
+                   pz, py, px, lsr::kYsepMaxPZ, lsr::kYsepMaxPYX);
 }
 
 }  // namespace
@@ -358,35 +481,18 @@ extern "C" int lsr_correlate_sep_strided_stats_f32(const float* in, int64_t in_p
   LSR_REQUIRE_PTR(wz);
   LSR_REQUIRE_PTR(wy);
   LSR_REQUIRE_PTR(wx);
-  LSR_REQUIRE(Z > 0 && Y > 0 && X > 0, LSR_E_SHAPE, "shape (%lld,%lld,%lld) must be positive",
-              (long long)Z, (long long)Y, (long long)X);
-  LSR_REQUIRE_VOLUME(Z, Y, X);
+  if (int rc = check_volume(Z, Y, X)) return rc;
   if (int rc = check_taps(pz, py, px)) return rc;
-  LSR_REQUIRE(epilogue == LSR_EPI_NONE || epilogue == LSR_EPI_RATIO || epilogue == LSR_EPI_UPDATE,
-              LSR_E_ARG, "unknown epilogue %d", epilogue);
-  if (epilogue != LSR_EPI_NONE) LSR_REQUIRE_PTR(aux);
-  if (epilogue == LSR_EPI_UPDATE) {
-    LSR_REQUIRE_PTR(nz);
-    LSR_REQUIRE_PTR(ny);
-    LSR_REQUIRE_PTR(nx);
-  }
+  if (int rc = check_epilogue(epilogue, false, aux)) return rc;
+  if (int rc = check_sep_norms(epilogue, nz, ny, nx)) return rc;
   LSR_REQUIRE(in != out, LSR_E_ARG, "out must not alias in");
   int PZ, PYX;
   sep_compiled_taps(pz, py, px, &PZ, &PYX);
   int64_t need[4];
   lsr_sep_padded_shape(Y, X, pz, py, px, need);
-  LSR_REQUIRE_STRIDES(in_pitch, in_plane);
-  LSR_REQUIRE(in_pitch >= need[1] && in_plane >= need[0] * in_pitch, LSR_E_SHAPE,
-              "in strides (%lld,%lld) are smaller than the padded shape (%lld rows x %lld) that "
-              "lsr_sep_padded_shape asks for",
-              (long long)in_pitch, (long long)in_plane, (long long)need[0], (long long)need[1]);
-  LSR_REQUIRE(in_pitch % 4 == 0 && in_plane % 4 == 0, LSR_E_ARG,
-              "pitch and plane stride of the padded input must be multiples of 4 floats");
-  const int64_t lim = int64_t(1) << 30;
-  LSR_REQUIRE(in_plane < lim && aux_plane < lim && out_plane < lim && Z < lim, LSR_E_UNSUPPORTED,
-              "plane strides exceed the kernel's 32-bit in-plane offsets");
+  if (int rc = check_padded_input("in", in_pitch, in_plane, need, int64_t(1) << 30, aux_plane, out_plane, Z)) return rc;
   LSR_REQUIRE(out_pitch >= X && (epilogue == LSR_EPI_NONE || aux_pitch >= X), LSR_E_SHAPE,
-              "aux/out pitch smaller than X");
+              "aux/out pitch (%lld,%lld) smaller than X = %lld", (long long)aux_pitch, (long long)out_pitch, (long long)X);
 
   lsr::SepArgs p{};
   p.in = in; p.aux = aux; p.out = out;
@@ -403,23 +509,10 @@ extern "C" int lsr_correlate_sep_strided_stats_f32(const float* in, int64_t in_p
   p.tiles_x = static_cast<int>(lsr::ceil_div(X, lsr::kSepWideTileX));
   p.tiles_y = static_cast<int>(lsr::ceil_div(Y, lsr::sep_wide_tile_y(PZ)));
   p.z_chunk = static_cast<int>(pick_z_chunk(Z, int64_t(p.tiles_x) * p.tiles_y, PZ));
-  const int64_t blocks64 = int64_t(p.tiles_x) * p.tiles_y * lsr::ceil_div(Z, p.z_chunk);
-  LSR_REQUIRE(blocks64 < (int64_t(1) << 31), LSR_E_SHAPE, "grid of %lld workgroups is too large",
-              (long long)blocks64);
-  const unsigned blocks = static_cast<unsigned>(blocks64);
-  hipStream_t s = lsr::as_stream(stream);
-  bool ok = false;
-  switch (PZ) {
-    case 3: ok = lsr::launch_sep_pz3(PYX, p, blocks, s); break;
-    case 5: ok = lsr::launch_sep_pz5(PYX, p, blocks, s); break;
-    case 7: ok = lsr::launch_sep_pz7(PYX, p, blocks, s); break;
-    case 9: ok = lsr::launch_sep_pz9(PYX, p, blocks, s); break;
-    case 11: ok = lsr::launch_sep_pz11(PYX, p, blocks, s); break;
-    case 13: ok = lsr::launch_sep_pz13(PYX, p, blocks, s); break;
-    case 15: ok = lsr::launch_sep_pz15(PYX, p, blocks, s); break;
-    default: break;
-  }
-  LSR_REQUIRE(ok, LSR_E_UNSUPPORTED, "no separable specialisation for taps (%d,%d,%d)", pz, py, px);
+  const int64_t blocks = int64_t(p.tiles_x) * p.tiles_y * lsr::ceil_div(Z, p.z_chunk);
+  if (int rc = check_grid(blocks)) return rc;
+  LSR_REQUIRE(lsr::launch_sep(PZ, PYX, p, static_cast<unsigned>(blocks), lsr::as_stream(stream)), LSR_E_UNSUPPORTED,
+              "no separable specialisation for taps (%d,%d,%d)", pz, py, px);
   return lsr::launch_status("lsr_correlate_sep_strided_f32");
 }
 
@@ -450,39 +543,21 @@ extern "C" int lsr_correlate_dense_f32(const float* in, float* out, const float*
 }
 
 extern "C" int lsr_rl_sep_stats_f32(const float* y, int64_t y_pitch, int64_t y_plane, int init_from_y, float* x_pad, float* ratio_pad, float* x_out, int64_t Z, int64_t Y, int64_t X, const float* kz, const float* kz_flipped, int pz, const float* ky, const float* ky_flipped, int py, const float* kx, const float* kx_flipped, int px, const float* nz, const float* ny, const float* nx, int iters, float eps, double* stats, lsr_stream_t stream) {
-  LSR_REQUIRE_PTR(y);
-  LSR_REQUIRE_PTR(x_pad);
-  LSR_REQUIRE_PTR(ratio_pad);
-  LSR_REQUIRE(iters >= 1, LSR_E_ARG, "iters %d must be >= 1", iters);
-  LSR_REQUIRE(ratio_pad != x_pad, LSR_E_ARG, "x_pad and ratio_pad must be distinct");
-  int64_t ps[4];
-  if (int rc = lsr_sep_padded_shape(Y, X, pz, py, px, ps)) return rc;
-  const int64_t pitch = ps[1], plane = ps[0] * ps[1];
-  const int64_t origin = ps[2] * pitch + ps[3];
-  float* xl = x_pad + origin;        // logical (0,0,0) inside the padded volumes
-  float* rl = ratio_pad + origin;
-  if (int rc = zero_stats(stats, iters, stream)) return rc;
-  for (int it = 0; it < iters; ++it) {
-    // ratio = y / (H x + eps);  H x = convolve(x, psf) = correlate(x, flipped psf).
-    // With init_from_y the first iteration reads x = y straight from the (padded) y volume.
-    const bool from_y = init_from_y && it == 0;
-    const float* xin = from_y ? y : xl;
-    const int64_t xin_pitch = from_y ? y_pitch : pitch, xin_plane = from_y ? y_plane : plane;
-    int rc = lsr_correlate_sep_strided_f32(xin, xin_pitch, xin_plane, y, y_pitch, y_plane, rl, pitch,
-                                           plane, Z, Y, X, kz_flipped, pz, ky_flipped, py,
-                                           kx_flipped, px, LSR_EPI_RATIO, eps, nullptr, nullptr,
-                                           nullptr, stream);
-    if (rc) return rc;
-    // x <- x * H^T ratio / H^T 1;  H^T r = correlate(r, psf).  The last update may go straight
-    // to the dense result.
-    const bool last = it + 1 == iters && x_out != nullptr;
-    rc = lsr_correlate_sep_strided_stats_f32(rl, pitch, plane, xin, xin_pitch, xin_plane, last ? x_out : xl,
-                                             last ? X : pitch, last ? Y * X : plane, Z, Y, X, kz, pz, ky,
-                                             py, kx, px, LSR_EPI_UPDATE, eps, nz, ny, nx,
-                                             stats ? stats + lsr::kRlStats * it : nullptr, stream);
-    if (rc) return rc;
-  }
-  return LSR_OK;
+  // ratio = y / (H x + eps);  H x = convolve(x, psf) = correlate(x, flipped psf).
+  // x <- x * H^T ratio / H^T 1;  H^T r = correlate(r, psf).
+  return run_two_launch_rl(
+      y, y_pitch, y_plane, init_from_y, x_pad, ratio_pad, x_out, Y, X, pz, py, px, iters, stats, stream,
+      [&](const float* x, int64_t x_pitch, int64_t x_plane, float* r, int64_t r_pitch, int64_t r_plane) {
+        return lsr_correlate_sep_strided_f32(x, x_pitch, x_plane, y, y_pitch, y_plane, r, r_pitch, r_plane, Z, Y, X,
+                                             kz_flipped, pz, ky_flipped, py, kx_flipped, px, LSR_EPI_RATIO, eps, nullptr,
+                                             nullptr, nullptr, stream);
+      },
+      [&](const float* r, int64_t r_pitch, int64_t r_plane, const float* x, int64_t x_pitch, int64_t x_plane, float* out,
+          int64_t out_pitch, int64_t out_plane, double* st) {
+        return lsr_correlate_sep_strided_stats_f32(r, r_pitch, r_plane, x, x_pitch, x_plane, out, out_pitch, out_plane, Z,
+                                                   Y, X, kz, pz, ky, py, kx, px, LSR_EPI_UPDATE, eps, nz, ny, nx, st,
+                                                   stream);
+      });
 }
 
 extern "C" int lsr_rl_sep_f32(const float* y, int64_t y_pitch, int64_t y_plane, int init_from_y, float* x_pad, float* ratio_pad, float* x_out, int64_t Z, int64_t Y, int64_t X, const float* kz, const float* kz_flipped, int pz, const float* ky, const float* ky_flipped, int py, const float* kx, const float* kx_flipped, int px, const float* nz, const float* ny, const float* nx, int iters, float eps, lsr_stream_t stream) {
@@ -506,8 +581,8 @@ int device_cu_count() {
 // Work split of the fused kernel (one workgroup per CU; a piece of a tile column costs
 // 2 * (PZ - 1) halo planes): whole columns for as many full dispatch rounds as the tiles give,
 // the remaining tiles cut along z so that they fill one more round.
-void plan_fused_split(int64_t tiles_xy, int64_t Z, int PZ, int* n_full, int* pieces, int* z_chunk, int per_cu = 1) {
-  const int64_t cus = device_cu_count() * per_cu;   // workgroups resident at once
+void plan_fused_split(int64_t tiles_xy, int64_t Z, int PZ, int* n_full, int* pieces, int* z_chunk) {
+  const int64_t cus = device_cu_count();   // workgroups resident at once
   const int64_t min_chunk = 2 * (PZ - 1) > 8 ? 2 * (PZ - 1) : 8;  // halo no more than the payload
   int64_t full = tiles_xy / cus * cus;
   int64_t rest = tiles_xy - full;
@@ -540,10 +615,7 @@ extern "C" int lsr_rl_sep_fused_prepare_taps(const float* kz_host, int pz, const
   LSR_REQUIRE_PTR(kx_host);
   LSR_REQUIRE_PTR(taps_host);
   if (int rc = check_taps(pz, py, px)) return rc;
-  LSR_REQUIRE(lsr_rl_sep_fused_supported(pz, py, px), LSR_E_UNSUPPORTED,
-              "no fused RL specialisation for taps (%d,%d,%d) (up to %d x %d x %d, not 15 z taps with "
-              "11+ in-plane taps): use lsr_rl_sep_f32",
-              pz, py, px, lsr::kFusedMaxPZ, lsr::kFusedMaxPYX, lsr::kFusedMaxPYX);
+  if (!lsr_rl_sep_fused_supported(pz, py, px)) return fused_unsupported(pz, py, px);
   int PZ, PYX;
   sep_compiled_taps(pz, py, px, &PZ, &PYX);
   // rows: stage 1 (H = correlation with the flipped PSF) x, y, z; stage 2 (H^T, the PSF) x, y, z;
@@ -573,32 +645,16 @@ extern "C" int lsr_rl_sep_fused_stats_f32(const float* y, int64_t y_pitch, int64
   LSR_REQUIRE_PTR(x_b);
   LSR_REQUIRE_PTR(taps);
   LSR_REQUIRE_PTR(nz); LSR_REQUIRE_PTR(ny); LSR_REQUIRE_PTR(nx);
-  LSR_REQUIRE(Z > 0 && Y > 0 && X > 0, LSR_E_SHAPE, "shape (%lld,%lld,%lld) must be positive",
-              (long long)Z, (long long)Y, (long long)X);
-  LSR_REQUIRE_VOLUME(Z, Y, X);
+  if (int rc = check_volume(Z, Y, X)) return rc;
   LSR_REQUIRE(iters >= 1, LSR_E_ARG, "iters %d must be >= 1", iters);
   LSR_REQUIRE(x_a != x_b, LSR_E_ARG, "x_a and x_b must be distinct");
   if (int rc = check_taps(pz, py, px)) return rc;
-  LSR_REQUIRE(lsr_rl_sep_fused_supported(pz, py, px), LSR_E_UNSUPPORTED,
-              "no fused RL specialisation for taps (%d,%d,%d) (up to %d x %d x %d, not 15 z taps with "
-              "11+ in-plane taps): use lsr_rl_sep_f32",
-              pz, py, px, lsr::kFusedMaxPZ, lsr::kFusedMaxPYX, lsr::kFusedMaxPYX);
+  if (!lsr_rl_sep_fused_supported(pz, py, px)) return fused_unsupported(pz, py, px);
   int PZ, PYX;
   sep_compiled_taps(pz, py, px, &PZ, &PYX);
-  int64_t ps[4];
-  if (int rc = lsr_sep_padded_shape(Y, X, pz, py, px, ps)) return rc;
-  const int64_t pitch = ps[1], plane = ps[0] * ps[1];
-  const int64_t origin = ps[2] * pitch + ps[3];
-  LSR_REQUIRE_STRIDES(y_pitch, y_plane);
-  LSR_REQUIRE(y_pitch >= pitch && y_plane >= ps[0] * y_pitch, LSR_E_SHAPE,
-              "y strides (%lld,%lld) are smaller than the padded shape (%lld rows x %lld) that "
-              "lsr_sep_padded_shape asks for: y must be a zero-haloed padded volume",
-              (long long)y_pitch, (long long)y_plane, (long long)ps[0], (long long)pitch);
-  LSR_REQUIRE(y_pitch % 4 == 0 && y_plane % 4 == 0, LSR_E_ARG,
-              "pitch and plane stride of the padded y must be multiples of 4 floats");
-  const int64_t lim = int64_t(1) << 29;
-  LSR_REQUIRE(plane < lim && y_plane < lim && Y * X < lim && Z < lim, LSR_E_UNSUPPORTED,
-              "plane strides exceed the kernel's 32-bit in-plane offsets");
+  PaddedGeometry g;
+  if (int rc = padded_geometry(Y, X, pz, py, px, &g)) return rc;
+  if (int rc = check_padded_input("y", y_pitch, y_plane, g.shape, int64_t(1) << 29, g.plane, Y * X, Z)) return rc;
 
   lsr::FusedArgs p{};
 #ifdef LSR_FUSED_PROBE_TIME
@@ -612,40 +668,13 @@ extern "C" int lsr_rl_sep_fused_stats_f32(const float* y, int64_t y_pitch, int64
   p.tiles_y = static_cast<int>(lsr::ceil_div(Y, 8 * lsr::fused_run(PZ, PYX)));
   const int64_t tiles_xy = int64_t(p.tiles_x) * p.tiles_y;
   plan_fused_split(tiles_xy, Z, PZ, &p.n_full, &p.pieces, &p.z_chunk);
-  const int64_t blocks64 = p.n_full + (tiles_xy - p.n_full) * p.pieces;
-  LSR_REQUIRE(blocks64 < (int64_t(1) << 31), LSR_E_SHAPE, "grid of %lld workgroups is too large",
-              (long long)blocks64);
-  const unsigned blocks = static_cast<unsigned>(blocks64);
-  hipStream_t s = lsr::as_stream(stream);
-
-  float* bufs[2] = {x_a + origin, x_b + origin};  // logical (0,0,0) of the two working volumes
-  if (int rc = zero_stats(stats, iters, stream)) return rc;
-  for (int it = 0; it < iters; ++it) {
-    const bool from_y = init_from_y && it == 0;
-    const bool last = it + 1 == iters && x_out != nullptr;
-    p.x = from_y ? y : bufs[it & 1];
-    p.pitch = static_cast<int>(from_y ? y_pitch : pitch);
-    p.plane = from_y ? y_plane : plane;
-    p.out = last ? x_out : bufs[(it + 1) & 1];
-    p.out_pitch = static_cast<int>(last ? X : pitch);
-    p.out_plane = last ? Y * X : plane;
-    p.mask_out = last ? 1 : 0;
-    p.stats = stats ? stats + lsr::kRlStats * it : nullptr;
-    bool ok = false;
-    switch (PZ) {
-      case 3: ok = lsr::launch_fused_pz3(PYX, p, blocks, s); break;
-      case 5: ok = lsr::launch_fused_pz5(PYX, p, blocks, s); break;
-      case 7: ok = lsr::launch_fused_pz7(PYX, p, blocks, s); break;
-      case 9: ok = lsr::launch_fused_pz9(PYX, p, blocks, s); break;
-      case 11: ok = lsr::launch_fused_pz11(PYX, p, blocks, s); break;
-      case 13: ok = lsr::launch_fused_pz13(PYX, p, blocks, s); break;
-      case 15: ok = lsr::launch_fused_pz15(PYX, p, blocks, s); break;
-      default: break;
-    }
-    LSR_REQUIRE(ok, LSR_E_UNSUPPORTED, "no fused specialisation for taps (%d,%d,%d)", pz, py, px);
-    if (int rc = lsr::launch_status("lsr_rl_sep_fused_f32")) return rc;
-  }
-  return LSR_OK;
+  const int64_t blocks = p.n_full + (tiles_xy - p.n_full) * p.pieces;
+  if (int rc = check_grid(blocks)) return rc;
+  return run_fused_rl(p, "lsr_rl_sep_fused_f32", "fused", y, y_pitch, y_plane, init_from_y, x_a, x_b, x_out, g, Y, X, pz, py,
+                      px, iters, stats, stream, [&](lsr::FusedArgs& q, bool last) {
+                        q.mask_out = last ? 1 : 0;
+                        return lsr::launch_fused(PZ, PYX, q, static_cast<unsigned>(blocks), lsr::as_stream(stream));
+                      });
 }
 
 extern "C" int lsr_rl_sep_fused_f32(const float* y, int64_t y_pitch, int64_t y_plane, int init_from_y, float* x_a, float* x_b, float* x_out, int64_t Z, int64_t Y, int64_t X, const float* taps, int pz, int py, int px, const float* nz, const float* ny, const float* nx, int iters, float eps, lsr_stream_t stream) {
@@ -668,9 +697,7 @@ extern "C" int lsr_rl_ysep_fused_prepare_taps(const float* ky_host, int py, cons
   LSR_REQUIRE_PTR(kzx_host);
   LSR_REQUIRE_PTR(taps_host);
   if (int rc = check_taps(pz, py, px)) return rc;
-  LSR_REQUIRE(lsr_rl_ysep_fused_supported(pz, py, px), LSR_E_UNSUPPORTED,
-              "no fused ky (x) kzx specialisation for taps (%d,%d,%d) (up to %d z taps, %d in-plane): use "
-              "lsr_correlate_zxy_padded_f32", pz, py, px, lsr::kYsepMaxPZ, lsr::kYsepMaxPYX);
+  if (!lsr_rl_ysep_fused_supported(pz, py, px)) return ysep_unsupported(pz, py, px);
   const int PZ = lsr::sep_round_taps(pz), PYX = lsr::sep_round_taps(py > px ? py : px);
   const int oz = (PZ - pz) / 2, oy = (PYX - py) / 2, ox = (PYX - px) / 2;
   for (int i = 0; i < 2 * lsr::kYsepTapStage; ++i) taps_host[i] = 0.0f;
@@ -696,30 +723,15 @@ extern "C" int lsr_rl_ysep_fused_stats_f32(const float* y, int64_t y_pitch, int6
   LSR_REQUIRE_PTR(x_b);
   LSR_REQUIRE_PTR(taps);
   LSR_REQUIRE_PTR(norm_table);
-  LSR_REQUIRE(Z > 0 && Y > 0 && X > 0, LSR_E_SHAPE, "shape (%lld,%lld,%lld) must be positive", (long long)Z, (long long)Y,
-              (long long)X);
-  LSR_REQUIRE_VOLUME(Z, Y, X);
+  if (int rc = check_volume(Z, Y, X)) return rc;
   LSR_REQUIRE(iters >= 1, LSR_E_ARG, "iters %d must be >= 1", iters);
   LSR_REQUIRE(x_a != x_b, LSR_E_ARG, "x_a and x_b must be distinct");
   if (int rc = check_taps(pz, py, px)) return rc;
-  LSR_REQUIRE(lsr_rl_ysep_fused_supported(pz, py, px), LSR_E_UNSUPPORTED,
-              "no fused ky (x) kzx specialisation for taps (%d,%d,%d) (up to %d z taps, %d in-plane): use "
-              "lsr_correlate_zxy_padded_f32", pz, py, px, lsr::kYsepMaxPZ, lsr::kYsepMaxPYX);
+  if (!lsr_rl_ysep_fused_supported(pz, py, px)) return ysep_unsupported(pz, py, px);
   const int PZ = lsr::sep_round_taps(pz), PYX = lsr::sep_round_taps(py > px ? py : px);
-  int64_t ps[4];
-  if (int rc = lsr_sep_padded_shape(Y, X, pz, py, px, ps)) return rc;
-  const int64_t pitch = ps[1], plane = ps[0] * ps[1];
-  const int64_t origin = ps[2] * pitch + ps[3];
-  LSR_REQUIRE_STRIDES(y_pitch, y_plane);
-  LSR_REQUIRE(y_pitch >= pitch && y_plane >= ps[0] * y_pitch, LSR_E_SHAPE,
-              "y strides (%lld,%lld) are smaller than the padded shape (%lld rows x %lld) that lsr_sep_padded_shape asks "
-              "for: y must be a zero-haloed padded volume", (long long)y_pitch, (long long)y_plane, (long long)ps[0],
-              (long long)pitch);
-  LSR_REQUIRE(y_pitch % 4 == 0 && y_plane % 4 == 0, LSR_E_ARG,
-              "pitch and plane stride of the padded y must be multiples of 4 floats");
-  const int64_t lim = int64_t(1) << 29;
-  LSR_REQUIRE(plane < lim && y_plane < lim && Y * X < lim && Z < lim, LSR_E_UNSUPPORTED,
-              "plane strides exceed the kernel's 32-bit in-plane offsets");
+  PaddedGeometry g;
+  if (int rc = padded_geometry(Y, X, pz, py, px, &g)) return rc;
+  if (int rc = check_padded_input("y", y_pitch, y_plane, g.shape, int64_t(1) << 29, g.plane, Y * X, Z)) return rc;
 
   lsr::YsepArgs p{};
   p.y = y; p.y_pitch = static_cast<int>(y_pitch); p.y_plane = y_plane;
@@ -730,41 +742,16 @@ extern "C" int lsr_rl_ysep_fused_stats_f32(const float* y, int64_t y_pitch, int6
   // one shape: 512 threads on 32 x 128 tiles, one workgroup per CU.  (Rounds 3-4 also had 256-thread workgroups on
   // 32 x 64 tiles, two per CU: once the border normalisation stopped setting the launch time it was the slower one --
   // 4.98 against 4.63 ms per iteration on config 2, its halo is 1.72 x the tile against 1.55 x -- and is gone.)
-  p.narrow = 0;
-  p.tiles_x = static_cast<int>(lsr::ceil_div(X, p.narrow ? 64 : lsr::kSepWideTileX));
+  p.tiles_x = static_cast<int>(lsr::ceil_div(X, lsr::kSepWideTileX));
   p.tiles_y = static_cast<int>(lsr::ceil_div(Y, lsr::ysep_tile_rows(PZ, PYX)));
   const int64_t tiles_xy = int64_t(p.tiles_x) * p.tiles_y;
-  plan_fused_split(tiles_xy, Z, PZ, &p.n_full, &p.pieces, &p.z_chunk, p.narrow ? 2 : 1);
-  const int64_t blocks64 = p.n_full + (tiles_xy - p.n_full) * p.pieces;
-  LSR_REQUIRE(blocks64 < (int64_t(1) << 31), LSR_E_SHAPE, "grid of %lld workgroups is too large", (long long)blocks64);
-  const unsigned blocks = static_cast<unsigned>(blocks64);
-  hipStream_t s = lsr::as_stream(stream);
-
-  float* bufs[2] = {x_a + origin, x_b + origin};  // logical (0,0,0) of the two working volumes
-  if (int rc = zero_stats(stats, iters, stream)) return rc;
-  for (int it = 0; it < iters; ++it) {
-    const bool from_y = init_from_y && it == 0;
-    const bool last = it + 1 == iters && x_out != nullptr;
-    p.x = from_y ? y : bufs[it & 1];
-    p.pitch = static_cast<int>(from_y ? y_pitch : pitch);
-    p.plane = from_y ? y_plane : plane;
-    p.out = last ? x_out : bufs[(it + 1) & 1];
-    p.out_pitch = static_cast<int>(last ? X : pitch);
-    p.out_plane = last ? Y * X : plane;
-    p.stats = stats ? stats + lsr::kRlStats * it : nullptr;
-    bool ok = false;
-    switch (PZ) {
-      case 3: ok = lsr::launch_ysep_pz3(PYX, p, blocks, s); break;
-      case 5: ok = lsr::launch_ysep_pz5(PYX, p, blocks, s); break;
-      case 7: ok = lsr::launch_ysep_pz7(PYX, p, blocks, s); break;
-      case 9: ok = lsr::launch_ysep_pz9(PYX, p, blocks, s); break;
-      case 11: ok = lsr::launch_ysep_pz11(PYX, p, blocks, s); break;
-      default: break;
-    }
-    LSR_REQUIRE(ok, LSR_E_UNSUPPORTED, "no fused ky (x) kzx specialisation for taps (%d,%d,%d)", pz, py, px);
-    if (int rc = lsr::launch_status("lsr_rl_ysep_fused_f32")) return rc;
-  }
-  return LSR_OK;
+  plan_fused_split(tiles_xy, Z, PZ, &p.n_full, &p.pieces, &p.z_chunk);
+  const int64_t blocks = p.n_full + (tiles_xy - p.n_full) * p.pieces;
+  if (int rc = check_grid(blocks)) return rc;
+  return run_fused_rl(p, "lsr_rl_ysep_fused_f32", "fused ky (x) kzx", y, y_pitch, y_plane, init_from_y, x_a, x_b, x_out, g,
+                      Y, X, pz, py, px, iters, stats, stream, [&](lsr::YsepArgs& q, bool) {
+                        return lsr::launch_ysep(PZ, PYX, q, static_cast<unsigned>(blocks), lsr::as_stream(stream));
+                      });
 }
 
 extern "C" int lsr_rl_ysep_fused_f32(const float* y, int64_t y_pitch, int64_t y_plane, int init_from_y, float* x_a, float* x_b, float* x_out, int64_t Z, int64_t Y, int64_t X, const float* taps, int pz, int py, int px, const double* norm_table, float norm_full, int iters, float eps, lsr_stream_t stream) {
@@ -854,33 +841,20 @@ int dense_padded_launch(const char* what, int mode, const float* ky,
   LSR_REQUIRE_PTR(in);
   LSR_REQUIRE_PTR(out);
   LSR_REQUIRE_PTR(taps);
-  LSR_REQUIRE(Z > 0 && Y > 0 && X > 0, LSR_E_SHAPE, "shape (%lld,%lld,%lld) must be positive",
-              (long long)Z, (long long)Y, (long long)X);
-  LSR_REQUIRE_VOLUME(Z, Y, X);
+  if (int rc = check_volume(Z, Y, X)) return rc;
   if (int rc = check_taps(pz, py, px)) return rc;
   int PZ, PYX;
   LSR_REQUIRE(dense_compiled_taps(pz, py, px, &PZ, &PYX), LSR_E_UNSUPPORTED,
               "the tuned dense kernel covers pz <= 11 and py, px <= 9 (got %d,%d,%d)", pz, py, px);
-  LSR_REQUIRE(epilogue == LSR_EPI_NONE || epilogue == LSR_EPI_RATIO || epilogue == LSR_EPI_UPDATE ||
-                  epilogue == LSR_EPI_SCALE,
-              LSR_E_ARG, "unknown epilogue %d", epilogue);
+  if (int rc = check_epilogue(epilogue, true, aux)) return rc;
   const bool has_aux = epilogue == LSR_EPI_RATIO || epilogue == LSR_EPI_UPDATE;
-  if (has_aux) LSR_REQUIRE_PTR(aux);
   if (epilogue == LSR_EPI_UPDATE || epilogue == LSR_EPI_SCALE) LSR_REQUIRE_PTR(norm_table);
   LSR_REQUIRE(in != out, LSR_E_ARG, "out must not alias in");
   int64_t need[4];
   lsr_sep_padded_shape(Y, X, pz, py, px, need);
-  LSR_REQUIRE_STRIDES(in_pitch, in_plane);
-  LSR_REQUIRE(in_pitch >= need[1] && in_plane >= need[0] * in_pitch, LSR_E_SHAPE,
-              "in strides (%lld,%lld) are smaller than the padded shape (%lld rows x %lld)",
-              (long long)in_pitch, (long long)in_plane, (long long)need[0], (long long)need[1]);
-  LSR_REQUIRE(in_pitch % 4 == 0 && in_plane % 4 == 0, LSR_E_ARG,
-              "pitch and plane stride of the padded input must be multiples of 4 floats");
-  const int64_t lim = int64_t(1) << 30;
-  LSR_REQUIRE(in_plane < lim && aux_plane < lim && out_plane < lim && Z < lim, LSR_E_UNSUPPORTED,
-              "plane strides exceed the kernel's 32-bit in-plane offsets");
+  if (int rc = check_padded_input("in", in_pitch, in_plane, need, int64_t(1) << 30, aux_plane, out_plane, Z)) return rc;
   LSR_REQUIRE(out_pitch >= X && (!has_aux || aux_pitch >= X), LSR_E_SHAPE,
-              "aux/out pitch smaller than X");
+              "aux/out pitch (%lld,%lld) smaller than X = %lld", (long long)aux_pitch, (long long)out_pitch, (long long)X);
 
   lsr::DenseArgs p{};
   p.ysep = mode == 2 ? 2 : (py == 1 ? 1 : 0);
@@ -905,21 +879,10 @@ int dense_padded_launch(const char* what, int mode, const float* ky,
   p.tiles_x = static_cast<int>(lsr::ceil_div(X, lsr::kSepTileX));
   p.tiles_y = static_cast<int>(lsr::ceil_div(Y, lsr::kSepTileY));
   p.z_chunk = static_cast<int>(pick_z_chunk(Z, int64_t(p.tiles_x) * p.tiles_y, PZ));
-  const int64_t blocks64 = int64_t(p.tiles_x) * p.tiles_y * lsr::ceil_div(Z, p.z_chunk);
-  LSR_REQUIRE(blocks64 < (int64_t(1) << 31), LSR_E_SHAPE, "grid of %lld workgroups is too large",
-              (long long)blocks64);
-  const unsigned blocks = static_cast<unsigned>(blocks64);
-  hipStream_t s = lsr::as_stream(stream);
-  bool ok = false;
-  switch (PZ) {
-    case 3: ok = lsr::launch_dense_pz3(PYX, p, blocks, s); break;
-    case 5: ok = lsr::launch_dense_pz5(PYX, p, blocks, s); break;
-    case 7: ok = lsr::launch_dense_pz7(PYX, p, blocks, s); break;
-    case 9: ok = lsr::launch_dense_pz9(PYX, p, blocks, s); break;
-    case 11: ok = lsr::launch_dense_pz11(PYX, p, blocks, s); break;
-    default: break;
-  }
-  LSR_REQUIRE(ok, LSR_E_UNSUPPORTED, "no dense specialisation for taps (%d,%d,%d)", pz, py, px);
+  const int64_t blocks = int64_t(p.tiles_x) * p.tiles_y * lsr::ceil_div(Z, p.z_chunk);
+  if (int rc = check_grid(blocks)) return rc;
+  LSR_REQUIRE(lsr::launch_dense(PZ, PYX, p, static_cast<unsigned>(blocks), lsr::as_stream(stream)), LSR_E_UNSUPPORTED,
+              "no dense specialisation for taps (%d,%d,%d)", pz, py, px);
   return lsr::launch_status(what);
 }
 }  // namespace
@@ -945,34 +908,18 @@ extern "C" int lsr_correlate_zxy_padded_f32(const float* in, int64_t in_pitch, i
 }
 
 extern "C" int lsr_rl_dense_padded_stats_f32(const float* y, int64_t y_pitch, int64_t y_plane, int init_from_y, float* x_pad, float* ratio_pad, float* x_out, int64_t Z, int64_t Y, int64_t X, const float* taps, const float* taps_flipped, int pz, int py, int px, const double* norm_table, float norm_full, int iters, float eps, double* stats, lsr_stream_t stream) {
-  LSR_REQUIRE_PTR(y);
-  LSR_REQUIRE_PTR(x_pad);
-  LSR_REQUIRE_PTR(ratio_pad);
-  LSR_REQUIRE(iters >= 1, LSR_E_ARG, "iters %d must be >= 1", iters);
-  LSR_REQUIRE(ratio_pad != x_pad, LSR_E_ARG, "x_pad and ratio_pad must be distinct");
-  int64_t ps[4];
-  if (int rc = lsr_sep_padded_shape(Y, X, pz, py, px, ps)) return rc;
-  const int64_t pitch = ps[1], plane = ps[0] * ps[1];
-  const int64_t origin = ps[2] * pitch + ps[3];
-  float* xl = x_pad + origin;
-  float* rl = ratio_pad + origin;
-  if (int rc = zero_stats(stats, iters, stream)) return rc;
-  for (int it = 0; it < iters; ++it) {
-    const bool from_y = init_from_y && it == 0;
-    const float* xin = from_y ? y : xl;
-    const int64_t xin_pitch = from_y ? y_pitch : pitch, xin_plane = from_y ? y_plane : plane;
-    int rc = lsr_correlate_dense_padded_f32(xin, xin_pitch, xin_plane, y, y_pitch, y_plane, rl, pitch,
-                                            plane, Z, Y, X, taps_flipped, pz, py, px, LSR_EPI_RATIO,
-                                            eps, nullptr, 0.0f, stream);
-    if (rc) return rc;
-    const bool last = it + 1 == iters && x_out != nullptr;
-    rc = lsr_correlate_dense_padded_stats_f32(rl, pitch, plane, xin, xin_pitch, xin_plane, last ? x_out : xl,
-                                              last ? X : pitch, last ? Y * X : plane, Z, Y, X, taps, pz,
-                                              py, px, LSR_EPI_UPDATE, eps, norm_table, norm_full,
-                                              stats ? stats + lsr::kRlStats * it : nullptr, stream);
-    if (rc) return rc;
-  }
-  return LSR_OK;
+  return run_two_launch_rl(
+      y, y_pitch, y_plane, init_from_y, x_pad, ratio_pad, x_out, Y, X, pz, py, px, iters, stats, stream,
+      [&](const float* x, int64_t x_pitch, int64_t x_plane, float* r, int64_t r_pitch, int64_t r_plane) {
+        return lsr_correlate_dense_padded_f32(x, x_pitch, x_plane, y, y_pitch, y_plane, r, r_pitch, r_plane, Z, Y, X,
+                                              taps_flipped, pz, py, px, LSR_EPI_RATIO, eps, nullptr, 0.0f, stream);
+      },
+      [&](const float* r, int64_t r_pitch, int64_t r_plane, const float* x, int64_t x_pitch, int64_t x_plane, float* out,
+          int64_t out_pitch, int64_t out_plane, double* st) {
+        return lsr_correlate_dense_padded_stats_f32(r, r_pitch, r_plane, x, x_pitch, x_plane, out, out_pitch, out_plane,
+                                                    Z, Y, X, taps, pz, py, px, LSR_EPI_UPDATE, eps, norm_table,
+                                                    norm_full, st, stream);
+      });
 }
 
 extern "C" int lsr_rl_dense_padded_f32(const float* y, int64_t y_pitch, int64_t y_plane, int init_from_y, float* x_pad, float* ratio_pad, float* x_out, int64_t Z, int64_t Y, int64_t X, const float* taps, const float* taps_flipped, int pz, int py, int px, const double* norm_table, float norm_full, int iters, float eps, lsr_stream_t stream) {

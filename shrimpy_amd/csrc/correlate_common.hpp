@@ -155,7 +155,6 @@ struct YsepArgs {
   int tiles_x, tiles_y;
   int n_full, pieces, z_chunk;        // work split, as FusedArgs
   double* stats;                      // three running sums of this iteration (rl_stats below) or NULL
-  int narrow;                         // 1: 256-thread workgroups on 32 x 64 tiles (two per CU); 0: 512 threads, 32 x 128
 };
 // tile rows: the accumulators of both stencils (PZ planes each) must fit 256 VGPRs per thread
 // (9 x 9 in-plane taps on 32 rows would be six pairs per thread in stage 1: 256 VGPRs and a spill)
@@ -228,49 +227,39 @@ __device__ __forceinline__ void rl_stats_flush(const RlStats& s, float* lds, dou
 
 inline int sep_wide_stage_cols(int PX) { return kSepWideTileX - 4 + 4 * ((4 + PX - 1 + 3) / 4); }
 
-// correlate_sep.hip, compiled once per PZ (-DLSR_SEP_PZ=n).  `pyx` is the (square) in-plane tap
-// count; false = no such specialisation.
-#define LSR_DECL_SEP(n) \
-  bool launch_sep_pz##n(int pyx, const SepArgs& p, unsigned blocks, hipStream_t s);
-LSR_DECL_SEP(3)
-LSR_DECL_SEP(5)
-LSR_DECL_SEP(7)
-LSR_DECL_SEP(9)
-LSR_DECL_SEP(11)
-LSR_DECL_SEP(13)
-LSR_DECL_SEP(15)
-#undef LSR_DECL_SEP
+// The tuned kernels are compiled once per z tap count PZ, one translation unit each (-DLSR_<FAMILY>_PZ=n), and export
+// launch_<family>_pz<n>(pyx, args, blocks, stream); `pyx` is the (square) in-plane tap count, false = no such
+// specialisation.  A new PZ is one entry in its family's list here, plus the Makefile's list.
+//   sep    correlate_sep.hip    pyx in {3,...,15}
+//   fused  rl_fused_sep.hip     pyx in {3,...,15}
+//   ysep   rl_fused_ysep.hip    pyx in {3,5,7,9}
+//   dense  correlate_dense.hip  pyx in {3,5,7,9}, PZ*pyx*pyx <= 900
+#define LSR_SEP_PZ_LIST(X, ...)   X(3, __VA_ARGS__) X(5, __VA_ARGS__) X(7, __VA_ARGS__) X(9, __VA_ARGS__) X(11, __VA_ARGS__) X(13, __VA_ARGS__) X(15, __VA_ARGS__)
+#define LSR_FUSED_PZ_LIST(X, ...) X(3, __VA_ARGS__) X(5, __VA_ARGS__) X(7, __VA_ARGS__) X(9, __VA_ARGS__) X(11, __VA_ARGS__) X(13, __VA_ARGS__) X(15, __VA_ARGS__)
+#define LSR_YSEP_PZ_LIST(X, ...)  X(3, __VA_ARGS__) X(5, __VA_ARGS__) X(7, __VA_ARGS__) X(9, __VA_ARGS__) X(11, __VA_ARGS__)
+#define LSR_DENSE_PZ_LIST(X, ...) X(3, __VA_ARGS__) X(5, __VA_ARGS__) X(7, __VA_ARGS__) X(9, __VA_ARGS__) X(11, __VA_ARGS__)
 
-// rl_fused_sep.hip, compiled once per PZ (-DLSR_FUSED_PZ=n); pyx in {3,...,15}.
-#define LSR_DECL_FUSED(n) \
-  bool launch_fused_pz##n(int pyx, const FusedArgs& p, unsigned blocks, hipStream_t s);
-LSR_DECL_FUSED(3)
-LSR_DECL_FUSED(5)
-LSR_DECL_FUSED(7)
-LSR_DECL_FUSED(9)
-LSR_DECL_FUSED(11)
-LSR_DECL_FUSED(13)
-LSR_DECL_FUSED(15)
-#undef LSR_DECL_FUSED
+// Each list is expanded twice: the declarations, and launch_<family>(PZ, ...) that picks among them (false = no such PZ).
+#define LSR_LAUNCH_DECL(n, family, Args) bool launch_##family##_pz##n(int pyx, const Args& p, unsigned blocks, hipStream_t s);
+#define LSR_LAUNCH_CASE(n, family, Args) case n: return launch_##family##_pz##n(pyx, p, blocks, s);
+#define LSR_LAUNCH_FAMILY(LIST, family, Args)                                                      \
+  LIST(LSR_LAUNCH_DECL, family, Args)                                                              \
+  inline bool launch_##family(int PZ, int pyx, const Args& p, unsigned blocks, hipStream_t s) {    \
+    switch (PZ) {                                                                                  \
+      LIST(LSR_LAUNCH_CASE, family, Args)                                                          \
+      default: return false;                                                                       \
+    }                                                                                              \
+  }
+LSR_LAUNCH_FAMILY(LSR_SEP_PZ_LIST, sep, SepArgs)
+LSR_LAUNCH_FAMILY(LSR_FUSED_PZ_LIST, fused, FusedArgs)
+LSR_LAUNCH_FAMILY(LSR_YSEP_PZ_LIST, ysep, YsepArgs)
+LSR_LAUNCH_FAMILY(LSR_DENSE_PZ_LIST, dense, DenseArgs)
+#undef LSR_LAUNCH_FAMILY
+#undef LSR_LAUNCH_CASE
+#undef LSR_LAUNCH_DECL
 
-// rl_fused_ysep.hip, compiled once per PZ (-DLSR_YSEP_PZ=n); pyx in {3,5,7,9}.
-#define LSR_DECL_YSEP(n) \
-  bool launch_ysep_pz##n(int pyx, const YsepArgs& p, unsigned blocks, hipStream_t s);
-LSR_DECL_YSEP(3)
-LSR_DECL_YSEP(5)
-LSR_DECL_YSEP(7)
-LSR_DECL_YSEP(9)
-LSR_DECL_YSEP(11)
-#undef LSR_DECL_YSEP
-
-// correlate_dense.hip, compiled once per PZ (-DLSR_DENSE_PZ=n); pyx in {3,5,7,9}, PZ*pyx*pyx <= 900.
-#define LSR_DECL_DENSE(n) \
-  bool launch_dense_pz##n(int pyx, const DenseArgs& p, unsigned blocks, hipStream_t s);
-LSR_DECL_DENSE(3)
-LSR_DECL_DENSE(5)
-LSR_DECL_DENSE(7)
-LSR_DECL_DENSE(9)
-LSR_DECL_DENSE(11)
-#undef LSR_DECL_DENSE
+// the name a translation unit defines: LSR_CAT(launch_sep_pz, LSR_SEP_PZ)
+#define LSR_CAT2(a, b) a##b
+#define LSR_CAT(a, b) LSR_CAT2(a, b)
 
 }  // namespace lsr

@@ -21,6 +21,7 @@
 
 #include "common.hpp"
 #include "correlate_common.hpp"
+#include "stencil_prims.hpp"
 
 #ifndef LSR_DENSE_PZ
 #error "compile with -DLSR_DENSE_PZ=<odd tap count along z>"
@@ -29,13 +30,13 @@
 namespace {
 
 using lsr::DenseArgs;
+using namespace lsr::prims;   // fast_rcp, gload_x4 / gload_x1, lds_barrier, dense_norm, the tile walk
 
 constexpr int kTY = lsr::kSepTileY;      // 32
 constexpr int kTX = lsr::kSepTileX;      // 64
 constexpr int kRun = 4;                  // rows per thread
 constexpr int kWaves = kTY / kRun;       // 8
 constexpr int kThreads = 64 * kWaves;    // 512
-constexpr int kBand = 8;
 
 template <int PYX>
 struct Tile {
@@ -50,13 +51,6 @@ struct Tile {
   static_assert(SL == 2, "the hand-counted waits assume two staging loads per thread");
 };
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float fast_rcp(float d) {
-  float r = __builtin_amdgcn_rcpf(d);
-  return fmaf(fmaf(-d, r, 1.0f), r, r);
-}
 // A wave-uniform pointer the register allocator must keep in SGPRs (under SGPR pressure hipcc
 // otherwise hands the "s" operand of the asm loads a VGPR pair, which does not assemble).
 __device__ __forceinline__ const float* uniform_ptr(const float* p) {
@@ -65,12 +59,6 @@ __device__ __forceinline__ const float* uniform_ptr(const float* p) {
   const unsigned hi = __builtin_amdgcn_readfirstlane(static_cast<unsigned>(v >> 32));
   return reinterpret_cast<const float*>((static_cast<unsigned long long>(hi) << 32) | lo);
 }
-__device__ __forceinline__ void gload_x4(f32x4& dst, const float* sbase, int voff_bytes) {
-  asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(dst) : "v"(voff_bytes), "s"(sbase) : "memory");
-}
-__device__ __forceinline__ void gload_x1(float& dst, const float* sbase, int voff_bytes) {
-  asm volatile("global_load_dword %0, %1, %2" : "+v"(dst) : "v"(voff_bytes), "s"(sbase) : "memory");
-}
 template <int N>
 __device__ __forceinline__ void wait_loads(f32x4& a, f32x4& b) {
   asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a), "+v"(b) : "n"(N) : "memory");
@@ -78,27 +66,6 @@ __device__ __forceinline__ void wait_loads(f32x4& a, f32x4& b) {
 template <int N>
 __device__ __forceinline__ void wait_loads(float (&a)[kRun]) {
   asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]) : "n"(N) : "memory");
-}
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-// H^T 1 at (z, y, x): the sum of the taps whose sample lies inside the volume, from the prefix-sum
-// table P[a][b][c] = sum_{a'<a, b'<b, c'<c} w of the CALLER's pz x py x px PSF.
-// (P: the table, staged in LDS by the UPDATE kernel -- eight dependent global loads per border
-// voxel made the UPDATE launch 22 % slower than the RATIO launch)
-__device__ float dense_norm(const DenseArgs& p, const double* P, int z, int y, int x) {
-  const int cz = p.pz / 2, cy = p.py / 2, cx = p.px / 2;
-  const int a0 = max(0, cz - z), a1 = min(p.pz, p.Z - z + cz);
-  const int b0 = max(0, cy - y), b1 = min(p.py, p.Y - y + cy);
-  const int c0 = max(0, cx - x), c1 = min(p.px, p.X - x + cx);
-  const int sb = p.px + 1, sa = (p.py + 1) * sb;
-  return static_cast<float>(((P[a1 * sa + b1 * sb + c1] - P[a0 * sa + b1 * sb + c1]) -
-                             (P[a1 * sa + b0 * sb + c1] - P[a0 * sa + b0 * sb + c1])) -
-                            ((P[a1 * sa + b1 * sb + c0] - P[a0 * sa + b1 * sb + c0]) -
-                             (P[a1 * sa + b0 * sb + c0] - P[a0 * sa + b0 * sb + c0])));
 }
 
 // MODE 0: the full PZ x PYX x PYX stencil.
@@ -134,21 +101,12 @@ __global__ __launch_bounds__(kThreads) void correlate_dense_kernel(DenseArgs p) 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
   // XCD-aware, band-swizzled tile order (see correlate_sep.hip)
-  int bid = blockIdx.x;
-  {
-    const int nblk = gridDim.x;
-    const int per = nblk / 8, rem = nblk % 8;
-    const int xcd = bid % 8, idx = bid / 8;
-    bid = xcd * per + (xcd < rem ? xcd : rem) + idx;
-  }
+  const int bid = xcd_contiguous(blockIdx.x, gridDim.x);
   const int tiles_xy = p.tiles_x * p.tiles_y;
   const int zc = bid / tiles_xy;
   const int lin = bid - zc * tiles_xy;
-  const int band = lin / (p.tiles_x * kBand);
-  const int lb = lin - band * (p.tiles_x * kBand);
-  const int band_h = min(kBand, p.tiles_y - band * kBand);
-  const int tx = lb / band_h;
-  const int ty = band * kBand + (lb - tx * band_h);
+  int tx, ty;
+  band_tile(lin, p.tiles_x, p.tiles_y, tx, ty);
 
   const int Z = p.Z, Y = p.Y, X = p.X;
   const int x0 = tx * kTX, y0 = ty * kTY;
@@ -447,8 +405,6 @@ bool launch_one(const DenseArgs& p, dim3 grid, hipStream_t s) {
 
 namespace lsr {
 
-#define LSR_CAT2(a, b) a##b
-#define LSR_CAT(a, b) LSR_CAT2(a, b)
 bool LSR_CAT(launch_dense_pz, LSR_DENSE_PZ)(int pyx, const DenseArgs& p, unsigned blocks, hipStream_t s) {
   constexpr int PZ = LSR_DENSE_PZ;
   const dim3 grid(blocks);

@@ -41,6 +41,7 @@
 
 #include "common.hpp"
 #include "correlate_common.hpp"
+#include "stencil_prims.hpp"
 
 #ifndef LSR_SEP_PZ
 #error "compile with -DLSR_SEP_PZ=<odd tap count along z>"
@@ -49,6 +50,7 @@
 namespace {
 
 using lsr::SepArgs;
+using namespace lsr::prims;   // fast_rcp, gload_x4 / gload_x1, lds_barrier, the tile walk
 
 constexpr int kCols = lsr::kSepCols;     // 64-wide column groups per workgroup (2)
 constexpr int kRun = lsr::sep_run(LSR_SEP_PZ);  // consecutive y per thread in the y / z passes
@@ -57,7 +59,6 @@ constexpr int kTX = lsr::kSepWideTileX; // 64 * kCols (128)
 constexpr int kPts = kRun * kCols;      // output points per thread
 constexpr int kWaves = 8;
 constexpr int kThreads = 64 * kWaves;    // 512
-constexpr int kBand = 8;                 // tile rows per band of the tile walk (see the kernel)
 
 template <int PY, int PX>
 struct Tile {
@@ -78,25 +79,7 @@ struct Tile {
   static_assert(2 * (ASZ + BSZ) * 4 <= 160 * 1024, "LDS per workgroup");
 };
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));  // native 16-byte vector (one VGPR quad)
-
-__device__ __forceinline__ float fast_rcp(float d) {
-  float r = __builtin_amdgcn_rcpf(d);    // v_rcp_f32, 1 ulp
-  return fmaf(fmaf(-d, r, 1.0f), r, r);  // + one Newton step
-}
-
-// ---- hand-managed global loads: scalar base + unsigned 32-bit byte offset per lane -------------
-// The destination is an IN/OUT operand ("+v"), as in rl_fused_sep.hip: a register that is loaded again before its value
-// was read -- the prologue's placeholder loads, the prefetches of the planes past the last one -- must stay the same
-// physical register while the older load is in flight.  As a pure output ("=v") the older value is dead to the compiler
-// and the register free between the two loads: round 4 found the <13, 9, 9> instance computing LDS offsets in such a
-// register, and the in-flight load landing on top of them (results that differed from run to run).
-__device__ __forceinline__ void gload_x4(f32x4& dst, const float* sbase, int voff_bytes) {
-  asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(dst) : "v"(voff_bytes), "s"(sbase) : "memory");
-}
-__device__ __forceinline__ void gload_x1(float& dst, const float* sbase, int voff_bytes) {
-  asm volatile("global_load_dword %0, %1, %2" : "+v"(dst) : "v"(voff_bytes), "s"(sbase) : "memory");
-}
+// (the loads themselves: stencil_prims.hpp, gload_x4 / gload_x1)
 // Wait until at most N vector-memory operations are outstanding; the registers are passed
 // through so that every later use depends on this statement.
 template <int N, int SL>
@@ -126,11 +109,6 @@ __device__ __forceinline__ void wait_aux(float (&a)[kPts], float& b) {
                  : "n"(N)
                  : "memory");
   }
-}
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's LDS writes have landed
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
 }
 
 // ds_read_b128 is serviced in four fixed 16-lane groups: {0-3,12-15,20-27}, {4-11,16-19,28-31} and
@@ -171,23 +149,14 @@ __global__ __launch_bounds__(kThreads) void correlate_sep_kernel(SepArgs p) {
 
   // XCD-aware tile order: workgroups b, b+8, ... share an XCD (round-robin dispatch), so give
   // each XCD a contiguous run of tiles ...
-  int bid = blockIdx.x;
-  {
-    const int nblk = gridDim.x;
-    const int per = nblk / 8, rem = nblk % 8;
-    const int xcd = bid % 8, idx = bid / 8;
-    bid = xcd * per + (xcd < rem ? xcd : rem) + idx;  // XCD k owns per + (k < rem) tiles
-  }
+  const int bid = xcd_contiguous(blockIdx.x, gridDim.x);
   // ... and walk the (y, x) tile grid in bands of 8 tile rows, column-major inside a band, so
   // that the workgroups an XCD keeps resident form a compact patch.
   const int tiles_xy = p.tiles_x * p.tiles_y;
   const int zc = bid / tiles_xy;
   const int lin = bid - zc * tiles_xy;
-  const int band = lin / (p.tiles_x * kBand);
-  const int lb = lin - band * (p.tiles_x * kBand);
-  const int band_h = min(kBand, p.tiles_y - band * kBand);
-  const int tx = lb / band_h;
-  const int ty = band * kBand + (lb - tx * band_h);
+  int tx, ty;
+  band_tile(lin, p.tiles_x, p.tiles_y, tx, ty);
 
   const int Z = p.Z, Y = p.Y, X = p.X;
   const int x0 = tx * kTX, y0 = ty * kTY;
@@ -464,8 +433,6 @@ bool launch_one(const SepArgs& p, dim3 grid, hipStream_t s) {
 namespace lsr {
 
 // One definition per translation unit: -DLSR_SEP_PZ=3 ... 15.
-#define LSR_CAT2(a, b) a##b
-#define LSR_CAT(a, b) LSR_CAT2(a, b)
 bool LSR_CAT(launch_sep_pz, LSR_SEP_PZ)(int pyx, const SepArgs& p, unsigned blocks, hipStream_t s) {
   constexpr int PZ = LSR_SEP_PZ;
   const dim3 grid(blocks);

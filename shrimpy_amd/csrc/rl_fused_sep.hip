@@ -44,17 +44,26 @@
 #error "compile with -DLSR_FUSED_PZ=<odd tap count along z>"
 #endif
 
+// Cache policies of the stores and of the LDS-DMA (stencil_prims.hpp: gstore, glds_x4), open to probe builds here
+#ifndef LSR_FUSED_STORE_POLICY
+#define LSR_FUSED_STORE_POLICY "nt"   // probes (round 2): "sc1", "nt sc1", "sc0 sc1" -- see DESIGN.md section 4.3
+#endif
+#ifndef LSR_FUSED_GLDS_POLICY
+#define LSR_FUSED_GLDS_POLICY ""      // probe: "nt" on the LDS-DMA of the x window
+#endif
+#define LSR_PRIMS_STORE_SUFFIX " " LSR_FUSED_STORE_POLICY
+#define LSR_PRIMS_GLDS_SUFFIX " " LSR_FUSED_GLDS_POLICY
+#include "stencil_prims.hpp"
+
 namespace {
 
 using lsr::FusedArgs;
+using namespace lsr::prims;   // packed pairs, gload / gstore / glds_x4, wait_vm / tie, lds_barrier, fused_work
 
 constexpr int kTX = lsr::kSepWideTileX;  // 128
 constexpr int kWaves = 8;
 constexpr int kThreads = 64 * kWaves;
-constexpr int kBand = 8;
 constexpr int kRing = 3;                 // LDS ring slots of staged x planes
-
-constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 template <int PZ, int PYX, int RUN>
 struct Geo {
@@ -104,24 +113,6 @@ struct Geo {
   static_assert(OFF_B1 % 4 == 0 && OFF_R % 4 == 0 && OFF_B2 % 4 == 0, "16-byte aligned buffers");
 };
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-// Two floats in an even-aligned register pair: the operand of the packed fp32 instructions
-// (v_pk_fma_f32 / v_pk_mul_f32: two lanes' worth of work per issue slot).  Each component is an
-// ordinary IEEE operation, so packing never changes a result.  The pairs are chosen by hand -- the
-// two column groups of a thread, which ds_read2 delivers in adjacent registers -- because hipcc's
-// own pairing (rows of one column) costs two v_mov per packed instruction.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float fast_rcp(float d) {
-  float r = __builtin_amdgcn_rcpf(d);
-  return fmaf(fmaf(-d, r, 1.0f), r, r);
-}
-__device__ __forceinline__ f32x2 splat(float a) { return f32x2{a, a}; }
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ f32x2 fast_rcp2(f32x2 d) {  // fast_rcp on both components
-  const f32x2 r = f32x2{__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
-  return pk_fma(pk_fma(-d, r, splat(1.0f)), r, r);
-}
 // One x-pass item: 4 consecutive outputs from 4 + PX - 1 inputs held in NP 16-byte pieces.
 template <int PX, int NP>
 __device__ __forceinline__ f32x4 xpass_item(const f32x4* src, const float (&wx)[PX]) {
@@ -139,55 +130,6 @@ __device__ __forceinline__ f32x4 xpass_item(const f32x4* src, const float (&wx)[
     o23 = pk_fma(splat(wx[c]), f32x2{w[c + 2], w[c + 3]}, o23);
   }
   return f32x4{o01.x, o01.y, o23.x, o23.y};
-}
-
-// ---- hand-managed memory operations: scalar base + unsigned 32-bit byte offset per lane -------
-// The destination is an in/out operand: a register that is loaded again before its value was used
-// (the prologue does that) must stay the same physical register while the older load is in flight.
-template <int IMM>
-__device__ __forceinline__ void gload(float& dst, const float* sbase, int voff) {
-  asm volatile("global_load_dword %0, %1, %2 offset:%3" : "+v"(dst) : "v"(voff), "s"(sbase), "n"(IMM) : "memory");
-}
-// Stores are non-temporal: x_new is not read again before the next launch, and keeping it out of
-// the way leaves more of L2 / MALL to the x planes that ARE read again nine planes later
-// (measured 2.56 -> 2.50 ms per launch; `nt` on the y loads instead made it slower, 2.66 ms).
-#ifndef LSR_FUSED_STORE_POLICY
-#define LSR_FUSED_STORE_POLICY "nt"   // probes (round 2): "sc1", "nt sc1", "sc0 sc1" -- see DESIGN.md section 4.3
-#endif
-#ifndef LSR_FUSED_GLDS_POLICY
-#define LSR_FUSED_GLDS_POLICY ""      // probe: "nt" on the LDS-DMA of the x window
-#endif
-template <int IMM>
-__device__ __forceinline__ void gstore(float* sbase, int voff, float v) {
-  asm volatile("global_store_dword %0, %1, %2 offset:%3 " LSR_FUSED_STORE_POLICY
-               :
-               : "v"(voff), "v"(v), "s"(sbase), "n"(IMM)
-               : "memory");
-}
-// LDS-DMA: 16 bytes per lane, LDS address = m0 + 16 * lane.  One wait state between the write of
-// m0 and the load (s_nop).
-__device__ __forceinline__ void glds_x4(const float* sbase, int voff, unsigned lds_byte_addr) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 " LSR_FUSED_GLDS_POLICY
-               :
-               : "v"(voff), "s"(sbase), "s"(lds_byte_addr)
-               : "memory");  // (m0 is a reserved register: hipcc sets it right at each of its own uses)
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory");
-}
-// After a wait: pass the loaded registers through an (empty) volatile asm, so that every later use
-// depends on a statement the compiler keeps behind the wait.
-template <int K>
-__device__ __forceinline__ void tie(float (&a)[K]) {
-#pragma unroll
-  for (int i = 0; i < K; ++i) asm volatile("" : "+v"(a[i]));
-}
-__device__ __forceinline__ void tie(float& a) { asm volatile("" : "+v"(a)); }
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
 }
 
 // STATS: the iteration's reduction scalars (correlate_common.hpp: RlStats) are summed in the epilogue and added to
@@ -218,24 +160,21 @@ __global__ __launch_bounds__(kThreads) void rl_fused_sep_kernel(FusedArgs p) {
   // 2 * (PZ - 1) halo planes twice).  Workgroups that run side by side stay on neighbouring tiles
   // AND on the same planes: their halo reads then hit L2 / MALL -- an even split of the tile-major
   // plane sequence over the CUs (tried) loses that and was 17 % slower.
-  // XCD-aware order inside each class: workgroups b, b+8, ... share an XCD (round-robin dispatch),
-  // so every XCD gets a contiguous run of tiles.
-  auto xcd_contiguous = [](int b, int n) {
+  // XCD-aware order inside each class (stencil_prims.hpp: xcd_contiguous; the band arithmetic stays spelled out here,
+  // see the note there).
 #ifdef LSR_FUSED_PLAIN_ORDER   // probe build: blocks in launch order, one per XCD in turn
-    return b;
+  auto tile_order = [](int b, int) { return b; };
+#else
+  auto tile_order = [](int b, int n) { return xcd_contiguous(b, n); };
 #endif
-    const int per = n / 8, rem = n % 8;
-    const int xcd = b % 8, idx = b / 8;
-    return xcd * per + (xcd < rem ? xcd : rem) + idx;
-  };
   const int Z = p.Z, Y = p.Y, X = p.X;
   int lin, zb, ze;
   if (static_cast<int>(blockIdx.x) < p.n_full) {
-    lin = xcd_contiguous(blockIdx.x, p.n_full);
+    lin = tile_order(blockIdx.x, p.n_full);
     zb = 0;
     ze = Z;
   } else {
-    const int t = xcd_contiguous(blockIdx.x - p.n_full, gridDim.x - p.n_full);
+    const int t = tile_order(blockIdx.x - p.n_full, gridDim.x - p.n_full);
     const int col = t / p.pieces;
     lin = p.n_full + col;
     zb = (t - col * p.pieces) * p.z_chunk;
@@ -681,8 +620,6 @@ bool launch_one(const FusedArgs& p, dim3 grid, hipStream_t s) {
 
 namespace lsr {
 
-#define LSR_CAT2(a, b) a##b
-#define LSR_CAT(a, b) LSR_CAT2(a, b)
 bool LSR_CAT(launch_fused_pz, LSR_FUSED_PZ)(int pyx, const FusedArgs& p, unsigned blocks, hipStream_t s) {
   constexpr int PZ = LSR_FUSED_PZ;
   const dim3 grid(blocks);

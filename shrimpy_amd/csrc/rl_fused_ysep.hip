@@ -19,10 +19,9 @@
 // voxel (y chain first: product, then FMAs in tap order; (z, x) chain plane by plane in z, tap by tap in x;
 // rcp with one Newton step) is the two-launch kernels', so both forms return bit-identical volumes.
 //
-// Two shapes of the same kernel (template <NW, NCG>): 8 waves owning a 32 x 128 tile (a thread: 4 rows of two
-// 64-column groups, packed pairs = the two groups of a row; one workgroup per CU), and 4 waves owning a
-// 32 x 64 tile (a thread: 8 rows of one column, packed pairs = two neighbouring rows; ~78 KB of LDS, so TWO
-// workgroups share a CU and one's LDS-bound y passes and barriers overlap the other's FMAs).
+// One shape: 8 waves owning a 32 x 128 tile (a thread: 4 rows of two 64-column groups, packed pairs = the two groups
+// of a row; one workgroup per CU).  (Why the 256-thread shape on 32 x 64 tiles went: correlate.hip,
+// lsr_rl_ysep_fused_stats_f32.)
 //
 // Volumes, work split, the LDS ring of staged x planes (global_load_lds_dwordx4), the hand-counted
 // s_waitcnt vmcnt scheme and the per-iteration schedule (two workgroup barriers) are rl_fused_sep.hip's;
@@ -32,6 +31,7 @@
 
 #include "common.hpp"
 #include "correlate_common.hpp"
+#include "stencil_prims.hpp"
 
 #ifndef LSR_YSEP_PZ
 #error "compile with -DLSR_YSEP_PZ=<odd tap count along z>"
@@ -40,21 +40,20 @@
 namespace {
 
 using lsr::YsepArgs;
+using namespace lsr::prims;   // packed pairs, gload / gstore / glds_x4, wait_vm / tie, lds_barrier, dense_norm, fused_work
 
-constexpr int kBand = 8;
 constexpr int kRing = 3;
+constexpr int kWaves = 8;                 // waves per workgroup
 
-constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
-
-// NW waves per workgroup, NCG column groups (of 64) per thread; RPW = tile rows per wave.
-template <int PZ, int PYX, int NW, int NCG>
+// A thread owns two column groups (of 64) of its rows; RPW = tile rows per wave.
+template <int PZ, int PYX>
 struct Geo {
-  static constexpr int NT = 64 * NW;                      // threads
-  static constexpr int TXW = 64 * NCG;                    // tile width
+  static constexpr int NT = 64 * kWaves;                      // threads
+  static constexpr int TXW = lsr::kSepWideTileX;          // tile width (128)
   static constexpr int C = PYX / 2, CZ = PZ / 2;
   static constexpr int TY = lsr::ysep_tile_rows(PZ, PYX);      // tile rows
-  static constexpr int RPW = TY / NW;                     // stage-2 rows per wave
-  static constexpr int NP2 = RPW * NCG / 2;               // stage-2 packed pairs per thread
+  static constexpr int RPW = TY / kWaves;                     // stage-2 rows per wave
+  static constexpr int NP2 = RPW;                         // stage-2 packed pairs per thread
   static constexpr int WL = lsr::fused_window_halo(PYX);  // staged columns left/right of the tile
   static constexpr int AR = TY + 4 * C;                   // staged rows
   static constexpr int PA = TXW + 2 * WL;                 // staged columns = pitch of A and of B1
@@ -66,12 +65,12 @@ struct Geo {
   // Stage 1 computes the ratio on the grown tile: R1 rows of TXW + E columns.  A thread holds NP1 packed pairs; a pair is
   // (row, lane) and (row, lane + 64) of one row -- except the LAST pair of the waves that own one row fewer than the
   // others: it holds two neighbouring EDGE columns (TXW + 2 k, TXW + 2 k + 1) of some row.  The rows are dealt so that
-  // every wave runs the same NP1 pairs: waves [0, NFULL) own NP1 rows, waves [NFULL, NW) own NP1 - 1 rows and 64 edge
-  // pairs each.  (Rounds 3-4 gave every wave ceil(R1 / NW) rows -- two of them padding for the last wave at 9 x 7 x 7 --
+  // every wave runs the same NP1 pairs: waves [0, NFULL) own NP1 rows, waves [NFULL, kWaves) own NP1 - 1 rows and 64 edge
+  // pairs each.  (Rounds 3-4 gave every wave ceil(R1 / kWaves) rows -- two of them padding for the last wave at 9 x 7 x 7 --
   // and the edge columns to the first waves as an extra scalar chain: the waves the barrier waits for did 5 pairs + 63
   // scalar FMAs per plane, the others 5 or 3 useful pairs.)
-  static constexpr int NP1 = R1 % NW == 0 ? R1 / NW + 1 : cdiv(R1, NW);   // stage-1 packed pairs per thread
-  static constexpr int NFULL = R1 - NW * (NP1 - 1);       // waves with NP1 rows (the others: NP1 - 1 rows + an edge pair)
+  static constexpr int NP1 = R1 % kWaves == 0 ? R1 / kWaves + 1 : cdiv(R1, kWaves);   // stage-1 packed pairs per thread
+  static constexpr int NFULL = R1 - kWaves * (NP1 - 1);       // waves with NP1 rows (the others: NP1 - 1 rows + an edge pair)
   static constexpr int NIT1 = R1 * CH;                    // chunks of t1 (zero fill)
   static constexpr int XIT1 = cdiv(NIT1, NT);
   static constexpr int B1SZ = R1 * PA;
@@ -97,8 +96,8 @@ struct Geo {
   static constexpr int NY = 2 * NP1;                      // y loads per thread and iteration
   static constexpr int NXC = 2 * NP2;                     // x (centre) loads
   static constexpr int NTAP = PYX * PZ;                   // (z, x) taps of one stage
-  static_assert(TY % NW == 0 && NCG == 2, "rows per wave; pairs are the two column groups of a row");
-  static_assert(NFULL >= 0 && NFULL <= NW && (NW - NFULL) * 64 >= NEP && E % 2 == 0, "the edge pairs fit the short waves");
+  static_assert(TY % kWaves == 0 && TXW == 128, "rows per wave; pairs are the two column groups of a row");
+  static_assert(NFULL >= 0 && NFULL <= kWaves && (kWaves - NFULL) * 64 >= NEP && E % 2 == 0, "the edge pairs fit the short waves");
   static_assert(TOTAL * 4 <= 160 * 1024, "LDS per workgroup");
   static_assert(2 * C <= WL && WL <= lsr::kSepOriginCol && 2 * C <= 8, "halo columns");
   static_assert(SL + 2 * (NY + NXC) <= 63, "vmcnt is a 6-bit counter");
@@ -106,68 +105,12 @@ struct Geo {
   static_assert(PZ <= lsr::kYsepTapGroup && PYX <= lsr::kYsepMaxPYX, "the tap block's groups");
 };
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float fast_rcp(float d) {
-  float r = __builtin_amdgcn_rcpf(d);
-  return fmaf(fmaf(-d, r, 1.0f), r, r);
-}
-__device__ __forceinline__ f32x2 splat(float a) { return f32x2{a, a}; }
-__device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ f32x2 fast_rcp2(f32x2 d) {
-  const f32x2 r = f32x2{__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
-  return pk_fma(pk_fma(-d, r, splat(1.0f)), r, r);
-}
-
-// ---- hand-managed memory operations (as rl_fused_sep.hip) ----------------------------------------
-template <int IMM>
-__device__ __forceinline__ void gload(float& dst, const float* sbase, int voff) {
-  asm volatile("global_load_dword %0, %1, %2 offset:%3" : "+v"(dst) : "v"(voff), "s"(sbase), "n"(IMM) : "memory");
-}
-template <int IMM>
-__device__ __forceinline__ void gstore(float* sbase, int voff, float v) {
-  asm volatile("global_store_dword %0, %1, %2 offset:%3 nt" : : "v"(voff), "v"(v), "s"(sbase), "n"(IMM) : "memory");
-}
-__device__ __forceinline__ void glds_x4(const float* sbase, int voff, unsigned lds_byte_addr) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-               :
-               : "v"(voff), "s"(sbase), "s"(lds_byte_addr)
-               : "memory");  // (m0 is a reserved register: hipcc sets it right at each of its own uses)
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory");
-}
-template <int K>
-__device__ __forceinline__ void tie(float (&a)[K]) {
-#pragma unroll
-  for (int i = 0; i < K; ++i) asm volatile("" : "+v"(a[i]));
-}
 // The FMAs of a tap group have no side effect, and their results are next used a whole plane later: left
 // alone, the optimiser sinks them to the end of the loop body -- away from the taps, which were fetched in
 // place (volatile) and would all have to stay live until then.  Passing an accumulator through an empty
 // volatile asm pins its computation where it is written.
 __device__ __forceinline__ void pin(f32x2& a) { asm volatile("" : "+v"(a)); }
 __device__ __forceinline__ void pin(float& a) { asm volatile("" : "+v"(a)); }
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-}
-
-// H^T 1 at (z, y, x) from the prefix-sum table of the caller's pz x py x px PSF (as correlate_dense.hip)
-__device__ float dense_norm(const YsepArgs& p, const double* P, int z, int y, int x) {
-  const int cz = p.pz / 2, cy = p.py / 2, cx = p.px / 2;
-  const int a0 = max(0, cz - z), a1 = min(p.pz, p.Z - z + cz);
-  const int b0 = max(0, cy - y), b1 = min(p.py, p.Y - y + cy);
-  const int c0 = max(0, cx - x), c1 = min(p.px, p.X - x + cx);
-  const int sb = p.px + 1, sa = (p.py + 1) * sb;
-  return static_cast<float>(((P[a1 * sa + b1 * sb + c1] - P[a0 * sa + b1 * sb + c1]) -
-                             (P[a1 * sa + b0 * sb + c1] - P[a0 * sa + b0 * sb + c1])) -
-                            ((P[a1 * sa + b1 * sb + c0] - P[a0 * sa + b1 * sb + c0]) -
-                             (P[a1 * sa + b0 * sb + c0] - P[a0 * sa + b0 * sb + c0])));
-}
 
 // dst[r][g] = sum_b w[b] * src[r + b][g] for rows r < rows and 16-byte chunks g < chunks (both arrays `chunks`
 // wide); item i -> (row group i / chunks, chunk i % chunks), `items` = ceil(rows / RY) * chunks of them.
@@ -195,17 +138,15 @@ __device__ __forceinline__ void ypass(const f32x4* src, f32x4* dst, int chunks, 
   }
 }
 
-// Where the two halves of a thread's packed pair i sit: NCG == 2: row i, column groups 0 and 1; NCG == 1: rows
-// 2 i and 2 i + 1 of the one column group.  (row of half h, its column offset in floats)
-template <int NCG>
-__device__ __forceinline__ constexpr int pair_row(int i, int h) { return NCG == 2 ? i : 2 * i + h; }
-template <int NCG>
-__device__ __forceinline__ constexpr int pair_col(int h) { return NCG == 2 ? 64 * h : 0; }
+// The two halves of a thread's packed pair i are row i of the wave's rows in column groups 0 and 1.  The epilogue's row
+// tests and store bases keep that row behind this call: with a plain `i` there, hipcc commutes the operands of three
+// multiplies in the <9, 9> and <11, *> instances (profiles/stencil_prims_isa.txt), and the streams are to stay put.
+__device__ __forceinline__ constexpr int pair_row(int i) { return i; }
 
 // STATS: the iteration's reduction scalars (correlate_common.hpp: RlStats) are summed in the epilogue and added to p.stats.
-template <int PZ, int PYX, int NW, int NCG, bool STATS>
-__global__ __launch_bounds__(64 * NW, 2) void rl_fused_ysep_kernel(YsepArgs p) {   // (2 waves per SIMD: <= 256 VGPRs)
-  using T = Geo<PZ, PYX, NW, NCG>;
+template <int PZ, int PYX, bool STATS>
+__global__ __launch_bounds__(64 * kWaves, 2) void rl_fused_ysep_kernel(YsepArgs p) {   // (2 waves per SIMD: <= 256 VGPRs)
+  using T = Geo<PZ, PYX>;
   constexpr int C = T::C, CZ = T::CZ, TY = T::TY, NT = T::NT, TXW = T::TXW;
   constexpr int NP1 = T::NP1, NP2 = T::NP2, RPW = T::RPW, LP = T::NP1 - 1;
   constexpr int NY = T::NY, NXC = T::NXC, SL = T::SL;
@@ -224,12 +165,7 @@ __global__ __launch_bounds__(64 * NW, 2) void rl_fused_ysep_kernel(YsepArgs p) {
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-  // work items, longest first, XCD-contiguous, tiles in bands of 8 rows (rl_fused_sep.hip)
-  auto xcd_contiguous = [](int b, int n) {
-    const int per = n / 8, rem = n % 8;
-    const int xcd = b % 8, idx = b / 8;
-    return xcd * per + (xcd < rem ? xcd : rem) + idx;
-  };
+  // work items, longest first, XCD-contiguous, tiles in bands of 8 rows (as rl_fused_sep.hip, which says why)
   const int Z = p.Z, Y = p.Y, X = p.X;
   int lin, zb, ze;
   if (static_cast<int>(blockIdx.x) < p.n_full) {
@@ -320,7 +256,7 @@ __global__ __launch_bounds__(64 * NW, 2) void rl_fused_ysep_kernel(YsepArgs p) {
   const int ry = p.py / 2, rx = p.px / 2, rz = p.pz / 2;
   // every point of the tile has all its in-plane taps inside the volume (wave-uniform: the fast path of the norm)
   const bool tile_norm_interior = x0 >= rx && x0 + TXW <= X - rx && y0 >= ry && y0 + TY <= Y - ry;
-  const bool okc[2] = {x0 + lane < X, x0 + lane + pair_col<NCG>(1) < X};
+  const bool okc[2] = {x0 + lane < X, x0 + lane + 64 < X};
 
   f32x2 acc1[PZ][NP1], acc2[PZ][NP2];
 #pragma unroll
@@ -343,8 +279,7 @@ __global__ __launch_bounds__(64 * NW, 2) void rl_fused_ysep_kernel(YsepArgs p) {
 #pragma unroll 1
       for (int k = 0; k < 2 * NP2; ++k) {
         const int i = k >> 1, h = k & 1;
-        const int row = NCG == 2 ? i : 2 * i + h, col = NCG == 2 ? 64 * h : 0;
-        const int gy = min(y0 + wave * RPW + row, Y - 1), gx = min(x0 + lane + col, X - 1);
+        const int gy = min(y0 + wave * RPW + i, Y - 1), gx = min(x0 + lane + 64 * h, X - 1);
         const bool inside = o >= rz && o < Z - rz && gy >= ry && gy < Y - ry && gx >= rx && gx < X - rx;
         const float r = fast_rcp(inside ? p.norm_full : dense_norm(p, p.norm_table, o, gy, gx));
 #pragma unroll
@@ -384,8 +319,8 @@ __global__ __launch_bounds__(64 * NW, 2) void rl_fused_ysep_kernel(YsepArgs p) {
     const float* base = xc_tile + (static_cast<int64_t>(clampz(o)) * p.plane + static_cast<int64_t>(wave * RPW) * p.pitch);
 #pragma unroll
     for (int i = 0; i < NP2; ++i) {
-      gload<0>(xc[2 * i], base + pair_row<NCG>(i, 0) * p.pitch, lane_off);
-      gload<4 * pair_col<NCG>(1)>(xc[2 * i + 1], base + pair_row<NCG>(i, 1) * p.pitch, lane_off);
+      gload<0>(xc[2 * i], base + i * p.pitch, lane_off);
+      gload<4 * 64>(xc[2 * i + 1], base + i * p.pitch, lane_off);
     }
   };
   auto issue_y = [&](int q) {  // NY loads: y at the ratio points of plane q
@@ -469,7 +404,7 @@ __global__ __launch_bounds__(64 * NW, 2) void rl_fused_ysep_kernel(YsepArgs p) {
       // the PZ taps of ONE group in SGPRs (all PZ * PYX at once spill)
       const float* base = B2 + t2_col;
       auto ld = [&](int i, int c) {
-        return f32x2{base[pair_row<NCG>(i, 0) * T::PR + c], base[pair_row<NCG>(i, 1) * T::PR + pair_col<NCG>(1) + c]};
+        return f32x2{base[i * T::PR + c], base[i * T::PR + 64 + c]};
       };
       f32x2 vb[2][NP2];   // two register sets, indexed by the (compile-time) parity of c: no copies
       float wq[2][PZ];    // ... and two SGPR sets of taps
@@ -521,12 +456,12 @@ __global__ __launch_bounds__(64 * NW, 2) void rl_fused_ysep_kernel(YsepArgs p) {
           // (x * u) * rcp(H^T 1): the two-launch UPDATE's order
           const float xu0 = xc[2 * i] * acc2[0][i].x, xu1 = xc[2 * i + 1] * acc2[0][i].y;
           const float v0 = xu0 * rn[2 * i], v1 = xu1 * rn[2 * i + 1];
-          if (y0 + wave * RPW + pair_row<NCG>(i, 0) < Y && okc[0]) {   // (row test wave-uniform)
-            gstore<0>(obase + pair_row<NCG>(i, 0) * p.out_pitch, lane_off, v0);
+          if (y0 + wave * RPW + pair_row(i) < Y && okc[0]) {   // (row test wave-uniform)
+            gstore<0>(obase + pair_row(i) * p.out_pitch, lane_off, v0);
             if constexpr (STATS) st.add(xc[2 * i], xu0, v0);
           }
-          if (y0 + wave * RPW + pair_row<NCG>(i, 1) < Y && okc[NCG == 2 ? 1 : 0]) {
-            gstore<4 * pair_col<NCG>(1)>(obase + pair_row<NCG>(i, 1) * p.out_pitch, lane_off, v1);
+          if (y0 + wave * RPW + pair_row(i) < Y && okc[1]) {
+            gstore<4 * 64>(obase + pair_row(i) * p.out_pitch, lane_off, v1);
             if constexpr (STATS) st.add(xc[2 * i + 1], xu1, v1);
           }
         }
@@ -626,15 +561,14 @@ __global__ __launch_bounds__(64 * NW, 2) void rl_fused_ysep_kernel(YsepArgs p) {
     lsr::keep_until_here(xc);    // (in-flight prefetches: correlate_common.hpp, keep_until_here)
     lsr::keep_until_here(yv);
     st.pin();
-    lsr::rl_stats_flush<NW>(st, smem + T::OFF_B2, p.stats);
+    lsr::rl_stats_flush<kWaves>(st, smem + T::OFF_B2, p.stats);
   }
 }
 
 template <int PZ, int PYX>
 bool launch_one(const YsepArgs& p, dim3 grid, hipStream_t s) {
-  if (p.narrow) return false;   // (the 256-thread shape <PZ, PYX, 4, 1> is no longer instantiated)
-  if (p.stats != nullptr) hipLaunchKernelGGL((rl_fused_ysep_kernel<PZ, PYX, 8, 2, true>), grid, dim3(512), 0, s, p);
-  else hipLaunchKernelGGL((rl_fused_ysep_kernel<PZ, PYX, 8, 2, false>), grid, dim3(512), 0, s, p);
+  if (p.stats != nullptr) hipLaunchKernelGGL((rl_fused_ysep_kernel<PZ, PYX, true>), grid, dim3(64 * kWaves), 0, s, p);
+  else hipLaunchKernelGGL((rl_fused_ysep_kernel<PZ, PYX, false>), grid, dim3(64 * kWaves), 0, s, p);
   return true;
 }
 
@@ -642,8 +576,6 @@ bool launch_one(const YsepArgs& p, dim3 grid, hipStream_t s) {
 
 namespace lsr {
 
-#define LSR_CAT2(a, b) a##b
-#define LSR_CAT(a, b) LSR_CAT2(a, b)
 bool LSR_CAT(launch_ysep_pz, LSR_YSEP_PZ)(int pyx, const YsepArgs& p, unsigned blocks, hipStream_t s) {
   constexpr int PZ = LSR_YSEP_PZ;
   const dim3 grid(blocks);

@@ -1,6 +1,6 @@
 """Instruction ledger of a kernel's main loop, from the compiler's listing.
 
-    python tools/isa_ledger.py --tu rl_fused_ysep --define LSR_YSEP_PZ=9 --kernel 'rl_fused_ysep_kernelILi9ELi7ELi8ELi2ELb0E'
+    python tools/isa_ledger.py --tu rl_fused_ysep --define LSR_YSEP_PZ=9 --kernel 'rl_fused_ysep_kernelILi9ELi7ELb0E'
     python tools/isa_ledger.py --asm listing.s --kernel <substring of the mangled name>
 
 Finds the kernel, takes its largest innermost-or-not loop (the label .. back-edge span with the most instructions: the
