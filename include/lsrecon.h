@@ -800,6 +800,24 @@ int lsr_psf_accumulate_f32(const float* vol, int64_t Z, int64_t Y, int64_t X, co
                            int pz, int py, int px, double* bead_stats, float* psf, lsr_stream_t stream);
 
 /*
+ * One level of a multiscale pyramid (csrc/pyramid.hip, shrimpy_amd/pyramid.py): the 2x mean of the level above it,
+ * factors (fz, 2, 2) with fz 1 or 2 (LSR_E_ARG otherwise) -- iohub's compute_pyramid is not vendored, PARITY UNPINNED,
+ * the rule is defined here (tests/pyramid_ref.py restates it).  The output has ceil(n / f) voxels per axis
+ * (lsr_downsample2_shape: out3 <- (Zo, Yo, Xo), host only); output voxel (z, y, x) is the mean over the input voxels
+ * (fz z + a, 2 y + b, 2 x + c), a < fz, b < 2, c < 2, INSIDE the volume: nothing is padded, nothing dropped, a window
+ * holds 1, 2, 4 or 8 = 2^k voxels.
+ *   float32: s = ((v000 + v001) + (v010 + v011)) + ((v100 + v101) + (v110 + v111)), v[a][b][c]: x pairs, then y, then z,
+ *     float32 additions, a neighbour outside the volume left out (never added as zero); out = s * 2^-k, exact.  Three
+ *     roundings: |out - exact| <= 3 * 2^-24 * mean|v| over the window.  A NaN or Inf reaches its own window only.
+ *   uint16: the sum in 32 bits, out = (sum + (2^k >> 1)) >> k: round half up, exact.
+ * in (Z, Y, X) and out (Zo, Yo, Xo) are dense C-order device volumes that must not overlap; any X, any row alignment,
+ * volumes beyond 2^31 bytes (64-bit indices).  One launch, no scratch, no LDS.
+ */
+int lsr_downsample2_shape(int64_t Z, int64_t Y, int64_t X, int fz, int64_t out3[3]);
+int lsr_downsample2_f32(const float* in, int64_t Z, int64_t Y, int64_t X, float* out, int fz, lsr_stream_t stream);
+int lsr_downsample2_u16(const uint16_t* in, int64_t Z, int64_t Y, int64_t X, uint16_t* out, int fz, lsr_stream_t stream);
+
+/*
  * Host twins (csrc/host_twins.hip): the same signatures with HOST pointers, the same argument checks and the
  * same arithmetic in the same order, so the results equal the device entry points' bit for bit.  They serve
  * the boxes where the reference itself resolves to the CPU (shrimpy/preprocessing.py:78-82 -- its CI has no
@@ -896,6 +914,10 @@ int lsr_local_max_candidates_f32_cpu(const float* s, int64_t Z, int64_t Y, int64
 int lsr_psf_accumulate_f32_cpu(const float* vol, int64_t Z, int64_t Y, int64_t X, const long long* centres,
                                int64_t n_beads, int pz, int py, int px, double* bead_stats, float* psf,
                                lsr_stream_t stream);
+
+/* ... of the pyramid level (csrc/pyramid.hip): the same window arithmetic from the same header, the same bits */
+int lsr_downsample2_f32_cpu(const float* in, int64_t Z, int64_t Y, int64_t X, float* out, int fz, lsr_stream_t stream);
+int lsr_downsample2_u16_cpu(const uint16_t* in, int64_t Z, int64_t Y, int64_t X, uint16_t* out, int fz, lsr_stream_t stream);
 
 #ifdef __cplusplus
 }

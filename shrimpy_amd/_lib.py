@@ -140,6 +140,9 @@ SIGNATURES: dict[str, list] = {
                                      ctypes.c_void_p, ctypes.c_void_p, _stream],
     "lsr_psf_accumulate_f32": [_c_f32p, _i64, _i64, _i64, ctypes.c_void_p, _i64, _int, _int, _int, ctypes.c_void_p, _c_f32p,
                                _stream],
+    "lsr_downsample2_shape": [_i64, _i64, _i64, _int, ctypes.POINTER(ctypes.c_int64)],
+    "lsr_downsample2_f32": [_c_f32p, _i64, _i64, _i64, _c_f32p, _int, _stream],
+    "lsr_downsample2_u16": [ctypes.c_void_p, _i64, _i64, _i64, ctypes.c_void_p, _int, _stream],
     "lsr_crc32c_host": [ctypes.c_void_p, _i64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)],
     "lsr_crc32c_host_portable": [ctypes.c_void_p, _i64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)],
     "lsr_average_slices_f32": [_c_f32p, _i64, _i64, _i64, _c_f32p, _i64, _int, _stream],
@@ -217,7 +220,9 @@ for _name in ("lsr_deskew_f32", "lsr_deskew_u16", "lsr_deskew_cval", "lsr_affine
               # ... and of the bead detection and the PSF average (csrc/peaks.hip)
               "lsr_box_smooth_f32", "lsr_local_max_candidates_f32", "lsr_psf_accumulate_f32",
               # ... and of the focus measure (csrc/focus.hip)
-              "lsr_band_power_f32"):
+              "lsr_band_power_f32",
+              # ... and of the pyramid level (csrc/pyramid.hip)
+              "lsr_downsample2_f32", "lsr_downsample2_u16"):
     SIGNATURES[_name + "_cpu"] = SIGNATURES[_name]
 SIGNATURES["lsr_rl_tv_scale_f32_cpu"] = SIGNATURES["lsr_rl_tv_scale_f32"][:-1]     # (this twin takes no stream)
 for _name in ("lsr_rl_accel_dots_f32", "lsr_rl_accel_predict_f32"):                    # (nor do these)

@@ -14,6 +14,7 @@ CPU path (biahub's; the reference's own CLI has only ``acquire`` and ``gui``,
     python -m shrimpy_amd.cli phase       -i deskewed.zarr -c phase.yml  -o phase.zarr
     python -m shrimpy_amd.cli estimate-stabilization -i series.zarr -c estimate.yml -o stabilization/
     python -m shrimpy_amd.cli stabilize   -i series.zarr -c stabilization/ -o stabilized.zarr
+    python -m shrimpy_amd.cli pyramid     -i store.zarr --levels 4        (adds levels to the store in place)
 
 Every (position, timepoint, channel) volume is an independent unit.  Launched under
 ``python -m torch.distributed.run --nproc-per-node N`` each rank takes the units
@@ -161,7 +162,18 @@ def _common(fn, input_required: bool = True):
                            "left out and recorded under <output>/.lsr_failed/ (every other unit is written; the command "
                            "exits with status 3 and --resume retries only the failed units) -- the reference likewise "
                            "turns a failed stack into an error record and carries on (shrimpy/dynatrack/worker.py:262-271).")(fn)
+    fn = click.option("--levels", type=click.IntRange(1, 8), default=1, show_default=True,
+                      help="Multiscale levels per position: arrays \"0\" .. \"N-1\", each the 2x mean of the one above it, "
+                           "computed on the device beside the result (1: level \"0\" only).")(fn)
+    fn = click.option("--level-factor-z", "level_factor_z", type=click.Choice(["1", "2"]), default="2", show_default=True,
+                      help="z factor between pyramid levels (y and x are always 2); 1 for stacks already coarse in z.")(fn)
     return fn
+
+
+def _pyramid_options(levels, level_factor_z) -> dict:
+    """``--levels`` / ``--level-factor-z`` as ``run_store`` keywords; nothing at all for the default of one level (the z
+    factor has no meaning then), so that such a run is the call it always was."""
+    return {} if int(levels) == 1 else {"levels": int(levels), "level_factor_z": int(level_factor_z)}
 
 
 def _finish(result: dict) -> None:
@@ -320,15 +332,19 @@ class _DoneLedger:
     def _file(self, u) -> Path:
         return self.dir / u.position.replace("/", "__") / f"t{u.t}_c{u.c}"
 
+    def check(self) -> None:
+        """Refuse a store that records another run's fingerprint (writes nothing)."""
+        tag = self.dir / "fingerprint"
+        if tag.exists() and tag.read_text().strip() != self.fingerprint:
+            raise click.ClickException(
+                f"{self.dir.parent} was written from a different input or with different settings; "
+                "--resume only continues the same run")
+
     def begin(self) -> None:
         self.dir.mkdir(parents=True, exist_ok=True)
+        self.check()
         tag = self.dir / "fingerprint"
-        if tag.exists():
-            if tag.read_text().strip() != self.fingerprint:
-                raise click.ClickException(
-                    f"{self.dir.parent} was written from a different input or with different settings; "
-                    "--resume only continues the same run")
-        else:
+        if not tag.exists():
             tag.write_text(self.fingerprint + "\n")
 
     def is_done(self, u) -> bool:
@@ -379,7 +395,7 @@ def run_store(input_path: Path, output_path: Path, settings: ReconstructSettings
               zarr_version: str = "0.4", reconstructor_factory=None, stage_through_pinned: bool = True,
               resume: bool = False, io_backend: str = "auto", compression: str | None = None,
               device_codec: bool | None = None, on_error: str = "raise", output_channel_names=None,
-              fingerprint_extra=None) -> dict:
+              fingerprint_extra=None, levels: int = 1, level_factor_z: int = 2) -> dict:
     """Apply ``settings`` to every (position, t, c) volume of ``input_path`` -> ``output_path``.
 
     ``output_channel_names(names) -> names``: the output store's channel names from the input's (default: the same);
@@ -400,7 +416,18 @@ def run_store(input_path: Path, output_path: Path, settings: ReconstructSettings
     ``reconstructor_factory(raw_shape, settings, device)`` defaults to
     :class:`shrimpy_amd.pipeline.VolumeReconstructor` (tests inject a stand-in).
     ``resume``: the output may exist; units recorded as complete (``_DoneLedger``) are skipped.
+
+    ``levels`` > 1: every position gets the multiscale arrays ``"0" .. str(levels - 1)`` (``io.omezarr.create_pyramid``).
+    The lower levels of a unit are computed from its result while that is on the device (``pyramid.build_levels``, factors
+    ``(level_factor_z, 2, 2)``, on the stream of the kernels), copied to the host and encoded there, and written with the
+    unit: it counts as complete only when every level is stored.  Level 0 keeps its route, device-written frames included.
     """
+    from .pyramid import MAX_LEVELS
+
+    if not 1 <= int(levels) <= MAX_LEVELS or level_factor_z not in (1, 2):
+        raise click.ClickException(f"levels must be in 1 .. {MAX_LEVELS} and level_factor_z 1 or 2")
+    if int(levels) > 1 and io_backend == "iohub":
+        raise click.ClickException("--levels > 1 needs this package's own writer: it cannot be combined with --io iohub")
     rank, world, device, created = _distributed()
     try:
         min_blocks = 0
@@ -409,7 +436,7 @@ def run_store(input_path: Path, output_path: Path, settings: ReconstructSettings
             min_blocks = int(os.environ.get("LSR_DEVICE_DECODE_MIN_BLOCKS", "8192") or 0)
         return _run_store(input_path, output_path, settings, positions, zarr_version, reconstructor_factory,
                           stage_through_pinned, resume, io_backend, compression, rank, world, device, device_codec,
-                          on_error, min_blocks, output_channel_names, fingerprint_extra)
+                          on_error, min_blocks, output_channel_names, fingerprint_extra, int(levels), int(level_factor_z))
     finally:
         if created:
             import torch.distributed as dist
@@ -419,10 +446,11 @@ def run_store(input_path: Path, output_path: Path, settings: ReconstructSettings
 
 def _run_store(input_path, output_path, settings, positions, zarr_version, reconstructor_factory,
                stage_through_pinned, resume, io_backend, compression, rank, world, device, device_codec=True,
-               on_error="raise", min_decode_blocks=0, output_channel_names=None, fingerprint_extra=None) -> dict:
+               on_error="raise", min_decode_blocks=0, output_channel_names=None, fingerprint_extra=None, levels=1,
+               level_factor_z=2) -> dict:
     import torch
 
-    from .io.omezarr import as_volume_array, create_level, open_ome_zarr, position_scale
+    from .io.omezarr import as_volume_array, create_pyramid, open_ome_zarr, position_scale
     from .pipeline import Unit, VolumeReconstructor, enumerate_units, run_sharded
 
     factory = reconstructor_factory or VolumeReconstructor
@@ -475,11 +503,16 @@ def _run_store(input_path, output_path, settings, positions, zarr_version, recon
     # where output index 0 sits in the target's physical frame: non-zero only when keep_overhang grew the grid below zero
     origin = tuple(getattr(rec, "register_origin", (0, 0, 0)))
     out_translation = [0.0, 0.0] + [float(o) * float(sc) for o, sc in zip(origin, out_scale[2:])] if any(origin) else None
+    if levels > 1:     # (a run without a pyramid keeps the fingerprint it always had)
+        fingerprint_extra = {"step": fingerprint_extra, "pyramid": {"levels": levels, "fz": level_factor_z}}
     ledger = _DoneLedger(output_path, _fingerprint(input_path, settings, shape5, raw_dtype, keys, fingerprint_extra))
     if output_channel_names is not None:
         channel_names = list(output_channel_names(channel_names or [str(c) for c in range(nc)]))
     fail_ledger = _FailLedger(output_path)
     out_shape5 = (nt, nc, oz, oy, ox)
+    from .pyramid import build_levels, level_shapes
+
+    level_shapes5 = [(nt, nc) + tuple(s) for s in level_shapes((oz, oy, ox), levels, level_factor_z)[0]]
 
     def open_output(mode):
         if use_iohub_out:
@@ -501,18 +534,25 @@ def _run_store(input_path, output_path, settings, positions, zarr_version, recon
             if exists and not resume:
                 raise FileExistsError(f"{output_path} exists (never overwritten, like the reference); "
                                       "use --resume to continue an interrupted run")
+            if exists:
+                ledger.check()       # another run's store (other settings, other --levels) is refused as that, first
             dst = open_output("a" if exists else "w")
             have = dict(dst.positions()) if exists else {}
             for key in keys:
                 if key in have:
-                    got = tuple(as_volume_array(have[key]["0"]).shape)
-                    if got != out_shape5:
-                        raise ValueError(f"{output_path}: position {key} has shape {got}, this run writes {out_shape5}")
+                    for k, want in enumerate(level_shapes5):
+                        try:
+                            got = tuple(as_volume_array(have[key][str(k)]).shape)
+                        except (FileNotFoundError, KeyError) as exc:
+                            raise ValueError(f"{output_path}: position {key} has no level {k}") from exc
+                        if got != want:
+                            raise ValueError(f"{output_path}: position {key} level {k} has shape {got}, this run writes {want}")
                     continue
                 row, col, fov = key.split("/")
                 pos = dst.create_position(row, col, fov)
                 extra = {} if use_iohub_out or compression in (None, "none") else {"compress": compression}
-                create_level(pos, out_shape5, "float32", out_scale, translation=out_translation, **extra)
+                create_pyramid(pos, out_shape5, "float32", out_scale, levels, level_factor_z, translation=out_translation,
+                               **extra)
             dst.close()
             ledger.begin()
         except click.ClickException as exc:
@@ -521,7 +561,11 @@ def _run_store(input_path, output_path, settings, positions, zarr_version, recon
             error = f"{type(exc).__name__}: {exc}"
     _agree(error)
     dst = open_output("a")
-    dst_arrays = {k: as_volume_array(p["0"]) for k, p in dict(dst.positions()).items() if k in keys}
+    dst_positions = {k: p for k, p in dict(dst.positions()).items() if k in keys}
+    dst_arrays = {k: as_volume_array(p["0"]) for k, p in dst_positions.items()}
+    # the lower pyramid levels: arrays per position, and per unit in flight what `process` handed over for `store`
+    lower_arrays = {k: [as_volume_array(p[str(lv)]) for lv in range(1, levels)] for k, p in dst_positions.items()}
+    lower_pending: dict = {}
 
     units = enumerate_units(keys, nt, range(nc))
     todo = [u for u in units if not (resume and ledger.is_done(u))]
@@ -544,6 +588,12 @@ def _run_store(input_path, output_path, settings, positions, zarr_version, recon
         else:
             host = vol if isinstance(vol, np.ndarray) else vol.cpu().numpy()
             dst_arrays[u.position].write_volume(u.t, u.c, host)
+        if levels > 1:
+            hosts, ready = lower_pending.pop(u)
+            if ready is not None:
+                ready.synchronize()           # the copies of this unit's lower levels have landed
+            for arr, lv in zip(lower_arrays[u.position], hosts):
+                arr.write_volume(u.t, u.c, lv.numpy())
         ledger.mark(u)
         fail_ledger.clear(u)
 
@@ -551,7 +601,24 @@ def _run_store(input_path, output_path, settings, positions, zarr_version, recon
         step = rec if warp[unit.c] else rec_unwarped
         # a step that works differently from unit to unit (stabilize: one matrix per timepoint) hands out its callable
         for_unit = getattr(step, "for_unit", None)
-        return (step if for_unit is None else for_unit(unit))(data)
+        result = (step if for_unit is None else for_unit(unit))(data)
+        if levels > 1:
+            lower_pending[unit] = lower_levels(result)
+        return result
+
+    def lower_levels(result):
+        """Levels 1 .. of a unit's result, on their way to the host: (host tensors, the event behind their copies or None).
+        Computed where the result lives, on the current stream -- behind the kernels that wrote it."""
+        vol = torch.as_tensor(result)
+        if vol.dtype != torch.float32 or not vol.is_contiguous():
+            vol = vol.to(torch.float32).contiguous()
+        lower = build_levels(vol, levels, level_factor_z)
+        if vol.device.type != "cuda":
+            return lower, None
+        hosts = [torch.empty(lv.shape, dtype=lv.dtype, pin_memory=True).copy_(lv, non_blocking=True) for lv in lower]
+        ready = torch.cuda.Event()
+        ready.record(torch.cuda.current_stream(vol.device))
+        return hosts, ready
 
     stager = None
     if (stage_through_pinned and torch.device(device).type == "cuda"
@@ -642,12 +709,14 @@ def cli(verbose: bool):
 
 @cli.command(cls=_eat_all_command("-i", "--input-position-dirpaths"))
 @_common
-def deskew(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error):
+def deskew(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error, levels,
+           level_factor_z):
     """Deskew oblique-plane stacks (config: DeskewSettings YAML)."""
     input_path, positions = _inputs(input_path, positions)
     s = ReconstructSettings(deskew=DeskewSettings.from_yaml(config))
     _finish(run_store(input_path, output_path, s, positions, zarr_version, resume=resume,
-                      io_backend=io_backend, compression=compression, on_error=on_error))
+                      io_backend=io_backend, compression=compression, on_error=on_error,
+                      **_pyramid_options(levels, level_factor_z)))
 
 
 def _target_shape_zyx(target_path) -> tuple[int, int, int]:
@@ -674,7 +743,7 @@ def _target_shape_zyx(target_path) -> tuple[int, int, int]:
                    "no output_shape_zyx.")
 @functools.partial(_common, input_required=False)
 def register(input_path, source_path, target_path, config, output_path, positions, zarr_version, resume, io_backend,
-             compression, on_error):
+             compression, on_error, levels, level_factor_z):
     """Apply an affine registration (config: RegisterSettings YAML with affine_transform_zyx)."""
     input_path, source_path, target_path = (input_path or None), (source_path or None), (target_path or None)
     if (input_path is None) == (source_path is None):
@@ -685,7 +754,8 @@ def register(input_path, source_path, target_path, config, output_path, position
         reg = reg.model_copy(update={"output_shape_zyx": _target_shape_zyx(target_path)})
     s = ReconstructSettings(registration=reg)
     _finish(run_store(input_path, output_path, s, positions, zarr_version, resume=resume,
-                      io_backend=io_backend, compression=compression, on_error=on_error))
+                      io_backend=io_backend, compression=compression, on_error=on_error,
+                      **_pyramid_options(levels, level_factor_z)))
 
 
 @cli.command(cls=_eat_all_command("-i", "--input-position-dirpaths"))
@@ -694,7 +764,7 @@ def register(input_path, source_path, target_path, config, output_path, position
                    "ZYX array; overrides psf_path of the config ([RECALLED] biahub's -p, which is the position filter here).")
 @_common
 def deconvolve(input_path, psf_dirpath, config, output_path, positions, zarr_version, resume, io_backend, compression,
-               on_error):
+               on_error, levels, level_factor_z):
     """Richardson-Lucy deconvolution (config: DeconvolveSettings YAML)."""
     input_path, positions = _inputs(input_path, positions)
     dec = DeconvolveSettings.from_yaml(config)
@@ -702,19 +772,22 @@ def deconvolve(input_path, psf_dirpath, config, output_path, positions, zarr_ver
         dec = dec.model_copy(update={"psf_path": str(psf_dirpath)})
     s = ReconstructSettings(deconvolution=dec)
     _finish(run_store(input_path, output_path, s, positions, zarr_version, resume=resume,
-                      io_backend=io_backend, compression=compression, on_error=on_error))
+                      io_backend=io_backend, compression=compression, on_error=on_error,
+                      **_pyramid_options(levels, level_factor_z)))
 
 
 @cli.command(cls=_eat_all_command("-i", "--input-position-dirpaths"))
 @_common
-def reconstruct(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error):
+def reconstruct(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error, levels,
+                level_factor_z):
     """deskew -> register -> deconvolve in one pass (config: ReconstructSettings YAML)."""
     input_path, positions = _inputs(input_path, positions)
     s = ReconstructSettings.from_yaml(config)
     if s.deskew is None and s.registration is None and s.deconvolution is None:
         raise click.ClickException("the config enables no step")
     _finish(run_store(input_path, output_path, s, positions, zarr_version, resume=resume,
-                      io_backend=io_backend, compression=compression, on_error=on_error))
+                      io_backend=io_backend, compression=compression, on_error=on_error,
+                      **_pyramid_options(levels, level_factor_z)))
 
 
 class _PhaseReconstructor:
@@ -737,7 +810,8 @@ class _PhaseReconstructor:
 
 @cli.command(cls=_eat_all_command("-i", "--input-position-dirpaths"))
 @_common
-def phase(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error):
+def phase(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error, levels,
+          level_factor_z):
     """Label-free 3-D phase reconstruction of (deskewed) bright-field volumes (config: PhaseSettings YAML)."""
     from .settings import PhaseSettings
 
@@ -747,7 +821,7 @@ def phase(input_path, config, output_path, positions, zarr_version, resume, io_b
                       reconstructor_factory=functools.partial(_PhaseReconstructor, s), resume=resume, io_backend=io_backend,
                       compression=compression, on_error=on_error,
                       output_channel_names=lambda names: ["Phase3D"] if len(names) == 1 else [f"Phase3D_{n}" for n in names],
-                      fingerprint_extra={"phase": s.model_dump(mode="json")}))
+                      fingerprint_extra={"phase": s.model_dump(mode="json")}, **_pyramid_options(levels, level_factor_z)))
 
 
 @cli.command("estimate-registration")
@@ -1016,10 +1090,12 @@ class _StabilizeStep:
 
 @cli.command(cls=_eat_all_command("-i", "--input-position-dirpaths"))
 @_common
-def stabilize(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error):
+def stabilize(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error, levels,
+              level_factor_z):
     """Apply per-timepoint translations (config: a StabilizationSettings YAML, or the directory estimate-stabilization wrote)."""
     input_path, positions = _inputs(input_path, positions)
-    _finish(run_stabilize(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error))
+    _finish(run_stabilize(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error,
+                          **_pyramid_options(levels, level_factor_z)))
 
 
 # (`-c` of this command may be a directory)
@@ -1029,7 +1105,8 @@ for _p in stabilize.params:
 
 
 def run_stabilize(input_path, config, output_path, positions=(), zarr_version: str = "0.5", resume: bool = False,
-                  io_backend: str = "auto", compression=None, on_error: str = "raise") -> dict:
+                  io_backend: str = "auto", compression=None, on_error: str = "raise", levels: int = 1,
+                  level_factor_z: int = 2) -> dict:
     """``stabilize``: every ``(position, t, c)`` volume of a stabilized channel is moved by its timepoint's matrix, the other
     channels are copied.  ``config``: one ``StabilizationSettings`` file for every position, or a directory that holds
     ``<row>_<col>_<fov>.yml`` per position.  Everything is checked before the output store is created."""
@@ -1081,7 +1158,99 @@ def run_stabilize(input_path, config, output_path, positions=(), zarr_version: s
     return run_store(input_path, output_path, plan, tuple(keys) if positions else (), zarr_version,
                      reconstructor_factory=factory, resume=resume, io_backend=io_backend, compression=compression,
                      on_error=on_error,
-                     fingerprint_extra={"stabilize": {k: s.model_dump(mode="json") for k, s in per_position.items()}})
+                     fingerprint_extra={"stabilize": {k: s.model_dump(mode="json") for k, s in per_position.items()}},
+                     levels=levels, level_factor_z=level_factor_z)
+
+
+@cli.command("pyramid", cls=_eat_all_command("-i", "--input-position-dirpaths"))
+@click.option("-i", "--input-position-dirpaths", "input_path", required=True, multiple=True, type=click.UNPROCESSED,
+              help="The store to add levels to, IN PLACE (HCS plate or single FOV), or position directories of one plate.")
+@click.option("-p", "--position", "positions", multiple=True, help='Restrict to these position keys ("row/col/fov").')
+@click.option("--levels", type=click.IntRange(2, 8), required=True,
+              help="Levels the positions have afterwards: arrays \"1\" .. \"N-1\" are added beside \"0\".")
+@click.option("--level-factor-z", "level_factor_z", type=click.Choice(["1", "2"]), default="2", show_default=True,
+              help="z factor between levels (y and x are always 2).")
+def pyramid_cmd(input_path, positions, levels, level_factor_z):
+    """Add multiscale levels to an existing store: each the 2x mean of the one above it (uint16 or float32 data)."""
+    input_path, positions = _inputs(input_path, positions)
+    _finish(run_pyramid(input_path, positions, levels, int(level_factor_z)))
+
+
+def run_pyramid(store_path, positions=(), levels: int = 2, level_factor_z: int = 2) -> dict:
+    """``pyramid``: levels ``1 .. levels - 1`` of every selected position of ``store_path``, written into it.  One
+    (position, t, c) volume at a time (``pipeline.run_sharded``): level 0 is read, the levels are computed where the run's
+    device is (``pyramid.build_levels``) and stored.  Level 0's files are not touched; only new arrays and the positions'
+    group metadata are written (``io.omezarr.add_pyramid_levels``).  Refused: a position that has a level ``"1"``, data
+    that is neither uint16 nor float32, an array this package's reader cannot decode."""
+    import torch
+
+    from .io.omezarr import Position, UnsupportedCodec, open_ome_zarr
+    from .pipeline import Unit, enumerate_units, run_sharded
+    from .pyramid import MAX_LEVELS, build_levels
+
+    if not 2 <= int(levels) <= MAX_LEVELS or level_factor_z not in (1, 2):
+        raise click.ClickException(f"levels must be in 2 .. {MAX_LEVELS} and level_factor_z 1 or 2")
+    rank, world, device, created = _distributed()
+    try:
+        store = open_ome_zarr(store_path, layout="auto", mode="a", prefer_iohub=False)
+        available = dict(store.positions()) if hasattr(store, "positions") else {"0/0/0": store}
+        keys = [k for k in available if not positions or k in positions]
+        missing = [p for p in positions if p not in available]
+        if missing:
+            raise click.ClickException(f"positions {missing} not found; available: {list(available)}")
+        if not keys:
+            raise click.ClickException("no positions to process")
+        # everything is checked on every rank before rank 0 writes anything
+        try:
+            level0 = {k: available[k]["0"] for k in keys}
+        except UnsupportedCodec as exc:
+            raise click.ClickException(str(exc)) from exc
+        shape5, dtype = tuple(level0[keys[0]].shape), np.dtype(level0[keys[0]].dtype)
+        for k, a in level0.items():
+            if len(a.shape) != 5:
+                raise click.ClickException(f"position {k}: expected 5-D TCZYX data, got shape {tuple(a.shape)}")
+            if np.dtype(a.dtype) not in (np.dtype("uint16"), np.dtype("float32")):
+                raise click.ClickException(f"position {k}: data type {a.dtype}; pyramid levels are computed for uint16 and float32")
+            if tuple(a.shape) != shape5 or np.dtype(a.dtype) != dtype:
+                raise click.ClickException(f"position {k} {tuple(a.shape)} {a.dtype} differs from {keys[0]} {shape5} {dtype}; "
+                                           "run them separately (-p)")
+            if not isinstance(available[k], Position) or (available[k].path / "1").exists() or len(available[k].levels) > 1:
+                raise click.ClickException(f"position {k} already has a level '1': this command only adds levels")
+        _agree(None)           # (every rank has looked at the store as it was)
+        error = None
+        if rank == 0:
+            try:
+                for k in keys:
+                    from .io.omezarr import add_pyramid_levels
+
+                    add_pyramid_levels(available[k], levels, level_factor_z)
+            except Exception as exc:  # noqa: BLE001 -- reported on every rank, see _agree
+                error = f"{type(exc).__name__}: {exc}"
+        _agree(error)
+        lower = {k: [available[k][str(lv)] for lv in range(1, levels)] for k in keys}
+        units = enumerate_units(keys, shape5[0], range(shape5[1]))
+
+        def load(u: Unit):
+            return level0[u.position].read_volume(u.t, u.c)
+
+        def process(vol):
+            return [lv.cpu() for lv in build_levels(torch.as_tensor(np.ascontiguousarray(vol), device=device), levels,
+                                                    level_factor_z)]
+
+        def store_levels(u: Unit, hosts):
+            for arr, lv in zip(lower[u.position], hosts):
+                arr.write_volume(u.t, u.c, lv.numpy())
+
+        on_gpu = torch.device(device).type == "cuda"
+        report = run_sharded(units, load, process, store_levels, synchronize=torch.cuda.synchronize if on_gpu else None)
+        return {"rank": rank, "world_size": world, "units": len(report.units), "units_total": len(units),
+                "levels": int(levels), "level_factor_z": int(level_factor_z), "seconds": report.seconds,
+                "job_seconds": report.max_seconds, "failed": []}
+    finally:
+        if created:
+            import torch.distributed as dist
+
+            dist.destroy_process_group()
 
 
 def main():

@@ -991,3 +991,47 @@ extern "C" int lsr_band_power_f32_cpu(const float* in, int64_t Z, int64_t Y, int
   LSR_REQUIRE(!failed.load(), LSR_E_ARG, "lsr_band_power_f32_cpu: out of memory for the plane buffers");
   return LSR_OK;
 }
+
+// ---- 2x mean downsampling (pyramid.hip): the window arithmetic of pyramid.hpp, voxel by voxel ----
+#include "pyramid.hpp"
+
+namespace {
+
+template <typename T>
+int downsample2_host(const T* in, int64_t Z, int64_t Y, int64_t X, T* out, int fz) {
+  namespace py = lsr::pyramid;
+  LSR_REQUIRE_HOST_FMA();
+  if (int rc = py::check(in, Z, Y, X, out, fz)) return rc;
+  const int64_t Zo = py::out_extent(Z, fz), Yo = py::out_extent(Y, 2), Xo = py::out_extent(X, 2), plane = Y * X;
+  parallel_ranges(Zo * Yo, [&](int64_t first, int64_t last) {
+    for (int64_t row = first; row < last; ++row) {
+      const int64_t zo = row / Yo, yo = row - zo * Yo, z0 = zo * fz, y0 = 2 * yo;
+      const bool hz = fz == 2 && z0 + 1 < Z, hy = y0 + 1 < Y;
+      const T* r00 = in + (z0 * Y + y0) * X;
+      const T* r01 = hy ? r00 + X : r00;            // (a row that does not exist is never read: finish() ignores its pair)
+      const T* r10 = hz ? r00 + plane : r00;
+      const T* r11 = hz ? r01 + plane : r01;
+      T* dst = out + row * Xo;
+      for (int64_t xo = 0; xo < Xo; ++xo) {
+        const int64_t x0 = 2 * xo;
+        const bool hx = x0 + 1 < X;
+        const int64_t x1 = hx ? x0 + 1 : x0;
+        const int k = static_cast<int>(hx) + static_cast<int>(hy) + static_cast<int>(hz);
+        dst[xo] = py::finish(py::pair(r00[x0], r00[x1], hx), py::pair(r01[x0], r01[x1], hx), py::pair(r10[x0], r10[x1], hx),
+                             py::pair(r11[x0], r11[x1], hx), hy, hz, k);
+      }
+    }
+  });
+  return LSR_OK;
+}
+
+}  // namespace
+
+extern "C" int lsr_downsample2_f32_cpu(const float* in, int64_t Z, int64_t Y, int64_t X, float* out, int fz, lsr_stream_t) {
+  return downsample2_host<float>(in, Z, Y, X, out, fz);
+}
+
+extern "C" int lsr_downsample2_u16_cpu(const uint16_t* in, int64_t Z, int64_t Y, int64_t X, uint16_t* out, int fz,
+                                       lsr_stream_t) {
+  return downsample2_host<uint16_t>(in, Z, Y, X, out, fz);
+}

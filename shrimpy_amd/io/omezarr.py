@@ -183,6 +183,21 @@ class _Node:
             _write_json(self.path / ".zattrs", attrs)
 
 
+    def _patch_zattrs(self, mutate) -> None:
+        """``mutate(attrs)`` on the stored NGFF attributes in place: every other key of the group's metadata file --
+        whatever another writer put there -- stays as it is."""
+        if self.mode == "r":
+            raise PermissionError("store opened read-only")
+        if self.version == "0.5":
+            meta = _read_json(self.path / "zarr.json")
+            mutate(meta.setdefault("attributes", {}).setdefault("ome", {}))
+            _write_json(self.path / "zarr.json", meta)
+        else:
+            attrs = self.zattrs
+            mutate(attrs)
+            _write_json(self.path / ".zattrs", attrs)
+
+
 class _BlockCodec:
     """bytes <-> one chunk-shaped block.  ``kind``: None (raw little-endian), ``gzip`` / ``zlib``,
     ``zstd`` (bare frames) or ``blosc`` (c-blosc 1.x frames, ``io/codecs.py``)."""
@@ -261,7 +276,10 @@ class _BlockCodec:
     def named(cls, name: str | None, dtype: np.dtype, blocksize: int = 0) -> "_BlockCodec":
         """``None`` | "gzip" | "zlib" | "zstd" | "blosc-zstd" (the acquisition's) | "blosc-lz4".  ``blocksize``: bytes
         per blosc block (0: this package's default of 256 KB; c-blosc itself picks 32 KB for zstd at level 1, which is
-        what the acquisition's frames have)."""
+        what the acquisition's frames have).  A codec object is returned as it is (a new level array of an existing
+        position takes level 0's)."""
+        if isinstance(name, cls):
+            return cls(name.kind, **dict(name.params))
         if name in (None, "", "raw", "none"):
             return cls(None)
         if name in ("gzip", "zlib"):
@@ -1000,6 +1018,15 @@ class ZarrArray:
         return out[key]
 
 
+def _dataset(path: str, scale, translation=None) -> dict:
+    """One entry of ``multiscales[0].datasets``.  NGFF: scale first, then translation, in physical units (where index 0
+    of this level sits); a zero translation is left out."""
+    transforms = [{"type": "scale", "scale": [float(v) for v in scale]}]
+    if translation is not None and any(float(v) != 0.0 for v in translation):
+        transforms.append({"type": "translation", "translation": [float(v) for v in translation]})
+    return {"path": path, "coordinateTransformations": transforms}
+
+
 class Position(_Node):
     """One field of view: an NGFF image group with multiscale level arrays ("0", ...)."""
 
@@ -1023,6 +1050,12 @@ class Position(_Node):
             if t.get("type") == "scale":
                 return tuple(float(v) for v in t["scale"])
         return (1.0,) * 5
+
+    @property
+    def levels(self) -> list[str]:
+        """Paths of the multiscale level arrays, finest first (``["0"]`` for a store without a pyramid)."""
+        ms = self.zattrs.get("multiscales", [{}])
+        return [str(d["path"]) for d in (ms[0].get("datasets", []) if ms else []) if "path" in d]
 
     def __getitem__(self, name: str) -> ZarrArray:
         return ZarrArray(self.path / name, self.version, self.mode)
@@ -1049,21 +1082,22 @@ class Position(_Node):
             shards = (1, 1) + tuple(-(-n // c) * c for n, c in zip(shape[2:], chunks[2:]))
         arr = ZarrArray.create(self.path / name, self.version, shape, chunks, dtype, compress, shards, blocksize)
         scale = [float(s) for s in (scale if scale is not None else (1, 1, 1, 1, 1))]
-        transforms = [{"type": "scale", "scale": scale}]
-        if translation is not None and any(float(v) != 0.0 for v in translation):
-            # NGFF: scale first, then translation, in physical units (where index 0 of this level sits)
-            transforms.append({"type": "translation", "translation": [float(v) for v in translation]})
+        self._write_multiscales([_dataset(name, scale, translation)], shape[1])
+        return arr
+
+    def _write_multiscales(self, datasets: list, n_channels: int, downsampling: str | None = None) -> None:
+        """The group's metadata: ONE ``multiscales`` entry with ``datasets`` (finest first) and the ``omero`` channels;
+        ``downsampling`` names how the lower levels were made (NGFF's ``type``)."""
+        entry = {"version": self.version, "axes": AXES, "name": "0", "datasets": datasets}
+        if downsampling is not None:
+            entry["type"] = downsampling
         attrs = {
-            "multiscales": [{
-                "version": self.version, "axes": AXES, "name": "0",
-                "datasets": [{"path": name, "coordinateTransformations": transforms}],
-            }],
+            "multiscales": [entry],
             "omero": {"channels": [{"label": n, "active": True, "color": "FFFFFF",
                                     "window": {"start": 0, "end": 65535, "min": 0, "max": 65535}}
-                                   for n in (self._channel_names or [str(i) for i in range(shape[1])])]},
+                                   for n in (self._channel_names or [str(i) for i in range(n_channels)])]},
         }
         self._write_group(attrs)
-        return arr
 
     def positions(self) -> Iterator[tuple[str, "Position"]]:
         yield "0/0/0", self
@@ -1269,9 +1303,7 @@ def create_level(position, shape, dtype, scale, chunks=None, name: str = "0", tr
         # in 32-plane chunks is three 650 MB files, and buffered writes to ONE file serialise on its
         # inode lock (measured: 6 GB/s, 0.29 s per volume against 0.03 s of kernels); ~64 MB chunks
         # are 29 files that sixteen threads write side by side
-        plane_bytes = shape[3] * shape[4] * np.dtype(dtype).itemsize
-        zc = max(1, min(32, shape[2], (64 << 20) // max(plane_bytes, 1)))
-        chunks = (1, 1, zc, shape[3], shape[4])
+        chunks = _level_chunks(shape, dtype)
     if isinstance(position, Position):
         return position.create_zeros(name, shape=shape, dtype=dtype, chunks=chunks, scale=scale, translation=translation, **kw)
     from iohub.ngff.models import TransformationMeta
@@ -1280,3 +1312,96 @@ def create_level(position, shape, dtype, scale, chunks=None, name: str = "0", tr
     if translation is not None and any(float(v) != 0.0 for v in translation):
         transform.append(TransformationMeta(type="translation", translation=[float(v) for v in translation]))
     return position.create_zeros(name, shape=shape, dtype=dtype, chunks=chunks, transform=transform)
+
+
+def _level_chunks(shape5, dtype) -> tuple:
+    """``create_level``'s default chunks for a level of this shape."""
+    plane_bytes = shape5[3] * shape5[4] * np.dtype(dtype).itemsize
+    zc = max(1, min(32, shape5[2], (64 << 20) // max(plane_bytes, 1)))
+    return (1, 1, zc, shape5[3], shape5[4])
+
+
+def pyramid_datasets(shape5, scale, levels: int, fz: int = 2, translation=None) -> list[tuple[tuple, list, list]]:
+    """``(shape5, scale, translation)`` of levels ``0 .. levels - 1`` of a mean pyramid with factors ``(fz, 2, 2)``
+    (``shrimpy_amd/pyramid.py``).  Level ``k``: the level-0 scale times ``(1, 1, fz^k, 2^k, 2^k)``; its voxel 0 is the mean
+    of ``f^k`` level-0 voxels per axis, whose centre lies ``(f^k - 1) / 2`` level-0 voxels behind that of voxel 0 of level 0,
+    so the translation grows by ``(f^k - 1) / 2 *`` the level-0 scale per spatial axis (the NGFF rule)."""
+    from ..pyramid import level_shapes
+
+    shape5 = tuple(int(n) for n in shape5)
+    if len(shape5) != 5:
+        raise ValueError(f"expected a 5-D TCZYX shape, got {shape5}")
+    scale = [float(v) for v in scale]
+    base = [float(v) for v in translation] if translation is not None else [0.0] * 5
+    shapes, factors = level_shapes(shape5[2:], levels, fz)
+    out = []
+    for shp, f in zip(shapes, factors):
+        sc = scale[:2] + [s * q for s, q in zip(scale[2:], f)]
+        tr = base[:2] + [b + (q - 1) / 2.0 * s for b, s, q in zip(base[2:], scale[2:], f)]
+        out.append((shape5[:2] + tuple(shp), sc, tr))
+    return out
+
+
+def create_pyramid(position, shape5, dtype, scale, levels: int = 1, fz: int = 2, translation=None, **kw):
+    """Level arrays ``"0" .. str(levels - 1)`` of a new position and ONE ``multiscales`` entry that lists them, with
+    ``"type": "mean"``; returns the arrays, finest first.  Chunks follow ``create_level``'s rule level by level; ``kw``
+    (``compress``, ``blocksize``, ``shards="volume"``) applies to every level.  ``levels = 1`` IS ``create_level``: the same
+    array and the same metadata, byte for byte."""
+    if int(levels) == 1:
+        from ..pyramid import level_shapes
+
+        level_shapes(tuple(shape5)[2:], 1, fz)
+        return [create_level(position, shape5, dtype, scale, translation=translation, **kw)]
+    if not isinstance(position, Position):
+        raise TypeError("pyramid levels are written by this package's own store classes (not through iohub)")
+    if kw.get("shards") is not None and not isinstance(kw["shards"], str):
+        raise ValueError("an explicit shard shape fits one level only: use shards='volume' with levels > 1")
+    plan = pyramid_datasets(shape5, scale, levels, fz, translation)
+    arrays, datasets = [], []
+    for k, (shp, sc, tr) in enumerate(plan):
+        chunks = _level_chunks(shp, dtype)
+        shards = kw.get("shards")
+        if isinstance(shards, str):
+            if shards != "volume":
+                raise ValueError("shards must be a shape or 'volume'")
+            shards = (1, 1) + tuple(-(-n // c) * c for n, c in zip(shp[2:], chunks[2:]))
+        arrays.append(ZarrArray.create(position.path / str(k), position.version, shp, chunks, dtype, kw.get("compress"),
+                                       shards, kw.get("blocksize", 0)))
+        datasets.append(_dataset(str(k), sc, tr))
+    position._write_multiscales(datasets, int(shape5[1]), downsampling="mean")
+    return arrays
+
+
+def add_pyramid_levels(position, levels: int, fz: int = 2) -> list:
+    """Empty level arrays ``"1" .. str(levels - 1)`` beside an existing level 0, and their entries in the position's
+    ``multiscales`` (every other attribute of the group stays).  They take level 0's data type and compressor, chunks by
+    ``create_level``'s rule, no sharding.  Returns the new arrays."""
+    if not isinstance(position, Position):
+        raise TypeError("pyramid levels are written by this package's own store classes (not through iohub)")
+    if int(levels) < 2:
+        raise ValueError("levels must be at least 2: level 0 is there already")
+    if (position.path / "1").exists() or len(position.levels) > 1:
+        raise FileExistsError(f"{position.path} already has a level '1'")
+    base = position["0"]
+    if len(base.shape) != 5:
+        raise ValueError(f"{position.path}: expected 5-D TCZYX data, got shape {tuple(base.shape)}")
+    ms = position.zattrs.get("multiscales") or [{}]
+    first = (ms[0].get("datasets") or [{}])[0]
+    translation = None
+    for t in first.get("coordinateTransformations", []):
+        if t.get("type") == "translation":
+            translation = [float(v) for v in t["translation"]]
+    plan = pyramid_datasets(base.shape, position.scale, levels, fz, translation)
+    arrays = [ZarrArray.create(position.path / str(k), position.version, shp, _level_chunks(shp, base.dtype), base.dtype,
+                               base._codec)
+              for k, (shp, _, _) in enumerate(plan) if k > 0]
+    lower = [_dataset(str(k), sc, tr) for k, (_, sc, tr) in enumerate(plan) if k > 0]
+
+    def mutate(attrs):
+        entries = attrs.setdefault("multiscales", [{"version": position.version, "axes": AXES, "name": "0"}])
+        datasets = entries[0].setdefault("datasets", [_dataset("0", position.scale, translation)])
+        datasets.extend(lower)
+        entries[0]["type"] = "mean"
+
+    position._patch_zattrs(mutate)
+    return arrays

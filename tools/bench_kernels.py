@@ -54,6 +54,10 @@ def main():
     ap.add_argument("--phase", action="store_true", help="only: one application of the phase reconstruction (yaml optics) on "
                     "--rl-grid, per launch and in total, the warm-up (host transfer function) time, and one Fourier-domain RL "
                     "convolution on the same volume as the yardstick; appended to profiles/phase_config2.jsonl")
+    ap.add_argument("--pyramid", action="store_true", help="only: ms of lsr_downsample2_f32 for pyramid levels 1-3 of "
+                    "--rl-grid (fz = 2) beside torch's avg_pool3d on the same tensor and a device-to-device copy in the same "
+                    "run (median of --reps launches between HIP events, after a warm-up); appended to "
+                    "profiles/pyramid_config2.jsonl")
     ap.add_argument("--psf-sweep-wide", action="store_true", help="with --psf-sweep: every pz for in-plane extents 9-15")
     args = ap.parse_args()
 
@@ -68,6 +72,9 @@ def main():
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(3)
 
+    if args.pyramid:
+        _pyramid(args, torch, dev, g, tuple(int(v) for v in args.rl_grid.split(",")))
+        return
     if args.phase:
         _phase(args, torch, dev, g, tuple(int(v) for v in args.rl_grid.split(",")))
         return
@@ -340,6 +347,60 @@ def _rl_tv(args, torch, dev, g, bench, RichardsonLucyPlan, oshape):
         print(json.dumps({"kernel": label, "path": plan.path, "grid": oshape, "iterations": iters,
                           "ms_per_iteration": ev[0].elapsed_time(ev[1]) / iters}), flush=True)
     plan.release()
+
+
+def _median_ms(fn, reps, torch):
+    """Median over `reps` launches, each between its own pair of HIP events, after one warm-up."""
+    fn()
+    torch.cuda.synchronize()
+    events = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+    for e0, e1 in events:
+        e0.record()
+        fn()
+        e1.record()
+    torch.cuda.synchronize()
+    return float(np.median([e0.elapsed_time(e1) for e0, e1 in events]))
+
+
+def _pyramid(args, torch, dev, g, oshape):
+    """Pyramid levels (csrc/pyramid.hip): lsr_downsample2_f32 level by level at fz = 2, 4.5 algorithmic bytes per input
+    voxel (4 read, 0.5 written), against the copy rate of this card in this run (2 x 4 bytes per voxel, the figure
+    tools/bw_probe.py reports) and against torch.nn.functional.avg_pool3d with the same partial-window rule."""
+    from shrimpy_amd import _lib, pyramid
+
+    reps = max(args.reps, 5)
+    vol = torch.empty(oshape, dtype=torch.float32, device=dev).normal_(generator=g)
+    other = torch.empty_like(vol)
+    copy_ms = _median_ms(lambda: other.copy_(vol), reps, torch)
+    copy_gbps = 8.0 * vol.numel() / copy_ms / 1e6
+    del other
+    records = [{"kernel": "device copy (torch copy_)", "grid": list(oshape), "ms": copy_ms, "GBps": copy_gbps}]
+    cur = vol
+    for level in (1, 2, 3):
+        z, y, x = (int(n) for n in cur.shape)
+        out = pyramid.downsample2(cur, 2)
+
+        def launch(cur=cur, out=out, z=z, y=y, x=x):
+            _lib.call("lsr_downsample2_f32", cur.data_ptr(), z, y, x, out.data_ptr(), 2, _lib.stream_ptr(dev))
+
+        ms = _median_ms(launch, reps, torch)
+        nbytes = 4.0 * cur.numel() + 4.0 * out.numel()
+        pool = lambda cur=cur: torch.nn.functional.avg_pool3d(cur[None, None], 2, ceil_mode=True, count_include_pad=False)  # noqa: E731
+        pool_ms = _median_ms(pool, reps, torch)
+        same = bool(torch.allclose(pool()[0, 0], out, rtol=0.0, atol=4 * 2.0 ** -24 * float(cur.abs().max())))
+        records.append({"kernel": "lsr_downsample2_f32", "level": level, "fz": 2, "in": [z, y, x], "out": list(out.shape),
+                        "ms": ms, "algorithmic_GBps": nbytes / ms / 1e6, "frac_of_copy_rate": nbytes / ms / 1e6 / copy_gbps,
+                        "avg_pool3d_ms": pool_ms, "speedup_over_avg_pool3d": pool_ms / ms, "agrees_with_avg_pool3d": same})
+        cur = out
+    records.append({"kernel": "lsr_downsample2_f32, levels 1-3", "grid": list(oshape),
+                    "ms": sum(r["ms"] for r in records[1:]), "avg_pool3d_ms": sum(r["avg_pool3d_ms"] for r in records[1:])})
+    stamp = {"sources": _lib.kernel_source_sha16(), "device": torch.cuda.get_device_name(dev), "reps": reps}
+    path = ROOT / "profiles" / "pyramid_config2.jsonl"
+    with open(path, "a") as f:
+        for r in records:
+            line = json.dumps({**r, **stamp})
+            print(line, flush=True)
+            f.write(line + "\n")
 
 
 def _peaks(args, torch, dev, g, oshape):
