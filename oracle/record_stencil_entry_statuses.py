@@ -37,6 +37,7 @@ INTS = [-(1 << 40), -1, 0, 1, 2, 3, 4, 5, 7, 8, 9, 11, 15, 16, 17, 63, 64, 65, 1
         (1 << 30) - 1, 1 << 30, (1 << 31) - 1, 1 << 31, 1 << 32, 1 << 40, (1 << 62)]
 SMALL = [-1, 0, 1, 2, 3, 4, 5, 7, 9, 15, 16, 17, 256, 257, (1 << 31) - 1]
 FLOATS = [0.0, -0.0, 1.0, -1.0, 0.5, 1e-6, 1e30, float("inf"), float("nan")]
+BAD_EXTENTS = [-(1 << 40), -1, 0, 1 << 30, 1 << 31, 1 << 40, 1 << 62]
 
 SLOT = 1 << 16          # bytes between two pointer slots: 16384 floats, more than any tap block or PSF (15^3 floats)
 Z, Y, X = 6, 20, 70     # the baseline volume; its padded shape for 3 x 3 x 3 taps (asserted when the rows are built)
@@ -169,6 +170,24 @@ for _n in ("lsr_rl_sep_fused_prepare_taps", "lsr_rl_ysep_fused_prepare_taps", "l
 CODES["lsr_dense_taps_count"] = {E_UNSUPPORTED}
 
 
+class Tables:
+    """One family of entries: what the caller and the row machinery below read.  ``output``: bytes of the output slot
+    that are hashed, per entry that fills one; ``output_args``: the names an output array goes by; ``baseline``: what
+    the baseline of a pure host function answers where that is not 0."""
+
+    def __init__(self, fixture, entries, breaks, output, host_only, codes, output_args=("shape", "taps_host"), baseline=None):
+        self.fixture, self.entries, self.breaks, self.output, self.host_only, self.codes = (
+            fixture, entries, breaks, output, host_only, codes)
+        self.output_args, self.baseline = output_args, baseline or {}
+
+    def output_at(self, name):
+        """Index of the argument that is the entry's output array."""
+        return next(i for i, (a, _, _) in enumerate(self.entries[name]) if a in self.output_args)
+
+
+STENCIL = Tables(FIXTURE, ENTRIES, BREAKS, OUTPUT, HOST_ONLY, CODES)
+
+
 class Caller:
     """Calls entries of the loaded library with rows of plain values; pointer slot k -> buffer + k * SLOT."""
 
@@ -187,34 +206,35 @@ class Caller:
     def pointer(self, slot):
         return None if slot is None else self.buf.ctypes.data + slot * SLOT
 
-    def call(self, name, kinds, values):
+    def call(self, name, kinds, values, t=STENCIL):
         sig, args = self.sigs[name], []
         assert len(sig) == len(kinds), name
-        for t, kind, v in zip(sig, kinds, values):
+        for ctype, kind, v in zip(sig, kinds, values):
             if kind in "pn":
                 p = self.pointer(v)
-                args.append(p if t is ctypes.c_void_p or p is None else ctypes.cast(p, t))
+                args.append(p if ctype is ctypes.c_void_p or p is None else ctypes.cast(p, ctype))
             elif kind == "f":
                 args.append(ctypes.c_float(v))
             else:
                 args.append(int(v))
-        if name in OUTPUT:
-            ctypes.memset(self.pointer(11), 0xA5, OUTPUT[name])
+        if name in t.output:
+            ctypes.memset(self.pointer(11), 0xA5, t.output[name])
         rc = int(getattr(self.lib, name)(*args))
-        if name not in HOST_ONLY:
+        if name not in t.host_only:
             return rc if rc < 0 else "ok"
-        if name in OUTPUT and values[-1] is not None:
-            return [rc, hashlib.sha256(ctypes.string_at(self.pointer(11), OUTPUT[name])).hexdigest()[:16]]
+        if name in t.output and values[t.output_at(name)] is not None:
+            return [rc, hashlib.sha256(ctypes.string_at(self.pointer(11), t.output[name])).hexdigest()[:16]]
         return rc
 
 
-def rows_of(name):
+def rows_of(name, t=STENCIL):
     """The baseline, then its broken copies: (values, expected status or None)."""
-    spec = ENTRIES[name]
+    spec = t.entries[name]
     names = [a for a, _, _ in spec]
     base = [v for _, _, v in spec]
-    out = [(base, "ok" if name not in HOST_ONLY else 0 if name in OUTPUT else None)]   # (None: a value, recorded as it is)
-    for change, want in BREAKS[name]:
+    # (None: a value, recorded as it is)
+    out = [(base, "ok" if name not in t.host_only else t.baseline.get(name, 0) if name in t.output else None)]
+    for change, want in t.breaks[name]:
         row = list(base)
         for k, v in change.items():
             row[names.index(k)] = v
@@ -222,13 +242,16 @@ def rows_of(name):
     return out
 
 
-def draws_of(name, index):
-    """DRAWS argument lists from the fuzzer's pools (pointers: 5 % NULL, else a slot; the stream always NULL)."""
+def draws_of(name, index, t=STENCIL):
+    """DRAWS argument lists from the fuzzer's pools (pointers: 5 % NULL, else a slot; the stream always NULL).  Kind
+    "s": an extent of a volume that the entry really reads or writes -- 1 to 6, or (10 %) one that validation refuses."""
     rng = np.random.default_rng([SEED, index])
     for _ in range(DRAWS):
         row = []
-        for _, kind, _ in ENTRIES[name]:
-            if kind == "l":
+        for _, kind, _ in t.entries[name]:
+            if kind == "s":
+                row.append(int(rng.choice(BAD_EXTENTS)) if rng.random() < 0.1 else int(rng.integers(1, 7)))
+            elif kind == "l":
                 row.append(int(rng.choice(INTS)) if rng.random() < 0.6 else int(rng.integers(1, 70)))
             elif kind == "i":
                 row.append(int(rng.choice(SMALL)) if rng.random() < 0.6 else int(rng.integers(0, 12)))
@@ -238,38 +261,37 @@ def draws_of(name, index):
                 row.append(None if rng.random() < 0.05 else int(rng.integers(0, 11)))
             else:
                 row.append(None)
-        if ENTRIES[name] and ENTRIES[name][-1][0] in ("shape", "taps_host") and row[-1] is not None:
-            row[-1] = 11    # an output array goes to the output slot
+        if name in t.output and row[t.output_at(name)] is not None:
+            row[t.output_at(name)] = 11    # an output array goes to the output slot
         yield row
 
 
-def measure(caller):
+def measure(caller, t=STENCIL):
     """{entry: {"rows": [status per row of rows_of], "draws": [status per draw]}}"""
     result = {}
-    for index, name in enumerate(ENTRIES):
-        kinds = [k for _, k, _ in ENTRIES[name]]
-        result[name] = {"rows": [caller.call(name, kinds, row) for row, _ in rows_of(name)],
-                        "draws": [caller.call(name, kinds, row) for row in draws_of(name, index)] if kinds else []}
+    for index, name in enumerate(t.entries):
+        kinds = ["l" if k == "s" else k for _, k, _ in t.entries[name]]
+        result[name] = {"rows": [caller.call(name, kinds, row, t) for row, _ in rows_of(name, t)],
+                        "draws": [caller.call(name, kinds, row, t) for row in draws_of(name, index, t)] if kinds else []}
     return result
 
 
-def main():
-    caller = Caller()
-    got = measure(caller)
+def main(t=STENCIL, caller=None):
+    got = measure(caller or Caller(), t)
     for name, rec in got.items():
-        expect = [want for _, want in rows_of(name)]
+        expect = [want for _, want in rows_of(name, t)]
         status = [r[0] if isinstance(r, list) else r for r in rec["rows"]]
         assert all(s == e for s, e in zip(status, expect) if e is not None), \
             (name, [(i, s, e) for i, (s, e) in enumerate(zip(status, expect)) if s != e])
         every = status + [r[0] if isinstance(r, list) else r for r in rec["draws"]]
         assert any(s == "ok" or (isinstance(s, int) and s >= 0) for s in every), name
-        assert CODES[name] <= {s for s in every if isinstance(s, int) and s < 0}, (name, CODES[name])
-        if name not in HOST_ONLY or name in OUTPUT:
-            first_null = sum(1 for row in list(r for r, _ in rows_of(name)) + list(draws_of(name, list(ENTRIES).index(name)))
+        assert t.codes[name] <= {s for s in every if isinstance(s, int) and s < 0}, (name, t.codes[name])
+        if name not in t.host_only or name in t.output:
+            first_null = sum(1 for row in list(r for r, _ in rows_of(name, t)) + list(draws_of(name, list(t.entries).index(name), t))
                              if row[0] is None)
             assert 2 * first_null <= len(every), (name, first_null)
-    FIXTURE.write_text(json.dumps({"seed": SEED, "draws": DRAWS, "entries": got}, separators=(",", ":")) + "\n")
-    print(f"{FIXTURE}: {sum(len(r['rows']) + len(r['draws']) for r in got.values())} calls, {FIXTURE.stat().st_size} bytes")
+    t.fixture.write_text(json.dumps({"seed": SEED, "draws": DRAWS, "entries": got}, separators=(",", ":")) + "\n")
+    print(f"{t.fixture}: {sum(len(r['rows']) + len(r['draws']) for r in got.values())} calls, {t.fixture.stat().st_size} bytes")
 
 
 if __name__ == "__main__":

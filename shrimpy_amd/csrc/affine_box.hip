@@ -32,7 +32,7 @@
 //
 // Algorithmic HBM bytes: 4 * N_src + 4 * N_out.
 
-#include "common.hpp"
+#include "resample.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -64,15 +64,9 @@ struct BoxArgs {
   int probe;                 // diagnostics (-DLSR_BOX_PROBES, env LSR_BOX_PROBE): 1 = no staging, 3 = staging + stores only
 };
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void glds_x4(const float* sbase, unsigned voff, unsigned lds_byte_addr) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-               :
-               : "v"(voff), "s"(sbase), "s"(lds_byte_addr)
-               : "memory");  // (m0 is a RESERVED register to hipcc: naming it as a clobber is refused with a
-                             // warning; the compiler re-loads m0 right before each of its own uses instead)
-}
+using lsr::f32x2u;
+using lsr::f32x4;
+using lsr::glds_x4;
 
 // extremes of one coordinate over the block.  The coordinate expression is monotone in each index
 // (every product and every rounded sum is), so the minimum sits at the corner that takes, per axis,
@@ -258,7 +252,6 @@ __device__ __forceinline__ void compute(const BoxArgs& p, const Blk& b, const fl
   const int row_b = box_x * 4, plane_b = plane_floats * 4;
   const int o_max = (box_z * plane_floats - plane_floats - box_x - 2) * 4;   // clamp for dropped voxels
   const char* const smem_b = reinterpret_cast<const char*>(smem);
-  typedef float f32x2 __attribute__((ext_vector_type(2), aligned(4)));
   // G = 4 voxels at a time (P pixels x U planes): their coordinate chains, LDS reads and
   // interpolations are independent, and nothing in between is conditional, so they overlap
   constexpr int U = P >= 4 ? 1 : 4 / P;
@@ -273,7 +266,7 @@ __device__ __forceinline__ void compute(const BoxArgs& p, const Blk& b, const fl
   }
   for (int dz = 0; dz < nz; dz += U) {
     Tap az[G], ay[G], ax[G];
-    f32x2 v[G][4];
+    f32x2u v[G][4];
     bool inside[G];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -297,15 +290,17 @@ __device__ __forceinline__ void compute(const BoxArgs& p, const Blk& b, const fl
         // voxel (whose result is dropped) inside the LDS image
         int o = (__mul24(az[g].i - zlo, plane_floats) + __mul24(ay[g].i - ylo, box_x) + (ax[g].i - xlo)) * 4;
         o = min(max(o, 0), o_max);
-        v[g][0] = *reinterpret_cast<const f32x2*>(smem_b + o);
-        v[g][1] = *reinterpret_cast<const f32x2*>(smem_b + o + row_b);
-        v[g][2] = *reinterpret_cast<const f32x2*>(smem_b + o + plane_b);
-        v[g][3] = *reinterpret_cast<const f32x2*>(smem_b + o + plane_b + row_b);
+        v[g][0] = *reinterpret_cast<const f32x2u*>(smem_b + o);
+        v[g][1] = *reinterpret_cast<const f32x2u*>(smem_b + o + row_b);
+        v[g][2] = *reinterpret_cast<const f32x2u*>(smem_b + o + plane_b);
+        v[g][3] = *reinterpret_cast<const f32x2u*>(smem_b + o + plane_b + row_b);
       }
     }
     // every LDS read of the group is issued before the first interpolation waits for one
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (GRID) {   // taps outside the volume carry cval (a blind block: all of them, whatever LDS holds)
+      // (the eight selects of affine_planar.hip's plane loop, spelled here too: as one shared function over the four
+      // pairs this kernel needs up to 128 VGPRs and scratch; profiles/resample_isa.txt)
 #pragma unroll
       for (int g = 0; g < G; ++g) {
         const unsigned zf = live ? az[g].out : 3u, yf = ay[g].out, xf = ax[g].out;
@@ -325,18 +320,16 @@ __device__ __forceinline__ void compute(const BoxArgs& p, const Blk& b, const fl
     for (int g = 0; g < G; ++g) {
       float result;
       if constexpr (F32) {
-        const float gx = static_cast<float>(ax[g].f), gy = static_cast<float>(ay[g].f), gz = static_cast<float>(az[g].f);
-        const float a0 = fmaf(gx, v[g][0].y - v[g][0].x, v[g][0].x), a1 = fmaf(gx, v[g][1].y - v[g][1].x, v[g][1].x);
-        const float b0 = fmaf(gx, v[g][2].y - v[g][2].x, v[g][2].x), b1 = fmaf(gx, v[g][3].y - v[g][3].x, v[g][3].x);
-        const float c0 = fmaf(gy, a1 - a0, a0), c1 = fmaf(gy, b1 - b0, b0);
-        result = fmaf(gz, c1 - c0, c0);
+        result = lsr::trilinear_f32(v[g], static_cast<float>(ax[g].f), static_cast<float>(ay[g].f), static_cast<float>(az[g].f));
       } else {
+        // lsr::tap_weights, the three lower weights first: as three calls of it the listing moved in all twelve exact
+        // instances (profiles/resample_isa.txt)
         const double wz0 = 1.0 - az[g].f, wy0 = 1.0 - ay[g].f, wx0 = 1.0 - ax[g].f;
         const double wz1 = 1.0 - wz0, wy1 = 1.0 - wy0, wx1 = 1.0 - wx0;
-        // scipy's corner order and product order: ((v * wz) * wy) * wx, summed in sequence
+        // scipy's corner order (as affine_planar.hip: the eight calls spelled out)
         double t = 0.0;
         auto corner = [&](float val, double wz, double wy, double wx) {
-          t = lsr::dadd(t, lsr::dmul(lsr::dmul(lsr::dmul(static_cast<double>(val), wz), wy), wx));
+          t = lsr::add_corner(t, static_cast<double>(val), wz, wy, wx);
         };
         corner(v[g][0].x, wz0, wy0, wx0);
         corner(v[g][0].y, wz0, wy0, wx1);
@@ -393,7 +386,7 @@ __global__ __launch_bounds__(NT, 4) void affine_box_kernel(BoxArgs p) {
   // workgroups b, b + 8, ... share an XCD (round-robin dispatch); every XCD gets a contiguous run of
   // the patch-major block order
   const int bid = blockIdx.x;
-  const Blk b = locate<TZ, GRID>(p, p.linear ? bid : (bid & 7) * p.per_xcd + (bid >> 3));
+  const Blk b = locate<TZ, GRID>(p, p.linear ? bid : lsr::xcd_run(bid, p.per_xcd));
   if (!b.valid) return;
   if (!b.blind && probe != 1) stage<NT>(p, b, lds_base, tid, wave);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -407,8 +400,7 @@ struct BoxShape {
   int64_t lds_bytes;
 };
 
-// box of a tz x ty x tx block under M: span of floor() over the block + the upper neighbour
-// [+ 3 + 3 in x: 16-byte alignment of the first column, rows rounded up to whole chunks]
+// box of a tz x ty x tx block under M (lsr::box_rows per axis)
 bool box_of(const double M[12], int tz, int ty, int tx, BoxShape* s) {
   auto ab = [](double v) { return v < 0 ? -v : v; };
   const double e[3] = {ab(M[0]) * (tz - 1) + ab(M[1]) * (ty - 1) + ab(M[2]) * (tx - 1),
@@ -416,22 +408,16 @@ bool box_of(const double M[12], int tz, int ty, int tx, BoxShape* s) {
                        ab(M[8]) * (tz - 1) + ab(M[9]) * (ty - 1) + ab(M[10]) * (tx - 1)};
   for (double v : e)
     if (!(v < 2048.0)) return false;
-  // floor(cmax) - floor(cmin) <= floor(e) + 1 (e is summed here in another order than on the
-  // device: 1e-6 absorbs that), + 1 for the upper neighbour, + 1 for the count
   s->tz = tz; s->ty = ty; s->tx = tx;
-  s->bz = static_cast<int>(e[0] + 1e-6) + 3;
-  s->by = static_cast<int>(e[1] + 1e-6) + 3;
-  s->bx = (static_cast<int>(e[2] + 1e-6) + 3 + 3 + 3) & ~3;
-  const int64_t floats = int64_t(s->bz) * s->by * s->bx;
-  s->lds_bytes = ((floats + 255) & ~int64_t(255)) * 4;
+  s->bz = lsr::box_rows(e[0]); s->by = lsr::box_rows(e[1]); s->bx = lsr::box_row_floats(e[2]);
+  s->lds_bytes = lsr::box_slot_floats(int64_t(s->bz) * s->by * s->bx) * 4;
   return true;
 }
 
 // Block shape and box of the box path for this matrix and moving volume; false = not applicable.
 bool pick_shape(int64_t Zi, int64_t Yi, int64_t Xi, int64_t pitch, int64_t plane, const double M[12], BoxShape* best) {
   if (!lsr::volume_in_range(Zi, Yi, Xi) || !lsr::strides_in_range(pitch, plane)) return false;
-  // rows start on 16-byte boundaries (LDS-DMA moves 16-byte chunks) and hold whole chunks up to the last column
-  if (pitch % 4 != 0 || plane % 4 != 0 || pitch < ((Xi + 3) & ~int64_t(3)) || Xi < 8 || Yi < 2 || Zi < 2) return false;
+  if (!lsr::lds_dma_rows_ok(Yi, Xi, pitch) || plane % 4 != 0 || Zi < 2) return false;
   if (plane >= (int64_t(1) << 32)) return false;
   // 4096 voxels, tx >= 32 (stores stay 128-byte runs), tz in {8, 16} (the compiled walks)
   static const int shapes[][3] = {{8, 8, 64}, {16, 8, 32}, {8, 16, 32}, {16, 4, 64}, {8, 4, 128}, {16, 2, 128}};

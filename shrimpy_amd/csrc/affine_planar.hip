@@ -22,7 +22,7 @@
 //
 // Algorithmic HBM bytes: 4 * N_src + 4 * N_out.
 
-#include "common.hpp"
+#include "resample.hpp"
 
 #include <cstdio>
 #include <cstdlib>
@@ -63,15 +63,10 @@ struct PlanarArgs {
 // (see the kernel's block -> tile mapping).
 constexpr int kPatchSize = 64;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using lsr::f32x2u;
+using lsr::f32x4;
+using lsr::glds_x4;
 
-__device__ __forceinline__ void glds_x4(const float* sbase, int voff, unsigned lds_byte_addr) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1"
-               :
-               : "v"(voff), "s"(sbase), "s"(lds_byte_addr)
-               : "memory");  // (m0 is a RESERVED register to hipcc: naming it as a clobber is refused with a
-                             // warning; the compiler re-loads m0 right before each of its own uses instead)
-}
 // One output value = exactly ONE vector-memory operation, whatever the optimiser thinks of its neighbours:
 // the counted wait of the plane loop (`s_waitcnt vmcnt(kPts)`) is only right while every plane issues at
 // least kPts stores behind its DMAs.
@@ -116,7 +111,7 @@ __global__ __launch_bounds__(64 * NW, 4) void affine_planar_kernel(PlanarArgs p)
     // the fp64-issue-bound mode: every XCD gets a contiguous run of the patch-major order (chunk, patch row,
     // patch column | tile in patch); its 64 resident workgroups march over the same planes and the halo rows
     // and columns their windows share are L2 hits (HBM read 4.4 GB for a 4.3 GB source, 5.8 GB before)
-    const int linear = (static_cast<int>(blockIdx.x) & 7) * p.per_xcd + (static_cast<int>(blockIdx.x) >> 3);
+    const int linear = lsr::xcd_run(static_cast<int>(blockIdx.x), p.per_xcd);
     const int inner = linear & (kPatchSize - 1);
     int patch = linear / kPatchSize;
     const int px = patch % p.px_n;
@@ -143,7 +138,7 @@ __global__ __launch_bounds__(64 * NW, 4) void affine_planar_kernel(PlanarArgs p)
   const int ylo = static_cast<int>(fmin(fmax(floor(cy_min), kLow), static_cast<double>(p.Yi - 1)));
   const int xlo = static_cast<int>(fmin(fmax(floor(cx_min), kLow), static_cast<double>(p.Xi - 1))) & ~3;   // (-1 -> -4)
   const int box_x = p.box_x, box_y = p.box_y;
-  const int slot_floats = (box_y * box_x + 255) & ~255;  // whole waves of 16-byte chunks
+  const int slot_floats = lsr::box_slot_floats(box_y * box_x);
 
   // ---- per-pixel in-plane taps, once ------------------------------------------------------
   // The upper neighbour of a tap is always read one element / one row further on, also when it lies
@@ -164,8 +159,8 @@ __global__ __launch_bounds__(64 * NW, 4) void affine_planar_kernel(PlanarArgs p)
                         !(cx < 0.0) && !(cx > static_cast<double>(p.Xi - 1));
     const double fy = floor(cy), fx = floor(cx);
     const double ry = cy - fy, rx = cx - fx;
-    wy0[i] = 1.0 - ry; wy1[i] = 1.0 - wy0[i];
-    wx0[i] = 1.0 - rx; wx1[i] = 1.0 - wx0[i];
+    lsr::tap_weights(ry, wy0[i], wy1[i]);
+    lsr::tap_weights(rx, wx0[i], wx1[i]);
     int iy0 = 0, ix0 = 0;
     outside[i] = 0;
     if constexpr (GRID) {
@@ -240,12 +235,12 @@ __global__ __launch_bounds__(64 * NW, 4) void affine_planar_kernel(PlanarArgs p)
   // `zout` bit 0 / 1 = the lower / upper source plane lies outside the volume (z0 / z1 are then clamped
   // stand-ins whose values are replaced by cval)
   auto z_taps = [&](int zo, int& z0, int& z1, double& wz0, double& wz1, unsigned& zout) {
+    // (lsr::axis_tap<GRID, int> with the flags packed: as a call of it the listing moved in all 32 instances)
     zout = 0;
     const double cz = lsr::dadd(lsr::dmul(static_cast<double>(zo), p.a), p.tz);
     if (!GRID && (cz < 0.0 || cz > static_cast<double>(p.Zi - 1))) return false;
     const double fz = floor(cz), rz = cz - fz;
-    wz0 = 1.0 - rz;
-    wz1 = 1.0 - wz0;
+    lsr::tap_weights(rz, wz0, wz1);
     if constexpr (GRID) {
       const int sz = static_cast<int>(fmin(fmax(fz, -2.0), static_cast<double>(p.Zi) + 1.0));
       zout = (sz < 0 || sz >= p.Zi ? 1u : 0u) | (sz + 1 < 0 || sz + 1 >= p.Zi ? 2u : 0u);
@@ -306,7 +301,6 @@ __global__ __launch_bounds__(64 * NW, 4) void affine_planar_kernel(PlanarArgs p)
     float* orow = p.out + static_cast<int64_t>(zo) * p.oplane + static_cast<int64_t>(y0) * p.opitch + x0;
     const char* s0 = reinterpret_cast<const char*>(smem + slot_of(z0) * slot_floats);
     const char* s1 = reinterpret_cast<const char*>(smem + slot_of(z1) * slot_floats);
-    typedef float f32x2 __attribute__((ext_vector_type(2), aligned(4)));
     const int row_b = box_x * 4;
     // G pixels at a time: all their LDS reads first, then the arithmetic -- nothing in between is
     // conditional, so the pixels overlap (an `if (inside)` per pixel made hipcc run them one by one,
@@ -315,17 +309,19 @@ __global__ __launch_bounds__(64 * NW, 4) void affine_planar_kernel(PlanarArgs p)
     static_assert(kPts % G == 0, "pixels per thread come in whole groups");
 #pragma unroll
     for (int h = 0; h < kPts; h += G) {
-      f32x2 v[G][4];
+      f32x2u v[G][4];
 #pragma unroll
       for (int k = 0; k < G; ++k) {
         const int o = idx00[h + k];
-        v[k][0] = *reinterpret_cast<const f32x2*>(s0 + o);
-        v[k][1] = *reinterpret_cast<const f32x2*>(s0 + o + row_b);
-        v[k][2] = *reinterpret_cast<const f32x2*>(s1 + o);
-        v[k][3] = *reinterpret_cast<const f32x2*>(s1 + o + row_b);
+        v[k][0] = *reinterpret_cast<const f32x2u*>(s0 + o);
+        v[k][1] = *reinterpret_cast<const f32x2u*>(s0 + o + row_b);
+        v[k][2] = *reinterpret_cast<const f32x2u*>(s1 + o);
+        v[k][3] = *reinterpret_cast<const f32x2u*>(s1 + o + row_b);
       }
       __builtin_amdgcn_sched_barrier(0);
       if constexpr (GRID) {   // taps outside the volume carry cval (flags: in-plane per pixel, z per plane)
+        // (the eight selects of affine_box.hip's compute(), spelled here too: as one shared function over the four pairs
+        // hipcc commutes operands here and needs up to 128 VGPRs and scratch there; profiles/resample_isa.txt)
 #pragma unroll
         for (int k = 0; k < G; ++k) {
           const unsigned f = outside[h + k];
@@ -346,17 +342,13 @@ __global__ __launch_bounds__(64 * NW, 4) void affine_planar_kernel(PlanarArgs p)
         const int i = h + k;
         float result;
         if constexpr (F32) {
-          const float fx = static_cast<float>(wx1[i]), fy = static_cast<float>(wy1[i]),
-                      fz = static_cast<float>(wz1);
-          const float a0 = fmaf(fx, v[k][0].y - v[k][0].x, v[k][0].x), a1 = fmaf(fx, v[k][1].y - v[k][1].x, v[k][1].x);
-          const float b0 = fmaf(fx, v[k][2].y - v[k][2].x, v[k][2].x), b1 = fmaf(fx, v[k][3].y - v[k][3].x, v[k][3].x);
-          const float c0 = fmaf(fy, a1 - a0, a0), c1 = fmaf(fy, b1 - b0, b0);
-          result = fmaf(fz, c1 - c0, c0);
+          result = lsr::trilinear_f32(v[k], static_cast<float>(wx1[i]), static_cast<float>(wy1[i]), static_cast<float>(wz1));
         } else {
-          // scipy's corner order and product order: ((v * wz) * wy) * wx, summed in sequence
+          // scipy's corner order: the eight calls stay spelled out in both LDS-staged kernels (as one function over the
+          // four pairs, hipcc commuted fp64 operands in the grid-constant instances; profiles/resample_isa.txt)
           double t = 0.0;
           auto corner = [&](float val, double wz, double wy, double wx) {
-            t = lsr::dadd(t, lsr::dmul(lsr::dmul(lsr::dmul(static_cast<double>(val), wz), wy), wx));
+            t = lsr::add_corner(t, static_cast<double>(val), wz, wy, wx);
           };
           corner(v[k][0].x, wz0, wy0[i], wx0[i]);
           corner(v[k][0].y, wz0, wy0[i], wx1[i]);
@@ -395,21 +387,17 @@ bool affine_planar_geometry(int64_t Yi, int64_t Xi, int64_t pitch, const double 
   if (!volume_in_range(1, Yi, Xi) || !strides_in_range(pitch, 0)) return false;
   if (M[1] != 0.0 || M[2] != 0.0 || M[4] != 0.0 || M[8] != 0.0) return false;
   const double a = M[0] < 0 ? -M[0] : M[0];
-  // rows start on 16-byte boundaries (LDS-DMA moves 16-byte chunks) and hold whole chunks up to the last column
-  if (a > 1.5 || pitch % 4 != 0 || pitch < ((Xi + 3) & ~int64_t(3)) || Xi < 8 || Yi < 2) return false;
+  if (a > 1.5 || !lds_dma_rows_ok(Yi, Xi, pitch)) return false;
   auto ab = [](double v) { return v < 0 ? -v : v; };
   if (Yi * pitch * 4 >= (int64_t(1) << 31)) return false;  // 32-bit in-plane byte offsets
   const int slots = a <= 1.0 ? 3 : 4;
-  // the largest tile whose ring fits.  Source box of a tile: span of floor() over the tile (<= floor(extent) + 2; the
-  // 1e-6 absorbs the different summation order on the device) + 1 for the upper neighbour [+ 3 + 3: 16-byte alignment
-  // of the first column, rows rounded up to whole chunks]
+  // the largest tile whose ring fits
   for (int t = 0; t < static_cast<int>(sizeof(kTiles) / sizeof(kTiles[0])); ++t) {
     const int ty = waves * kTiles[t].nr, tx = 64 * kTiles[t].nc;
     const double ey = ab(M[5]) * (ty - 1) + ab(M[6]) * (tx - 1), ex = ab(M[9]) * (ty - 1) + ab(M[10]) * (tx - 1);
     if (!(ey < 4096.0) || !(ex < 4096.0)) continue;
-    const int box_y = static_cast<int>(ey + 1e-6) + 3;
-    const int box_x = (static_cast<int>(ex + 1e-6) + 3 + 3 + 3) & ~3;
-    const int64_t lds_bytes = int64_t(slots) * ((int64_t(box_y) * box_x + 255) & ~int64_t(255)) * 4;
+    const int box_y = box_rows(ey), box_x = box_row_floats(ex);
+    const int64_t lds_bytes = int64_t(slots) * box_slot_floats(int64_t(box_y) * box_x) * 4;
     if (lds_bytes > 150 * 1024 || int64_t(box_y) * (box_x / 4) > 8 * 64 * waves) continue;
     *box_y_out = box_y; *box_x_out = box_x; *slots_out = slots; *lds_bytes_out = lds_bytes;
     if (tile_out != nullptr) *tile_out = t;

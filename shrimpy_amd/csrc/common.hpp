@@ -96,23 +96,3 @@ inline bool strides_in_range(int64_t pitch, int64_t plane) {
   LSR_REQUIRE(lsr::strides_in_range((pitch), (plane)), LSR_E_UNSUPPORTED,                                      \
               "strides (%lld, %lld): a row stride must be in [0, 2^31), a plane stride in [0, 2^32) elements", \
               (long long)(pitch), (long long)(plane))
-
-// ---- device-side exact fp64 helpers (no FMA contraction: results must match scipy's C) ----
-#if defined(__HIPCC__)
-namespace lsr {
-
-__device__ __forceinline__ double dmul(double a, double b) { return __dmul_rn(a, b); }
-__device__ __forceinline__ double dadd(double a, double b) { return __dadd_rn(a, b); }
-
-// Coordinate of one input axis for output index (zo, yo, xo), evaluated in scipy's order:
-// ((zo*m0 + yo*m1) + xo*m2) + shift, every product and sum rounded separately.
-__device__ __forceinline__ double affine_coord(double zo, double yo, double xo, double m0,
-                                               double m1, double m2, double shift) {
-  double c = dmul(zo, m0);
-  c = dadd(c, dmul(yo, m1));
-  c = dadd(c, dmul(xo, m2));
-  return dadd(c, shift);
-}
-
-}  // namespace lsr
-#endif

@@ -15,9 +15,9 @@
 //
 // HBM traffic per launch: 4*N_in (each raw voxel read ~once; neighbouring X' tiles share
 // 1-2 slab rows) + 4*N_out.  fp64 work is ~10 DP ops per pre-average voxel, far below the
-// HBM time, so the arithmetic follows scipy.ndimage exactly (see common.hpp).
+// HBM time, so the arithmetic follows scipy.ndimage exactly (see resample.hpp).
 
-#include "common.hpp"
+#include "resample.hpp"
 
 #include <cstdlib>
 #include <type_traits>
@@ -164,9 +164,8 @@ __global__ __launch_bounds__(kThreads) void deskew_kernel(DeskewArgs p) {
                     (p.grid ? (z_in > -1.0 && z_in < zmax_d + 1.0) : (!(z_in < 0.0) && !(z_in > zmax_d)));
     if (ok) {
       const double zf = floor(z_in);
-      const double f = z_in - zf;
-      const double w0 = 1.0 - f;
-      const double w1 = 1.0 - w0;
+      double w0, w1;
+      lsr::tap_weights(z_in - zf, w0, w1);
       const int64_t z0 = static_cast<int64_t>(zf);              // -1 .. Z-1
       const int r0 = static_cast<int>(max(z0, static_cast<int64_t>(0)) - z_lo);
       const int r1 = static_cast<int>(min(z0 + 1, p.Z - 1) - z_lo);
@@ -250,8 +249,7 @@ int deskew_impl(const char* what, const void* in, bool u16, int64_t Z, int64_t Y
   LSR_REQUIRE(out_pitch >= Xo && out_plane >= Yo * out_pitch, LSR_E_SHAPE,
               "output strides (%lld, %lld) are smaller than the output plane (%lld x %lld)",
               (long long)out_pitch, (long long)out_plane, (long long)Yo, (long long)Xo);
-  for (int i = 0; i < 12; ++i)
-    LSR_REQUIRE(M[i] == M[i] && M[i] - M[i] == 0.0, LSR_E_ARG, "M[%d] is not finite", i);
+  if (int rc = lsr::check_matrix(M)) return rc;
 
   // deskew structure: only z_in is fractional
   const bool structured = M[1] == 0.0 && (M[4] == 1.0 || M[4] == -1.0) && M[5] == 0.0 &&

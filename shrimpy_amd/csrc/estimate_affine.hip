@@ -19,7 +19,7 @@
 // results do not depend on scheduling.  The taps are plain global gathers: this runs a few dozen
 // times per registration on subsampled grids, not once per volume.
 
-#include "common.hpp"
+#include "resample.hpp"
 
 namespace {
 
@@ -151,7 +151,7 @@ extern "C" int lsr_affine_normal_equations_f32(const float* moving, int64_t Zi, 
   LSR_REQUIRE(stride[0] >= 1 && stride[1] >= 1 && stride[2] >= 1, LSR_E_ARG, "strides must be >= 1, got (%d,%d,%d)",
               stride[0], stride[1], stride[2]);
   LSR_REQUIRE(scale > 0.0, LSR_E_ARG, "scale must be positive");
-  for (int i = 0; i < 12; ++i) LSR_REQUIRE(M[i] == M[i] && M[i] - M[i] == 0.0, LSR_E_ARG, "M[%d] is not finite", i);
+  if (int rc = lsr::check_matrix(M)) return rc;
   NormalArgs p;
   p.moving = moving; p.target = target;
   p.Zi = static_cast<int>(Zi); p.Yi = static_cast<int>(Yi); p.Xi = static_cast<int>(Xi);

@@ -14,11 +14,15 @@
 //   lsr_flatfield_pattern_f32_cpu / _u16_cpu  <->  lsr_flatfield_pattern_f32 / _u16    (flatfield.hip)
 //   lsr_flatfield_apply_f32_cpu / _u16_cpu    <->  lsr_flatfield_apply_f32 / _u16      (flatfield.hip)
 //   lsr_rl_accel_dots_f32_cpu / _predict_f32_cpu  <->  lsr_rl_accel_dots_f32 / _predict_f32  (rl_accel.hip)
+//   lsr_box_smooth_f32_cpu, lsr_local_max_candidates_f32_cpu, lsr_psf_accumulate_f32_cpu
+//                                             <->  the same names without _cpu         (peaks.hip)
+//   lsr_band_power_f32_cpu                    <->  lsr_band_power_f32                  (focus.hip)
+//   lsr_downsample2_f32_cpu / _u16_cpu        <->  lsr_downsample2_f32 / _u16          (pyramid.hip)
 //
 // Arithmetic (what "the same" means):
-//   resamplers -- coordinates ((zo*m0 + yo*m1) + xo*m2) + shift, weights w0 = 1 - f, w1 = 1 - w0 and the
-//     8-corner sum ((v*wz)*wy)*wx accumulated z-major in fp64, every operation rounded on its own (the TU is
-//     built with -ffp-contract=off), the result rounded to f32 once: scipy.ndimage.affine_transform(order=1);
+//   resamplers -- the text the kernels compile (resample.hpp): coordinates, axis taps with their weights and the
+//     8-corner sum accumulated z-major in fp64, every operation rounded on its own (the TU is built with
+//     -ffp-contract=off), the result rounded to f32 once: scipy.ndimage.affine_transform(order=1);
 //   averaging  -- ((d0 + d1) + ...) / n in f32, the last group edge-padded;
 //   stencils   -- f32 FMA chains in tap order (separable: x, then y, then z; dense: z-major), zeros outside the
 //     volume, the Richardson-Lucy epilogues of correlate.hip.
@@ -38,9 +42,9 @@
 #include <thread>
 #include <vector>
 
-#include "common.hpp"
 #include "correlate_common.hpp"
 #include "host_parallel.hpp"
+#include "resample.hpp"
 #include "rl_accel.hpp"
 
 namespace {
@@ -67,39 +71,11 @@ inline void row_fma(float* __restrict__ acc, float w, const float* __restrict__ 
   for (int64_t x = hi; x < X; ++x) acc[x] = std::fmaf(w, 0.0f, acc[x]);
 }
 
-struct AxisTap {
-  int64_t i0, i1;
-  double w0, w1;
-  bool out0, out1;
-};
-
-template <bool GRID>
-inline bool axis_tap(double c, int64_t n, AxisTap& t) {
-  if (!GRID && (c < 0.0 || c > static_cast<double>(n - 1))) return false;
-  const double fl = std::floor(c);
-  const double f = c - fl;
-  t.w0 = 1.0 - f;
-  t.w1 = 1.0 - t.w0;
-  if (!GRID) {
-    t.i0 = static_cast<int64_t>(fl);
-    t.i1 = t.i0 + 1 < n ? t.i0 + 1 : n - 1;
-    t.out0 = t.out1 = false;
-  } else {
-    const double lo = fl < -2.0 ? -2.0 : fl;
-    const int64_t start = static_cast<int64_t>(lo > static_cast<double>(n) + 1.0 ? static_cast<double>(n) + 1.0 : lo);
-    t.out0 = start < 0 || start >= n;
-    t.out1 = start + 1 < 0 || start + 1 >= n;
-    t.i0 = start < 0 ? 0 : (start > n - 1 ? n - 1 : start);
-    t.i1 = start + 1 < 0 ? 0 : (start + 1 > n - 1 ? n - 1 : start + 1);
-  }
-  return true;
-}
+using AxisTap = lsr::AxisTap<int64_t>;
+using lsr::axis_tap;
 
 inline double coord(double zo, double yo, double xo, const double* row) {
-  double c = zo * row[0];
-  c = c + yo * row[1];
-  c = c + xo * row[2];
-  return c + row[3];
+  return lsr::affine_coord(zo, yo, xo, row[0], row[1], row[2], row[3]);
 }
 
 template <typename T, bool GRID>
@@ -122,10 +98,7 @@ inline float sample(const T* in, int64_t Z, int64_t Y, int64_t X, const double M
       for (int c = 0; c < 2; ++c) {
         double v = static_cast<double>(in[oy + (c ? tx.i1 : tx.i0)]);
         if (GRID && (bz || by || (c ? tx.out1 : tx.out0))) v = cv;
-        v = v * wz;
-        v = v * wy;
-        v = v * (c ? tx.w1 : tx.w0);
-        t = t + v;
+        t = lsr::add_corner(t, v, wz, wy, c ? tx.w1 : tx.w0);
       }
     }
   }
@@ -134,18 +107,12 @@ inline float sample(const T* in, int64_t Z, int64_t Y, int64_t X, const double M
 
 bool is_integer(double v) { return v == static_cast<double>(static_cast<int64_t>(v)); }
 
-int check_matrix(const double M[12]) {
-  LSR_REQUIRE_PTR(M);
-  for (int i = 0; i < 12; ++i) LSR_REQUIRE(M[i] == M[i] && M[i] - M[i] == 0.0, LSR_E_ARG, "M[%d] is not finite", i);
-  return LSR_OK;
-}
-
 template <typename T>
 int deskew_cpu(const T* in, int64_t Z, int64_t Y, int64_t X, float* out, int64_t Zo, int64_t Yo, int64_t Xo,
                int64_t out_pitch, int64_t out_plane, int64_t Zd, const double M[12], int avg_n, float cval = 0.0f) {
   LSR_REQUIRE_PTR(in);
   LSR_REQUIRE_PTR(out);
-  if (int rc = check_matrix(M)) return rc;
+  if (int rc = lsr::check_matrix(M)) return rc;
   LSR_REQUIRE(Z > 0 && Y > 0 && X > 0, LSR_E_SHAPE, "raw shape (%lld,%lld,%lld) must be positive", (long long)Z, (long long)Y,
               (long long)X);
   LSR_REQUIRE_VOLUME(Z, Y, X);
@@ -308,16 +275,12 @@ extern "C" int lsr_deskew_u16_cpu(const uint16_t* in, int64_t Z, int64_t Y, int6
 extern "C" int lsr_affine_f32_cpu(const float* in, int64_t Zi, int64_t Yi, int64_t Xi, float* out, int64_t Zo, int64_t Yo,
                                   int64_t Xo, const double M[12], float cval, int mode, lsr_stream_t) {
   LSR_REQUIRE_HOST_FMA();
-  LSR_REQUIRE_PTR(in);
-  LSR_REQUIRE_PTR(out);
-  if (int rc = check_matrix(M)) return rc;
-  LSR_REQUIRE(Zi > 0 && Yi > 0 && Xi > 0 && Zo > 0 && Yo > 0 && Xo > 0, LSR_E_SHAPE, "shapes must be positive");
-  LSR_REQUIRE_VOLUME(Zi, Yi, Xi);
-  LSR_REQUIRE_VOLUME(Zo, Yo, Xo);
-  LSR_REQUIRE(mode == LSR_MODE_CONSTANT || mode == LSR_MODE_GRID_CONSTANT, LSR_E_ARG,
-              "mode %d: LSR_MODE_CONSTANT or LSR_MODE_GRID_CONSTANT (the f32-interpolation flag has no host twin: "
-              "the host arithmetic is always scipy's fp64)", mode);
-  const bool grid = mode == LSR_MODE_GRID_CONSTANT;
+  int rc;
+  bool grid;
+  if ((rc = lsr::require_buffers(in, out, M)) || (rc = lsr::check_matrix(M)) ||
+      (rc = lsr::require_positive(Zi, Yi, Xi, Zo, Yo, Xo)) || (rc = lsr::require_volumes(Zi, Yi, Xi, Zo, Yo, Xo)) ||
+      (rc = lsr::require_border(mode, &grid)))
+    return rc;
   parallel_ranges(Zo, [&](int64_t z_first, int64_t z_last) {
     for (int64_t zo = z_first; zo < z_last; ++zo)
       for (int64_t yo = 0; yo < Yo; ++yo) {

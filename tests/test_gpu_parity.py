@@ -313,7 +313,7 @@ def _planar_matrix(theta_deg, scale_zyx, shift_zyx, shear=0.0):
     return m
 
 
-@pytest.mark.parametrize("case", [
+PLANAR_CASES = [
     dict(shape=(20, 96, 132), theta=2.0, scale=(1.0, 0.98, 1.02), shift=(3.5, -12.25, 20.75)),
     dict(shape=(9, 40, 72), out=(12, 40, 64), theta=-7.0, scale=(1.0, 1.0, 1.0), shift=(0.0, 3.0, -2.0)),
     dict(shape=(17, 70, 260), theta=0.0, scale=(-1.0, 1.0, 1.0), shift=(16.0, 0.0, 0.0)),        # z flip, identity plane
@@ -327,12 +327,10 @@ def _planar_matrix(theta_deg, scale_zyx, shift_zyx, shear=0.0):
     dict(shape=(6, 200, 520), out=(6, 100, 260), theta=0.0, scale=(1.0, 2.0, 2.0), shift=(0.0, 0.25, 0.5)),
     dict(shape=(5, 260, 532), out=(7, 70, 200), theta=3.0, scale=(0.9, 3.0, 2.5), shift=(0.5, 4.0, 3.0), shear=0.03),
     dict(shape=(4, 300, 700), out=(4, 61, 129), theta=-2.0, scale=(1.0, 4.5, 5.0), shift=(0.0, 2.0, 1.0)),
-])
-@pytest.mark.parametrize("exact", [True, False])
-@pytest.mark.parametrize("mode", ["constant", "grid-constant"])
-def test_affine_planar_kernel_vs_oracle(device, case, exact, mode):
-    """z-decoupled maps run affine_planar.hip (LDS-staged source boxes, z march) under either border rule:
-    bit-identical to scipy in exact mode, ~1e-6 with f32 interpolation, same border decisions."""
+]
+
+
+def _check_planar_case(device, case, exact, mode):
     from shrimpy_amd import _lib
     from shrimpy_amd.geometry import as_matrix_3x4
     from shrimpy_amd.register import apply_affine_transform_zyx
@@ -355,6 +353,72 @@ def test_affine_planar_kernel_vs_oracle(device, case, exact, mode):
         assert np.array_equal(out == -3.0, ref == -3.0)
         np.testing.assert_allclose(out, ref, rtol=2e-5, atol=2e-3)
     else:   # blended borders: no exact cval pattern to compare, the values carry the decision
+        np.testing.assert_allclose(out, ref, rtol=2e-5, atol=2e-3)
+
+
+@pytest.mark.parametrize("case", PLANAR_CASES)
+@pytest.mark.parametrize("exact", [True, False])
+@pytest.mark.parametrize("mode", ["constant", "grid-constant"])
+def test_affine_planar_kernel_vs_oracle(device, case, exact, mode):
+    """z-decoupled maps run affine_planar.hip (LDS-staged source boxes, z march) under either border rule:
+    bit-identical to scipy in exact mode, ~1e-6 with f32 interpolation, same border decisions."""
+    _check_planar_case(device, case, exact, mode)
+
+
+@pytest.mark.parametrize("case", PLANAR_CASES)
+@pytest.mark.parametrize("exact", [True, False])
+@pytest.mark.parametrize("mode", ["constant", "grid-constant"])
+def test_affine_planar_four_wave_instances_vs_oracle(device, case, exact, mode, monkeypatch):
+    """The same cases on the half-height tiles of four waves (sixteen of the 32 planar instances): the launcher picks
+    them on its own only from 256 tiles of a rotating map on, LSR_PLANAR_WAVES=4 (read per launch) asks for them."""
+    monkeypatch.setenv("LSR_PLANAR_WAVES", "4")
+    _check_planar_case(device, case, exact, mode)
+
+
+_ROTATED_12 = {}
+
+
+def _rotated_12_degrees(mode):
+    """A (3, 512, 2048) volume rotated 12 degrees in the plane about its centre, and scipy's answer (once per mode)."""
+    if mode not in _ROTATED_12:
+        shape = (3, 512, 2048)
+        m = _planar_matrix(12.0, (1.0, 1.0, 1.0), (0.0, 0.0, 0.0))
+        centre = np.array([1.0, 255.5, 1023.5])
+        m[:3, 3] = centre - m[:3, :3] @ centre
+        vol = (np.random.default_rng(12).random(shape) * 1000 - 100).astype(np.float32)
+        _ROTATED_12[mode] = (vol, m, o.affine_apply_4x4(vol, m, shape, cval=-3.0, mode=mode))
+    return _ROTATED_12[mode]
+
+
+@pytest.mark.parametrize("exact", [True, False])
+@pytest.mark.parametrize("mode", ["constant", "grid-constant"])
+def test_affine_planar_takes_four_waves_on_its_own_for_a_rotation(device, exact, mode):
+    """16 x 16 tiles of 32 x 128, a source box of 59 x 136 floats (more than 1.6 x the tile) and |sin| = 0.21 > 0.1: the
+    launcher's own rule sends this map to the four-wave instances.  Same bars as the other planar cases."""
+    from shrimpy_amd import _lib
+    from shrimpy_amd.geometry import as_matrix_3x4
+    from shrimpy_amd.register import apply_affine_transform_zyx
+
+    vol, m, ref = _rotated_12_degrees(mode)
+    code = _lib.MODE_CONSTANT if mode == "constant" else _lib.MODE_GRID_CONSTANT
+    assert _lib.call_value("lsr_affine_kernel_choice", vol.shape[1], vol.shape[2], _lib.matrix12(as_matrix_3x4(m)), code) == 1
+    # the launcher's three conditions, from the sizing rule of csrc/resample.hpp (box_rows, box_row_floats): the source
+    # box of a 32 x 128 tile against 1.6 tiles, the tile count, the rotation; and the 16 x 128 tile's ring of 3 fits
+    def box(ty, tx):
+        ey = abs(m[1, 1]) * (ty - 1) + abs(m[1, 2]) * (tx - 1)
+        ex = abs(m[2, 1]) * (ty - 1) + abs(m[2, 2]) * (tx - 1)
+        return int(ey + 1e-6) + 3, (int(ex + 1e-6) + 3 + 3 + 3) & ~3
+
+    assert box(32, 128) == (59, 136) and 59 * 136 * 10 > 32 * 128 * 16
+    assert abs(m[1, 2]) > 0.1 and math.ceil(vol.shape[1] / 32) * math.ceil(vol.shape[2] / 128) >= 256
+    by4, bx4 = box(16, 128)
+    assert 3 * ((by4 * bx4 + 255) & ~255) * 4 <= 150 * 1024 and by4 * (bx4 // 4) <= 8 * 64 * 4
+    out = apply_affine_transform_zyx(_t(vol, device), m, vol.shape, cval=-3.0, exact=exact, mode=mode).cpu().numpy()
+    if exact:
+        np.testing.assert_array_equal(out, ref)
+    else:
+        if mode == "constant":
+            assert np.array_equal(out == -3.0, ref == -3.0)
         np.testing.assert_allclose(out, ref, rtol=2e-5, atol=2e-3)
 
 
@@ -403,7 +467,28 @@ BOX_CASES = [
     dict(shape=(8, 24, 64), m=_tilted_matrix([(1, 3.0)], shift=(0.0, 0.0, 5000.0))),
     # one plane / one row outputs
     dict(shape=(9, 17, 32), out=(1, 1, 130), m=_tilted_matrix([(1, 3.0), (2, 2.0)], (1.0, 1.0, 0.24), (3.0, 5.0, 0.0))),
+    # a tilt about X (x_in free of zo) of a volume upsampled 2x along z: blocks of 16 planes
+    dict(shape=(12, 40, 64), m=_tilted_matrix([(2, 3.0)], (0.5, 1.0, 1.0))),
+    # a tilt about Y (y_in free of zo) of a volume downsampled 2x along z: blocks of 8 planes
+    dict(shape=(30, 40, 64), m=_tilted_matrix([(1, 3.0)], (2.0, 1.0, 1.0))),
 ]
+
+
+def test_box_cases_reach_every_compiled_walk():
+    """affine_box.hip compiles blocks of 8 or 16 planes times three walks (DEP 3, 5, 7: which source coordinates depend
+    on zo, as launch_shape decides) times exact / f32 times the two border rules; BOX_CASES holds all six (tz, DEP), the
+    parametrisation of the test below does the rest."""
+    from shrimpy_amd import _lib
+    from shrimpy_amd.geometry import as_matrix_3x4
+
+    seen = set()
+    for case in BOX_CASES:
+        m12 = np.asarray(as_matrix_3x4(case["m"]), dtype=np.float64).ravel()
+        out6 = (ctypes.c_int * 6)()
+        assert _lib.load().lsr_affine_box_shape(*case["shape"], _lib.matrix12(as_matrix_3x4(case["m"])), out6) == 1
+        dz, dy, dx = m12[0] != 0.0, m12[4] != 0.0, m12[8] != 0.0
+        seen.add((out6[0], 5 if dz and not dy and dx else 3 if dz and dy and not dx else 7))
+    assert seen == {(tz, dep) for tz in (8, 16) for dep in (3, 5, 7)}
 
 
 @pytest.mark.parametrize("case", BOX_CASES)
