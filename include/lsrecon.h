@@ -818,6 +818,37 @@ int lsr_downsample2_f32(const float* in, int64_t Z, int64_t Y, int64_t X, float*
 int lsr_downsample2_u16(const uint16_t* in, int64_t Z, int64_t Y, int64_t X, uint16_t* out, int fz, lsr_stream_t stream);
 
 /*
+ * Stitching (csrc/stitch.hip, shrimpy_amd/stitch.py): K overlapping tiles composed into one box of their common canvas --
+ * biahub's stitch is not vendored, PARITY UNPINNED, the rule is defined in csrc/stitch.hpp (tests/stitch_ref.py restates
+ * it in float64).  Tile k is a dense float32 (Zk, Yk, Xk) with a float64 translation t_k (z, y, x) in canvas voxels: tile
+ * voxel i sits at canvas coordinate i + t_k.  lsr_stitch_canvas (host only): origin = floor(min_k t_k),
+ * shape = ceil(max_k (t_k + n_k)) - origin.
+ *   Per tile and axis: ti = floor(t), tf = t - ti (float64, host); j = c - ti for the absolute canvas index c.  tf == 0:
+ *   one tap i = j, covered iff 0 <= j <= n - 1; otherwise the taps j - 1 and j with the float32 weights float32(tf) and
+ *   float32(1 - tf), covered iff 1 <= j <= n - 1.  A tile covers a voxel iff all three axes are covered; nothing is
+ *   interpolated against cval.  The sample s_k interpolates over the fractional axes only (x, then y, then z; two products
+ *   and one sum per axis, unfused); the weight is w_k = (dy dx)^p, p in 0 .. 4 by repeated multiplication,
+ *   d = min(float(j) + float32(1 - tf), float(n - j) + float32(tf)): the distance to the nearer tile edge counted from 1.
+ *   out = cval where no tile covers the voxel, s_k itself where exactly one does (an integer placement copies bits),
+ *   (sum w_k s_k) / (sum w_k) in float32 in ascending tile index otherwise.
+ * The tile table is lsr_stitch_table_bytes(n_tiles) bytes (0 for a count outside 1 .. lsr_stitch_max_tiles()), filled on
+ * the HOST by lsr_stitch_prepare_table from the tiles' addresses (device addresses for lsr_stitch_f32), their shapes
+ * (n_tiles x 3, int64) and translations (n_tiles x 3, float64) -- a NULL tile is LSR_E_NULL, a non-positive extent
+ * LSR_E_SHAPE, a count over the cap or a y / x extent over 2^24 LSR_E_UNSUPPORTED, a translation that is not finite or reaches 2^30 LSR_E_ARG -- and
+ * then copied to device memory by the caller.  lsr_stitch_f32 writes `out`, a dense box of the canvas given by its origin
+ * and shape in absolute canvas coordinates (|origin| < 2^31); tiles outside the box contribute nothing, so a canvas can be
+ * composed box by box with the same bits.  One launch for a box of any size, every voxel of the box written once, nothing
+ * else written; no scratch, no LDS, no atomics.  `out` must not overlap a tile.
+ */
+int lsr_stitch_max_tiles(void);
+int lsr_stitch_table_bytes(int n_tiles);
+int lsr_stitch_canvas(const int64_t* shapes, const double* translations, int n_tiles, int64_t origin[3], int64_t shape[3]);
+int lsr_stitch_prepare_table(const float* const* tiles, const int64_t* shapes, const double* translations, int n_tiles,
+                             void* table);
+int lsr_stitch_f32(const void* table, int n_tiles, float* out, const int64_t box_origin[3], const int64_t box_shape[3],
+                   int p, float cval, lsr_stream_t stream);
+
+/*
  * Host twins (csrc/host_twins.hip): the same signatures with HOST pointers, the same argument checks and the
  * same arithmetic in the same order, so the results equal the device entry points' bit for bit.  They serve
  * the boxes where the reference itself resolves to the CPU (shrimpy/preprocessing.py:78-82 -- its CI has no
@@ -918,6 +949,10 @@ int lsr_psf_accumulate_f32_cpu(const float* vol, int64_t Z, int64_t Y, int64_t X
 /* ... of the pyramid level (csrc/pyramid.hip): the same window arithmetic from the same header, the same bits */
 int lsr_downsample2_f32_cpu(const float* in, int64_t Z, int64_t Y, int64_t X, float* out, int fz, lsr_stream_t stream);
 int lsr_downsample2_u16_cpu(const uint16_t* in, int64_t Z, int64_t Y, int64_t X, uint16_t* out, int fz, lsr_stream_t stream);
+
+/* ... of the stitching composite (csrc/stitch.hip): table and tiles in HOST memory (the table's entries are checked here) */
+int lsr_stitch_f32_cpu(const void* table, int n_tiles, float* out, const int64_t box_origin[3], const int64_t box_shape[3],
+                       int p, float cval, lsr_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -15,6 +15,8 @@ CPU path (biahub's; the reference's own CLI has only ``acquire`` and ``gui``,
     python -m shrimpy_amd.cli estimate-stabilization -i series.zarr -c estimate.yml -o stabilization/
     python -m shrimpy_amd.cli stabilize   -i series.zarr -c stabilization/ -o stabilized.zarr
     python -m shrimpy_amd.cli pyramid     -i store.zarr --levels 4        (adds levels to the store in place)
+    python -m shrimpy_amd.cli estimate-stitch -i tiles.zarr -c estimate.yml -o stitch.yml
+    python -m shrimpy_amd.cli stitch      -i tiles.zarr -c stitch.yml    -o stitched.zarr
 
 Every (position, timepoint, channel) volume is an independent unit.  Launched under
 ``python -m torch.distributed.run --nproc-per-node N`` each rank takes the units
@@ -1160,6 +1162,269 @@ def run_stabilize(input_path, config, output_path, positions=(), zarr_version: s
                      on_error=on_error,
                      fingerprint_extra={"stabilize": {k: s.model_dump(mode="json") for k, s in per_position.items()}},
                      levels=levels, level_factor_z=level_factor_z)
+
+
+def _position_translation(position) -> tuple[float, ...]:
+    """(T, C, Z, Y, X) NGFF ``translation`` of a position's level 0 (zeros when absent)."""
+    ms = position.zattrs.get("multiscales", [{}])
+    ds = ms[0].get("datasets", [{}]) if ms else [{}]
+    for t in ds[0].get("coordinateTransformations", []):
+        if t.get("type") == "translation":
+            return tuple(float(v) for v in t["translation"])
+    return (0.0,) * 5
+
+
+def _wells(keys) -> dict:
+    """``{"row/col": [position keys in sorted order]}``."""
+    wells: dict = {}
+    for k in sorted(keys):
+        wells.setdefault(k.rsplit("/", 1)[0], []).append(k)
+    return wells
+
+
+@cli.command("estimate-stitch", cls=_eat_all_command("-i", "--input-position-dirpaths"))
+@click.option("-i", "--input-position-dirpaths", "input_path", required=True, multiple=True, type=click.UNPROCESSED,
+              help="Tiled store (HCS plate: the fields of view of a well are its tiles), or position directories of one plate.")
+@click.option("-c", "--config-filepath", "config", required=True, type=click.Path(exists=True, dir_okay=False, path_type=Path),
+              help="EstimateStitchSettings YAML.")
+@click.option("-o", "--output-filepath", "output_path", required=True, type=click.Path(dir_okay=False, path_type=Path),
+              help="The StitchSettings YAML to write (what `stitch -c` takes).")
+@click.option("-p", "--position", "positions", multiple=True, help='Restrict to these position keys ("row/col/fov").')
+@click.option("--io", "io_backend", type=click.Choice(["auto", "native", "iohub"]), default="auto", show_default=True)
+def estimate_stitch_cmd(input_path, config, output_path, positions, io_backend):
+    """Estimate where every field of view of a well sits on the well's canvas (config: EstimateStitchSettings YAML)."""
+    input_path, positions = _inputs(input_path, positions)
+    click.echo(run_estimate_stitch(input_path, config, output_path, positions, io_backend))
+
+
+def run_estimate_stitch(input_path, config, output_path, positions=(), io_backend: str = "auto") -> dict:
+    """``estimate-stitch``: one ``StitchSettings`` YAML for the whole store, ``total_translation`` keyed by position.  Per well
+    the positions in sorted name order are the tiles; timepoint 0 of the estimation channel is correlated.  The store reader
+    moves whole volumes: a tile's volume is read once, when its overlap crops are cut (``estimate_translations`` asks for all
+    crops of a tile in a row), and only the crops are kept and moved to the device -- one volume is on the host at a time."""
+    import torch
+
+    from .io.omezarr import as_volume_array, position_scale
+    from .settings import EstimateStitchSettings, StitchSettings
+    from .stitch import estimate_translations, grid_placement
+
+    try:
+        settings = EstimateStitchSettings.from_yaml(config)
+    except (ValueError, TypeError) as exc:
+        raise click.ClickException(f"{config}: {exc}") from exc
+    rank, world, device, created = _distributed()
+    try:
+        src, src_positions = _open_source(Path(input_path), io_backend)
+        keys = [k for k in src_positions if not positions or k in positions]
+        missing = [p for p in positions if p not in src_positions]
+        if missing:
+            raise click.ClickException(f"positions {missing} not found; available: {list(src_positions)}")
+        if not keys:
+            raise click.ClickException("no positions to process")
+        total: dict = {}
+        for well, names in _wells(keys).items():
+            arrays = {k: as_volume_array(src_positions[k]["0"]) for k in names}
+            for k, a in arrays.items():
+                if len(a.shape) != 5:
+                    raise click.ClickException(f"position {k}: expected 5-D TCZYX data, got shape {tuple(a.shape)}")
+            channel_names = list(src_positions[names[0]].channel_names)
+            if settings.channel not in channel_names:
+                raise click.ClickException(f"well {well}: channel {settings.channel!r} not in the store (it has {channel_names})")
+            c = channel_names.index(settings.channel)
+            shapes = {k: tuple(int(n) for n in a.shape[2:]) for k, a in arrays.items()}
+            if settings.initial_placement == "grid":
+                initial = dict(zip(names, grid_placement([shapes[k] for k in names], settings.grid_columns,
+                                                         settings.percent_overlap)))
+            else:
+                initial = {k: tuple(t / sc for t, sc in zip(_position_translation(src_positions[k])[2:],
+                                                            position_scale(src_positions[k])[2:])) for k in names}
+
+            @functools.lru_cache(maxsize=1)
+            def volume(k, arrays=arrays, c=c):
+                return arrays[k].read_volume(0, c)
+
+            def crop(k, sl):
+                return torch.as_tensor(np.ascontiguousarray(volume(k)[sl], dtype=np.float32), device=device)
+
+            placed = estimate_translations(crop, shapes, initial, settings)
+            total.update({k: [float(v) for v in t] for k, t in placed.items()})
+            logger.info("well %s: %d tiles placed", well, len(names))
+        close = getattr(src, "close", None)
+        if close:
+            close()
+        if rank == 0:
+            Path(output_path).parent.mkdir(parents=True, exist_ok=True)
+            StitchSettings(total_translation=total).to_yaml(output_path)
+        return {"rank": rank, "world_size": world, "output": str(output_path), "positions": len(total)}
+    finally:
+        if created:
+            import torch.distributed as dist
+
+            dist.destroy_process_group()
+
+
+# share of the free device memory that the tiles of a unit plus its canvas may take before the canvas is composed in bands
+STITCH_RESIDENT_SHARE = 0.8
+
+
+@cli.command(cls=_eat_all_command("-i", "--input-position-dirpaths"))
+@_common
+def stitch(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error, levels,
+           level_factor_z):
+    """Compose the fields of view of every well into one position per well (config: the StitchSettings YAML of estimate-stitch)."""
+    input_path, positions = _inputs(input_path, positions)
+    _finish(run_stitch(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error,
+                       **_pyramid_options(levels, level_factor_z)))
+
+
+def run_stitch(input_path, config, output_path, positions=(), zarr_version: str = "0.5", resume: bool = False,
+               io_backend: str = "auto", compression=None, on_error: str = "raise", levels: int = 1,
+               level_factor_z: int = 2) -> dict:
+    """``stitch``: per well, timepoint and channel the tiles named in ``total_translation`` are composed
+    (``stitch.stitch_tiles``; ``stitch.stitch_banded`` when the tiles plus the canvas exceed ``STITCH_RESIDENT_SHARE`` of the
+    free device memory, or ``LSR_STITCH_MAX_RESIDENT_BYTES``) into the output position ``row/col/0``: float32 (uint16 tiles
+    are converted on load, exactly), the inputs' ``scale``, ``translation = origin * scale``.  The input is read through
+    ``io_backend``; the output is written by this package's own writer.  A unit is one (well, t, c) canvas."""
+    import torch
+
+    from .io.omezarr import as_volume_array, create_pyramid, open_ome_zarr, position_scale
+    from .pipeline import Unit, enumerate_units, run_sharded
+    from .pyramid import MAX_LEVELS, build_levels
+    from .settings import StitchSettings
+    from .stitch import canvas_geometry, stitch_banded, stitch_tiles
+
+    if not 1 <= int(levels) <= MAX_LEVELS or level_factor_z not in (1, 2):
+        raise click.ClickException(f"levels must be in 1 .. {MAX_LEVELS} and level_factor_z 1 or 2")
+    try:
+        settings = StitchSettings.from_yaml(config)
+    except (ValueError, TypeError) as exc:
+        raise click.ClickException(f"{config}: {exc}") from exc
+    rank, world, device, created = _distributed()
+    try:
+        src, src_positions = _open_source(Path(input_path), io_backend)
+        keys = [k for k in src_positions if (not positions or k in positions) and k in settings.total_translation]
+        unknown = [k for k in settings.total_translation if k not in src_positions]
+        if unknown:
+            raise click.ClickException(f"total_translation names positions {unknown} that the store does not have")
+        unplaced = [k for k in src_positions if (not positions or k in positions) and k not in settings.total_translation]
+        if unplaced:
+            raise click.ClickException(f"positions {unplaced} have no total_translation: restrict the run with -p or estimate them")
+        if not keys:
+            raise click.ClickException("no positions to process")
+        wells = _wells(keys)
+        arrays = {k: as_volume_array(src_positions[k]["0"]) for k in keys}
+        first = src_positions[keys[0]]
+        nt, nc = (int(n) for n in arrays[keys[0]].shape[:2])
+        channel_names = list(first.channel_names) or [str(i) for i in range(nc)]
+        scale = list(position_scale(first))
+        for k, a in arrays.items():
+            if len(a.shape) != 5 or tuple(int(n) for n in a.shape[:2]) != (nt, nc):
+                raise click.ClickException(f"position {k}: shape {tuple(a.shape)}; expected TCZYX with T = {nt}, C = {nc}")
+            if np.dtype(a.dtype) not in (np.dtype("uint16"), np.dtype("float32")):
+                raise click.ClickException(f"position {k}: data type {a.dtype}; tiles are uint16 or float32")
+            if list(position_scale(src_positions[k])) != scale:
+                raise click.ClickException(f"position {k}: scale {position_scale(src_positions[k])} differs from {keys[0]}'s")
+        wanted = list(settings.channels) if settings.channels else channel_names
+        absent = [n for n in wanted if n not in channel_names]
+        if absent:
+            raise click.ClickException(f"channels {absent} not in the store (it has {channel_names})")
+        source_channel = [channel_names.index(n) for n in wanted]
+        translations = {w: np.asarray([settings.total_translation[k] for k in ks], dtype=np.float64) for w, ks in wells.items()}
+        shapes = {w: [tuple(int(n) for n in arrays[k].shape[2:]) for k in ks] for w, ks in wells.items()}
+        geometry = {w: canvas_geometry(shapes[w], translations[w]) for w in wells}
+        out_keys = {w: w + "/0" for w in wells}
+        fingerprint = _fingerprint(Path(input_path), settings, (nt, len(wanted)), "float32", keys,
+                                   {"stitch": {w: list(g[0]) for w, g in geometry.items()}, "levels": int(levels),
+                                    "fz": int(level_factor_z)})
+        ledger, fail_ledger = _DoneLedger(output_path, fingerprint), _FailLedger(output_path)
+
+        def open_output(mode):
+            return open_ome_zarr(output_path, layout="hcs", mode=mode, channel_names=wanted, version=zarr_version,
+                                 prefer_iohub=False)
+
+        error = None
+        if rank == 0:
+            try:
+                exists = Path(output_path).exists() and any(Path(output_path).iterdir())
+                if exists and not resume:
+                    raise FileExistsError(f"{output_path} exists (never overwritten); use --resume to continue an interrupted run")
+                if exists:
+                    ledger.check()
+                dst = open_output("a" if exists else "w")
+                have = dict(dst.positions()) if exists else {}
+                for w in wells:
+                    if out_keys[w] in have:
+                        continue
+                    shape, origin = geometry[w]
+                    row, col = w.split("/")
+                    extra = {} if compression in (None, "none") else {"compress": compression}
+                    tr = [0.0, 0.0] + [float(o) * float(sc) for o, sc in zip(origin, scale[2:])]
+                    create_pyramid(dst.create_position(row, col, "0"), (nt, len(wanted)) + shape, "float32", scale, int(levels),
+                                   int(level_factor_z), translation=tr if any(origin) else None, **extra)
+                dst.close()
+                ledger.begin()
+            except click.ClickException as exc:
+                error = exc.message
+            except Exception as exc:  # noqa: BLE001 -- reported on every rank, see _agree
+                error = f"{type(exc).__name__}: {exc}"
+        _agree(error)
+        dst = open_output("a")
+        dst_positions = dict(dst.positions())
+        level_arrays = {w: [as_volume_array(dst_positions[out_keys[w]][str(lv)]) for lv in range(int(levels))] for w in wells}
+        well_of = {v: k for k, v in out_keys.items()}
+        units = enumerate_units(list(out_keys.values()), nt, range(len(wanted)))
+        todo = [u for u in units if not (resume and ledger.is_done(u))]
+        on_gpu = torch.device(device).type == "cuda"
+
+        def load(u: Unit):
+            c = source_channel[u.c]
+            return [np.ascontiguousarray(arrays[k].read_volume(u.t, c), dtype=np.float32) for k in wells[well_of[u.position]]]
+
+        def process(data, u: Unit):
+            w = well_of[u.position]
+            need = 4 * (sum(int(v.size) for v in data) + int(np.prod(geometry[w][0])))
+            budget = os.environ.get("LSR_STITCH_MAX_RESIDENT_BYTES")
+            if budget is None and on_gpu:
+                budget = STITCH_RESIDENT_SHARE * torch.cuda.mem_get_info(device)[0]
+            if budget is not None and need > float(budget):
+                canvas = stitch_banded(lambda k: torch.as_tensor(data[k], device=device), shapes[w], translations[w],
+                                       settings.blending_exponent, settings.cval, max_resident_bytes=int(float(budget)))
+            else:
+                canvas = stitch_tiles([torch.as_tensor(v, device=device) for v in data], translations[w],
+                                      settings.blending_exponent, settings.cval)
+            return [lv.cpu().numpy() for lv in [canvas] + build_levels(canvas, int(levels), int(level_factor_z))]
+
+        def store(u: Unit, hosts):
+            for arr, lv in zip(level_arrays[well_of[u.position]], hosts):
+                arr.write_volume(u.t, u.c, lv)
+            ledger.mark(u)
+            fail_ledger.clear(u)
+
+        try:
+            report = run_sharded(todo, load, process, store, synchronize=torch.cuda.synchronize if on_gpu else None,
+                                 process_takes_unit=True, on_error=on_error)
+        finally:
+            for s_ in (src, dst):
+                close = getattr(s_, "close", None)
+                if close:
+                    close()
+        failed = [{"position": u.position, "t": u.t, "c": u.c, "stage": stage, "error": msg} for u, stage, msg in report.failures]
+        for u, stage, msg in report.failures:
+            fail_ledger.mark(u, stage, msg)
+        if world > 1:
+            import torch.distributed as dist
+
+            box: list = [None] * world
+            dist.all_gather_object(box, failed)
+            failed = [f for part in box for f in part]
+        return {"rank": rank, "world_size": world, "units": len(report.units), "units_total": len(units),
+                "units_skipped": len(units) - len(todo), "failed": failed, "seconds": report.seconds,
+                "job_seconds": report.max_seconds, "wells": {out_keys[w]: list(geometry[w][0]) for w in wells}}
+    finally:
+        if created:
+            import torch.distributed as dist
+
+            dist.destroy_process_group()
 
 
 @cli.command("pyramid", cls=_eat_all_command("-i", "--input-position-dirpaths"))

@@ -18,6 +18,7 @@
 //                                             <->  the same names without _cpu         (peaks.hip)
 //   lsr_band_power_f32_cpu                    <->  lsr_band_power_f32                  (focus.hip)
 //   lsr_downsample2_f32_cpu / _u16_cpu        <->  lsr_downsample2_f32 / _u16          (pyramid.hip)
+//   lsr_stitch_f32_cpu                        <->  lsr_stitch_f32                      (stitch.hip)
 //
 // Arithmetic (what "the same" means):
 //   resamplers -- the text the kernels compile (resample.hpp): coordinates, axis taps with their weights and the
@@ -997,4 +998,60 @@ extern "C" int lsr_downsample2_f32_cpu(const float* in, int64_t Z, int64_t Y, in
 extern "C" int lsr_downsample2_u16_cpu(const uint16_t* in, int64_t Z, int64_t Y, int64_t X, uint16_t* out, int fz,
                                        lsr_stream_t) {
   return downsample2_host<uint16_t>(in, Z, Y, X, out, fz);
+}
+
+// ---- stitching (stitch.hip): the coverage, sample, weight and blend of stitch.hpp, row by row ----
+#include "stitch.hpp"
+
+extern "C" int lsr_stitch_f32_cpu(const void* table, int n_tiles, float* out, const int64_t box_origin[3],
+                                  const int64_t box_shape[3], int p, float cval, lsr_stream_t) {
+  namespace st = lsr::stitch;
+  LSR_REQUIRE_HOST_FMA();
+  if (int rc = st::check_launch(table, n_tiles, out, box_origin, box_shape, p)) return rc;
+  const st::Tile* tab = static_cast<const st::Tile*>(table);
+  for (int k = 0; k < n_tiles; ++k) {       // (a host table can be read here; the device entry trusts lsr_stitch_prepare_table)
+    LSR_REQUIRE(tab[k].data != nullptr, LSR_E_NULL, "tile %d is NULL", k);
+    LSR_REQUIRE(tab[k].n[0] > 0 && tab[k].n[1] > 0 && tab[k].n[2] > 0, LSR_E_SHAPE, "tile %d: shape (%lld,%lld,%lld) must be positive",
+                k, (long long)tab[k].n[0], (long long)tab[k].n[1], (long long)tab[k].n[2]);
+    LSR_REQUIRE_VOLUME(tab[k].n[0], tab[k].n[1], tab[k].n[2]);
+    LSR_REQUIRE(tab[k].n[1] <= st::kMaxEdgeExtent && tab[k].n[2] <= st::kMaxEdgeExtent, LSR_E_UNSUPPORTED,
+                "tile %d: the y and x extents are at most 2^24", k);
+  }
+  const int64_t Bz = box_shape[0], By = box_shape[1], Bx = box_shape[2];
+  std::atomic<bool> failed{false};
+  parallel_ranges(Bz * By, [&](int64_t first, int64_t last) {
+    std::vector<st::Acc> acc(static_cast<size_t>(Bx));
+    for (int64_t row = first; row < last; ++row) {
+      const int64_t zb = row / By, yb = row - zb * By, cz = box_origin[0] + zb, cy = box_origin[1] + yb;
+      for (st::Acc& a : acc) a.clear();
+      for (int k = 0; k < n_tiles; ++k) {
+        const st::Tile& e = tab[k];
+        const int fz = e.frac[0], fy = e.frac[1], fx = e.frac[2];
+        const int64_t ny = e.n[1], nx = e.n[2], plane = ny * nx;
+        const int64_t jz = cz - e.ti[0], jy = cy - e.ti[1];
+        if (!st::covered(jz, e.n[0], fz) || !st::covered(jy, ny, fy)) continue;
+        // rows r[z tap][y tap], tap 0 = j - 1: it exists only on a fractional axis, otherwise the name points at tap j's row
+        const float* r11 = e.data + (jz * ny + jy) * nx;
+        const float* r10 = fy ? r11 - nx : r11;
+        const float* r01 = fz ? r11 - plane : r11;
+        const float* r00 = fz ? r10 - plane : r10;
+        const float dy = st::edge(jy, ny, e.w0[1], e.w1[1]);
+        const float wx0 = e.w0[2], wx1 = e.w1[2];
+        const int64_t x_first = std::max<int64_t>(0, e.ti[2] + fx - box_origin[2]);
+        const int64_t x_last = std::min<int64_t>(Bx - 1, e.ti[2] + nx - 1 - box_origin[2]);
+        for (int64_t x = x_first; x <= x_last; ++x) {
+          const int64_t j = box_origin[2] + x - e.ti[2], j0 = fx ? j - 1 : j;
+          const float a00 = st::tap(r00[j0], r00[j], fx, wx0, wx1), a01 = st::tap(r01[j0], r01[j], fx, wx0, wx1);
+          const float a10 = st::tap(r10[j0], r10[j], fx, wx0, wx1), a11 = st::tap(r11[j0], r11[j], fx, wx0, wx1);
+          const float v = st::tap(st::tap(a00, a01, fy, e.w0[1], e.w1[1]), st::tap(a10, a11, fy, e.w0[1], e.w1[1]), fz, e.w0[0],
+                                  e.w1[0]);
+          acc[static_cast<size_t>(x)].add(v, st::weight(dy, st::edge(j, nx, e.w0[2], e.w1[2]), p));
+        }
+      }
+      float* dst = out + row * Bx;
+      for (int64_t x = 0; x < Bx; ++x) dst[x] = acc[static_cast<size_t>(x)].finish(cval);
+    }
+  }, failed);
+  LSR_REQUIRE(!failed.load(), LSR_E_ARG, "lsr_stitch_f32_cpu: out of memory for the row accumulators");
+  return LSR_OK;
 }

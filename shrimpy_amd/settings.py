@@ -478,6 +478,64 @@ class StabilizationSettings(_StrictModel):
         return [_check_matrix_4x4(m, f"affine_transform_zyx_list[{i}]") for i, m in enumerate(v)]
 
 
+class EstimateStitchSettings(_StrictModel):
+    """Placement estimation of a well's tiles (``shrimpy_amd/stitch.py``, the ``estimate-stitch`` command).  biahub's field
+    names where recalled [RECALLED] (``percent_overlap``); PARITY UNPINNED.
+
+    ``initial_placement`` ``"metadata"``: each position's level-0 NGFF ``translation`` divided by its ``scale``;
+    ``"grid"``: ``grid_columns`` columns at ``percent_overlap``, the positions of a well in sorted name order, row-major.
+    ``maximum_shift`` is the padding factor of ``dynatrack._phase_cross_corr``; a pair whose shift reaches
+    ``maximum_shift_voxels`` on an axis is dropped, as is one whose least-squares residual exceeds
+    ``outlier_threshold_voxels``."""
+
+    channel: str
+    initial_placement: Literal["metadata", "grid"] = "metadata"
+    grid_columns: Optional[PositiveInt] = None
+    percent_overlap: Optional[NonNegativeFloat] = None
+    maximum_shift: PositiveFloat = 1.0
+    maximum_shift_voxels: PositiveInt = 32
+    min_overlap_voxels: PositiveInt = 8
+    outlier_threshold_voxels: PositiveFloat = 2.0
+    round_to_integer: bool = True
+
+    @model_validator(mode="after")
+    def _check_grid(self):
+        if self.initial_placement == "grid":
+            if self.grid_columns is None or self.percent_overlap is None:
+                raise ValueError('initial_placement "grid" needs grid_columns and percent_overlap')
+            if not self.percent_overlap < 100.0:
+                raise ValueError("percent_overlap must be below 100")
+        return self
+
+
+class StitchSettings(_StrictModel):
+    """What ``estimate-stitch`` writes and ``stitch`` applies: ``total_translation[position] = [z, y, x]`` in voxels of the
+    well's canvas (tile voxel ``i`` sits at ``i + t``), the blend (``csrc/stitch.hpp``: weight ``(dy dx)^blending_exponent``)
+    and the fill value.  ``channels``: the channels to stitch (default: all)."""
+
+    total_translation: dict[str, list[float]]
+    blending_exponent: int = 1
+    cval: float = 0.0
+    channels: Optional[list[str]] = None
+
+    @field_validator("total_translation")
+    @classmethod
+    def _check_translations(cls, v):
+        if not v:
+            raise ValueError("total_translation is empty")
+        for key, t in v.items():
+            if len(t) != 3 or not all(np.isfinite(float(x)) for x in t):
+                raise ValueError(f"total_translation[{key!r}] must be three finite numbers (z, y, x), got {t}")
+        return {k: [float(x) for x in t] for k, t in v.items()}
+
+    @field_validator("blending_exponent")
+    @classmethod
+    def _check_exponent(cls, v):
+        if not 0 <= v <= 4:
+            raise ValueError("blending_exponent must be in 0 .. 4")
+        return v
+
+
 class ReconstructSettings(_StrictModel):
     """Whole per-volume pipeline: (flat-field) -> deskew -> (register) -> (deconvolve)."""
 

@@ -7,6 +7,7 @@ RL launch, and the deskew kernel alone.  Prints one JSON object per kernel.
 from __future__ import annotations
 
 import argparse
+import ctypes
 import json
 import sys
 
@@ -58,6 +59,10 @@ def main():
                     "--rl-grid (fz = 2) beside torch's avg_pool3d on the same tensor and a device-to-device copy in the same "
                     "run (median of --reps launches between HIP events, after a warm-up); appended to "
                     "profiles/pyramid_config2.jsonl")
+    ap.add_argument("--stitch", action="store_true", help="only: ms of lsr_stitch_f32 for a 2 x 2 grid of --rl-grid tiles at "
+                    "10 % overlap (p = 1; integer placement, then a placement fractional on x) beside the torch scatter "
+                    "formulation and a device-to-device copy in the same run (median of 5 launches between HIP events after "
+                    "2 warm-ups); appended to profiles/stitch_config2.jsonl")
     ap.add_argument("--psf-sweep-wide", action="store_true", help="with --psf-sweep: every pz for in-plane extents 9-15")
     args = ap.parse_args()
 
@@ -72,6 +77,9 @@ def main():
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(3)
 
+    if args.stitch:
+        _stitch(args, torch, dev, g, tuple(int(v) for v in args.rl_grid.split(",")))
+        return
     if args.pyramid:
         _pyramid(args, torch, dev, g, tuple(int(v) for v in args.rl_grid.split(",")))
         return
@@ -396,6 +404,74 @@ def _pyramid(args, torch, dev, g, oshape):
                     "ms": sum(r["ms"] for r in records[1:]), "avg_pool3d_ms": sum(r["avg_pool3d_ms"] for r in records[1:])})
     stamp = {"sources": _lib.kernel_source_sha16(), "device": torch.cuda.get_device_name(dev), "reps": reps}
     path = ROOT / "profiles" / "pyramid_config2.jsonl"
+    with open(path, "a") as f:
+        for r in records:
+            line = json.dumps({**r, **stamp})
+            print(line, flush=True)
+            f.write(line + "\n")
+
+
+def _stitch(args, torch, dev, g, tshape):
+    """Stitching (csrc/stitch.hip): one launch for the canvas of a 2 x 2 grid of tiles at 10 % overlap, p = 1.  Algorithmic
+    bytes: 4 * (tile voxels touched + canvas voxels) -- every tile voxel is read once, every canvas voxel written once --
+    against the copy rate of this card in this run and against the torch scatter formulation (per tile
+    acc[box] += w * v; wsum[box] += w, then acc / wsum)."""
+    from shrimpy_amd import _lib, stitch
+
+    reps = 5
+    z, y, x = tshape
+    sy, sx = int(round(0.9 * y)), int(round(0.9 * x))
+    tiles = [torch.empty(tshape, dtype=torch.float32, device=dev).normal_(generator=g) for _ in range(4)]
+    other = torch.empty_like(tiles[0])
+    other.copy_(tiles[0])
+    copy_ms = _median_ms(lambda: other.copy_(tiles[0]), reps, torch)
+    copy_gbps = 8.0 * other.numel() / copy_ms / 1e6
+    del other
+    records = [{"kernel": "device copy (torch copy_)", "grid": list(tshape), "ms": copy_ms, "GBps": copy_gbps}]
+    for label, fx in (("integer placement", 0.0), ("fractional on x", 0.5)):
+        tr = [(0.0, 0.0, 0.0), (0.0, 0.0, sx + fx), (0.0, float(sy), 0.0), (0.0, float(sy), sx + fx)]
+        shape, origin = stitch.canvas_geometry([tshape] * 4, tr)
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+        table = torch.from_numpy(stitch._host_table(tiles, tr)).to(dev)
+        o3, s3 = (ctypes.c_int64 * 3)(*origin), (ctypes.c_int64 * 3)(*shape)
+
+        def launch():
+            _lib.call("lsr_stitch_f32", table.data_ptr(), 4, out.data_ptr(), o3, s3, 1, 0.0, _lib.stream_ptr(dev))
+
+        launch()
+        ms = _median_ms(launch, reps, torch)
+        touched = 4 * z * y * x
+        nbytes = 4.0 * (touched + out.numel())
+        rec = {"kernel": "lsr_stitch_f32", "placement": label, "tiles": [list(tshape)] * 4, "translations": [list(t) for t in tr],
+               "canvas": list(shape), "p": 1, "ms": ms, "algorithmic_GBps": nbytes / ms / 1e6,
+               "frac_of_copy_rate": nbytes / ms / 1e6 / copy_gbps}
+        if fx == 0.0:
+            yy = torch.arange(y, device=dev, dtype=torch.float32)
+            xx = torch.arange(x, device=dev, dtype=torch.float32)
+            w = (torch.minimum(yy + 1, y - yy)[:, None] * torch.minimum(xx + 1, x - xx)[None, :])[None]
+            acc, wsum = torch.empty_like(out), torch.empty_like(out)
+
+            def scatter():
+                acc.zero_()
+                wsum.zero_()
+                for tile, t in zip(tiles, tr):
+                    oy, ox = int(t[1]) - origin[1], int(t[2]) - origin[2]
+                    acc[:, oy:oy + y, ox:ox + x] += w * tile
+                    wsum[:, oy:oy + y, ox:ox + x] += w
+                return acc / wsum
+
+            scatter()
+            scatter_ms = _median_ms(scatter, reps, torch)
+            ref = scatter()
+            launch()
+            worst = float((ref - out).abs().max())
+            rec.update({"torch_scatter_ms": scatter_ms, "speedup_over_torch_scatter": scatter_ms / ms,
+                        "max_abs_difference_from_torch_scatter": worst})
+            del acc, wsum, ref, w
+        records.append(rec)
+        del out
+    stamp = {"sources": _lib.kernel_source_sha16(), "device": torch.cuda.get_device_name(dev), "reps": reps, "warmups": 2}
+    path = ROOT / "profiles" / "stitch_config2.jsonl"
     with open(path, "a") as f:
         for r in records:
             line = json.dumps({**r, **stamp})
