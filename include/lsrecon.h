@@ -630,6 +630,14 @@ int lsr_mask_centroid_f32(const float* in, int64_t Z, int64_t Y, int64_t X, floa
                           double* out4, void* scratch, lsr_stream_t stream);
 int lsr_blur_reflect_f32(const float* in, float* out, int64_t Z, int64_t Y, int64_t X, int axis,
                          const float* taps, int radius, float sub, float div, lsr_stream_t stream);
+/* Which of its five kernels lsr_blur_reflect_f32 runs for these arguments (host only, nothing is launched; the
+ * launcher itself switches on this answer): 0 contiguous (axis 2), 1 marching (radius <= 12, axis length >= 32),
+ * 2 packed (two columns per lane: radius 13..28, even inner extent, axis length > 32, both arrays 8-byte aligned),
+ * 3 tiled-128 (radius <= 60, axis length > 64), 4 tiled-64 (the rest); a negative status for what the launcher
+ * refuses.  in_align_bytes / out_align_bytes stand in for the two addresses: any value with their low three bits --
+ * the address modulo 16, or the alignment it is known to have (4, 8, 16). */
+int lsr_blur_reflect_form(int64_t Z, int64_t Y, int64_t X, int axis, int radius, int in_align_bytes,
+                          int out_align_bytes);
 /*
  * Element-wise steps of _phase_cross_corr (:266-378); the FFTs between them are library calls.
  *   lsr_match_shape_f32       _match_shape: per axis reflect-pad (left = d / 2) or centre-crop to the FFT shape

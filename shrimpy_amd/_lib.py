@@ -70,6 +70,7 @@ SIGNATURES: dict[str, list] = {
     "lsr_weighted_centroid_f32": [_c_f32p, _i64, _i64, _i64, _f32, ctypes.c_void_p, ctypes.c_void_p, _stream],
     "lsr_mask_centroid_f32": [_c_f32p, _i64, _i64, _i64, _f32, ctypes.c_void_p, ctypes.c_void_p, _stream],
     "lsr_blur_reflect_f32": [_c_f32p, _c_f32p, _i64, _i64, _i64, _int, _c_f32p, _int, _f32, _f32, _stream],
+    "lsr_blur_reflect_form": [_i64, _i64, _i64, _int, _int, _int, _int],
     "lsr_match_shape_f32": [_c_f32p, _i64, _i64, _i64, _c_f32p, _i64, _i64, _i64, _stream],
     "lsr_cross_power_c64": [_c_f32p, _c_f32p, _i64, _stream],
     "lsr_rfft_rows_supported": [_i64],

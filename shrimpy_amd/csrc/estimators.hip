@@ -706,14 +706,38 @@ __global__ __launch_bounds__(kThreads) void peak_final_kernel(const float* __res
   if (threadIdx.x == 0) out[0] = static_cast<long long>(s_i[0]);
 }
 
-int check_volume(const float* in, int64_t Z, int64_t Y, int64_t X) {
-  LSR_REQUIRE_PTR(in);
+int check_shape(int64_t Z, int64_t Y, int64_t X) {
   LSR_REQUIRE(Z > 0 && Y > 0 && X > 0, LSR_E_SHAPE, "shape (%lld,%lld,%lld) must be positive",
               (long long)Z, (long long)Y, (long long)X);
   LSR_REQUIRE_VOLUME(Z, Y, X);
   LSR_REQUIRE(Z < (int64_t(1) << 30) && Y < (int64_t(1) << 30) && X < (int64_t(1) << 30), LSR_E_UNSUPPORTED,
               "a dimension exceeds 2^30");
   return LSR_OK;
+}
+
+int check_volume(const float* in, int64_t Z, int64_t Y, int64_t X) {
+  LSR_REQUIRE_PTR(in);
+  return check_shape(Z, Y, X);
+}
+
+// Which kernel a one-axis blur takes (lsr_blur_reflect_form): the launcher switches on this and nothing else.
+// `align_bits`: the low bits of the input and output addresses, or'ed -- the packed form moves float2s.
+enum BlurForm { kBlurContiguous = 0, kBlurMarching = 1, kBlurPacked = 2, kBlurTiled128 = 3, kBlurTiled64 = 4 };
+int blur_form(int64_t Z, int64_t Y, int64_t X, int axis, int radius, unsigned align_bits) {
+  LSR_REQUIRE(axis >= 0 && axis <= 2, LSR_E_ARG, "axis %d must be 0 (z), 1 (y) or 2 (x)", axis);
+  LSR_REQUIRE(radius >= 0 && radius <= kBlurMaxR, LSR_E_UNSUPPORTED, "radius %d outside [0, %d]", radius,
+              kBlurMaxR);
+  const int64_t dims[3] = {Z, Y, X};
+  const int64_t L = dims[axis], inner = axis == 0 ? Y * X : (axis == 1 ? X : 1);
+  LSR_REQUIRE(radius < L, LSR_E_ARG, "reflect padding needs radius %d < axis length %lld", radius, (long long)L);
+  if (axis == 2) return kBlurContiguous;
+  if (radius <= kMarchMaxR && L >= 2 * kMarchRows) return kBlurMarching;
+  // long kernels: two columns per lane, packed FMAs
+  if (radius > kMarchMaxR && inner % 2 == 0 && L > 32 && (align_bits & 7) == 0 &&
+      (64 + 2 * radius + kTapBlock) * 128 * sizeof(float) <= 65536)
+    return kBlurPacked;
+  // 128-position segments (less halo per output) while the tile stays within 64 KB of LDS
+  return (128 + 2 * radius + kTapBlock) * 64 * sizeof(float) <= 65536 && L > 64 ? kBlurTiled128 : kBlurTiled64;
 }
 
 int grid_for(int64_t work_items) {
@@ -807,24 +831,22 @@ extern "C" int lsr_blur_reflect_f32(const float* in, float* out, int64_t Z, int6
   LSR_REQUIRE_PTR(out);
   LSR_REQUIRE_PTR(taps);
   LSR_REQUIRE(in != out, LSR_E_ARG, "out must not alias in");
-  LSR_REQUIRE(axis >= 0 && axis <= 2, LSR_E_ARG, "axis %d must be 0 (z), 1 (y) or 2 (x)", axis);
-  LSR_REQUIRE(radius >= 0 && radius <= kBlurMaxR, LSR_E_UNSUPPORTED, "radius %d outside [0, %d]", radius,
-              kBlurMaxR);
+  const int form = blur_form(Z, Y, X, axis, radius,
+                             static_cast<unsigned>((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15));
+  if (form < 0) return form;
   const int64_t dims[3] = {Z, Y, X};
-  LSR_REQUIRE(radius < dims[axis], LSR_E_ARG, "reflect padding needs radius %d < axis length %lld", radius,
-              (long long)dims[axis]);
   BlurArgs p;
   p.in = in; p.out = out; p.taps = taps; p.r = radius; p.sub = sub; p.div = div;
   p.L = dims[axis];
   p.outer = axis == 0 ? 1 : (axis == 1 ? Z : Z * Y);
   p.inner = axis == 0 ? Y * X : (axis == 1 ? X : 1);
   hipStream_t s = lsr::as_stream(stream);
-  if (axis == 2) {
+  if (form == kBlurContiguous) {
     const int64_t items = p.outer * lsr::ceil_div(p.L, static_cast<int64_t>(kRowSeg));
     const int64_t blocks = items < 16384 ? items : 16384;
     hipLaunchKernelGGL(blur_contiguous_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads),
                        sizeof(float) * (kRowSeg + 2 * radius + kTapBlock + 4), s, p);
-  } else if (radius <= kMarchMaxR && p.L >= 2 * kMarchRows) {
+  } else if (form == kBlurMarching) {
     BlurMarchArgs q;
     q.b = p;
     q.seg_len = p.L > 768 ? 512 : static_cast<int>(p.L);
@@ -834,18 +856,14 @@ extern "C" int lsr_blur_reflect_f32(const float* in, float* out, int64_t Z, int6
                 (long long)blocks);
     hipLaunchKernelGGL(blur_march_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads),
                        sizeof(float) * (2 * radius + kMarchRows) * kMarchCols, s, q);
-  } else if (radius > kMarchMaxR && p.inner % 2 == 0 && p.L > 32 &&
-             ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 7) == 0 &&
-             (64 + 2 * radius + kTapBlock) * 128 * sizeof(float) <= 65536) {
-    // long kernels: two columns per lane, packed FMAs
+  } else if (form == kBlurPacked) {
     const int64_t blocks = p.outer * lsr::ceil_div(p.L, int64_t(64)) * lsr::ceil_div(p.inner, int64_t(128));
     LSR_REQUIRE(blocks < (int64_t(1) << 31), LSR_E_SHAPE, "grid of %lld workgroups is too large",
                 (long long)blocks);
     hipLaunchKernelGGL(blur_strided_pk_kernel<16>, dim3(static_cast<unsigned>(blocks)), dim3(kThreads),
                        sizeof(float) * (64 + 2 * radius + kTapBlock) * 128, s, p);
   } else {
-    // 128-position segments (less halo per output) while the tile stays within 64 KB of LDS
-    const bool wide = (128 + 2 * radius + kTapBlock) * 64 * sizeof(float) <= 65536 && p.L > 64;
+    const bool wide = form == kBlurTiled128;
     const int seg = wide ? 128 : 64;
     const int64_t blocks = p.outer * lsr::ceil_div(p.L, static_cast<int64_t>(seg)) * lsr::ceil_div(p.inner, int64_t(64));
     LSR_REQUIRE(blocks < (int64_t(1) << 31), LSR_E_SHAPE, "grid of %lld workgroups is too large",
@@ -857,6 +875,13 @@ extern "C" int lsr_blur_reflect_f32(const float* in, float* out, int64_t Z, int6
       hipLaunchKernelGGL(blur_strided_kernel<16>, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), lds, s, p);
   }
   return lsr::launch_status("lsr_blur_reflect_f32");
+}
+
+// 0 contiguous, 1 marching, 2 packed, 3 tiled-128, 4 tiled-64; a negative status for what the launcher refuses
+extern "C" int lsr_blur_reflect_form(int64_t Z, int64_t Y, int64_t X, int axis, int radius, int in_align_bytes,
+                                     int out_align_bytes) {
+  if (int rc = check_shape(Z, Y, X)) return rc;
+  return blur_form(Z, Y, X, axis, radius, static_cast<unsigned>(in_align_bytes) | static_cast<unsigned>(out_align_bytes));
 }
 
 extern "C" int lsr_match_shape_f32(const float* in, int64_t Zi, int64_t Yi, int64_t Xi, float* out, int64_t Zo,

@@ -87,12 +87,16 @@ def _run(device, entry: str, *args) -> None:
 
 def _minmax(img) -> tuple[float, float]:
     """``(float(img.min()), float(img.max()))`` -- one pass, one host round trip (the reference's
-    ``float(vmin)`` / ``float(vmax)`` synchronise too)."""
+    ``float(vmin)`` / ``float(vmax)`` synchronise too).  NaN samples are skipped; a volume of nothing else is a
+    ValueError.  An infinite sample is a sample: a range with an infinite end is passed on as it is."""
     import torch
 
     out = torch.empty((2,), dtype=torch.float32, device=img.device)
     _run(img.device, "lsr_minmax_f32", img.data_ptr(), img.numel(), out.data_ptr(), _scratch(img.device).data_ptr())
     lo, hi = out.cpu().tolist()
+    if lo > hi:
+        # (+inf, -inf): no sample replaced the starting values -- every voxel is NaN.  Not a range to histogram or rescale by
+        raise ValueError(f"the volume of shape {tuple(img.shape)} has no sample that is not NaN: no minimum or maximum")
     return lo, hi
 
 
@@ -492,7 +496,12 @@ def _phase_cross_corr(ref_img, mov_img, maximum_shift: float = 1.0) -> tuple[int
         peak_index = torch.empty((1,), dtype=torch.int64, device=corr.device)
         _run(corr.device, "lsr_peak_abs_shifted_f32", corr.data_ptr(), *shape, peak_index.data_ptr(),
              _scratch(corr.device).data_ptr())
-    peak = np.unravel_index(int(peak_index.item()), shape)
+    flat = int(peak_index.item())
+    if flat < 0:
+        # the peak kernels answer ~0 when no |corr| compared >= the starting value: the correlation is NaN throughout
+        raise ValueError("phase cross-correlation has no finite peak: the correlation is NaN everywhere "
+                         "(a NaN or an infinite sample in ref_img or mov_img)")
+    peak = np.unravel_index(flat, shape)
     result = tuple(int(s // 2) - int(p) for s, p in zip(shape, peak))
     logger.debug("phase cross corr: peak at %s (device=%s)", result, ref_t.device)
     return result
