@@ -190,6 +190,38 @@ int lsr_affine_normal_equations_f32(const float* moving, int64_t Zi, int64_t Yi,
                                     lsr_stream_t stream);
 
 /*
+ * Affine registration, mutual-information metric (csrc/estimate_mi.hip; no reference symbol): for two channels whose
+ * intensities follow no linear map.  The conventions of lsr_affine_normal_equations_f32 (matrix, float64 coordinates,
+ * strided target grid, a sample counts when its moving coordinate lies in [0, n - 1) on every axis, parameters in
+ * centred, scaled coordinates).  Per sample, in float64 (csrc/mi_sample.hpp is the definition):
+ *     a  = clamp(floor((t - t_lo) * bins / (t_hi - t_lo)), 0, bins - 1)              target bin, zero order
+ *     u  = clamp((m - m_lo) * (bins - 1) / (m_hi - m_lo), 0, bins - 1)               m = trilinear moving value
+ *     b0 = min(floor(u), bins - 2), f = u - b0, w1 = floor(f * 65536 + 0.5), w0 = 65536 - w1
+ *     hist[a][b0] += w0, hist[a][b0 + 1] += w1                                       (a linear Parzen window)
+ * lsr_affine_joint_histogram_f32: `hist` ([bins][bins] 64-bit counters in units of 2^-16 sample) and `n_samples` (one
+ * counter) are DEVICE memory, zeroed by the entry on `stream` before the launch.  The sums are integer: the same bits on
+ * every run and from the host twin.  bins in [4, 64], t_hi > t_lo, m_hi > m_lo.  Size limit: the volumes every entry
+ * accepts (extents below 2^30, fewer than 2^48 voxels): 65536 * n stays below 2^64, and the kernel's 32-bit LDS
+ * counters are flushed before 65536 full-weight samples per lane could wrap them.
+ * lsr_affine_mi_gradient_f32: for every sample whose unclamped u lies strictly inside (0, bins - 1) -- a u of exactly 0
+ * or bins - 1 counts as clamped and adds nothing -- adds dL[a][b0] * (bins - 1) / (m_hi - m_lo) * (dm/dz, dm/dy, dm/dx)
+ * (x) ((x - centre) / scale, 1) to 12 fp64 sums.  `dL` ([bins][bins - 1], DEVICE memory) is the caller's
+ * L(a, b + 1) - L(a, b) with L = log(P(a, b) / P_m(b)) (0 where the count is 0).  `partial` receives
+ * lsr_affine_mi_gradient_blocks() rows of lsr_affine_mi_gradient_size() doubles; their sum in row order is the result
+ * (no atomics: the same bits on every run).
+ */
+int lsr_affine_joint_histogram_f32(const float* moving, int64_t Zi, int64_t Yi, int64_t Xi, const float* target,
+                                   int64_t Zo, int64_t Yo, int64_t Xo, const double M[12], const int stride[3],
+                                   int bins, double t_lo, double t_hi, double m_lo, double m_hi,
+                                   unsigned long long* hist, unsigned long long* n_samples, lsr_stream_t stream);
+int lsr_affine_mi_gradient_size(void);
+int lsr_affine_mi_gradient_blocks(void);
+int lsr_affine_mi_gradient_f32(const float* moving, int64_t Zi, int64_t Yi, int64_t Xi, const float* target,
+                               int64_t Zo, int64_t Yo, int64_t Xo, const double M[12], const int stride[3],
+                               const double centre[3], double scale, int bins, double t_lo, double t_hi, double m_lo,
+                               double m_hi, const double* dL, double* partial, lsr_stream_t stream);
+
+/*
  * Ingest, host side (no device work): the acquisition writes blosc frames (zstd, byte
  * shuffle; shrimpy/mantis/mantis_engine.py:474-481) and the reference reads them through iohub -> zarr ->
  * numcodecs.blosc.decompress.  lsr_blosc_decode_host walks one c-blosc 1.x frame, entropy-decodes every stream
@@ -961,6 +993,19 @@ int lsr_downsample2_u16_cpu(const uint16_t* in, int64_t Z, int64_t Y, int64_t X,
 /* ... of the stitching composite (csrc/stitch.hip): table and tiles in HOST memory (the table's entries are checked here) */
 int lsr_stitch_f32_cpu(const void* table, int n_tiles, float* out, const int64_t box_origin[3], const int64_t box_shape[3],
                        int p, float cval, lsr_stream_t stream);
+
+/* ... of the mutual-information metric (csrc/estimate_mi.hip): the per-sample rule of csrc/mi_sample.hpp on both sides.
+ * The histogram and the count are the kernel's bits; the gradient rows are sums over lsr_affine_mi_gradient_blocks()
+ * equal runs of samples (fp64, another order than the kernel's: equal to the last bits of a double, and the same at
+ * every lsr_set_host_threads value).  No stream; every pointer HOST memory. */
+int lsr_affine_joint_histogram_f32_cpu(const float* moving, int64_t Zi, int64_t Yi, int64_t Xi, const float* target,
+                                       int64_t Zo, int64_t Yo, int64_t Xo, const double M[12], const int stride[3],
+                                       int bins, double t_lo, double t_hi, double m_lo, double m_hi,
+                                       unsigned long long* hist, unsigned long long* n_samples);
+int lsr_affine_mi_gradient_f32_cpu(const float* moving, int64_t Zi, int64_t Yi, int64_t Xi, const float* target,
+                                   int64_t Zo, int64_t Yo, int64_t Xo, const double M[12], const int stride[3],
+                                   const double centre[3], double scale, int bins, double t_lo, double t_hi,
+                                   double m_lo, double m_hi, const double* dL, double* partial);
 
 #ifdef __cplusplus
 }

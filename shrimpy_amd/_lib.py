@@ -110,6 +110,15 @@ SIGNATURES: dict[str, list] = {
     "lsr_affine_normal_equations_f32": [_c_f32p, _i64, _i64, _i64, _c_f32p, _i64, _i64, _i64, _f64p, ctypes.c_double,
                                         ctypes.c_double, ctypes.POINTER(ctypes.c_int), _f64p, ctypes.c_double,
                                         ctypes.c_void_p, _stream],
+    "lsr_affine_joint_histogram_f32": [_c_f32p, _i64, _i64, _i64, _c_f32p, _i64, _i64, _i64, _f64p,
+                                       ctypes.POINTER(ctypes.c_int), _int, ctypes.c_double, ctypes.c_double,
+                                       ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, _stream],
+    "lsr_affine_mi_gradient_size": [],
+    "lsr_affine_mi_gradient_blocks": [],
+    "lsr_affine_mi_gradient_f32": [_c_f32p, _i64, _i64, _i64, _c_f32p, _i64, _i64, _i64, _f64p,
+                                   ctypes.POINTER(ctypes.c_int), _f64p, ctypes.c_double, _int, ctypes.c_double,
+                                   ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
+                                   _stream],
     "lsr_blosc_host_codec": [_int],
     "lsr_blosc_decode_host": [ctypes.c_void_p, _i64, ctypes.c_void_p, _i64, ctypes.POINTER(ctypes.c_int)],
     "lsr_blosc_host_encoder": [],
@@ -235,7 +244,9 @@ for _name in ("lsr_deskew_f32", "lsr_deskew_u16", "lsr_deskew_cval", "lsr_affine
               "lsr_stitch_f32"):
     SIGNATURES[_name + "_cpu"] = SIGNATURES[_name]
 SIGNATURES["lsr_rl_tv_scale_f32_cpu"] = SIGNATURES["lsr_rl_tv_scale_f32"][:-1]     # (this twin takes no stream)
-for _name in ("lsr_rl_accel_dots_f32", "lsr_rl_accel_predict_f32"):                    # (nor do these)
+for _name in ("lsr_rl_accel_dots_f32", "lsr_rl_accel_predict_f32",                     # (nor do these)
+              # ... nor those of the mutual-information metric (csrc/estimators_host.hip)
+              "lsr_affine_joint_histogram_f32", "lsr_affine_mi_gradient_f32"):
     SIGNATURES[_name + "_cpu"] = SIGNATURES[_name][:-1]
 
 

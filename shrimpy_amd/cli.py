@@ -839,19 +839,25 @@ def phase(input_path, config, output_path, positions, zarr_version, resume, io_b
 @click.option("--timepoint", type=int, default=0, show_default=True)
 @click.option("--model", type=click.Choice(["affine", "translation"]), default="affine", show_default=True)
 @click.option("--no-intensity", is_flag=True, help="Do not fit the gain / offset between the two volumes.")
+@click.option("--metric", type=click.Choice(["ssd", "mi"]), default="ssd", show_default=True,
+              help="ssd: squared differences under a linear intensity map; mi: mutual information, for two channels "
+                   "with different contrast (phase against fluorescence).")
+@click.option("--bins", type=click.IntRange(4, 64), default=32, show_default=True,
+              help="Histogram bins per axis of --metric mi.")
 @click.option("--io", "io_backend", type=click.Choice(["auto", "native", "iohub"]), default="auto", show_default=True)
 def estimate_registration(source_path, target_path, output_path, source_channel, target_channel, position, timepoint,
-                          model, no_intensity, io_backend):
+                          model, no_intensity, metric, bins, io_backend):
     """Estimate the affine that maps TARGET indices to SOURCE coordinates (what `register` applies)."""
     click.echo(run_estimate(source_path, target_path, output_path, source_channel, target_channel, position, timepoint,
-                            model, not no_intensity, io_backend))
+                            model, not no_intensity, io_backend, metric=metric, bins=bins))
 
 
 def run_estimate(source_path, target_path, output_path, source_channel=None, target_channel=None, position=None,
                  timepoint: int = 0, model: str = "affine", intensity: bool = True, io_backend: str = "auto",
-                 estimator=None) -> dict:
+                 estimator=None, metric: str = "ssd", bins: int = 32) -> dict:
     """Read one volume from each store, estimate, write the ``RegisterSettings`` YAML.
-    ``estimator(moving, target, model=, intensity=)`` defaults to :func:`estimate.estimate_affine_zyx`."""
+    ``estimator(moving, target, model=, intensity=)`` defaults to :func:`estimate.estimate_affine_zyx`; ``metric=`` and
+    ``bins=`` are handed to it only where they differ from its defaults (``"ssd"``, 32)."""
     import torch
     import yaml
 
@@ -882,7 +888,14 @@ def run_estimate(source_path, target_path, output_path, source_channel=None, tar
         target, tgt_name = read(target_path, target_channel)
         if estimator is None:
             from .estimate import estimate_affine_zyx as estimator
-        est = estimator(moving, target, model=model, intensity=intensity)
+        if metric not in ("ssd", "mi"):
+            raise click.ClickException(f"metric must be ssd or mi, got {metric!r}")
+        extra = {}
+        if metric != "ssd":
+            extra["metric"] = metric
+        if int(bins) != 32:
+            extra["bins"] = int(bins)
+        est = estimator(moving, target, model=model, intensity=intensity, **extra)
         doc = est.to_settings_dict(source_channel_names=[src_name], output_shape_zyx=[int(n) for n in target.shape])
         if Path(source_path).resolve() == Path(target_path).resolve() and tgt_name != src_name:
             doc["target_channel_name"] = tgt_name
@@ -890,9 +903,12 @@ def run_estimate(source_path, target_path, output_path, source_channel=None, tar
         Path(output_path).parent.mkdir(parents=True, exist_ok=True)
         with open(output_path, "w") as f:
             yaml.safe_dump(doc, f, sort_keys=False)
-        return {"output": str(output_path), "rms": est.rms, "gain": est.gain, "offset": est.offset,
-                "iterations": est.iterations, "converged": est.converged,
-                "affine_transform_zyx": doc["affine_transform_zyx"]}
+        result = {"output": str(output_path), "metric": metric, "rms": est.rms, "gain": est.gain, "offset": est.offset,
+                  "iterations": est.iterations, "converged": est.converged,
+                  "affine_transform_zyx": doc["affine_transform_zyx"]}
+        if metric == "mi":
+            result["mi"] = getattr(est, "mi", float("nan"))
+        return result
     finally:
         if created:
             import torch.distributed as dist

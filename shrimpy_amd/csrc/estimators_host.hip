@@ -11,6 +11,10 @@
 //   lsr_match_shape_f32_cpu        <->  lsr_match_shape_f32        _match_shape                  (:266-306)
 //   lsr_cross_power_c64_cpu / _into_c64_cpu, lsr_peak_abs_shifted_f32_cpu
 //                                  <->  the element-wise steps of _phase_cross_corr             (:309-378)
+//   lsr_affine_joint_histogram_f32_cpu, lsr_affine_mi_gradient_f32_cpu
+//                                  <->  the mutual-information entries of estimate_mi.hip (no reference code): the
+//                                       per-sample rule of mi_sample.hpp on both sides -- the histogram is integer and
+//                                       bit-equal, the gradient's fp64 sums are added in another order
 //
 // What "the same" means: min / max, histogram bins (the float32 expression of torch.histc), the shape map, the cross
 // power and the peak (first maximum in fftshift order) are identical values; the blur is the kernels' FMA chain in
@@ -18,12 +22,14 @@
 // kernels reduce in a tree): equal to the last bits of a double, not bit for bit.  `scratch` and `stream` are
 // ignored (kept so the signatures are identical).  Threads: host_parallel.hpp.
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
 #include "common.hpp"
 #include "host_parallel.hpp"
+#include "mi_sample.hpp"
 
 namespace {
 
@@ -288,5 +294,87 @@ extern "C" int lsr_peak_abs_shifted_f32_cpu(const float* in, int64_t Z, int64_t 
   Best best{-1.0f, ~0ull};
   for (int k = 0; k < used; ++k) merge(best, part[static_cast<size_t>(k)].v, part[static_cast<size_t>(k)].i);
   out_index[0] = static_cast<long long>(best.i);
+  return LSR_OK;
+}
+
+// ---- mutual-information metric of the registration estimate (estimate_mi.hip) -----------------------------------------
+
+extern "C" int lsr_affine_joint_histogram_f32_cpu(const float* moving, int64_t Zi, int64_t Yi, int64_t Xi,
+                                                  const float* target, int64_t Zo, int64_t Yo, int64_t Xo,
+                                                  const double M[12], const int stride[3], int bins, double t_lo,
+                                                  double t_hi, double m_lo, double m_hi, unsigned long long* hist,
+                                                  unsigned long long* n_samples) {
+  namespace mi = lsr::mi;
+  LSR_REQUIRE_HOST_FMA();
+  if (int rc = mi::require_sampling(moving, Zi, Yi, Xi, target, Zo, Yo, Xo, M, stride, bins, t_lo, t_hi, m_lo, m_hi)) return rc;
+  LSR_REQUIRE_PTR(hist);
+  LSR_REQUIRE_PTR(n_samples);
+  mi::Geometry p;
+  mi::Binning q;
+  mi::fill(p, q, moving, Zi, Yi, Xi, target, Zo, Yo, Xo, M, stride, bins, t_lo, t_hi, m_lo, m_hi);
+  const size_t cells = static_cast<size_t>(bins) * bins;
+  const int64_t total = static_cast<int64_t>(p.nz) * p.ny * p.nx;
+  // one table per range, added up afterwards: integer sums, the same bits at every thread count
+  std::vector<std::vector<unsigned long long>> tables(kMaxWorkers);
+  std::atomic<bool> failed{false};
+  const int used = parallel_ranges_indexed(total, [&](int k, int64_t first, int64_t last) {
+    std::vector<unsigned long long>& t = tables[static_cast<size_t>(k)];
+    t.assign(cells + 1, 0ull);   // (the last entry: the range's sample count)
+    for (int64_t s = first; s < last; ++s) {
+      double tv, mval;
+      if (!mi::sample<false>(p, s, tv, mval, nullptr, nullptr)) continue;
+      int b0;
+      unsigned w1;
+      mi::parzen(q, mi::moving_position(q, mval), b0, w1);
+      unsigned long long* cell = t.data() + static_cast<size_t>(mi::target_bin(q, tv)) * bins + b0;
+      cell[0] += mi::kWeightOne - w1;
+      cell[1] += w1;
+      ++t[cells];
+    }
+  }, failed);
+  LSR_REQUIRE(!failed.load(), LSR_E_ARG, "lsr_affine_joint_histogram_f32_cpu: out of memory for a worker's table");
+  std::memset(hist, 0, sizeof(unsigned long long) * cells);
+  unsigned long long n = 0;
+  for (int k = 0; k < used; ++k) {
+    const std::vector<unsigned long long>& t = tables[static_cast<size_t>(k)];
+    for (size_t i = 0; i < cells; ++i) hist[i] += t[i];
+    n += t[cells];
+  }
+  n_samples[0] = n;
+  return LSR_OK;
+}
+
+extern "C" int lsr_affine_mi_gradient_f32_cpu(const float* moving, int64_t Zi, int64_t Yi, int64_t Xi, const float* target,
+                                              int64_t Zo, int64_t Yo, int64_t Xo, const double M[12], const int stride[3],
+                                              const double centre[3], double scale, int bins, double t_lo, double t_hi,
+                                              double m_lo, double m_hi, const double* dL, double* partial) {
+  namespace mi = lsr::mi;
+  LSR_REQUIRE_HOST_FMA();
+  if (int rc = mi::require_sampling(moving, Zi, Yi, Xi, target, Zo, Yo, Xo, M, stride, bins, t_lo, t_hi, m_lo, m_hi)) return rc;
+  LSR_REQUIRE_PTR(centre);
+  LSR_REQUIRE_PTR(dL);
+  LSR_REQUIRE_PTR(partial);
+  LSR_REQUIRE(scale > 0.0, LSR_E_ARG, "scale must be positive");
+  mi::Geometry p;
+  mi::Binning q;
+  mi::fill(p, q, moving, Zi, Yi, Xi, target, Zo, Yo, Xo, M, stride, bins, t_lo, t_hi, m_lo, m_hi);
+  const mi::Normalise c{centre[0], centre[1], centre[2], 1.0 / scale};
+  const double du = (bins - 1) / q.m_range;
+  const int64_t total = static_cast<int64_t>(p.nz) * p.ny * p.nx;
+  // row k = the sums over the k-th of lsr_affine_mi_gradient_blocks() equal runs of samples: the rows, and their sum in
+  // row order, do not depend on the thread count
+  const int64_t rows = lsr_affine_mi_gradient_blocks();
+  const int64_t per = lsr::ceil_div(total, rows);
+  parallel_ranges(rows, [&](int64_t first, int64_t last) {
+    for (int64_t k = first; k < last; ++k) {
+      double acc[mi::kGradParams] = {0.0};
+      const int64_t s1 = std::min(total, (k + 1) * per);
+      for (int64_t s = k * per; s < s1; ++s) {
+        double tv, mval, g[3], xyz[3];
+        if (mi::sample<true>(p, s, tv, mval, g, xyz)) mi::gradient_add(q, c, dL, du, tv, mval, g, xyz, acc);
+      }
+      std::memcpy(partial + k * mi::kGradParams, acc, sizeof(acc));
+    }
+  });
   return LSR_OK;
 }

@@ -63,6 +63,12 @@ def main():
                     "10 % overlap (p = 1; integer placement, then a placement fractional on x) beside the torch scatter "
                     "formulation and a device-to-device copy in the same run (median of 5 launches between HIP events after "
                     "2 warm-ups); appended to profiles/stitch_config2.jsonl")
+    ap.add_argument("--mi", action="store_true", help="only: ms per launch of the mutual-information kernels (csrc/estimate_mi.hip: "
+                    "joint histogram, gradient) on --mi-grid at strides 1 and 4, 32 and 64 bins, on bench.synthetic_raw "
+                    "(background-dominated) and on uniform noise (spread over all cells), beside a torch formulation "
+                    "(grid_sample + bincount) and a device copy of the two volumes in the same run (median of 5 launches "
+                    "between HIP events after 2 warm-ups); appended to profiles/mi_config3.jsonl")
+    ap.add_argument("--mi-grid", default="256,2048,2048", help="Z,Y,X of the --mi section (BASELINE config 3)")
     ap.add_argument("--psf-sweep-wide", action="store_true", help="with --psf-sweep: every pz for in-plane extents 9-15")
     args = ap.parse_args()
 
@@ -77,6 +83,9 @@ def main():
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(3)
 
+    if args.mi:
+        _mi(args, torch, dev, g, bench, tuple(int(v) for v in args.mi_grid.split(",")))
+        return
     if args.stitch:
         _stitch(args, torch, dev, g, tuple(int(v) for v in args.rl_grid.split(",")))
         return
@@ -477,6 +486,122 @@ def _stitch(args, torch, dev, g, tshape):
             line = json.dumps({**r, **stamp})
             print(line, flush=True)
             f.write(line + "\n")
+
+
+def _mi(args, torch, dev, g, bench, shape):
+    """Mutual-information metric (csrc/estimate_mi.hip): one joint-histogram launch (the entry's two memsets included) and
+    one gradient launch under the config-3 registration matrix.  Algorithmic bytes: 4 per sampled target voxel plus the
+    moving voxels the samples touch (at most the whole volume) -- reported against the copy rate of this card in this run.
+    Torch formulation of the histogram: grid_sample (trilinear, float32 coordinates) slab by slab, the bin rule in tensor
+    ops, two weighted bincounts per slab."""
+    from shrimpy_amd import _lib, estimate
+
+    reps = 5
+    m = bench.registration_matrix()
+    m12 = _lib.matrix12(m[:3])
+    z, y, x = shape
+    centre = np.array([(n - 1) / 2 for n in shape])
+    c3, scale = centre.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), max(shape) / 2
+    d = ctypes.c_double
+    rows, width = _lib.call_value("lsr_affine_mi_gradient_blocks"), _lib.call_value("lsr_affine_mi_gradient_size")
+    partial = torch.empty((rows, width), dtype=torch.float64, device=dev)
+    records = []
+
+    def torch_histogram(mov, tgt, stride, bins, t_lo, t_hi, m_lo, m_hi, slab=16):
+        mt = torch.as_tensor(m[:3], dtype=torch.float32, device=dev)
+        ys = torch.arange(0, y, stride, device=dev, dtype=torch.float32)
+        xs = torch.arange(0, x, stride, device=dev, dtype=torch.float32)
+        size = torch.tensor([x - 1, y - 1, z - 1], dtype=torch.float32, device=dev)
+        hist = torch.zeros(bins * bins + 1, dtype=torch.float64, device=dev)
+        for z0 in range(0, z, slab * stride):
+            zs = torch.arange(z0, min(z, z0 + slab * stride), stride, device=dev, dtype=torch.float32)
+            zz, yy, xx = torch.meshgrid(zs, ys, xs, indexing="ij")
+            coords = [mt[r, 0] * zz + mt[r, 1] * yy + mt[r, 2] * xx + mt[r, 3] for r in range(3)]
+            ok = ((coords[0] >= 0) & (coords[0] < z - 1) & (coords[1] >= 0) & (coords[1] < y - 1) & (coords[2] >= 0)
+                  & (coords[2] < x - 1))
+            grid = torch.stack([coords[2], coords[1], coords[0]], dim=-1) / size * 2 - 1
+            mval = torch.nn.functional.grid_sample(mov[None, None], grid[None], mode="bilinear", align_corners=True)[0, 0][ok]
+            tv = tgt[z0:min(z, z0 + slab * stride):stride, ::stride, ::stride][ok]
+            a = torch.clamp(torch.floor((tv - t_lo) * bins / (t_hi - t_lo)), 0, bins - 1).long()
+            u = torch.clamp((mval - m_lo) * (bins - 1) / (m_hi - m_lo), 0, bins - 1)
+            b0 = torch.clamp(torch.floor(u), max=bins - 2)
+            f = (u - b0).double()
+            cell = a * bins + b0.long()
+            hist += torch.bincount(cell, weights=1 - f, minlength=bins * bins + 1)
+            hist += torch.bincount(cell + 1, weights=f, minlength=bins * bins + 1)
+        return hist[:-1].reshape(bins, bins)
+
+    for label in ("bench.synthetic_raw (background-dominated)", "uniform noise (all cells)"):
+        if label.startswith("bench"):
+            mov = bench.synthetic_raw(shape, 3000, dev)
+            tgt = bench.synthetic_raw(shape, 3001, dev)
+        else:
+            mov = torch.empty(shape, dtype=torch.float32, device=dev).uniform_(0.0, 1000.0, generator=g)
+            tgt = torch.empty(shape, dtype=torch.float32, device=dev).uniform_(0.0, 1000.0, generator=g)
+        t_lo, t_hi, m_lo, m_hi = float(tgt.min()), float(tgt.max()), float(mov.min()), float(mov.max())
+        other = torch.empty_like(mov)
+
+        def copy_both():
+            other.copy_(mov)
+            other.copy_(tgt)
+
+        copy_both()
+        copy_ms = _median_ms(copy_both, reps, torch)
+        copy_gbps = 16.0 * mov.numel() / copy_ms / 1e6
+        del other
+        records.append({"kernel": "device copy of the two volumes (torch copy_)", "input": label, "grid": list(shape),
+                        "ms": copy_ms, "GBps": copy_gbps})
+        for stride in (1, 4):
+            st = (ctypes.c_int * 3)(stride, stride, stride)
+            for bins in (32, 64):
+                out = torch.zeros((bins * bins + 1,), dtype=torch.int64, device=dev)
+                head = (mov.data_ptr(), z, y, x, tgt.data_ptr(), z, y, x, m12, st)
+                tail = (bins, d(t_lo), d(t_hi), d(m_lo), d(m_hi))
+
+                def histogram():
+                    _lib.call("lsr_affine_joint_histogram_f32", *head, *tail, out.data_ptr(), out.data_ptr() + 8 * bins * bins,
+                              _lib.stream_ptr(dev))
+
+                histogram()
+                hist_ms = _median_ms(histogram, reps, torch)
+                host = out.cpu().numpy()
+                n = int(host[-1])
+                hist = host[:-1].reshape(bins, bins).astype(np.float64)
+                dl = torch.as_tensor(estimate._mi_dl(hist)).to(dev)
+
+                def gradient():
+                    _lib.call("lsr_affine_mi_gradient_f32", *head, c3, d(scale), *tail, dl.data_ptr(), partial.data_ptr(),
+                              _lib.stream_ptr(dev))
+
+                gradient()
+                grad_ms = _median_ms(gradient, reps, torch)
+                samples = -(-z // stride) * -(-y // stride) * -(-x // stride)
+                nbytes = 4.0 * samples + 4.0 * min(mov.numel(), 8 * samples)
+                rec = {"kernel": "lsr_affine_joint_histogram_f32 / lsr_affine_mi_gradient_f32", "input": label, "grid": list(shape),
+                       "stride": stride, "bins": bins, "samples": samples, "counted": n,
+                       "largest_cell_share": float(hist.max() / max(hist.sum(), 1.0)), "nonzero_cells": int((hist > 0).sum()),
+                       "histogram_ms": hist_ms, "gradient_ms": grad_ms, "histogram_Gsamples_per_s": samples / hist_ms / 1e6,
+                       "gradient_Gsamples_per_s": samples / grad_ms / 1e6,
+                       "histogram_frac_of_copy_rate": nbytes / hist_ms / 1e6 / copy_gbps,
+                       "mutual_information": estimate.mutual_information(hist)}
+                if bins == 32:
+                    fn = lambda: torch_histogram(mov, tgt, stride, bins, t_lo, t_hi, m_lo, m_hi)  # noqa: E731
+                    ref = fn()
+                    torch_ms = _median_ms(fn, reps, torch)
+                    rec.update({"torch_grid_sample_bincount_ms": torch_ms, "speedup_over_torch": torch_ms / hist_ms,
+                                "torch_total_over_kernel_total": float(ref.sum().item() * 65536.0 / max(hist.sum(), 1.0)),
+                                "max_cell_difference_from_torch_in_samples": float(np.abs(ref.cpu().numpy() - hist / 65536.0).max())})
+                    del ref
+                records.append(rec)
+                print(json.dumps(rec), flush=True)
+        del mov, tgt
+        torch.cuda.empty_cache()
+    stamp = {"sources": _lib.kernel_source_sha16(), "device": torch.cuda.get_device_name(dev), "reps": reps, "warmups": 2,
+             "library": str(_lib.LIB_PATH.name)}
+    path = ROOT / "profiles" / "mi_config3.jsonl"
+    with open(path, "a") as f:
+        for r in records:
+            f.write(json.dumps({**r, **stamp}) + "\n")
 
 
 def _peaks(args, torch, dev, g, oshape):
