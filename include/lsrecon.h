@@ -840,6 +840,36 @@ int lsr_psf_accumulate_f32(const float* vol, int64_t Z, int64_t Y, int64_t X, co
                            int pz, int py, int px, double* bead_stats, float* psf, lsr_stream_t stream);
 
 /*
+ * Per-bead Gaussian fits and the sub-voxel aligned PSF average (csrc/psf_fit.hip, csrc/psf_fit.hpp; shrimpy_amd/psf.py:
+ * fit_beads, average_psf_aligned).  PARITY UNPINNED as above; tests/psf_fit_ref.py restates both.
+ * lsr_bead_fit_f32: for each of the n_beads patches (odd extents <= 129, centred on the linear indices `centres`, device)
+ *   the unweighted least-squares fit of  m(r) = B + A exp(-1/2 (r - mu)^T W (r - mu)),  r = the voxel offset from the
+ *   centre voxel, by Levenberg-Marquardt with Marquardt's diagonal scaling in float64 (lambda from 1e-3, / 10 on an
+ *   accepted step, * 10 on a rejected one; at most max_iter >= 1 trial cost evaluations; start and stopping rule:
+ *   csrc/psf_fit.hpp).  One workgroup per bead, one launch.  fit (n_beads x 12 float64, device): B, A, mu_z, mu_y, mu_x,
+ *   w_zz, w_yy, w_xx, w_zy, w_zx, w_yx, then the final sum of squared residuals.  status (n_beads int, device): 0 converged,
+ *   1 iteration limit, 2 the damped system or the final W not positive definite, 3 some |mu_i| >= 1, 4 A <= 0, 5 a
+ *   non-finite voxel in the patch or a patch that does not fit the volume (nothing outside the volume is read); every
+ *   status but 0 leaves NaN in the bead's twelve numbers.  Device and twin agree to rounding (exp and the order of the
+ *   sums differ), not to the bit.
+ * lsr_psf_accumulate_shifted_f32: lsr_psf_accumulate_f32 with every patch moved by a sub-voxel offset before it is added:
+ *   c = patch - B goes through three separable circulant passes, x, then y, then z, out[i] = sum_j c[j] w[(i - j) mod N]
+ *   with j ascending in unfused float64; shifted / S is added in list order, psf = float(acc / used).  `weights`
+ *   (n_beads x (pz + py + px) float64, device; per bead the z, the y, then the x axis) are the CALLER's: for an offset mu
+ *   along an axis of N voxels w[k] = D_N(k + mu), D_N(t) = sin(pi t) / (N sin(pi t / N)), the periodic-sinc (Fourier)
+ *   shift -- an input, so that kernel and twin can be held to the same bits.  A bead with S <= 0, a patch that does not
+ *   fit or a non-finite weight contributes nothing.  bead_stats as lsr_psf_accumulate_f32 writes it.  Beads go through
+ *   `scratch` in batches of 64: lsr_psf_shift_scratch_bytes(n_beads, pz, py, px, &bytes) bytes of device memory, 8-byte
+ *   aligned (the float64 accumulator and two float64 patches per bead of a batch).  2 launches per batch + 2.
+ */
+int lsr_bead_fit_f32(const float* vol, int64_t Z, int64_t Y, int64_t X, const long long* centres, int64_t n_beads, int pz,
+                     int py, int px, int max_iter, double* fit, int* status, lsr_stream_t stream);
+int lsr_psf_shift_scratch_bytes(int64_t n_beads, int pz, int py, int px, int64_t* bytes);
+int lsr_psf_accumulate_shifted_f32(const float* vol, int64_t Z, int64_t Y, int64_t X, const long long* centres,
+                                   int64_t n_beads, int pz, int py, int px, double* bead_stats, const double* weights,
+                                   void* scratch, float* psf, lsr_stream_t stream);
+
+/*
  * One level of a multiscale pyramid (csrc/pyramid.hip, shrimpy_amd/pyramid.py): the 2x mean of the level above it,
  * factors (fz, 2, 2) with fz 1 or 2 (LSR_E_ARG otherwise) -- iohub's compute_pyramid is not vendored, PARITY UNPINNED,
  * the rule is defined here (tests/pyramid_ref.py restates it).  The output has ceil(n / f) voxels per axis
@@ -985,6 +1015,15 @@ int lsr_local_max_candidates_f32_cpu(const float* s, int64_t Z, int64_t Y, int64
 int lsr_psf_accumulate_f32_cpu(const float* vol, int64_t Z, int64_t Y, int64_t X, const long long* centres,
                                int64_t n_beads, int pz, int py, int px, double* bead_stats, float* psf,
                                lsr_stream_t stream);
+
+/* ... of the Gaussian fit and the shifted average (csrc/psf_fit.hip): the fit through the same steps (csrc/psf_fit.hpp)
+ * with the sums in C order -- the kernel's statuses, its parameters to rounding; the shifted average to the bit for the
+ * same weights.  Every pointer HOST memory, `scratch` unused. */
+int lsr_bead_fit_f32_cpu(const float* vol, int64_t Z, int64_t Y, int64_t X, const long long* centres, int64_t n_beads,
+                         int pz, int py, int px, int max_iter, double* fit, int* status, lsr_stream_t stream);
+int lsr_psf_accumulate_shifted_f32_cpu(const float* vol, int64_t Z, int64_t Y, int64_t X, const long long* centres,
+                                       int64_t n_beads, int pz, int py, int px, double* bead_stats, const double* weights,
+                                       void* scratch, float* psf, lsr_stream_t stream);
 
 /* ... of the pyramid level (csrc/pyramid.hip): the same window arithmetic from the same header, the same bits */
 int lsr_downsample2_f32_cpu(const float* in, int64_t Z, int64_t Y, int64_t X, float* out, int fz, lsr_stream_t stream);

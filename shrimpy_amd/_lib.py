@@ -150,6 +150,11 @@ SIGNATURES: dict[str, list] = {
                                      ctypes.c_void_p, ctypes.c_void_p, _stream],
     "lsr_psf_accumulate_f32": [_c_f32p, _i64, _i64, _i64, ctypes.c_void_p, _i64, _int, _int, _int, ctypes.c_void_p, _c_f32p,
                                _stream],
+    "lsr_bead_fit_f32": [_c_f32p, _i64, _i64, _i64, ctypes.c_void_p, _i64, _int, _int, _int, _int, ctypes.c_void_p,
+                         ctypes.c_void_p, _stream],
+    "lsr_psf_shift_scratch_bytes": [_i64, _int, _int, _int, ctypes.POINTER(ctypes.c_int64)],
+    "lsr_psf_accumulate_shifted_f32": [_c_f32p, _i64, _i64, _i64, ctypes.c_void_p, _i64, _int, _int, _int, ctypes.c_void_p,
+                                       ctypes.c_void_p, ctypes.c_void_p, _c_f32p, _stream],
     "lsr_downsample2_shape": [_i64, _i64, _i64, _int, ctypes.POINTER(ctypes.c_int64)],
     "lsr_downsample2_f32": [_c_f32p, _i64, _i64, _i64, _c_f32p, _int, _stream],
     "lsr_downsample2_u16": [ctypes.c_void_p, _i64, _i64, _i64, ctypes.c_void_p, _int, _stream],
@@ -236,6 +241,8 @@ for _name in ("lsr_deskew_f32", "lsr_deskew_u16", "lsr_deskew_cval", "lsr_affine
               "lsr_blosc_encode_device", "lsr_blosc_decode_device",
               # ... and of the bead detection and the PSF average (csrc/peaks.hip)
               "lsr_box_smooth_f32", "lsr_local_max_candidates_f32", "lsr_psf_accumulate_f32",
+              # ... and of the Gaussian fit and the shifted average (csrc/psf_fit.hip)
+              "lsr_bead_fit_f32", "lsr_psf_accumulate_shifted_f32",
               # ... and of the focus measure (csrc/focus.hip)
               "lsr_band_power_f32",
               # ... and of the pyramid level (csrc/pyramid.hip)

@@ -928,16 +928,25 @@ def run_estimate(source_path, target_path, output_path, source_channel=None, tar
 @click.option("--timepoint", type=int, default=0, show_default=True)
 @click.option("--channel", default=None, help="Channel name (default: the first).")
 @click.option("--io", "io_backend", type=click.Choice(["auto", "native", "iohub"]), default="auto", show_default=True)
-def characterize_psf(input_path, config, output_path, position, timepoint, channel, io_backend):
+@click.option("--gaussian-fit/--no-gaussian-fit", "gaussian_fit", default=None,
+              help="Fit a 3-D Gaussian to every isolated bead and to the average (overrides the YAML's gaussian_fit).")
+@click.option("--alignment", type=click.Choice(["voxel", "subvoxel"]), default=None,
+              help="Centre the patches on the peak voxel, or on the fitted sub-voxel centre (Fourier shift; implies the fit). "
+                   "Overrides the YAML's alignment.")
+def characterize_psf(input_path, config, output_path, position, timepoint, channel, io_backend, gaussian_fit, alignment):
     """Detect the beads of a volume and average them into a PSF (PARITY UNPINNED: the rule is this package's own)."""
-    click.echo(run_characterize(input_path, config, output_path, position, timepoint, channel, io_backend))
+    click.echo(run_characterize(input_path, config, output_path, position, timepoint, channel, io_backend,
+                                gaussian_fit=gaussian_fit, alignment=alignment))
 
 
 def run_characterize(input_path, config, output_path, position=None, timepoint: int = 0, channel=None,
-                     io_backend: str = "auto") -> dict:
+                     io_backend: str = "auto", gaussian_fit=None, alignment=None) -> dict:
     """Read one bead volume, characterise it (:func:`psf.characterize_psf`), write the PSF store -- HCS, position
     ``0/0/0``, array ``"0"``, T = C = 1, the input's scale: the layout ``DeconvolveSettings.load_psf`` reads -- with
-    ``peaks.csv`` (z, y, x, value, isolated, fwhm_z, fwhm_y, fwhm_x; widths in voxels) and ``report.json`` inside it."""
+    ``peaks.csv`` (z, y, x, value, isolated, fwhm_z, fwhm_y, fwhm_x; widths in voxels) and ``report.json`` inside it.
+    ``gaussian_fit`` / ``alignment`` (not None) override the YAML; when the fit ran, ``peaks.csv`` gains fit_status, mu_z,
+    mu_y, mu_x, fit_fwhm_z, fit_fwhm_y, fit_fwhm_x (along the axes) and fit_fwhm_p0, fit_fwhm_p1, fit_fwhm_p2 (principal,
+    widest first), and the report the fit's entries and the ``unfit`` indices."""
     import csv
     import json
 
@@ -948,6 +957,9 @@ def run_characterize(input_path, config, output_path, position=None, timepoint: 
     from .settings import CharacterizeSettings
 
     settings = CharacterizeSettings.from_yaml(config)
+    override = {k: v for k, v in (("gaussian_fit", gaussian_fit), ("alignment", alignment)) if v is not None}
+    if override:
+        settings = CharacterizeSettings(**dict(settings.model_dump(), **override))
     output_path = Path(output_path)
     if output_path.exists() and any(output_path.iterdir()):
         raise click.ClickException(f"-o: {output_path} exists and is not empty")
@@ -982,13 +994,22 @@ def run_characterize(input_path, config, output_path, position=None, timepoint: 
             out.write_volume(0, 0, psf)
         with open(output_path / "peaks.csv", "w", newline="") as f:
             w = csv.writer(f)
-            w.writerow(["z", "y", "x", "value", "isolated", "fwhm_z", "fwhm_y", "fwhm_x"])
-            for (z, y, x), v, iso, fw in zip(res.peaks, res.values, res.isolated, res.fwhm_vox_zyx):
-                w.writerow([int(z), int(y), int(x), repr(float(v)), int(iso)] + [repr(float(q)) for q in fw])
+            fit = res.fit
+            w.writerow(["z", "y", "x", "value", "isolated", "fwhm_z", "fwhm_y", "fwhm_x"] +
+                       ([] if fit is None else ["fit_status", "mu_z", "mu_y", "mu_x", "fit_fwhm_z", "fit_fwhm_y", "fit_fwhm_x",
+                                                "fit_fwhm_p0", "fit_fwhm_p1", "fit_fwhm_p2"]))
+            for i, ((z, y, x), v, iso, fw) in enumerate(zip(res.peaks, res.values, res.isolated, res.fwhm_vox_zyx)):
+                row = [int(z), int(y), int(x), repr(float(v)), int(iso)] + [repr(float(q)) for q in fw]
+                if fit is not None:
+                    row += [int(fit.status[i])] + [repr(float(q)) for q in (*fit.offset_zyx[i], *fit.fwhm_axis_zyx[i],
+                                                                            *fit.fwhm_principal[i])]
+                w.writerow(row)
         report = dict(res.report(), input=str(input_path), position=key, timepoint=int(timepoint),
                       channel=names[c] if names else str(c), volume_shape_zyx=[int(n) for n in volume.shape],
                       skipped=[int(i) for i in res.skipped], settings=settings.model_dump(mode="json"),
                       parity="UNPINNED: the detection rule is shrimpy_amd's own (biahub's _characterize_psf is not vendored)")
+        if res.unfit is not None:
+            report["unfit"] = [int(i) for i in res.unfit]
         with open(output_path / "report.json", "w") as f:
             json.dump(report, f, indent=1)
         return {"output": str(output_path), "n_peaks": report["n_peaks"], "n_isolated": report["n_isolated"],

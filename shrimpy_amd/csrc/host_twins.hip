@@ -16,6 +16,8 @@
 //   lsr_rl_accel_dots_f32_cpu / _predict_f32_cpu  <->  lsr_rl_accel_dots_f32 / _predict_f32  (rl_accel.hip)
 //   lsr_box_smooth_f32_cpu, lsr_local_max_candidates_f32_cpu, lsr_psf_accumulate_f32_cpu
 //                                             <->  the same names without _cpu         (peaks.hip)
+//   lsr_bead_fit_f32_cpu, lsr_psf_accumulate_shifted_f32_cpu
+//                                             <->  the same names without _cpu         (psf_fit.hip)
 //   lsr_band_power_f32_cpu                    <->  lsr_band_power_f32                  (focus.hip)
 //   lsr_downsample2_f32_cpu / _u16_cpu        <->  lsr_downsample2_f32 / _u16          (pyramid.hip)
 //   lsr_stitch_f32_cpu                        <->  lsr_stitch_f32                      (stitch.hip)
@@ -869,6 +871,193 @@ extern "C" int lsr_psf_accumulate_f32_cpu(const float* vol, int64_t Z, int64_t Y
       psf[e] = used > 0 ? static_cast<float>(acc / static_cast<double>(used)) : 0.0f;
     }
   });
+  return LSR_OK;
+}
+
+// ---- per-bead Gaussian fits and the Fourier-shifted average (psf_fit.hip): the steps of psf_fit.hpp ----
+#include "psf_fit.hpp"
+
+namespace {
+
+// B of one bead as bead_stats_kernel sums it: 256 strided partial sums, then the binary tree
+double face_mean(const float* corner, int64_t Y, int64_t X, int pz, int py, int px) {
+  namespace pk = lsr::peaks;
+  constexpr int kTree = pk::kTreeThreads;
+  const int n = pz * py * px;
+  double red[kTree];
+  for (int t = 0; t < kTree; ++t) {
+    double acc = 0.0;
+    for (int e = t; e < n; e += kTree) {
+      const int iz = e / (py * px), rem = e - iz * (py * px), iy = rem / px, ix = rem - iy * px;
+      if (pk::on_shell(iz, iy, ix, pz, py, px)) acc += static_cast<double>(corner[(iz * Y + iy) * X + ix]);
+    }
+    red[t] = acc;
+  }
+  for (int w = kTree / 2; w > 0; w >>= 1)
+    for (int t = 0; t < w; ++t) red[t] += red[t + w];
+  return red[0] / static_cast<double>(pk::shell_count(pz, py, px));
+}
+
+}  // namespace
+
+// The kernel's iteration with the sums taken voxel by voxel in C order: equal to the kernel's to rounding, not to the bit.
+extern "C" int lsr_bead_fit_f32_cpu(const float* vol, int64_t Z, int64_t Y, int64_t X, const long long* centres,
+                                    int64_t n_beads, int pz, int py, int px, int max_iter, double* fit, int* status,
+                                    lsr_stream_t) {
+  namespace pf = lsr::psffit;
+  namespace pk = lsr::peaks;
+  if (int rc = pf::check_bead_fit(vol, Z, Y, X, centres, n_beads, pz, py, px, max_iter, fit, status)) return rc;
+  const int n = pz * py * px, plane = py * px, hz = pz / 2, hy = py / 2, hx = px / 2;
+  parallel_ranges(n_beads, [&](int64_t first, int64_t last) {
+    pf::Lm lm;
+    for (int64_t b = first; b < last; ++b) {
+      double* out = fit + pf::kFitOut * b;
+      int64_t z0 = 0, y0 = 0, x0 = 0;
+      bool ok = pk::patch_origin(centres[b], Z, Y, X, pz, py, px, z0, y0, x0);
+      const float* corner = ok ? vol + (z0 * Y + y0) * X + x0 : nullptr;
+      auto at = [&](int e, int& iz, int& iy, int& ix) {
+        iz = e / plane;
+        const int rem = e - iz * plane;
+        iy = rem / px;
+        ix = rem - iy * px;
+        return corner[(iz * Y + iy) * X + ix];
+      };
+      int iz, iy, ix;
+      for (int e = 0; ok && e < n; ++e) ok = std::isfinite(at(e, iz, iy, ix));
+      if (!ok) {
+        for (int k = 0; k < pf::kFitOut; ++k) out[k] = std::numeric_limits<double>::quiet_NaN();
+        status[b] = pf::kBadInput;
+        continue;
+      }
+      const double bg = face_mean(corner, Y, X, pz, py, px);
+      const double centre = static_cast<double>(corner[(hz * Y + hy) * X + hx]), cut = bg + 0.5 * (centre - bg);
+      double s[pf::kSums] = {};
+      for (int e = 0; e < n; ++e) {
+        const double g = static_cast<double>(at(e, iz, iy, ix)) - cut;
+        if (g > 0.0) {
+          const double rz = iz - hz, ry = iy - hy, rx = ix - hx;
+          s[0] += g;
+          s[1] += g * rz; s[2] += g * ry; s[3] += g * rx;
+          s[4] += g * rz * rz; s[5] += g * ry * ry; s[6] += g * rx * rx;
+        }
+      }
+      int action = pf::lm_start(lm, bg, centre, s, max_iter) ? pf::kNeedSums : pf::kDone;
+      double t[pf::kParams];
+      while (action != pf::kDone) {
+        if (action == pf::kNeedSums) {
+          for (int k = 0; k < pf::kParams; ++k) t[k] = lm.theta[k];
+          for (int k = 0; k < pf::kSums; ++k) s[k] = 0.0;
+          for (int e = 0; e < n; ++e) {
+            const double v = static_cast<double>(at(e, iz, iy, ix));
+            pf::add_voxel<true>(t, v, iz - hz, iy - hy, ix - hx, s);
+          }
+          for (int k = 0; k < pf::kSums; ++k) lm.sums[k] = s[k];
+          lm.cost = s[pf::kSums - 1];
+        }
+        if (!pf::lm_solve(lm)) break;
+        for (int k = 0; k < pf::kParams; ++k) t[k] = lm.trial[k];
+        s[pf::kSums - 1] = 0.0;
+        for (int e = 0; e < n; ++e) {
+          const double v = static_cast<double>(at(e, iz, iy, ix));
+          pf::add_voxel<false>(t, v, iz - hz, iy - hy, ix - hx, s);
+        }
+        action = pf::lm_judge(lm, s[pf::kSums - 1]);
+      }
+      status[b] = pf::lm_finish(lm, out);
+    }
+  });
+  return LSR_OK;
+}
+
+extern "C" int lsr_psf_accumulate_shifted_f32_cpu(const float* vol, int64_t Z, int64_t Y, int64_t X, const long long* centres,
+                                                  int64_t n_beads, int pz, int py, int px, double* bead_stats,
+                                                  const double* weights, void* /* scratch: unused */, float* psf,
+                                                  lsr_stream_t) {
+  namespace pf = lsr::psffit;
+  namespace pk = lsr::peaks;
+  if (int rc = pf::check_psf_shift(vol, Z, Y, X, centres, n_beads, pz, py, px, bead_stats, weights, psf)) return rc;
+  const int n = pz * py * px, plane = py * px, nw = pz + py + px;
+  // (B, S) as lsr_psf_accumulate_f32_cpu computes them: the same tree
+  constexpr int kTree = pk::kTreeThreads;
+  parallel_ranges(n_beads, [&](int64_t first, int64_t last) {
+    double red[kTree];
+    for (int64_t b = first; b < last; ++b) {
+      int64_t z0 = 0, y0 = 0, x0 = 0;
+      if (!pk::patch_origin(centres[b], Z, Y, X, pz, py, px, z0, y0, x0)) {
+        bead_stats[2 * b] = bead_stats[2 * b + 1] = 0.0;
+        continue;
+      }
+      const float* corner = vol + (z0 * Y + y0) * X + x0;
+      const double bg = face_mean(corner, Y, X, pz, py, px);
+      for (int t = 0; t < kTree; ++t) {
+        double acc = 0.0;
+        for (int e = t; e < n; e += kTree) {
+          const int iz = e / plane, rem = e - iz * plane, iy = rem / px, ix = rem - iy * px;
+          acc += static_cast<double>(corner[(iz * Y + iy) * X + ix]) - bg;
+        }
+        red[t] = acc;
+      }
+      for (int w = kTree / 2; w > 0; w >>= 1)
+        for (int t = 0; t < w; ++t) red[t] += red[t + w];
+      bead_stats[2 * b] = bg;
+      bead_stats[2 * b + 1] = red[0];
+    }
+  });
+  // a batch of shifted patches at a time (the result does not depend on the batch: beads are added in list order)
+  const int64_t batch = std::min<int64_t>(n_beads, std::max(1, lsr::g_host_threads.load()));
+  std::vector<double> acc, patches;
+  std::vector<char> use;
+  try {
+    acc.assign(static_cast<size_t>(n), 0.0);
+    patches.resize(static_cast<size_t>(2 * batch * n));
+    use.resize(static_cast<size_t>(batch));
+  } catch (const std::bad_alloc&) {
+    return lsr::fail(LSR_E_ARG, "lsr_psf_accumulate_shifted_f32_cpu: out of memory for %lld float64 patches of %d voxels",
+                     (long long)(2 * batch + 1), n);
+  }
+  int64_t used = 0;
+  for (int64_t first = 0; first < n_beads; first += batch) {
+    const int64_t count = std::min(batch, n_beads - first);
+    parallel_ranges(count, [&](int64_t lo, int64_t hi) {
+      for (int64_t slot = lo; slot < hi; ++slot) {
+        const int64_t b = first + slot;
+        const double* w = weights + b * nw;
+        bool ok = true;
+        for (int k = 0; k < nw; ++k) ok = ok && std::isfinite(w[k]);
+        int64_t z0 = 0, y0 = 0, x0 = 0;
+        const double bg = bead_stats[2 * b], total = bead_stats[2 * b + 1];
+        ok = ok && total > 0.0 && pk::patch_origin(centres[b], Z, Y, X, pz, py, px, z0, y0, x0);
+        use[slot] = ok;
+        if (!ok) continue;
+        const float* corner = vol + (z0 * Y + y0) * X + x0;
+        double* p0 = patches.data() + slot * 2 * n;
+        double* p1 = p0 + n;
+        const double *wz = w, *wy = w + pz, *wx = w + pz + py;
+        for (int e = 0; e < n; ++e) {
+          const int iz = e / plane, rem = e - iz * plane, iy = rem / px, ix = rem - iy * px;
+          p0[e] = pf::circulant(corner + (iz * Y + iy) * X, int64_t(1), bg, wx, px, ix);
+        }
+        for (int e = 0; e < n; ++e) {
+          const int iz = e / plane, rem = e - iz * plane, iy = rem / px, ix = rem - iy * px;
+          p1[e] = pf::circulant(p0 + iz * plane + ix, int64_t(px), 0.0, wy, py, iy);
+        }
+        for (int e = 0; e < n; ++e) {
+          const int iz = e / plane, rem = e - iz * plane;
+          p0[e] = pf::circulant(p1 + rem, int64_t(plane), 0.0, wz, pz, iz);
+        }
+      }
+    });
+    parallel_ranges(n, [&](int64_t lo, int64_t hi) {
+      for (int64_t slot = 0; slot < count; ++slot) {
+        if (!use[slot]) continue;
+        const double total = bead_stats[2 * (first + slot) + 1];
+        const double* p0 = patches.data() + slot * 2 * n;
+        for (int64_t e = lo; e < hi; ++e) acc[e] += p0[e] / total;
+      }
+    });
+    for (int64_t slot = 0; slot < count; ++slot) used += use[slot] ? 1 : 0;
+  }
+  for (int e = 0; e < n; ++e) psf[e] = used > 0 ? static_cast<float>(acc[e] / static_cast<double>(used)) : 0.0f;
   return LSR_OK;
 }
 

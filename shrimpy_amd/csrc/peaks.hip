@@ -172,18 +172,7 @@ int launch_strided(bool fused, MaxArgs p, int64_t outer, hipStream_t s) {
 // ---- PSF averaging ----
 constexpr int kTree = lsr::peaks::kTreeThreads;
 
-__device__ __forceinline__ double tree_sum(double* red, double a) {
-  const int tid = threadIdx.x;
-  red[tid] = a;
-  __syncthreads();
-  for (int w = kTree / 2; w > 0; w >>= 1) {
-    if (tid < w) red[tid] += red[tid + w];
-    __syncthreads();
-  }
-  const double total = red[0];
-  __syncthreads();
-  return total;
-}
+using lsr::peaks::tree_sum;
 
 __global__ __launch_bounds__(kTree) void bead_stats_kernel(const float* __restrict__ vol, int64_t Z, int64_t Y, int64_t X,
                                                            const long long* __restrict__ centres, int pz, int py, int px,
@@ -236,6 +225,13 @@ __global__ __launch_bounds__(256) void psf_accumulate_kernel(const float* __rest
 }
 
 }  // namespace
+
+// the per-bead (B, S) of lsr_psf_accumulate_f32, for the shifted average of psf_fit.hip as well
+void lsr::peaks::launch_bead_stats(const float* vol, int64_t Z, int64_t Y, int64_t X, const long long* centres, int64_t n_beads,
+                                   int pz, int py, int px, double* bead_stats, hipStream_t st) {
+  hipLaunchKernelGGL(bead_stats_kernel, dim3(static_cast<unsigned>(n_beads)), dim3(kTree), 0, st, vol, Z, Y, X, centres, pz,
+                     py, px, bead_stats);
+}
 
 extern "C" int lsr_box_smooth_scratch_bytes(int64_t Z, int64_t Y, int64_t X, int64_t* bytes) {
   LSR_REQUIRE_PTR(bytes);
@@ -310,8 +306,7 @@ extern "C" int lsr_psf_accumulate_f32(const float* vol, int64_t Z, int64_t Y, in
                                       lsr_stream_t stream) {
   if (int rc = lsr::peaks::check_psf_accumulate(vol, Z, Y, X, centres, n_beads, pz, py, px, bead_stats, psf)) return rc;
   hipStream_t st = lsr::as_stream(stream);
-  hipLaunchKernelGGL(bead_stats_kernel, dim3(static_cast<unsigned>(n_beads)), dim3(kTree), 0, st, vol, Z, Y, X, centres, pz,
-                     py, px, bead_stats);
+  lsr::peaks::launch_bead_stats(vol, Z, Y, X, centres, n_beads, pz, py, px, bead_stats, st);
   const int n = pz * py * px;
   hipLaunchKernelGGL(psf_accumulate_kernel, dim3(static_cast<unsigned>(lsr::ceil_div(n, 256))), dim3(256), 0, st, vol, Z, Y,
                      X, centres, static_cast<int>(n_beads), pz, py, px, bead_stats, psf);

@@ -35,12 +35,8 @@ inline int check_local_max(const float* s, int64_t Z, int64_t Y, int64_t X, int 
   return LSR_OK;
 }
 
-inline int check_psf_accumulate(const float* vol, int64_t Z, int64_t Y, int64_t X, const long long* centres, int64_t n,
-                                int pz, int py, int px, const double* bead_stats, const float* psf) {
-  LSR_REQUIRE_PTR(vol);
-  LSR_REQUIRE_PTR(centres);
-  LSR_REQUIRE_PTR(bead_stats);
-  LSR_REQUIRE_PTR(psf);
+// a list of n odd patches of (pz, py, px) voxels in a (Z, Y, X) volume: what every per-bead entry point takes
+inline int check_patches(int64_t Z, int64_t Y, int64_t X, int64_t n, int pz, int py, int px) {
   LSR_REQUIRE(Z > 0 && Y > 0 && X > 0, LSR_E_SHAPE, "shape (%lld,%lld,%lld) must be positive", (long long)Z, (long long)Y,
               (long long)X);
   LSR_REQUIRE_VOLUME(Z, Y, X);
@@ -52,6 +48,15 @@ inline int check_psf_accumulate(const float* vol, int64_t Z, int64_t Y, int64_t 
   LSR_REQUIRE(pz <= Z && py <= Y && px <= X, LSR_E_SHAPE, "patch (%d,%d,%d) is larger than the volume (%lld,%lld,%lld)", pz, py,
               px, (long long)Z, (long long)Y, (long long)X);
   return LSR_OK;
+}
+
+inline int check_psf_accumulate(const float* vol, int64_t Z, int64_t Y, int64_t X, const long long* centres, int64_t n,
+                                int pz, int py, int px, const double* bead_stats, const float* psf) {
+  LSR_REQUIRE_PTR(vol);
+  LSR_REQUIRE_PTR(centres);
+  LSR_REQUIRE_PTR(bead_stats);
+  LSR_REQUIRE_PTR(psf);
+  return check_patches(Z, Y, X, n, pz, py, px);
 }
 
 constexpr int kMaxBoxTaps = 2 * kMaxHalfWidth + 1;
@@ -92,6 +97,24 @@ __host__ __device__ inline int64_t shell_count(int pz, int py, int px) {
   const int64_t inner = (pz > 2 && py > 2 && px > 2) ? int64_t(pz - 2) * (py - 2) * (px - 2) : 0;
   return int64_t(pz) * py * px - inner;
 }
+
+// The fixed tree of the per-bead sums: every thread of a kTreeThreads workgroup brings one partial sum.
+__device__ __forceinline__ double tree_sum(double* red, double a) {
+  const int tid = threadIdx.x;
+  red[tid] = a;
+  __syncthreads();
+  for (int w = kTreeThreads / 2; w > 0; w >>= 1) {
+    if (tid < w) red[tid] += red[tid + w];
+    __syncthreads();
+  }
+  const double total = red[0];
+  __syncthreads();
+  return total;
+}
+
+// bead_stats_kernel of peaks.hip on `st`: (B, S) per bead
+void launch_bead_stats(const float* vol, int64_t Z, int64_t Y, int64_t X, const long long* centres, int64_t n_beads, int pz,
+                       int py, int px, double* bead_stats, hipStream_t st);
 
 }  // namespace peaks
 }  // namespace lsr

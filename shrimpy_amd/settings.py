@@ -304,6 +304,11 @@ class CharacterizeSettings(_StrictModel):
     ``block_size``, ``nms_distance`` and ``device`` are accepted for call-site compatibility and **unused**: they
     parametrise biahub's block-pooling detector, detection here is an exact sliding window and runs where the volume is.
     ``axis_labels`` is recorded in the report only.
+
+    ``gaussian_fit``: also fit a 3-D Gaussian to every isolated bead and to the average (``psf.fit_beads``: centres,
+    widths along the axes and along the principal axes); ``alignment``: ``"voxel"`` centres the patches on the peak
+    voxel, ``"subvoxel"`` moves each onto its fitted centre with a Fourier shift before averaging (and implies the
+    fit); ``fit_max_iter``: the fit's iteration limit.  These three are this package's own, not the reference's.
     """
 
     block_size: tuple[PositiveInt, PositiveInt, PositiveInt] = (8, 8, 8)
@@ -316,6 +321,9 @@ class CharacterizeSettings(_StrictModel):
     device: str = "cuda"
     axis_labels: tuple[str, str, str] = ("Z", "Y", "X")
     patch_size: Optional[tuple[PositiveFloat, PositiveFloat, PositiveFloat]] = None
+    gaussian_fit: bool = False
+    alignment: Literal["voxel", "subvoxel"] = "voxel"
+    fit_max_iter: PositiveInt = 100
 
     @field_validator("blur_kernel_size")
     @classmethod

@@ -69,6 +69,11 @@ def main():
                     "(grid_sample + bincount) and a device copy of the two volumes in the same run (median of 5 launches "
                     "between HIP events after 2 warm-ups); appended to profiles/mi_config3.jsonl")
     ap.add_argument("--mi-grid", default="256,2048,2048", help="Z,Y,X of the --mi section (BASELINE config 3)")
+    ap.add_argument("--psf-fit", action="store_true", help="only: ms of lsr_bead_fit_f32 and of lsr_psf_accumulate_shifted_f32 for "
+                    "500 and 2000 beads at patches 15x19x19 and 31x37x19 (median of --reps launches between HIP events after a "
+                    "warm-up), and the wall time of their host twins on --host-threads threads; appended to "
+                    "profiles/psf_fit.jsonl")
+    ap.add_argument("--host-threads", type=int, default=16, help="threads of the host twins in the --psf-fit section")
     ap.add_argument("--psf-sweep-wide", action="store_true", help="with --psf-sweep: every pz for in-plane extents 9-15")
     args = ap.parse_args()
 
@@ -83,6 +88,9 @@ def main():
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(3)
 
+    if args.psf_fit:
+        _psf_fit(args, torch, dev)
+        return
     if args.mi:
         _mi(args, torch, dev, g, bench, tuple(int(v) for v in args.mi_grid.split(",")))
         return
@@ -413,6 +421,88 @@ def _pyramid(args, torch, dev, g, oshape):
                     "ms": sum(r["ms"] for r in records[1:]), "avg_pool3d_ms": sum(r["avg_pool3d_ms"] for r in records[1:])})
     stamp = {"sources": _lib.kernel_source_sha16(), "device": torch.cuda.get_device_name(dev), "reps": reps}
     path = ROOT / "profiles" / "pyramid_config2.jsonl"
+    with open(path, "a") as f:
+        for r in records:
+            line = json.dumps({**r, **stamp})
+            print(line, flush=True)
+            f.write(line + "\n")
+
+
+def _psf_fit(args, torch, dev):
+    """Gaussian fits and the shifted average (csrc/psf_fit.hip): one bead per patch-sized cell of a synthetic volume -- a
+    tilted Gaussian (principal sigmas 1.8, 1.0, 0.9 voxels) at a random sub-voxel offset, amplitude 1000-3000 on a background
+    of 100 with noise of sigma 10 -- fitted from the cell's centre voxel, then averaged with the fitted offsets."""
+    import time
+
+    from shrimpy_amd import _lib, psf
+
+    reps = max(args.reps, 5)
+    records = []
+    for patch in ((15, 19, 19), (31, 37, 19)):
+        for n in (500, 2000):
+            cells = (5, 10, n // 50)
+            gen = torch.Generator(device=dev).manual_seed(11)
+            mu = torch.rand((n, 3), generator=gen, device=dev, dtype=torch.float64) - 0.5
+            amp = 1000.0 + 2000.0 * torch.rand(n, generator=gen, device=dev, dtype=torch.float64)
+            a = np.deg2rad(20.0)
+            axes = np.array([[np.cos(a), 0.0, np.sin(a)], [0.0, 1.0, 0.0], [-np.sin(a), 0.0, np.cos(a)]])
+            w = torch.from_numpy((axes.T / np.array([1.8, 1.0, 0.9]) ** 2) @ axes).to(dev)
+            grid = torch.stack(torch.meshgrid(*[torch.arange(m, device=dev, dtype=torch.float64) - m // 2 for m in patch],
+                                              indexing="ij"), dim=-1)
+            d = grid[None] - mu[:, None, None, None, :]
+            beads = 100.0 + amp[:, None, None, None] * torch.exp(-0.5 * torch.einsum("...i,ij,...j->...", d, w, d))
+            beads = beads + 10.0 * torch.randn(beads.shape, generator=gen, device=dev, dtype=torch.float64)
+            vol = beads.reshape(*cells, *patch).permute(0, 3, 1, 4, 2, 5).reshape(cells[0] * patch[0], cells[1] * patch[1],
+                                                                                  cells[2] * patch[2]).float().contiguous()
+            del beads, d
+            idx = np.stack(np.meshgrid(*[np.arange(c) for c in cells], indexing="ij"), axis=-1).reshape(-1, 3)
+            peaks = idx * np.array(patch) + np.array(patch) // 2
+            fits = psf.fit_beads(vol, peaks, patch)
+            shape = tuple(int(v) for v in vol.shape)
+            centres = torch.from_numpy(psf._centres(peaks, shape)).to(dev)
+            fit = torch.empty((n, 12), dtype=torch.float64, device=dev)
+            status = torch.empty(n, dtype=torch.int32, device=dev)
+
+            def launch_fit():
+                _lib.call("lsr_bead_fit_f32", vol.data_ptr(), *shape, centres.data_ptr(), n, *patch, 100, fit.data_ptr(),
+                          status.data_ptr(), _lib.stream_ptr(dev))
+
+            fit_ms = _median_ms(launch_fit, reps, torch)
+            weights = torch.from_numpy(np.ascontiguousarray(np.concatenate(
+                [psf.shift_weights(np.nan_to_num(fits.offset_zyx[:, k]), m) for k, m in enumerate(patch)], axis=1))).to(dev)
+            nbytes = ctypes.c_int64(0)
+            _lib.call("lsr_psf_shift_scratch_bytes", n, *patch, ctypes.byref(nbytes))
+            scratch = torch.empty(nbytes.value // 8, dtype=torch.float64, device=dev)
+            stats = torch.empty((n, 2), dtype=torch.float64, device=dev)
+            out = torch.empty(patch, dtype=torch.float32, device=dev)
+
+            def launch_shift():
+                _lib.call("lsr_psf_accumulate_shifted_f32", vol.data_ptr(), *shape, centres.data_ptr(), n, *patch, stats.data_ptr(),
+                          weights.data_ptr(), scratch.data_ptr(), out.data_ptr(), _lib.stream_ptr(dev))
+
+            def launch_plain():
+                _lib.call("lsr_psf_accumulate_f32", vol.data_ptr(), *shape, centres.data_ptr(), n, *patch, stats.data_ptr(),
+                          out.data_ptr(), _lib.stream_ptr(dev))
+
+            shift_ms, plain_ms = _median_ms(launch_shift, reps, torch), _median_ms(launch_plain, reps, torch)
+            _lib.call("lsr_set_host_threads", int(args.host_threads))
+            host = vol.cpu()
+            t0 = time.perf_counter()
+            twin = psf.fit_beads(host, peaks, patch)
+            t1 = time.perf_counter()
+            psf._average_shifted(host, peaks, np.nan_to_num(twin.offset_zyx), patch)
+            t2 = time.perf_counter()
+            err = np.abs(fits.offset_zyx - mu.cpu().numpy())[fits.status == 0]
+            records.append({"kernel": "lsr_bead_fit_f32 / lsr_psf_accumulate_shifted_f32", "beads": n, "patch": list(patch),
+                            "volume": list(shape), "fit_ms": fit_ms, "shifted_average_ms": shift_ms, "plain_average_ms": plain_ms,
+                            "twin_fit_ms": 1e3 * (t1 - t0), "twin_shifted_average_ms": 1e3 * (t2 - t1),
+                            "host_threads": int(args.host_threads), "converged": int((fits.status == 0).sum()),
+                            "statuses_equal_the_twins": bool(np.array_equal(fits.status, twin.status)),
+                            "median_centre_error_vox": float(np.median(err)) if len(err) else None,
+                            "scratch_MB": nbytes.value / 1e6})
+            del vol, scratch
+    stamp = {"sources": _lib.kernel_source_sha16(), "device": torch.cuda.get_device_name(dev), "reps": reps}
+    path = ROOT / "profiles" / "psf_fit.jsonl"
     with open(path, "a") as f:
         for r in records:
             line = json.dumps({**r, **stamp})
