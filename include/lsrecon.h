@@ -919,6 +919,44 @@ int lsr_stitch_f32(const void* table, int n_tiles, float* out, const int64_t box
                    int p, float cval, lsr_stream_t stream);
 
 /*
+ * Connected-component labelling and the object table (csrc/label.hip, shrimpy_amd/segment.py).  The oracle is
+ * scipy.ndimage.label (tests/label_ref.py), held to exact equality.
+ *   Foreground is in[v] > threshold: NaN and the threshold itself are background.  connectivity is 6, 18 or 26, the
+ *   neighbourhoods scipy.ndimage.generate_binary_structure(3, 1 | 2 | 3) (LSR_E_ARG otherwise).  labels (int32, Z * Y * X)
+ *   receives 0 on the background and 1 .. N on the components, numbered in raster (C-order) rank of each component's
+ *   lowest linear index; *n_objects (int32, device memory for lsr_label_f32) receives N.  A volume holds at most
+ *   2^31 - 1 voxels (LSR_E_UNSUPPORTED beyond); a NULL pointer is LSR_E_NULL, a non-positive extent LSR_E_SHAPE.
+ * lsr_label_tile_shape: the (z, y, x) tile one workgroup labels in LDS.  lsr_label_scratch_bytes: the size of `scratch`
+ * (device memory; its contents on entry do not matter), or a negative status for a shape out of range.
+ * lsr_label_f32 runs seven launches on `stream` -- local (one tile per workgroup, the threshold fused into the load),
+ * merge (unions across tile faces, atomicMin on the parent words), flatten, count, scan, rank, final -- with the
+ * union-find kept in `labels` itself; no workgroup ever waits for another (csrc/label.hip states the two rules).
+ *
+ * lsr_label_regions_f32: one 96-byte record per label 1 .. n_objects, in `table`, which the CALLER HAS ZEROED:
+ *   int64 volume; int64 sum_z, sum_y, sum_x; float64 sum_v, sum_vz, sum_vy, sum_vx; int32 lo[3], hi[3] (the bounding box,
+ *   half-open); float32 v_min, v_max.
+ * The integer fields and the intensity range are exact and independent of the order of accumulation (integer atomics;
+ * min / max on the order-preserving integer image of the float); the float64 sums are float64 atomic adds of per-wave
+ * partial sums: within n_k * 2^-53 * sum|terms| of the exact sum, not reproducible to the bit.  `intensity` may be NULL:
+ * the intensity fields then stay zero.  A label outside 1 .. n_objects is ignored; a label no voxel carries keeps a zero
+ * record.  n_objects == 0 returns at once (table may be NULL).  Two launches.
+ *
+ * lsr_label_remap_i32: labels[v] = map[labels[v]] in place, map holding n_map int32 entries (map[0] is the background's
+ * and must be 0; a label outside 0 .. n_map - 1 becomes 0).  One launch.
+ */
+int lsr_label_tile_shape(int zyx[3]);
+int lsr_label_scratch_bytes(int64_t Z, int64_t Y, int64_t X);
+int lsr_label_f32(const float* in, int64_t Z, int64_t Y, int64_t X, float threshold, int connectivity, int32_t* labels,
+                  int32_t* n_objects, void* scratch, lsr_stream_t stream);
+int lsr_label_regions_f32(const int32_t* labels, const float* intensity, int64_t Z, int64_t Y, int64_t X, int64_t n_objects,
+                          void* table, lsr_stream_t stream);
+int lsr_label_remap_i32(int32_t* labels, int64_t n, const int32_t* map, int64_t n_map, lsr_stream_t stream);
+/* measurement only (tools/bench_kernels.py --label): lsr_label_f32 with a HIP event between its launches; waits for the
+ * stream and writes the times of local, merge, flatten, count, scan, rank and final in milliseconds to ms7 (HOST memory) */
+int lsr_label_profile_f32(const float* in, int64_t Z, int64_t Y, int64_t X, float threshold, int connectivity, int32_t* labels,
+                          int32_t* n_objects, void* scratch, float* ms7, lsr_stream_t stream);
+
+/*
  * Host twins (csrc/host_twins.hip): the same signatures with HOST pointers, the same argument checks and the
  * same arithmetic in the same order, so the results equal the device entry points' bit for bit.  They serve
  * the boxes where the reference itself resolves to the CPU (shrimpy/preprocessing.py:78-82 -- its CI has no
@@ -1032,6 +1070,14 @@ int lsr_downsample2_u16_cpu(const uint16_t* in, int64_t Z, int64_t Y, int64_t X,
 /* ... of the stitching composite (csrc/stitch.hip): table and tiles in HOST memory (the table's entries are checked here) */
 int lsr_stitch_f32_cpu(const void* table, int n_tiles, float* out, const int64_t box_origin[3], const int64_t box_shape[3],
                        int p, float cval, lsr_stream_t stream);
+
+/* ... of the labelling (csrc/label.hip): plain sequential code, scipy.ndimage.label's labels, the kernels' integer fields and
+ * intensity range; the float64 sums in raster order.  Every pointer HOST memory, `scratch` unused (but required). */
+int lsr_label_f32_cpu(const float* in, int64_t Z, int64_t Y, int64_t X, float threshold, int connectivity, int32_t* labels,
+                      int32_t* n_objects, void* scratch, lsr_stream_t stream);
+int lsr_label_regions_f32_cpu(const int32_t* labels, const float* intensity, int64_t Z, int64_t Y, int64_t X,
+                              int64_t n_objects, void* table, lsr_stream_t stream);
+int lsr_label_remap_i32_cpu(int32_t* labels, int64_t n, const int32_t* map, int64_t n_map, lsr_stream_t stream);
 
 /* ... of the mutual-information metric (csrc/estimate_mi.hip): the per-sample rule of csrc/mi_sample.hpp on both sides.
  * The histogram and the count are the kernel's bits; the gradient rows are sums over lsr_affine_mi_gradient_blocks()

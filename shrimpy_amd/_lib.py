@@ -165,6 +165,13 @@ SIGNATURES: dict[str, list] = {
     "lsr_stitch_prepare_table": [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_int64), _f64p, _int, ctypes.c_void_p],
     "lsr_stitch_f32": [ctypes.c_void_p, _int, _c_f32p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _int, _f32,
                        _stream],
+    "lsr_label_tile_shape": [ctypes.POINTER(ctypes.c_int)],
+    "lsr_label_scratch_bytes": [_i64, _i64, _i64],
+    "lsr_label_f32": [_c_f32p, _i64, _i64, _i64, _f32, _int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _stream],
+    "lsr_label_profile_f32": [_c_f32p, _i64, _i64, _i64, _f32, _int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                              ctypes.POINTER(ctypes.c_float), _stream],
+    "lsr_label_regions_f32": [ctypes.c_void_p, _c_f32p, _i64, _i64, _i64, _i64, ctypes.c_void_p, _stream],
+    "lsr_label_remap_i32": [ctypes.c_void_p, _i64, ctypes.c_void_p, _i64, _stream],
     "lsr_crc32c_host": [ctypes.c_void_p, _i64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)],
     "lsr_crc32c_host_portable": [ctypes.c_void_p, _i64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)],
     "lsr_average_slices_f32": [_c_f32p, _i64, _i64, _i64, _c_f32p, _i64, _int, _stream],
@@ -248,7 +255,9 @@ for _name in ("lsr_deskew_f32", "lsr_deskew_u16", "lsr_deskew_cval", "lsr_affine
               # ... and of the pyramid level (csrc/pyramid.hip)
               "lsr_downsample2_f32", "lsr_downsample2_u16",
               # ... and of the stitching composite (csrc/stitch.hip)
-              "lsr_stitch_f32"):
+              "lsr_stitch_f32",
+              # ... and of the labelling and the object table (csrc/label.hip)
+              "lsr_label_f32", "lsr_label_regions_f32", "lsr_label_remap_i32"):
     SIGNATURES[_name + "_cpu"] = SIGNATURES[_name]
 SIGNATURES["lsr_rl_tv_scale_f32_cpu"] = SIGNATURES["lsr_rl_tv_scale_f32"][:-1]     # (this twin takes no stream)
 for _name in ("lsr_rl_accel_dots_f32", "lsr_rl_accel_predict_f32",                     # (nor do these)

@@ -28,6 +28,7 @@ from __future__ import annotations
 import functools
 import logging
 import os
+import time
 
 from pathlib import Path
 
@@ -1457,6 +1458,147 @@ def run_stitch(input_path, config, output_path, positions=(), zarr_version: str 
         return {"rank": rank, "world_size": world, "units": len(report.units), "units_total": len(units),
                 "units_skipped": len(units) - len(todo), "failed": failed, "seconds": report.seconds,
                 "job_seconds": report.max_seconds, "wells": {out_keys[w]: list(geometry[w][0]) for w in wells}}
+    finally:
+        if created:
+            import torch.distributed as dist
+
+            dist.destroy_process_group()
+
+
+OBJECT_COLUMNS = ("t", "label", "volume_voxels", "volume_um3", "bbox_z0", "bbox_y0", "bbox_x0", "bbox_z1", "bbox_y1", "bbox_x1",
+                  "centroid_z", "centroid_y", "centroid_x", "centroid_z_um", "centroid_y_um", "centroid_x_um",
+                  "intensity_sum", "intensity_mean", "intensity_min", "intensity_max",
+                  "weighted_centroid_z", "weighted_centroid_y", "weighted_centroid_x")
+
+
+def object_rows(t: int, table: dict, scale_zyx, translation_zyx) -> list[list]:
+    """The ``objects.csv`` rows of one timepoint's table (``segment.region_table`` with intensities), in
+    ``OBJECT_COLUMNS`` order.  Physical centroids are ``translation + centroid * scale`` of the position's level 0."""
+    sz, sy, sx = (float(v) for v in scale_zyx)
+    rows = []
+    for k in range(len(table["label"])):
+        c = table["centroid"][k]
+        um = [float(o) + float(v) * sc for o, v, sc in zip(translation_zyx, c, (sz, sy, sx))]
+        rows.append([int(t), int(table["label"][k]), int(table["volume"][k]), float(table["volume"][k]) * sz * sy * sx,
+                     *(int(v) for v in table["bbox"][k]), *(float(v) for v in c), *um,
+                     float(table["intensity_sum"][k]), float(table["intensity_mean"][k]), float(table["intensity_min"][k]),
+                     float(table["intensity_max"][k]), *(float(v) for v in table["weighted_centroid"][k])])
+    return rows
+
+
+@cli.command(cls=_eat_all_command("-i", "--input-position-dirpaths"))
+@click.option("-i", "--input-position-dirpaths", "input_path", required=True, multiple=True, type=click.UNPROCESSED,
+              help="Input OME-Zarr store (HCS plate or single FOV), or the position directories of one plate.")
+@click.option("-c", "--config-filepath", "config", required=True, type=click.Path(exists=True, dir_okay=False, path_type=Path),
+              help="SegmentSettings YAML.")
+@click.option("-o", "--output-dirpath", "output_path", required=True, type=click.Path(path_type=Path),
+              help="Output OME-Zarr store of int32 labels (must not exist); objects.csv is written beside each position's array.")
+@click.option("-p", "--position", "positions", multiple=True, help='Restrict to these position keys ("row/col/fov"); repeatable.')
+@click.option("--zarr-version", type=click.Choice(["0.4", "0.5"]), default="0.5", show_default=True,
+              help="NGFF version of the output store.")
+@click.option("--io", "io_backend", type=click.Choice(["auto", "native", "iohub"]), default="auto", show_default=True,
+              help="Store access for the input: this package's reader, iohub, or native with iohub as the fallback.")
+@click.option("--compression", type=click.Choice(["none", "gzip", "zstd", "blosc-zstd"]), default="blosc-zstd", show_default=True,
+              help="Chunk compression of the output.")
+def segment(input_path, config, output_path, positions, zarr_version, io_backend, compression):
+    """Label the connected components of one thresholded channel and measure them (config: a SegmentSettings YAML).
+
+    Writes an int32 array "0" with the channel <channel_name>_labels per position, and objects.csv.  There is no --levels:
+    a mean pyramid of labels is meaningless (the mean of labels 2 and 4 is not label 3)."""
+    input_path, positions = _inputs(input_path, positions)
+    _finish(run_segment(input_path, config, output_path, positions, zarr_version, io_backend, compression))
+
+
+def run_segment(input_path, config, output_path, positions=(), zarr_version: str = "0.5", io_backend: str = "auto",
+                compression=None) -> dict:
+    """``segment``: every (position, t) volume of ``channel_name`` goes through ``segment.segment_zyx``; the labels are written
+    as ``int32`` (the input's ``scale`` and ``translation`` copied), the object tables of a position's timepoints as
+    ``<output>/<position>/objects.csv`` (``OBJECT_COLUMNS``).  Everything is checked before the output store is created; with
+    several ranks the positions are dealt out in turn.  The output is written by this package's own writer."""
+    import csv
+
+    import torch
+
+    from .io.omezarr import as_volume_array, open_ome_zarr, position_scale
+    from .segment import segment_zyx
+    from .settings import SegmentSettings
+
+    try:
+        settings = SegmentSettings.from_yaml(config)
+    except (ValueError, TypeError) as exc:
+        raise click.ClickException(f"{config}: {exc}") from exc
+    rank, world, device, created = _distributed()
+    try:
+        src, src_positions = _open_source(Path(input_path), io_backend)
+        try:
+            missing = [p for p in positions if p not in src_positions]
+            if missing:
+                raise click.ClickException(f"positions {missing} not found; available: {list(src_positions)}")
+            keys = [k for k in src_positions if not positions or k in positions]
+            if not keys:
+                raise click.ClickException("no positions to process")
+            arrays, channel, geometry = {}, {}, {}
+            for k in keys:
+                pos = src_positions[k]
+                names = list(pos.channel_names)
+                if settings.channel_name not in names:
+                    raise click.ClickException(f"channel_name {settings.channel_name!r} not in position {k} (it has {names})")
+                a = as_volume_array(pos["0"])
+                if len(a.shape) != 5:
+                    raise click.ClickException(f"position {k}: expected 5-D TCZYX data, got shape {tuple(a.shape)}")
+                if int(np.prod(a.shape[2:], dtype=np.int64)) > 2 ** 31 - 1:
+                    raise click.ClickException(f"position {k}: a volume of {tuple(a.shape[2:])} has more than 2^31 - 1 voxels")
+                arrays[k], channel[k] = a, names.index(settings.channel_name)
+                geometry[k] = (list(position_scale(pos)), list(_position_translation(pos)))
+            out_channel = f"{settings.channel_name}_labels"
+            error = None
+            if rank == 0:
+                try:
+                    if Path(output_path).exists() and any(Path(output_path).iterdir()):
+                        raise FileExistsError(f"{output_path} exists (never overwritten)")
+                    dst = open_ome_zarr(output_path, layout="hcs", mode="w", channel_names=[out_channel], version=zarr_version,
+                                        prefer_iohub=False)
+                    extra = {} if compression in (None, "none") else {"compress": compression}
+                    for k in keys:
+                        scale, translation = geometry[k]
+                        shape = (int(arrays[k].shape[0]), 1) + tuple(int(n) for n in arrays[k].shape[2:])
+                        dst.create_position(*k.split("/")).create_zeros("0", shape=shape, dtype="int32", scale=scale,
+                                                                        translation=translation if any(translation) else None,
+                                                                        **extra)
+                    dst.close()
+                except Exception as exc:  # noqa: BLE001 -- reported on every rank, see _agree
+                    error = f"{type(exc).__name__}: {exc}"
+            _agree(error)
+            dst = open_ome_zarr(output_path, layout="hcs", mode="a", channel_names=[out_channel], version=zarr_version,
+                                prefer_iohub=False)
+            dst_positions = dict(dst.positions())
+            counts = {}
+            t0 = time.perf_counter()
+            try:
+                for k in keys[rank::world]:
+                    out = as_volume_array(dst_positions[k]["0"])
+                    scale, translation = geometry[k]
+                    rows = []
+                    for t in range(int(arrays[k].shape[0])):
+                        vol = np.ascontiguousarray(arrays[k].read_volume(t, channel[k]), dtype=np.float32)
+                        labels, table, n = segment_zyx(torch.as_tensor(vol, device=device), settings)
+                        out.write_volume(t, 0, labels.cpu().numpy())
+                        rows += object_rows(t, table, scale[2:], translation[2:])
+                        counts.setdefault(k, []).append(int(n))
+                    with open(Path(output_path) / k / "objects.csv", "w", newline="") as fh:
+                        w = csv.writer(fh)
+                        w.writerow(OBJECT_COLUMNS)
+                        w.writerows([[repr(v) if isinstance(v, float) else v for v in row] for row in rows])
+            finally:
+                close = getattr(dst, "close", None)
+                if close:
+                    close()
+            return {"rank": rank, "world_size": world, "positions": len(keys[rank::world]), "objects": counts,
+                    "seconds": time.perf_counter() - t0, "failed": []}
+        finally:
+            close = getattr(src, "close", None)
+            if close:
+                close()
     finally:
         if created:
             import torch.distributed as dist

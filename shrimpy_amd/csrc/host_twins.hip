@@ -21,6 +21,8 @@
 //   lsr_band_power_f32_cpu                    <->  lsr_band_power_f32                  (focus.hip)
 //   lsr_downsample2_f32_cpu / _u16_cpu        <->  lsr_downsample2_f32 / _u16          (pyramid.hip)
 //   lsr_stitch_f32_cpu                        <->  lsr_stitch_f32                      (stitch.hip)
+//   lsr_label_f32_cpu, lsr_label_regions_f32_cpu, lsr_label_remap_i32_cpu
+//                                             <->  the same names without _cpu         (label.hip)
 //
 // Arithmetic (what "the same" means):
 //   resamplers -- the text the kernels compile (resample.hpp): coordinates, axis taps with their weights and the
@@ -1242,5 +1244,114 @@ extern "C" int lsr_stitch_f32_cpu(const void* table, int n_tiles, float* out, co
     }
   }, failed);
   LSR_REQUIRE(!failed.load(), LSR_E_ARG, "lsr_stitch_f32_cpu: out of memory for the row accumulators");
+  return LSR_OK;
+}
+
+// ---- labelling (label.hip): plain sequential code; scipy.ndimage.label's numbering, the kernels' integers ----
+#include "label.hpp"
+
+extern "C" int lsr_label_f32_cpu(const float* in, int64_t Z, int64_t Y, int64_t X, float threshold, int connectivity,
+                                 int32_t* labels, int32_t* n_objects, void* scratch, lsr_stream_t) {
+  namespace lb = lsr::label;
+  if (int rc = lb::check_label(in, Z, Y, X, connectivity, labels, n_objects, scratch)) return rc;
+  const int level = lb::level_of(connectivity);
+  const int64_t n = Z * Y * X, plane = Y * X;
+  int32_t* parent = labels;                    // a union-find rooted at the smallest index, as on the device
+  auto find = [&](int32_t a) {              // with path halving: a winding component stays near-linear
+    while (parent[a] != a) {
+      parent[a] = parent[parent[a]];
+      a = parent[a];
+    }
+    return a;
+  };
+  for (int64_t z = 0; z < Z; ++z) {
+    for (int64_t y = 0; y < Y; ++y) {
+      for (int64_t x = 0; x < X; ++x) {
+        const int64_t v = z * plane + y * X + x;
+        if (!(in[v] > threshold)) {
+          parent[v] = -1;
+          continue;
+        }
+        int32_t root = static_cast<int32_t>(v);
+        parent[v] = root;
+        for (int dz = -1; dz <= 0; ++dz) {
+          for (int dy = -1; dy <= 1; ++dy) {
+            for (int dx = -1; dx <= 1; ++dx) {
+              if (!lb::backward_neighbour(dz, dy, dx, level)) continue;
+              if (z + dz < 0 || y + dy < 0 || y + dy >= Y || x + dx < 0 || x + dx >= X) continue;
+              const int64_t t = v + dz * plane + dy * X + dx;
+              if (parent[t] < 0) continue;
+              const int32_t other = find(static_cast<int32_t>(t));
+              if (other == root) continue;
+              const int32_t lo = other < root ? other : root, hi = other < root ? root : other;
+              parent[hi] = lo;
+              root = lo;
+              parent[v] = lo;                   // (keeps the walk from v short)
+            }
+          }
+        }
+      }
+    }
+  }
+  // every chain is cut to its root, the roots are numbered in raster order (a numbered root holds -(label + 1), as on the
+  // device), and a root precedes every other voxel of its set
+  for (int64_t v = 0; v < n; ++v)
+    if (parent[v] >= 0) parent[v] = find(static_cast<int32_t>(v));
+  int32_t count = 0;
+  for (int64_t v = 0; v < n; ++v) {
+    const int32_t p = parent[v];
+    if (p < 0) continue;
+    if (p == v) parent[v] = -(++count) - 1;
+  }
+  for (int64_t v = 0; v < n; ++v) {
+    const int32_t p = labels[v];
+    labels[v] = p == -1 ? 0 : p < 0 ? -p - 1 : labels[p];       // (p < v is a root: it has its label already)
+  }
+  *n_objects = count;
+  return LSR_OK;
+}
+
+extern "C" int lsr_label_regions_f32_cpu(const int32_t* labels, const float* intensity, int64_t Z, int64_t Y, int64_t X,
+                                         int64_t n_objects, void* table, lsr_stream_t) {
+  namespace lb = lsr::label;
+  if (int rc = lb::check_regions(labels, Z, Y, X, n_objects, table)) return rc;
+  if (n_objects == 0) return LSR_OK;
+  lb::Region* rows = static_cast<lb::Region*>(table);
+  for (int64_t z = 0; z < Z; ++z) {
+    for (int64_t y = 0; y < Y; ++y) {
+      for (int64_t x = 0; x < X; ++x) {
+        const int64_t v = (z * Y + y) * X + x;
+        const int32_t l = labels[v];
+        if (l <= 0 || l > n_objects) continue;
+        lb::Region& r = rows[l - 1];
+        const int32_t c[3] = {static_cast<int32_t>(z), static_cast<int32_t>(y), static_cast<int32_t>(x)};
+        const bool first = r.volume == 0;
+        r.volume += 1;
+        for (int a = 0; a < 3; ++a) {
+          r.sum_zyx[a] += c[a];
+          r.lo[a] = first ? c[a] : std::min(r.lo[a], c[a]);
+          r.hi[a] = first ? c[a] + 1 : std::max(r.hi[a], c[a] + 1);
+        }
+        if (intensity == nullptr) continue;
+        const float f = intensity[v];
+        const double g = static_cast<double>(f);
+        r.sum_v += g;
+        for (int a = 0; a < 3; ++a) r.sum_vzyx[a] += g * c[a];
+        // (compared through the kernels' integer image, so that -0.0, +0.0 and NaNs fall where they fall on the device)
+        const uint32_t k = lb::float_key(f);
+        if (first || k < lb::float_key(r.v_min)) r.v_min = f;
+        if (first || k > lb::float_key(r.v_max)) r.v_max = f;
+      }
+    }
+  }
+  return LSR_OK;
+}
+
+extern "C" int lsr_label_remap_i32_cpu(int32_t* labels, int64_t n, const int32_t* map, int64_t n_map, lsr_stream_t) {
+  if (int rc = lsr::label::check_remap(labels, n, map, n_map)) return rc;
+  for (int64_t v = 0; v < n; ++v) {
+    const int32_t l = labels[v];
+    labels[v] = (l > 0 && l < n_map) ? map[l] : 0;
+  }
   return LSR_OK;
 }

@@ -1,0 +1,194 @@
+"""Segmentation: connected-component labels of a thresholded volume, one table row per object, and a filter.
+
+``csrc/label.hip`` labels on the device (a block-based union-find rooted at the smallest linear index, so that the
+numbering is a prefix count), ``csrc/host_twins.hip`` on the CPU; both equal ``scipy.ndimage.label`` element for element
+(``tests/label_ref.py``): foreground is ``vol > threshold`` (NaN and the threshold itself are background), labels are
+``1 .. N`` in raster order of each component's first voxel.
+
+* :func:`label_volume` -- ``(labels, n)``: an ``int32`` torch tensor on the volume's device and the object count.
+* :func:`region_table` -- per label: volume, bounding box (half-open), centroid, and with an intensity volume its sum,
+  mean, minimum, maximum and the intensity-weighted centroid.  The integer columns and the intensity range are exact; the
+  float64 sums are atomic adds on the device (within ``n_k * 2^-53 * sum|terms|`` of the exact sum, not bit-reproducible).
+* :func:`filter_objects` -- drop small objects or keep the largest; the kept labels stay consecutive, in their old order.
+* :func:`segment_zyx` -- threshold (a number or multi-Otsu, after an optional Gaussian blur), label, measure, filter.
+
+Not built: watershed or any splitting of touching objects, multi-GPU or slab labelling, tracking across timepoints, label
+pyramids, volumes above ``2^31 - 1`` voxels.
+"""
+
+from __future__ import annotations
+
+import ctypes
+
+import numpy as np
+
+from . import _lib
+
+__all__ = ["REGION_DTYPE", "tile_shape", "label_volume", "region_table", "filter_objects", "segment_zyx"]
+
+# one record of the object table (csrc/label.hpp ``Region``)
+REGION_DTYPE = np.dtype([("volume", "<i8"), ("sum_zyx", "<i8", (3,)), ("sum_v", "<f8"), ("sum_vzyx", "<f8", (3,)),
+                         ("lo", "<i4", (3,)), ("hi", "<i4", (3,)), ("v_min", "<f4"), ("v_max", "<f4")])
+assert REGION_DTYPE.itemsize == 96
+
+
+def tile_shape() -> tuple[int, int, int]:
+    """The ``(z, y, x)`` tile one workgroup labels in LDS (``lsr_label_tile_shape``)."""
+    zyx = (ctypes.c_int * 3)()
+    _lib.call("lsr_label_tile_shape", zyx)
+    return tuple(zyx)
+
+
+def _run(device, entry: str, *args) -> None:
+    import torch
+
+    if device.type == "cpu":
+        _lib.call(entry + "_cpu", *args, None)
+        return
+    with torch.cuda.device(device):
+        _lib.call(entry, *args, _lib.stream_ptr(device))
+
+
+def _check_volume(t, name: str, dtype):
+    import torch
+
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor, got {type(t).__name__}")
+    if t.dtype != dtype:
+        raise TypeError(f"{name} must be {dtype}, got {t.dtype}")
+    if t.dim() != 3:
+        raise ValueError(f"{name} must be (Z, Y, X), got shape {tuple(t.shape)}")
+    if t.device.type not in ("cpu", "cuda"):
+        raise ValueError(f"{name} is on {t.device}: a HIP device or the CPU")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    return t
+
+
+def label_volume(vol, threshold: float, connectivity: int = 6):
+    """Label the components of ``vol > threshold`` ((Z, Y, X) float32): ``(labels, n)``.
+
+    ``labels`` is a new ``int32`` tensor on ``vol``'s device (0 on the background, ``1 .. n`` in raster order of each
+    component's first voxel); ``n`` is a Python int (one small device-to-host copy).  ``connectivity`` is 6 (scipy's
+    default), 18 or 26."""
+    import torch
+
+    vol = _check_volume(vol, "vol", torch.float32)
+    z, y, x = (int(v) for v in vol.shape)
+    if connectivity not in (6, 18, 26):
+        raise ValueError(f"connectivity must be 6, 18 or 26, got {connectivity!r}")
+    if min(z, y, x) <= 0:
+        raise ValueError(f"vol must not be empty, got shape {(z, y, x)}")
+    scratch_bytes = _lib.call_value("lsr_label_scratch_bytes", z, y, x)
+    if scratch_bytes < 0:
+        _lib.call("lsr_label_scratch_bytes", z, y, x)       # (raises with the library's message)
+    labels = torch.empty((z, y, x), dtype=torch.int32, device=vol.device)
+    count = torch.empty((1,), dtype=torch.int32, device=vol.device)
+    scratch = torch.empty((max(scratch_bytes, 4),), dtype=torch.uint8, device=vol.device)
+    _run(vol.device, "lsr_label_f32", vol.data_ptr(), z, y, x, ctypes.c_float(float(threshold)), int(connectivity),
+         labels.data_ptr(), count.data_ptr(), scratch.data_ptr())
+    return labels, int(count.cpu().item())
+
+
+def _raw_table(labels, n: int, intensity=None) -> np.ndarray:
+    """The ``n`` records of ``lsr_label_regions_f32`` as a host structured array (``REGION_DTYPE``)."""
+    import torch
+
+    labels = _check_volume(labels, "labels", torch.int32)
+    n = int(n)
+    if n < 0:
+        raise ValueError(f"n must not be negative, got {n}")
+    if intensity is not None:
+        intensity = _check_volume(intensity, "intensity", torch.float32)
+        if intensity.shape != labels.shape or intensity.device != labels.device:
+            raise ValueError(f"intensity {tuple(intensity.shape)} on {intensity.device} does not match labels "
+                             f"{tuple(labels.shape)} on {labels.device}")
+    if n == 0:
+        return np.zeros((0,), dtype=REGION_DTYPE)
+    z, y, x = (int(v) for v in labels.shape)
+    table = torch.zeros((n * REGION_DTYPE.itemsize,), dtype=torch.uint8, device=labels.device)     # the host zeroes it
+    _run(labels.device, "lsr_label_regions_f32", labels.data_ptr(), None if intensity is None else intensity.data_ptr(),
+         z, y, x, n, table.data_ptr())
+    return table.cpu().numpy().view(REGION_DTYPE).copy()
+
+
+def region_table(labels, n: int, intensity=None) -> dict:
+    """One row per label ``1 .. n``, as a dict of numpy arrays of length ``n``:
+
+    ``label``, ``volume`` (voxels), ``bbox`` ((n, 6): z0, y0, x0, z1, y1, x1, half-open), ``sum_zyx`` ((n, 3) int64),
+    ``centroid`` ((n, 3) float64, in voxels); with ``intensity`` also ``intensity_sum``, ``intensity_mean``,
+    ``intensity_min``, ``intensity_max``, ``intensity_sum_zyx`` (sum of v * coordinate) and ``weighted_centroid``
+    (NaN where an object's intensities sum to zero)."""
+    raw = _raw_table(labels, n, intensity)
+    vol = raw["volume"].astype(np.int64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = {
+            "label": np.arange(1, len(raw) + 1, dtype=np.int32),
+            "volume": vol,
+            "bbox": np.concatenate([raw["lo"], raw["hi"]], axis=1).astype(np.int32).reshape(len(raw), 6),
+            "sum_zyx": raw["sum_zyx"].astype(np.int64).reshape(len(raw), 3),
+            "centroid": raw["sum_zyx"].reshape(len(raw), 3) / vol[:, None].astype(np.float64),
+        }
+        if intensity is not None:
+            out.update({
+                "intensity_sum": raw["sum_v"].astype(np.float64),
+                "intensity_mean": raw["sum_v"] / vol.astype(np.float64),
+                "intensity_min": raw["v_min"].astype(np.float32),
+                "intensity_max": raw["v_max"].astype(np.float32),
+                "intensity_sum_zyx": raw["sum_vzyx"].astype(np.float64).reshape(len(raw), 3),
+                "weighted_centroid": raw["sum_vzyx"].reshape(len(raw), 3) / raw["sum_v"][:, None],
+            })
+    return out
+
+
+def filter_map(volumes, min_volume: int = 0, keep_largest: bool = False) -> np.ndarray:
+    """``map`` (int32, ``len(volumes) + 1`` entries, ``map[0] == 0``) of :func:`filter_objects`: label ``k`` becomes
+    ``map[k]`` -- 0 if dropped, otherwise its rank among the kept labels."""
+    volumes = np.asarray(volumes, dtype=np.int64)
+    keep = volumes >= int(min_volume)
+    if keep_largest and keep.any():
+        best = int(np.argmax(np.where(keep, volumes, -1)))          # (argmax: the first of equals, the lowest label)
+        keep = np.zeros_like(keep)
+        keep[best] = True
+    out = np.zeros((len(volumes) + 1,), dtype=np.int32)
+    out[1:][keep] = np.arange(1, int(keep.sum()) + 1, dtype=np.int32)
+    return out
+
+
+def filter_objects(labels, table: dict, min_volume: int = 0, keep_largest: bool = False):
+    """Drop the objects of fewer than ``min_volume`` voxels and, with ``keep_largest``, all but the one of greatest volume
+    among the rest (ties: the lowest label).  The kept labels are renumbered ``1 .. M`` in their old order, IN PLACE in
+    ``labels`` (the host builds the map from the table, the device applies it).  Returns ``(labels, table_of_the_kept, M)``."""
+    import torch
+
+    labels = _check_volume(labels, "labels", torch.int32)
+    lut = filter_map(table["volume"], min_volume, keep_largest)
+    kept = lut[1:] > 0
+    if not kept.all():
+        d_lut = torch.from_numpy(lut).to(labels.device)
+        _run(labels.device, "lsr_label_remap_i32", labels.data_ptr(), labels.numel(), d_lut.data_ptr(), len(lut))
+        _lib.mark_written(labels)
+    out = {k: v[kept] for k, v in table.items()}
+    out["label"] = np.arange(1, int(kept.sum()) + 1, dtype=np.int32)
+    return labels, out, int(kept.sum())
+
+
+def segment_zyx(vol, settings):
+    """Threshold, label, measure and filter one (Z, Y, X) float32 volume by a :class:`~shrimpy_amd.settings.SegmentSettings`:
+    ``(labels, table, n)``.  With ``sigma > 0`` the blurred volume is thresholded; with ``threshold: otsu`` the threshold is
+    the multi-Otsu one of what is thresholded (a constant volume has no objects).  The table's intensities are ``vol``'s."""
+    import torch
+
+    from . import dynatrack as D
+
+    vol = _check_volume(vol, "vol", torch.float32)
+    work = D._gaussian_blur_3d(vol, float(settings.sigma)) if settings.sigma > 0 else vol
+    if settings.threshold == "otsu":
+        threshold = D._multiotsu_threshold(work, int(settings.otsu_component))
+    else:
+        threshold = float(settings.threshold)
+    labels, n = label_volume(work, threshold, int(settings.connectivity))
+    table = region_table(labels, n, vol)
+    if settings.min_volume > 0 or settings.keep_largest:
+        labels, table, n = filter_objects(labels, table, int(settings.min_volume), bool(settings.keep_largest))
+    return labels, table, n

@@ -544,6 +544,33 @@ class StitchSettings(_StrictModel):
         return v
 
 
+class SegmentSettings(_StrictModel):
+    """Connected-component segmentation of one channel (``shrimpy_amd/segment.py``, the ``segment`` command).
+
+    ``threshold``: a number, or ``"otsu"`` for the multi-Otsu threshold of the (blurred) volume -- ``sigma`` and
+    ``otsu_component`` are those of ``dynatrack._gaussian_blur_3d`` and ``dynatrack._multiotsu_threshold``; with
+    ``sigma > 0`` the blurred volume is what is thresholded, the table's intensities are always the input's.
+    ``connectivity`` is 6, 18 or 26 (faces; faces and edges; faces, edges and corners).  The default, 6, is
+    ``scipy.ndimage.label``'s default structure -- NOT skimage's: ``skimage.measure.label`` defaults to full
+    connectivity, 26 in 3-D.  Objects of fewer than ``min_volume`` voxels are dropped and the rest renumbered
+    ``1 .. M`` in their old order; ``keep_largest`` keeps the one object of greatest volume (ties: the lowest label)."""
+
+    channel_name: str
+    threshold: Union[float, Literal["otsu"]]
+    sigma: NonNegativeFloat = 0.0
+    otsu_component: NonNegativeInt = 0
+    connectivity: Literal[6, 18, 26] = 6
+    min_volume: NonNegativeInt = 0
+    keep_largest: bool = False
+
+    @field_validator("threshold")
+    @classmethod
+    def _check_threshold(cls, v):
+        if not isinstance(v, str) and not np.isfinite(float(v)):
+            raise ValueError("threshold must be a finite number or \"otsu\"")
+        return v
+
+
 class ReconstructSettings(_StrictModel):
     """Whole per-volume pipeline: (flat-field) -> deskew -> (register) -> (deconvolve)."""
 

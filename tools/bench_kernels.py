@@ -63,6 +63,12 @@ def main():
                     "10 % overlap (p = 1; integer placement, then a placement fractional on x) beside the torch scatter "
                     "formulation and a device-to-device copy in the same run (median of 5 launches between HIP events after "
                     "2 warm-ups); appended to profiles/stitch_config2.jsonl")
+    ap.add_argument("--label", action="store_true", help="only: ms per launch of the labelling (csrc/label.hip: local, merge, "
+                    "flatten, count, scan, rank, final; HIP events between the launches, median of --reps calls after a warm-up), "
+                    "of the object table and of the relabelling on --rl-grid, for bench.synthetic_raw at its multi-Otsu "
+                    "threshold, Bernoulli noise at p = 0.3 (connectivity 6) and an all-foreground volume, beside a device copy "
+                    "and scipy.ndimage.label on this box's host at --label-host-grid; appended to profiles/label_config2.jsonl")
+    ap.add_argument("--label-host-grid", default="43,512,568", help="Z,Y,X of the scipy.ndimage.label timing of --label")
     ap.add_argument("--mi", action="store_true", help="only: ms per launch of the mutual-information kernels (csrc/estimate_mi.hip: "
                     "joint histogram, gradient) on --mi-grid at strides 1 and 4, 32 and 64 bins, on bench.synthetic_raw "
                     "(background-dominated) and on uniform noise (spread over all cells), beside a torch formulation "
@@ -93,6 +99,9 @@ def main():
         return
     if args.mi:
         _mi(args, torch, dev, g, bench, tuple(int(v) for v in args.mi_grid.split(",")))
+        return
+    if args.label:
+        _label(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
         return
     if args.stitch:
         _stitch(args, torch, dev, g, tuple(int(v) for v in args.rl_grid.split(",")))
@@ -571,6 +580,93 @@ def _stitch(args, torch, dev, g, tshape):
         del out
     stamp = {"sources": _lib.kernel_source_sha16(), "device": torch.cuda.get_device_name(dev), "reps": reps, "warmups": 2}
     path = ROOT / "profiles" / "stitch_config2.jsonl"
+    with open(path, "a") as f:
+        for r in records:
+            line = json.dumps({**r, **stamp})
+            print(line, flush=True)
+            f.write(line + "\n")
+
+
+LABEL_LAUNCHES = ("local", "merge", "flatten", "count", "scan", "rank", "final")
+# algorithmic bytes per voxel of each launch (csrc/label.hip): what it must read and write once, chains and gathers aside
+LABEL_BYTES_PER_VOXEL = {"local": 8.0, "merge": 4.0, "flatten": 8.0, "count": 4.0, "scan": 0.0, "rank": 4.0, "final": 8.0,
+                         "regions": 8.0, "remap": 8.0}
+
+
+def _label(args, torch, dev, g, bench, oshape):
+    """Labelling (csrc/label.hip) at the config-2 deskewed shape: every launch of lsr_label_f32 on its own (HIP events between
+    them: lsr_label_profile_f32), lsr_label_regions_f32 with intensities and lsr_label_remap_i32, for three inputs -- the
+    bench's bead scene at its multi-Otsu threshold, Bernoulli noise at p = 0.3 (many winding components) and an all-foreground
+    volume (one component: the most contended case) -- under connectivity 6.  Beside them the bytes per voxel each launch
+    moves, a device copy in the same run, and scipy.ndimage.label on the host at a reduced shape."""
+    import time
+
+    from shrimpy_amd import _lib, dynatrack, segment
+
+    reps = max(args.reps, 5)
+    z, y, x = oshape
+    n = z * y * x
+    labels = torch.empty(oshape, dtype=torch.int32, device=dev)
+    other = torch.empty_like(labels)
+    copy_ms = _median_ms(lambda: other.copy_(labels), reps, torch)
+    del other
+    records = [{"kernel": "device copy (torch copy_)", "grid": list(oshape), "ms": copy_ms, "GBps": 8.0 * n / copy_ms / 1e6}]
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    scratch = torch.empty(_lib.call_value("lsr_label_scratch_bytes", z, y, x), dtype=torch.uint8, device=dev)
+    ms7 = (ctypes.c_float * 7)()
+
+    def scenes():
+        vol = bench.synthetic_raw(oshape, 1000, dev)
+        yield "bead scene (bench.synthetic_raw) at its multi-Otsu threshold", vol, float(dynatrack._multiotsu_threshold(vol, 0))
+        del vol
+        yield "Bernoulli noise, p = 0.3", torch.rand(oshape, device=dev, generator=g), 0.7
+        yield "all foreground", torch.ones(oshape, dtype=torch.float32, device=dev), 0.5
+
+    for name, vol, threshold in scenes():
+        times = []
+        for _ in range(reps + 1):
+            _lib.call("lsr_label_profile_f32", vol.data_ptr(), z, y, x, ctypes.c_float(threshold), 6, labels.data_ptr(),
+                      count.data_ptr(), scratch.data_ptr(), ms7, _lib.stream_ptr(dev))
+            times.append(list(ms7))
+        med = np.median(np.asarray(times[1:]), axis=0)
+        n_objects = int(count.item())
+        base = {"input": name, "grid": list(oshape), "connectivity": 6, "threshold": threshold, "objects": n_objects,
+                "foreground_fraction": float((labels != 0).sum().item()) / n}
+        for launch, ms in zip(LABEL_LAUNCHES, med):
+            bpv = LABEL_BYTES_PER_VOXEL[launch]
+            records.append({**base, "kernel": f"lsr_label_f32: {launch}", "ms": float(ms), "bytes_per_voxel": bpv,
+                            "algorithmic_GBps": bpv * n / float(ms) / 1e6})
+        records.append({**base, "kernel": "lsr_label_f32: all seven launches", "ms": float(med.sum()), "Mvox_per_s": n / float(med.sum()) / 1e3})
+        if 0 < n_objects <= 200_000_000:
+            table = torch.zeros(n_objects * segment.REGION_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+
+            def regions():
+                table.zero_()
+                _lib.call("lsr_label_regions_f32", labels.data_ptr(), vol.data_ptr(), z, y, x, n_objects, table.data_ptr(),
+                          _lib.stream_ptr(dev))
+
+            ms = _median_ms(regions, reps, torch)
+            records.append({**base, "kernel": "lsr_label_regions_f32 (with intensities; the table's memset included)", "ms": ms,
+                            "bytes_per_voxel": LABEL_BYTES_PER_VOXEL["regions"], "algorithmic_GBps": 8.0 * n / ms / 1e6})
+            del table
+        lut = torch.arange(n_objects + 1, dtype=torch.int32, device=dev)           # (the identity: labels stay what they are)
+        ms = _median_ms(lambda: _lib.call("lsr_label_remap_i32", labels.data_ptr(), n, lut.data_ptr(), n_objects + 1,
+                                          _lib.stream_ptr(dev)), reps, torch)
+        records.append({**base, "kernel": "lsr_label_remap_i32", "ms": ms, "bytes_per_voxel": LABEL_BYTES_PER_VOXEL["remap"],
+                        "algorithmic_GBps": 8.0 * n / ms / 1e6})
+        del vol, lut
+    # the step a user without these kernels would run: scipy on the host, at a shape it finishes in seconds
+    from scipy import ndimage
+
+    hshape = tuple(int(v) for v in args.label_host_grid.split(","))
+    mask = np.random.default_rng(3).random(hshape, dtype=np.float32) > 0.7
+    t0 = time.perf_counter()
+    _, n_host = ndimage.label(mask)
+    host_s = time.perf_counter() - t0
+    records.append({"kernel": "scipy.ndimage.label on the host (one thread)", "input": "Bernoulli noise, p = 0.3", "grid": list(hshape),
+                    "connectivity": 6, "objects": int(n_host), "ms": 1e3 * host_s, "Mvox_per_s": mask.size / host_s / 1e6})
+    stamp = {"sources": _lib.kernel_source_sha16(), "device": torch.cuda.get_device_name(dev), "reps": reps, "warmups": 1}
+    path = ROOT / "profiles" / "label_config2.jsonl"
     with open(path, "a") as f:
         for r in records:
             line = json.dumps({**r, **stamp})
