@@ -957,6 +957,46 @@ int lsr_label_profile_f32(const float* in, int64_t Z, int64_t Y, int64_t X, floa
                           int32_t* n_objects, void* scratch, float* ms7, lsr_stream_t stream);
 
 /*
+ * The exact Euclidean distance transform and the label expansion (csrc/edt.hip, shrimpy_amd/distance.py).  The rule is
+ * stated in csrc/edt.hpp:
+ *   Sites are a set of voxels; sampling[3] = (sz, sy, sx) are three HOST doubles, positive and finite (LSR_E_ARG otherwise).
+ *   nearest[v] (int32) is the linear index of a site that minimises (sz dz)^2 + (sy dy)^2 + (sx dx)^2, the SMALLEST linear
+ *   index among equals; dist[v] (float32) is the float32 rounding of the float64
+ *   sqrt(((sz*dz)*(sz*dz) + (sy*dy)*(sy*dy)) + (sx*dx)*(sx*dx)) to nearest[v] -- scipy.ndimage.distance_transform_edt(mask,
+ *   sampling) bit for bit wherever the costs are exact in float64 (integer and dyadic spacings), within one float32 ulp
+ *   otherwise.  A site has dist 0 and nearest v.  With NO site anywhere dist = +inf and nearest = -1 at every voxel: a
+ *   deliberate difference from scipy, which measures from index -1 there.  The index rule is this library's (scipy's
+ *   return_indices breaks ties differently).
+ * lsr_edt_f32: the sites are the background !(in > threshold) -- NaN is background, as in lsr_label_f32 -- so the result is
+ *   scipy's distance_transform_edt(in > threshold); with invert != 0 the sites are the foreground.
+ * lsr_edt_labels_i32: the sites are labels != 0, with invert != 0 labels == 0.
+ * Either of dist and nearest may be NULL, not both (LSR_E_NULL).  A volume holds at most 2^31 - 1 voxels
+ * (LSR_E_UNSUPPORTED beyond); a non-positive extent is LSR_E_SHAPE.  Three launches on `stream` (x: the nearest site of each
+ * row from wave ballots; y, z: the lower envelope of each line's parabolas, one lane per line, float64 costs), in place in
+ * the output words; no launch communicates between workgroups.  `scratch` (device memory, lsr_edt_scratch_bytes(Z, Y, X)
+ * bytes or a negative status; its contents on entry do not matter) holds the envelope stacks.
+ * lsr_edt_tiling: {voxels per step of the x pass, lines per workgroup of the y and z passes, rows the x pass holds at once,
+ * lines a y or z pass holds at once}: beyond the last two a wave or a lane takes a further row or line.
+ *
+ * lsr_label_expand_i32: out[v] = labels[nearest[v]] where nearest[v] >= 0 and the float64 distance of the rule from v to
+ * nearest[v] is <= distance, 0 elsewhere.  One launch.  distance must not be negative or NaN, out must not alias labels
+ * (LSR_E_ARG).  With nearest from lsr_edt_labels_i32(invert = 0) this is skimage.segmentation.expand_labels(labels,
+ * distance, spacing=sampling) up to the tie rule above.
+ */
+int lsr_edt_tiling(int tiling[4]);
+int64_t lsr_edt_scratch_bytes(int64_t Z, int64_t Y, int64_t X);
+int lsr_edt_f32(const float* in, int64_t Z, int64_t Y, int64_t X, float threshold, int invert, const double sampling[3],
+                float* dist, int32_t* nearest, void* scratch, lsr_stream_t stream);
+int lsr_edt_labels_i32(const int32_t* labels, int64_t Z, int64_t Y, int64_t X, int invert, const double sampling[3], float* dist,
+                       int32_t* nearest, void* scratch, lsr_stream_t stream);
+int lsr_label_expand_i32(const int32_t* labels, const int32_t* nearest, int64_t Z, int64_t Y, int64_t X, const double sampling[3],
+                         double distance, int32_t* out, lsr_stream_t stream);
+/* measurement only (tools/bench_kernels.py --edt): lsr_edt_f32 with a HIP event between its launches; waits for the stream
+ * and writes the times of the x, y and z passes in milliseconds to ms3 (HOST memory) */
+int lsr_edt_profile_f32(const float* in, int64_t Z, int64_t Y, int64_t X, float threshold, int invert, const double sampling[3],
+                        float* dist, int32_t* nearest, void* scratch, float* ms3, lsr_stream_t stream);
+
+/*
  * Host twins (csrc/host_twins.hip): the same signatures with HOST pointers, the same argument checks and the
  * same arithmetic in the same order, so the results equal the device entry points' bit for bit.  They serve
  * the boxes where the reference itself resolves to the CPU (shrimpy/preprocessing.py:78-82 -- its CI has no
@@ -1078,6 +1118,16 @@ int lsr_label_f32_cpu(const float* in, int64_t Z, int64_t Y, int64_t X, float th
 int lsr_label_regions_f32_cpu(const int32_t* labels, const float* intensity, int64_t Z, int64_t Y, int64_t X,
                               int64_t n_objects, void* table, lsr_stream_t stream);
 int lsr_label_remap_i32_cpu(int32_t* labels, int64_t n, const int32_t* map, int64_t n_map, lsr_stream_t stream);
+
+/* ... of the distance transform and the label expansion (csrc/edt.hip): plain sequential code over the same row rule and the
+ * same line pass (csrc/edt.hpp), so `nearest` and `dist` are the kernels' bits.  Every pointer HOST memory, `scratch` unused
+ * (but required). */
+int lsr_edt_f32_cpu(const float* in, int64_t Z, int64_t Y, int64_t X, float threshold, int invert, const double sampling[3],
+                    float* dist, int32_t* nearest, void* scratch, lsr_stream_t stream);
+int lsr_edt_labels_i32_cpu(const int32_t* labels, int64_t Z, int64_t Y, int64_t X, int invert, const double sampling[3],
+                           float* dist, int32_t* nearest, void* scratch, lsr_stream_t stream);
+int lsr_label_expand_i32_cpu(const int32_t* labels, const int32_t* nearest, int64_t Z, int64_t Y, int64_t X,
+                             const double sampling[3], double distance, int32_t* out, lsr_stream_t stream);
 
 /* ... of the mutual-information metric (csrc/estimate_mi.hip): the per-sample rule of csrc/mi_sample.hpp on both sides.
  * The histogram and the count are the kernel's bits; the gradient rows are sums over lsr_affine_mi_gradient_blocks()

@@ -1473,7 +1473,8 @@ OBJECT_COLUMNS = ("t", "label", "volume_voxels", "volume_um3", "bbox_z0", "bbox_
 
 def object_rows(t: int, table: dict, scale_zyx, translation_zyx) -> list[list]:
     """The ``objects.csv`` rows of one timepoint's table (``segment.region_table`` with intensities), in
-    ``OBJECT_COLUMNS`` order.  Physical centroids are ``translation + centroid * scale`` of the position's level 0."""
+    ``OBJECT_COLUMNS`` order.  Physical centroids are ``translation + centroid * scale`` of the position's level 0.  A table
+    with an ``inscribed_radius`` column (``SegmentSettings.inscribed_radius``) gets it appended as the last value."""
     sz, sy, sx = (float(v) for v in scale_zyx)
     rows = []
     for k in range(len(table["label"])):
@@ -1483,6 +1484,8 @@ def object_rows(t: int, table: dict, scale_zyx, translation_zyx) -> list[list]:
                      *(int(v) for v in table["bbox"][k]), *(float(v) for v in c), *um,
                      float(table["intensity_sum"][k]), float(table["intensity_mean"][k]), float(table["intensity_min"][k]),
                      float(table["intensity_max"][k]), *(float(v) for v in table["weighted_centroid"][k])])
+        if "inscribed_radius" in table:
+            rows[-1].append(float(table["inscribed_radius"][k]))
     return rows
 
 
@@ -1504,7 +1507,10 @@ def segment(input_path, config, output_path, positions, zarr_version, io_backend
     """Label the connected components of one thresholded channel and measure them (config: a SegmentSettings YAML).
 
     Writes an int32 array "0" with the channel <channel_name>_labels per position, and objects.csv.  There is no --levels:
-    a mean pyramid of labels is meaningless (the mean of labels 2 and 4 is not label 3)."""
+    a mean pyramid of labels is meaningless (the mean of labels 2 and 4 is not label 3).
+
+    expand_distance (micrometres, the position's scale) grows the filtered labels without overlap; inscribed_radius adds
+    the column inscribed_radius_um to objects.csv."""
     input_path, positions = _inputs(input_path, positions)
     _finish(run_segment(input_path, config, output_path, positions, zarr_version, io_backend, compression))
 
@@ -1513,8 +1519,10 @@ def run_segment(input_path, config, output_path, positions=(), zarr_version: str
                 compression=None) -> dict:
     """``segment``: every (position, t) volume of ``channel_name`` goes through ``segment.segment_zyx``; the labels are written
     as ``int32`` (the input's ``scale`` and ``translation`` copied), the object tables of a position's timepoints as
-    ``<output>/<position>/objects.csv`` (``OBJECT_COLUMNS``).  Everything is checked before the output store is created; with
-    several ranks the positions are dealt out in turn.  The output is written by this package's own writer."""
+    ``<output>/<position>/objects.csv`` (``OBJECT_COLUMNS``, and ``inscribed_radius_um`` behind them where the setting is on;
+    the position's ``(z, y, x)`` scale is the sampling of ``expand_distance`` and of the radius).  Everything is checked before
+    the output store is created; with several ranks the positions are dealt out in turn.  The output is written by this
+    package's own writer."""
     import csv
 
     import torch
@@ -1581,13 +1589,13 @@ def run_segment(input_path, config, output_path, positions=(), zarr_version: str
                     rows = []
                     for t in range(int(arrays[k].shape[0])):
                         vol = np.ascontiguousarray(arrays[k].read_volume(t, channel[k]), dtype=np.float32)
-                        labels, table, n = segment_zyx(torch.as_tensor(vol, device=device), settings)
+                        labels, table, n = segment_zyx(torch.as_tensor(vol, device=device), settings, sampling=scale[2:])
                         out.write_volume(t, 0, labels.cpu().numpy())
                         rows += object_rows(t, table, scale[2:], translation[2:])
                         counts.setdefault(k, []).append(int(n))
                     with open(Path(output_path) / k / "objects.csv", "w", newline="") as fh:
                         w = csv.writer(fh)
-                        w.writerow(OBJECT_COLUMNS)
+                        w.writerow(OBJECT_COLUMNS + (("inscribed_radius_um",) if settings.inscribed_radius else ()))
                         w.writerows([[repr(v) if isinstance(v, float) else v for v in row] for row in rows])
             finally:
                 close = getattr(dst, "close", None)

@@ -23,6 +23,8 @@
 //   lsr_stitch_f32_cpu                        <->  lsr_stitch_f32                      (stitch.hip)
 //   lsr_label_f32_cpu, lsr_label_regions_f32_cpu, lsr_label_remap_i32_cpu
 //                                             <->  the same names without _cpu         (label.hip)
+//   lsr_edt_f32_cpu, lsr_edt_labels_i32_cpu, lsr_label_expand_i32_cpu
+//                                             <->  the same names without _cpu         (edt.hip)
 //
 // Arithmetic (what "the same" means):
 //   resamplers -- the text the kernels compile (resample.hpp): coordinates, axis taps with their weights and the
@@ -1352,6 +1354,100 @@ extern "C" int lsr_label_remap_i32_cpu(int32_t* labels, int64_t n, const int32_t
   for (int64_t v = 0; v < n; ++v) {
     const int32_t l = labels[v];
     labels[v] = (l > 0 && l < n_map) ? map[l] : 0;
+  }
+  return LSR_OK;
+}
+
+// ---- distance transform (edt.hip): plain sequential code over edt.hpp's row rule and line pass ----
+#include "edt.hpp"
+
+namespace {
+
+struct HostStack {           // an envelope stack in host memory
+  std::vector<int32_t> words;
+  void put(int q, int k, int v, int t) {
+    int32_t* e = &words[static_cast<size_t>(q) * lsr::edt::kStackFields];
+    e[0] = k; e[1] = v; e[2] = t;
+  }
+  void get(int q, int& k, int& v, int& t) const {
+    const int32_t* e = &words[static_cast<size_t>(q) * lsr::edt::kStackFields];
+    k = e[0]; v = e[1]; t = e[2];
+  }
+};
+
+template <class Sites>
+int edt_host(Sites sites, int64_t Z, int64_t Y, int64_t X, const double* sampling, float* dist, int32_t* nearest) {
+  namespace ed = lsr::edt;
+  const ed::Sampling s = ed::make_sampling(sampling);
+  int32_t* work = nearest != nullptr ? nearest : reinterpret_cast<int32_t*>(dist);
+  const int64_t plane = Y * X;
+  const int iX = static_cast<int>(X);
+  HostStack stack;
+  try {
+    stack.words.resize(static_cast<size_t>(std::max(Y, Z)) * ed::kStackFields);
+  } catch (const std::bad_alloc&) {
+    return lsr::fail(LSR_E_ARG, "lsr_edt_*_cpu: out of memory for the envelope stack");
+  }
+  for (int64_t row = 0; row < Z * Y; ++row) {             // x: left-nearest forward, the nearer of left and right backward
+    int32_t* w = work + row * X;
+    int carry = -1;
+    for (int x = 0; x < iX; ++x) {
+      if (sites(row * X + x)) carry = x;
+      w[x] = carry;
+    }
+    carry = -1;
+    for (int x = iX - 1; x >= 0; --x) {
+      if (w[x] == x) carry = x;
+      w[x] = ed::nearer_in_row(x, w[x], carry);
+    }
+  }
+  for (int64_t z = 0; z < Z; ++z) {
+    for (int x = 0; x < iX; ++x) {
+      ed::YLine io{work + z * plane + x, X, x, iX, s.wx};
+      ed::line_pass(static_cast<int>(Y), s.wy, io, stack);
+    }
+  }
+  for (int64_t line = 0; line < plane; ++line) {
+    ed::ZLine io{work + line, nearest != nullptr ? nearest + line : nullptr,
+                 dist != nullptr ? reinterpret_cast<int32_t*>(dist) + line : nullptr, plane, static_cast<int>(line / X),
+                 static_cast<int>(line % X), iX, s};
+    ed::line_pass(static_cast<int>(Z), s.wz, io, stack);
+  }
+  return LSR_OK;
+}
+
+}  // namespace
+
+extern "C" int lsr_edt_f32_cpu(const float* in, int64_t Z, int64_t Y, int64_t X, float threshold, int invert, const double* sampling,
+                               float* dist, int32_t* nearest, void* scratch, lsr_stream_t) {
+  if (int rc = lsr::edt::check_edt(in, Z, Y, X, sampling, dist, nearest, scratch)) return rc;
+  const bool inv = invert != 0;
+  return edt_host([=](int64_t v) { return !(in[v] > threshold) != inv; }, Z, Y, X, sampling, dist, nearest);
+}
+
+extern "C" int lsr_edt_labels_i32_cpu(const int32_t* labels, int64_t Z, int64_t Y, int64_t X, int invert, const double* sampling,
+                                      float* dist, int32_t* nearest, void* scratch, lsr_stream_t) {
+  if (int rc = lsr::edt::check_edt(labels, Z, Y, X, sampling, dist, nearest, scratch)) return rc;
+  const bool inv = invert != 0;
+  return edt_host([=](int64_t v) { return (labels[v] != 0) != inv; }, Z, Y, X, sampling, dist, nearest);
+}
+
+extern "C" int lsr_label_expand_i32_cpu(const int32_t* labels, const int32_t* nearest, int64_t Z, int64_t Y, int64_t X,
+                                        const double* sampling, double distance, int32_t* out, lsr_stream_t) {
+  namespace ed = lsr::edt;
+  if (int rc = ed::check_expand(labels, nearest, Z, Y, X, sampling, distance, out)) return rc;
+  const ed::Sampling s = ed::make_sampling(sampling);
+  const int64_t n = Z * Y * X;
+  int64_t v = 0;
+  for (int z = 0; z < Z; ++z) {
+    for (int y = 0; y < Y; ++y) {
+      for (int x = 0; x < X; ++x, ++v) {
+        const int32_t site = nearest[v];
+        const bool in_reach = site >= 0 && site < n &&
+                              ed::distance_to(s, z, y, x, site, static_cast<int>(Y), static_cast<int>(X)) <= distance;
+        out[v] = in_reach ? labels[site] : 0;
+      }
+    }
   }
   return LSR_OK;
 }

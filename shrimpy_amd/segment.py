@@ -10,7 +10,8 @@ numbering is a prefix count), ``csrc/host_twins.hip`` on the CPU; both equal ``s
   mean, minimum, maximum and the intensity-weighted centroid.  The integer columns and the intensity range are exact; the
   float64 sums are atomic adds on the device (within ``n_k * 2^-53 * sum|terms|`` of the exact sum, not bit-reproducible).
 * :func:`filter_objects` -- drop small objects or keep the largest; the kept labels stay consecutive, in their old order.
-* :func:`segment_zyx` -- threshold (a number or multi-Otsu, after an optional Gaussian blur), label, measure, filter.
+* :func:`segment_zyx` -- threshold (a number or multi-Otsu, after an optional Gaussian blur), label, measure, filter, and on
+  request grow the labels by a distance and measure each object's inscribed radius (``shrimpy_amd/distance.py``).
 
 Not built: watershed or any splitting of touching objects, multi-GPU or slab labelling, tracking across timepoints, label
 pyramids, volumes above ``2^31 - 1`` voxels.
@@ -173,10 +174,16 @@ def filter_objects(labels, table: dict, min_volume: int = 0, keep_largest: bool 
     return labels, out, int(kept.sum())
 
 
-def segment_zyx(vol, settings):
+def segment_zyx(vol, settings, sampling=(1, 1, 1)):
     """Threshold, label, measure and filter one (Z, Y, X) float32 volume by a :class:`~shrimpy_amd.settings.SegmentSettings`:
     ``(labels, table, n)``.  With ``sigma > 0`` the blurred volume is thresholded; with ``threshold: otsu`` the threshold is
-    the multi-Otsu one of what is thresholded (a constant volume has no objects).  The table's intensities are ``vol``'s."""
+    the multi-Otsu one of what is thresholded (a constant volume has no objects).  The table's intensities are ``vol``'s.
+
+    ``sampling = (sz, sy, sx)`` is the voxel spacing the two distance settings measure in (``shrimpy_amd/distance.py``).  With
+    ``expand_distance > 0`` the labels that survive the filter grow into the background by at most that distance (a dropped
+    speck claims no space) and the table is that of the grown labels.  With ``inscribed_radius`` the table gains the column
+    ``inscribed_radius``: per object the greatest distance of one of its voxels to the nearest background voxel, of the final
+    labels (``+inf`` where the volume has no background)."""
     import torch
 
     from . import dynatrack as D
@@ -191,4 +198,14 @@ def segment_zyx(vol, settings):
     table = region_table(labels, n, vol)
     if settings.min_volume > 0 or settings.keep_largest:
         labels, table, n = filter_objects(labels, table, int(settings.min_volume), bool(settings.keep_largest))
+    if settings.expand_distance > 0 or settings.inscribed_radius:
+        from . import distance
+
+        if settings.expand_distance > 0:
+            labels = distance.expand_labels(labels, float(settings.expand_distance), sampling)
+            table = region_table(labels, n, vol)
+        if settings.inscribed_radius:
+            depth = distance.distance_transform_labels(labels, sampling, invert=True)
+            table["inscribed_radius"] = (region_table(labels, n, depth)["intensity_max"] if n > 0
+                                         else np.zeros((0,), dtype=np.float32))
     return labels, table, n

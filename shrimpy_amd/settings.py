@@ -553,7 +553,13 @@ class SegmentSettings(_StrictModel):
     ``connectivity`` is 6, 18 or 26 (faces; faces and edges; faces, edges and corners).  The default, 6, is
     ``scipy.ndimage.label``'s default structure -- NOT skimage's: ``skimage.measure.label`` defaults to full
     connectivity, 26 in 3-D.  Objects of fewer than ``min_volume`` voxels are dropped and the rest renumbered
-    ``1 .. M`` in their old order; ``keep_largest`` keeps the one object of greatest volume (ties: the lowest label)."""
+    ``1 .. M`` in their old order; ``keep_largest`` keeps the one object of greatest volume (ties: the lowest label).
+
+    ``expand_distance`` (in the units of the position's scale: micrometres from the ``segment`` command) grows the labels
+    that survive the filter into the background by at most that distance, without overlap (``skimage``'s ``expand_labels``
+    rule on the exact Euclidean distance transform, ``shrimpy_amd/distance.py``); the table is then that of the grown labels.
+    ``inscribed_radius`` adds a column of that name: per object the greatest distance from one of its voxels to the nearest
+    background voxel, of the final labels (``inscribed_radius_um`` in ``objects.csv``)."""
 
     channel_name: str
     threshold: Union[float, Literal["otsu"]]
@@ -562,6 +568,8 @@ class SegmentSettings(_StrictModel):
     connectivity: Literal[6, 18, 26] = 6
     min_volume: NonNegativeInt = 0
     keep_largest: bool = False
+    inscribed_radius: bool = False
+    expand_distance: NonNegativeFloat = 0.0
 
     @field_validator("threshold")
     @classmethod

@@ -69,6 +69,10 @@ def main():
                     "threshold, Bernoulli noise at p = 0.3 (connectivity 6) and an all-foreground volume, beside a device copy "
                     "and scipy.ndimage.label on this box's host at --label-host-grid; appended to profiles/label_config2.jsonl")
     ap.add_argument("--label-host-grid", default="43,512,568", help="Z,Y,X of the scipy.ndimage.label timing of --label")
+    ap.add_argument("--edt", action="store_true", help="only: ms per launch of the distance transform (csrc/edt.hip: x, y, z; HIP "
+                    "events between the launches, median of 5 calls after a warm-up) on --rl-grid, for bench.synthetic_raw at its "
+                    "multi-Otsu threshold, Bernoulli noise at p = 0.3 and an all-foreground volume with one background voxel, "
+                    "beside a device copy of an int32 volume in the same run; appended to profiles/edt_config2.jsonl")
     ap.add_argument("--mi", action="store_true", help="only: ms per launch of the mutual-information kernels (csrc/estimate_mi.hip: "
                     "joint histogram, gradient) on --mi-grid at strides 1 and 4, 32 and 64 bins, on bench.synthetic_raw "
                     "(background-dominated) and on uniform noise (spread over all cells), beside a torch formulation "
@@ -99,6 +103,9 @@ def main():
         return
     if args.mi:
         _mi(args, torch, dev, g, bench, tuple(int(v) for v in args.mi_grid.split(",")))
+        return
+    if args.edt:
+        _edt(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
         return
     if args.label:
         _label(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
@@ -667,6 +674,70 @@ def _label(args, torch, dev, g, bench, oshape):
                     "connectivity": 6, "objects": int(n_host), "ms": 1e3 * host_s, "Mvox_per_s": mask.size / host_s / 1e6})
     stamp = {"sources": _lib.kernel_source_sha16(), "device": torch.cuda.get_device_name(dev), "reps": reps, "warmups": 1}
     path = ROOT / "profiles" / "label_config2.jsonl"
+    with open(path, "a") as f:
+        for r in records:
+            line = json.dumps({**r, **stamp})
+            print(line, flush=True)
+            f.write(line + "\n")
+
+
+EDT_LAUNCHES = ("x", "y", "z")
+# algorithmic bytes per voxel of each launch (csrc/edt.hip) with both outputs asked for: what it must read and write once --
+# the x pass's second sweep over its own words and the envelope stacks of y and z aside
+EDT_BYTES_PER_VOXEL = {"x": 8.0, "y": 8.0, "z": 12.0}
+
+
+def _edt(args, torch, dev, g, bench, oshape):
+    """Distance transform (csrc/edt.hip) at the config-2 deskewed shape: every launch of lsr_edt_f32 on its own (HIP events
+    between them: lsr_edt_profile_f32), both outputs asked for, unit sampling, for three inputs -- the bench's bead scene at its
+    multi-Otsu threshold (sparse foreground: short envelopes), Bernoulli foreground at p = 0.3 and an all-foreground volume with
+    one background voxel (one site: every line's envelope is one parabola, the longest distances).  Beside them the bytes per
+    voxel each launch must move and a device copy of an int32 volume of the same size in the same run."""
+    from shrimpy_amd import _lib, dynatrack
+
+    reps = 5
+    z, y, x = oshape
+    n = z * y * x
+    nearest = torch.empty(oshape, dtype=torch.int32, device=dev)
+    other = torch.empty_like(nearest)
+    copy_ms = _median_ms(lambda: other.copy_(nearest), reps, torch)
+    del other
+    records = [{"kernel": "device copy of an int32 volume (torch copy_)", "grid": list(oshape), "ms": copy_ms,
+                "GBps": 8.0 * n / copy_ms / 1e6}]
+    dist = torch.empty(oshape, dtype=torch.float32, device=dev)
+    scratch_bytes = _lib.call_value("lsr_edt_scratch_bytes", z, y, x)
+    scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
+    sampling = (ctypes.c_double * 3)(1.0, 1.0, 1.0)
+    ms3 = (ctypes.c_float * 3)()
+
+    def scenes():
+        vol = bench.synthetic_raw(oshape, 1000, dev)
+        yield "bead scene (bench.synthetic_raw) at its multi-Otsu threshold", vol, float(dynatrack._multiotsu_threshold(vol, 0))
+        del vol
+        yield "Bernoulli foreground, p = 0.3", torch.rand(oshape, device=dev, generator=g), 0.7
+        one = torch.ones(oshape, dtype=torch.float32, device=dev)
+        one[z // 2, y // 2, x // 2] = 0.0
+        yield "all foreground but one voxel", one, 0.5
+
+    for name, vol, threshold in scenes():
+        times = []
+        for _ in range(reps + 1):
+            _lib.call("lsr_edt_profile_f32", vol.data_ptr(), z, y, x, ctypes.c_float(threshold), 0, sampling, dist.data_ptr(),
+                      nearest.data_ptr(), scratch.data_ptr(), ms3, _lib.stream_ptr(dev))
+            times.append(list(ms3))
+        med = np.median(np.asarray(times[1:]), axis=0)
+        base = {"input": name, "grid": list(oshape), "threshold": threshold, "sampling": [1.0, 1.0, 1.0],
+                "site_fraction": float((dist == 0).sum().item()) / n, "max_distance": float(dist.max().item()),
+                "scratch_bytes": scratch_bytes}
+        for launch, ms in zip(EDT_LAUNCHES, med):
+            bpv = EDT_BYTES_PER_VOXEL[launch]
+            records.append({**base, "kernel": f"lsr_edt_f32: {launch}", "ms": float(ms), "bytes_per_voxel": bpv,
+                            "algorithmic_GBps": bpv * n / float(ms) / 1e6, "copy_time_ratio": float(ms) / (copy_ms * bpv / 8.0)})
+        records.append({**base, "kernel": "lsr_edt_f32: all three launches", "ms": float(med.sum()),
+                        "Mvox_per_s": n / float(med.sum()) / 1e3})
+        del vol
+    stamp = {"sources": _lib.kernel_source_sha16(), "device": torch.cuda.get_device_name(dev), "reps": reps, "warmups": 1}
+    path = ROOT / "profiles" / "edt_config2.jsonl"
     with open(path, "a") as f:
         for r in records:
             line = json.dumps({**r, **stamp})
