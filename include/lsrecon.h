@@ -997,6 +997,46 @@ int lsr_edt_profile_f32(const float* in, int64_t Z, int64_t Y, int64_t X, float 
                         float* dist, int32_t* nearest, void* scratch, float* ms3, lsr_stream_t stream);
 
 /*
+ * Splitting touching objects: a watershed by steepest ascent (csrc/watershed.hip, shrimpy_amd/watershed.py).  PARITY
+ * UNPINNED: no upstream is pinned, the rule IS the specification (csrc/watershed.hpp; tests/watershed_ref.py restates it).
+ *   objects (int32, Z * Y * X): values <= 0 are background.  surface (float32): its values compare by the order-preserving
+ *   integer image of a float (-0.0 below +0.0, +inf an ordinary value; NaN is unsupported but cannot hang or fault anything).
+ *   connectivity is 6, 18 or 26, as in lsr_label_f32.  N(v) is the set of neighbours of v inside the volume with
+ *   objects[u] == objects[v]; up(v) is the element of N(v) + {v} with the greatest (surface, then the SMALLER linear index);
+ *   basins are the connected components of the edges {v, up(v)}, so no basin spans two objects.  basins (int32) receives 0
+ *   on the background and 1 .. B in raster order of each basin's smallest linear index; *n_basins (int32, device memory)
+ *   receives B, the number of summits up(v) == v.  basins must not alias objects or surface (LSR_E_ARG).  A volume holds at
+ *   most 2^31 - 1 voxels (LSR_E_UNSUPPORTED beyond); a NULL pointer is LSR_E_NULL, a non-positive extent LSR_E_SHAPE.
+ * lsr_watershed_tile_shape: the (z, y, x) tile one workgroup stages in LDS with a one-voxel halo.
+ * lsr_watershed_scratch_bytes: the size of `scratch` (device memory; its contents on entry do not matter) -- the block counts
+ * of the numbering and one direction byte per voxel -- or a negative status for a shape out of range.
+ * lsr_watershed_f32 runs seven launches on `stream` -- local (up(v) of every voxel of a tile, unions inside the tile), merge
+ * (unions where up(v) lies in another tile, atomicMin on the parent words), then lsr_label_f32's flatten, count, scan, rank,
+ * final -- with the union-find kept in `basins` itself; no workgroup ever waits for another and the result does not depend
+ * on the order of execution.
+ *
+ * lsr_watershed_saddles_f32: for every pair of neighbours v, u (under connectivity) of one object in different basins
+ * a < b, pass = min(surface[v], surface[u]); saddle(a, b) = the maximum of the passes.  `table` (device memory, WHICH THE
+ * CALLER HAS ZEROED) is an open-addressing hash table of `capacity` 16-byte slots, capacity a power of two in 1 .. 2^30
+ * (LSR_E_ARG otherwise): uint64 pair = a << 32 | b (0: the slot is empty); uint32 key = the integer image of saddle(a, b)
+ * (a float v with bits u maps to ~u where u's sign bit is set, to u | 0x80000000 otherwise); uint32 unused.  Probing is
+ * linear over at most min(capacity, 256) slots.  counts (int32[2], device memory, set by the entry): counts[0] = the slots
+ * claimed, counts[1] = the neighbour pairs that found no slot -- if it is not zero the table is incomplete: come back with a
+ * larger one.  Which slot a record lands in depends on the order of arrival: the contract is the set of records.  One
+ * launch (and the clearing of counts); the table's words are touched by atomics only, nothing waits for anything.
+ */
+int lsr_watershed_tile_shape(int zyx[3]);
+int64_t lsr_watershed_scratch_bytes(int64_t Z, int64_t Y, int64_t X);
+int lsr_watershed_f32(const int32_t* objects, const float* surface, int64_t Z, int64_t Y, int64_t X, int connectivity,
+                      int32_t* basins, int32_t* n_basins, void* scratch, lsr_stream_t stream);
+int lsr_watershed_saddles_f32(const int32_t* objects, const int32_t* basins, const float* surface, int64_t Z, int64_t Y, int64_t X,
+                              int connectivity, int64_t capacity, void* table, int32_t* counts, lsr_stream_t stream);
+/* measurement only (tools/bench_kernels.py --watershed): lsr_watershed_f32 with a HIP event between its launches; waits for
+ * the stream and writes the times of local, merge, flatten, count, scan, rank and final in milliseconds to ms7 (HOST memory) */
+int lsr_watershed_profile_f32(const int32_t* objects, const float* surface, int64_t Z, int64_t Y, int64_t X, int connectivity,
+                              int32_t* basins, int32_t* n_basins, void* scratch, float* ms7, lsr_stream_t stream);
+
+/*
  * Host twins (csrc/host_twins.hip): the same signatures with HOST pointers, the same argument checks and the
  * same arithmetic in the same order, so the results equal the device entry points' bit for bit.  They serve
  * the boxes where the reference itself resolves to the CPU (shrimpy/preprocessing.py:78-82 -- its CI has no
@@ -1128,6 +1168,15 @@ int lsr_edt_labels_i32_cpu(const int32_t* labels, int64_t Z, int64_t Y, int64_t 
                            float* dist, int32_t* nearest, void* scratch, lsr_stream_t stream);
 int lsr_label_expand_i32_cpu(const int32_t* labels, const int32_t* nearest, int64_t Z, int64_t Y, int64_t X,
                              const double sampling[3], double distance, int32_t* out, lsr_stream_t stream);
+
+/* ... of the watershed (csrc/watershed.hip): plain sequential code over the same `up` rule, slot record and hash
+ * (csrc/watershed.hpp): the kernels' basins element for element, the kernels' set of saddle records.  Every pointer HOST
+ * memory, `scratch` unused (but required). */
+int lsr_watershed_f32_cpu(const int32_t* objects, const float* surface, int64_t Z, int64_t Y, int64_t X, int connectivity,
+                          int32_t* basins, int32_t* n_basins, void* scratch, lsr_stream_t stream);
+int lsr_watershed_saddles_f32_cpu(const int32_t* objects, const int32_t* basins, const float* surface, int64_t Z, int64_t Y,
+                                  int64_t X, int connectivity, int64_t capacity, void* table, int32_t* counts,
+                                  lsr_stream_t stream);
 
 /* ... of the mutual-information metric (csrc/estimate_mi.hip): the per-sample rule of csrc/mi_sample.hpp on both sides.
  * The histogram and the count are the kernel's bits; the gradient rows are sums over lsr_affine_mi_gradient_blocks()

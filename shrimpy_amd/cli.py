@@ -1510,7 +1510,8 @@ def segment(input_path, config, output_path, positions, zarr_version, io_backend
     a mean pyramid of labels is meaningless (the mean of labels 2 and 4 is not label 3).
 
     expand_distance (micrometres, the position's scale) grows the filtered labels without overlap; inscribed_radius adds
-    the column inscribed_radius_um to objects.csv."""
+    the column inscribed_radius_um to objects.csv.  split: true splits touching objects before the size filter: a watershed
+    of each object's depth map blurred by split_sigma voxels, basins shallower than split_min_depth (micrometres) merged."""
     input_path, positions = _inputs(input_path, positions)
     _finish(run_segment(input_path, config, output_path, positions, zarr_version, io_backend, compression))
 

@@ -25,6 +25,8 @@
 //                                             <->  the same names without _cpu         (label.hip)
 //   lsr_edt_f32_cpu, lsr_edt_labels_i32_cpu, lsr_label_expand_i32_cpu
 //                                             <->  the same names without _cpu         (edt.hip)
+//   lsr_watershed_f32_cpu, lsr_watershed_saddles_f32_cpu
+//                                             <->  the same names without _cpu         (watershed.hip)
 //
 // Arithmetic (what "the same" means):
 //   resamplers -- the text the kernels compile (resample.hpp): coordinates, axis taps with their weights and the
@@ -1446,6 +1448,112 @@ extern "C" int lsr_label_expand_i32_cpu(const int32_t* labels, const int32_t* ne
         const bool in_reach = site >= 0 && site < n &&
                               ed::distance_to(s, z, y, x, site, static_cast<int>(Y), static_cast<int>(X)) <= distance;
         out[v] = in_reach ? labels[site] : 0;
+      }
+    }
+  }
+  return LSR_OK;
+}
+
+// ---- watershed (watershed.hip): plain sequential code over watershed.hpp's `up` rule, slot record and hash ----
+#include "watershed.hpp"
+
+extern "C" int lsr_watershed_f32_cpu(const int32_t* objects, const float* surface, int64_t Z, int64_t Y, int64_t X, int connectivity,
+                                     int32_t* basins, int32_t* n_basins, void* scratch, lsr_stream_t) {
+  namespace lb = lsr::label;
+  namespace ws = lsr::watershed;
+  if (int rc = ws::check_watershed(objects, surface, Z, Y, X, connectivity, basins, n_basins, scratch)) return rc;
+  const int level = lb::level_of(connectivity);
+  const int64_t n = Z * Y * X, plane = Y * X;
+  int32_t* parent = basins;                    // a union-find rooted at the smallest index, as on the device
+  auto find = [&](int32_t a) {              // with path halving
+    while (parent[a] != a) {
+      parent[a] = parent[parent[a]];
+      a = parent[a];
+    }
+    return a;
+  };
+  for (int64_t v = 0; v < n; ++v) parent[v] = objects[v] > 0 ? static_cast<int32_t>(v) : -1;
+  for (int64_t z = 0; z < Z; ++z) {
+    for (int64_t y = 0; y < Y; ++y) {
+      for (int64_t x = 0; x < X; ++x) {
+        const int64_t v = z * plane + y * X + x;
+        const int32_t o = objects[v];
+        if (o <= 0) continue;
+        const int code = ws::up_code(lb::float_key(surface[v]), level, [&](int dz, int dy, int dx, uint32_t* key) {
+          if (z + dz < 0 || z + dz >= Z || y + dy < 0 || y + dy >= Y || x + dx < 0 || x + dx >= X) return false;
+          const int64_t u = v + dz * plane + dy * X + dx;
+          if (objects[u] != o) return false;
+          *key = lb::float_key(surface[u]);
+          return true;
+        });
+        if (code == ws::kSelf) continue;
+        const int64_t t = v + (code / 9 - 1) * plane + (code / 3 % 3 - 1) * X + (code % 3 - 1);
+        const int32_t a = find(static_cast<int32_t>(v)), b = find(static_cast<int32_t>(t));
+        if (a != b) parent[a < b ? b : a] = a < b ? a : b;
+      }
+    }
+  }
+  // the numbering of lsr_label_f32_cpu: chains cut, the roots numbered in raster order, a root before the rest of its set
+  for (int64_t v = 0; v < n; ++v)
+    if (parent[v] >= 0) parent[v] = find(static_cast<int32_t>(v));
+  int32_t count = 0;
+  for (int64_t v = 0; v < n; ++v)
+    if (parent[v] == v) parent[v] = -(++count) - 1;
+  for (int64_t v = 0; v < n; ++v) {
+    const int32_t p = basins[v];
+    basins[v] = p == -1 ? 0 : p < 0 ? -p - 1 : basins[p];
+  }
+  *n_basins = count;
+  return LSR_OK;
+}
+
+extern "C" int lsr_watershed_saddles_f32_cpu(const int32_t* objects, const int32_t* basins, const float* surface, int64_t Z, int64_t Y,
+                                             int64_t X, int connectivity, int64_t capacity, void* table, int32_t* counts,
+                                             lsr_stream_t) {
+  namespace lb = lsr::label;
+  namespace ws = lsr::watershed;
+  if (int rc = ws::check_saddles(objects, basins, surface, Z, Y, X, connectivity, capacity, table, counts)) return rc;
+  const int level = lb::level_of(connectivity);
+  const int64_t plane = Y * X;
+  const uint32_t mask = static_cast<uint32_t>(capacity - 1);
+  const int probes = static_cast<int>(std::min<int64_t>(capacity, ws::kMaxProbes));
+  ws::Saddle* slots = static_cast<ws::Saddle*>(table);
+  counts[0] = counts[1] = 0;
+  for (int64_t z = 0; z < Z; ++z) {
+    for (int64_t y = 0; y < Y; ++y) {
+      for (int64_t x = 0; x < X; ++x) {
+        const int64_t v = z * plane + y * X + x;
+        const int32_t o = objects[v], a0 = basins[v];
+        if (o <= 0 || a0 <= 0) continue;
+        const uint32_t kv = lb::float_key(surface[v]);
+        for (int dz = 0; dz <= 1; ++dz) {
+          for (int dy = -1; dy <= 1; ++dy) {
+            for (int dx = -1; dx <= 1; ++dx) {
+              if (!ws::forward_neighbour(dz, dy, dx, level)) continue;
+              if (z + dz >= Z || y + dy < 0 || y + dy >= Y || x + dx < 0 || x + dx >= X) continue;
+              const int64_t u = v + dz * plane + dy * X + dx;
+              if (objects[u] != o) continue;
+              const int32_t b0 = basins[u];
+              if (b0 <= 0 || b0 == a0) continue;
+              const uint32_t ku = lb::float_key(surface[u]), pass = std::min(ku, kv);
+              const unsigned long long a = static_cast<uint32_t>(std::min(a0, b0)), b = static_cast<uint32_t>(std::max(a0, b0));
+              const unsigned long long pair = a << 32 | b;
+              uint32_t slot = ws::slot_of(pair, mask);
+              bool placed = false;
+              for (int p = 0; p < probes && !placed; ++p, slot = (slot + 1) & mask) {
+                if (slots[slot].pair == 0) {
+                  slots[slot].pair = pair;
+                  counts[0] += 1;
+                }
+                if (slots[slot].pair == pair) {
+                  slots[slot].key = std::max(slots[slot].key, pass);
+                  placed = true;
+                }
+              }
+              if (!placed) counts[1] += 1;
+            }
+          }
+        }
       }
     }
   }

@@ -28,49 +28,19 @@
 //    Every loop here ends because an index strictly decreases: find() walks parent[a] < a, and unite() either installs its
 //    link or continues from the strictly smaller value the atomicMin returned.
 
-#include <algorithm>
 #include <climits>
 
-#include "label.hpp"
+#include "label_uf.hpp"
 
 namespace {
 
 namespace lb = lsr::label;
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / lsr::kWave;
 constexpr int kRows = lb::kTileZ * lb::kTileY;            // tile rows of kTileX = 64 voxels: one wave step each
-constexpr int kPerThread = lb::kChunk / kThreads;         // numbering launches: voxels per thread
-constexpr int kScanThreads = 1024;
 static_assert(lb::kTileX == lsr::kWave, "a tile row is one wavefront");
-static_assert(kRows % kWaves == 0 && lb::kChunk % kThreads == 0, "whole steps");
+static_assert(kRows % kWaves == 0, "whole steps");
 
-// ---- union-find on LDS words (local) and on global words (merge, flatten) ------------------------------------------------
-
-__device__ __forceinline__ int ld_lds(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ __forceinline__ int ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-template <bool LDS>
-__device__ __forceinline__ int find(const int* P, int a) {
-  for (;;) {
-    const int p = LDS ? ld_lds(P + a) : ld(P + a);
-    if (p == a) return a;
-    a = p;                      // p < a: the walk ends
-  }
-}
-
-template <bool LDS>
-__device__ __forceinline__ void unite(int* P, int a, int b) {
-  for (;;) {
-    a = find<LDS>(P, a);
-    b = find<LDS>(P, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }          // a > b: hang a under b
-    const int old = atomicMin(P + a, b);
-    if (old == a) return;       // a was still a root: linked
-    a = old;                    // someone lowered parent[a] to old < a first: parent[a] = min(old, b) now, and uniting old with b
-  }                             // keeps the link that lost; a strictly decreased
-}
+// (the union-find on LDS and global words, and the launches flatten, count, scan, rank and final: label_uf.hpp)
 
 // ---- local: one tile in LDS -------------------------------------------------------------------------------------------------
 
@@ -177,107 +147,6 @@ __global__ __launch_bounds__(kThreads) void label_merge_kernel(int* parent, Shap
         }
       }
     }
-  }
-}
-
-// ---- flatten --------------------------------------------------------------------------------------------------------------------
-
-__global__ __launch_bounds__(kThreads) void label_flatten_kernel(int* parent, int64_t n) {
-  for (int64_t v = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; v < n; v += static_cast<int64_t>(gridDim.x) * kThreads) {
-    const int p = parent[v];                 // (this thread alone writes the word)
-    if (p < 0 || p == v) continue;
-    const int r = find<false>(parent, p);    // old and new values of the words on the way are both ancestors
-    if (r != p) parent[v] = r;
-  }
-}
-
-// ---- number: count, scan, rank, final ---------------------------------------------------------------------------------------------
-
-// The roots of one 4096-voxel block: bit k of the result is voxel base + k * 256 + thread.
-__device__ __forceinline__ unsigned root_bits(const int* __restrict__ parent, int64_t base, int64_t n) {
-  unsigned bits = 0;
-#pragma unroll
-  for (int k = 0; k < kPerThread; ++k) {
-    const int64_t v = base + k * kThreads + threadIdx.x;
-    if (v < n && parent[v] == static_cast<int>(v)) bits |= 1u << k;
-  }
-  return bits;
-}
-
-__global__ __launch_bounds__(kThreads) void label_count_kernel(const int* __restrict__ parent, int64_t n, int* __restrict__ counts) {
-  __shared__ int part[kWaves];
-  int c = __popc(root_bits(parent, static_cast<int64_t>(blockIdx.x) * lb::kChunk, n));
-  for (int d = lsr::kWave / 2; d > 0; d >>= 1) c += __shfl_down(c, d);
-  if (threadIdx.x % lsr::kWave == 0) part[threadIdx.x / lsr::kWave] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int total = 0;
-    for (int w = 0; w < kWaves; ++w) total += part[w];
-    counts[blockIdx.x] = total;
-  }
-}
-
-// one workgroup: counts[b] <- sum of counts[0 .. b), *n_objects <- the total
-__global__ __launch_bounds__(kScanThreads) void label_scan_kernel(int* counts, int64_t blocks, int* n_objects) {
-  __shared__ int sums[kScanThreads];
-  const int64_t per = (blocks + kScanThreads - 1) / kScanThreads;
-  const int64_t first = per * threadIdx.x, lo = first < blocks ? first : blocks, hi = lo + per < blocks ? lo + per : blocks;
-  int mine = 0;
-  for (int64_t b = lo; b < hi; ++b) mine += counts[b];
-  sums[threadIdx.x] = mine;
-  __syncthreads();
-  for (int d = 1; d < kScanThreads; d <<= 1) {            // inclusive scan
-    const int add = threadIdx.x >= static_cast<unsigned>(d) ? sums[threadIdx.x - d] : 0;
-    __syncthreads();
-    sums[threadIdx.x] += add;
-    __syncthreads();
-  }
-  int run = sums[threadIdx.x] - mine;
-  for (int64_t b = lo; b < hi; ++b) {
-    const int c = counts[b];
-    counts[b] = run;
-    run += c;
-  }
-  if (threadIdx.x == kScanThreads - 1) *n_objects = sums[kScanThreads - 1];
-}
-
-__global__ __launch_bounds__(kThreads) void label_rank_kernel(int* __restrict__ parent, int64_t n, const int* __restrict__ offsets) {
-  __shared__ unsigned long long masks[kPerThread][kWaves];
-  const int lane = threadIdx.x % lsr::kWave, wave = threadIdx.x / lsr::kWave;
-  const int64_t base = static_cast<int64_t>(blockIdx.x) * lb::kChunk;
-  const unsigned bits = root_bits(parent, base, n);
-#pragma unroll
-  for (int k = 0; k < kPerThread; ++k) {
-    const unsigned long long mask = __ballot((bits >> k) & 1u);
-    if (lane == 0) masks[k][wave] = mask;
-  }
-  __syncthreads();
-  if (bits == 0) return;
-  // voxel order inside the block: step k, then wave, then lane
-  int run = offsets[blockIdx.x];
-  for (int k = 0; k < kPerThread; ++k) {
-    for (int w = 0; w < kWaves; ++w) {
-      const unsigned long long mask = masks[k][w];
-      if (w == wave && ((bits >> k) & 1u)) {
-        const int rank = run + __popcll(mask & ((1ull << lane) - 1ull));
-        parent[base + k * kThreads + threadIdx.x] = -(rank + 2);         // (a root's own word: nobody else reads it in this launch)
-      }
-      run += __popcll(mask);
-    }
-  }
-}
-
-__global__ __launch_bounds__(kThreads) void label_final_kernel(int* labels, int64_t n) {
-  for (int64_t v = static_cast<int64_t>(blockIdx.x) * kThreads + threadIdx.x; v < n; v += static_cast<int64_t>(gridDim.x) * kThreads) {
-    const int p = labels[v];                 // (this thread alone writes the word)
-    int out;
-    if (p < 0) {
-      out = -p - 1;                          // background -1 -> 0, a root -(rank + 2) -> rank + 1
-    } else {
-      const int r = ld(labels + p);          // the root's word: -(rank + 2) before its own thread has passed, rank + 1 after
-      out = r < 0 ? -r - 1 : r;
-    }
-    labels[v] = out;
   }
 }
 
@@ -394,11 +263,6 @@ __global__ __launch_bounds__(kThreads) void label_remap_kernel(int* labels, int6
   }
 }
 
-constexpr int64_t kMaxBlocks = 1 << 16;      // grid-stride launches: 256 per CU
-constexpr int64_t kMaxTileBlocks = 1 << 22;  // local: 2^22 * 256 threads < 2^32 (the config-2 grid has 1.9e5 tiles)
-
-unsigned stride_grid(int64_t n) { return static_cast<unsigned>(std::min(lsr::ceil_div(n, kThreads), kMaxBlocks)); }
-
 }  // namespace
 
 extern "C" int lsr_label_tile_shape(int zyx[3]) {
@@ -423,7 +287,7 @@ int label_launches(const float* in, int64_t Z, int64_t Y, int64_t X, float thres
                    int32_t* n_objects, void* scratch, hipStream_t q, hipEvent_t* events) {
   const int level = lb::level_of(connectivity);
   const Shape s{static_cast<int>(Z), static_cast<int>(Y), static_cast<int>(X)};
-  const int64_t n = Z * Y * X, blocks = lb::number_blocks(n);
+  const int64_t n = Z * Y * X;
   const int64_t tz = lsr::ceil_div(Z, lb::kTileZ), ty = lsr::ceil_div(Y, lb::kTileY), tx = lsr::ceil_div(X, lb::kTileX);
   const int64_t pieces = lsr::ceil_div(X, kThreads), units = Z * Y * pieces;
   int* counts = static_cast<int*>(scratch);
@@ -439,16 +303,7 @@ int label_launches(const float* in, int64_t Z, int64_t Y, int64_t X, float thres
   mark();
   hipLaunchKernelGGL(label_merge_kernel, dim3(static_cast<unsigned>(std::min(units, kMaxBlocks))), dim3(kThreads), 0, q, labels, s,
                      level, pieces, units);
-  mark();
-  hipLaunchKernelGGL(label_flatten_kernel, dim3(stride_grid(n)), dim3(kThreads), 0, q, labels, n);
-  mark();
-  hipLaunchKernelGGL(label_count_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, q, labels, n, counts);
-  mark();
-  hipLaunchKernelGGL(label_scan_kernel, dim3(1), dim3(kScanThreads), 0, q, counts, blocks, n_objects);
-  mark();
-  hipLaunchKernelGGL(label_rank_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, q, labels, n, counts);
-  mark();
-  hipLaunchKernelGGL(label_final_kernel, dim3(stride_grid(n)), dim3(kThreads), 0, q, labels, n);
+  number_launches(labels, n, counts, n_objects, q, mark);
   mark();
   return lsr::launch_status("lsr_label_f32");
 }

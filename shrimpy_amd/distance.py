@@ -16,7 +16,7 @@ every y line and every z line, float64 costs), ``csrc/host_twins.hip`` on the CP
 * :func:`expand_labels` -- ``skimage.segmentation.expand_labels(labels, distance, spacing=sampling)`` up to the tie rule.
 
 Not built: a stand-alone ``distance`` command, a float distance channel in an output store, multi-GPU or slab transforms,
-volumes above ``2^31 - 1`` voxels, watershed or any splitting of touching objects.
+volumes above ``2^31 - 1`` voxels.
 """
 
 from __future__ import annotations

@@ -10,11 +10,12 @@ numbering is a prefix count), ``csrc/host_twins.hip`` on the CPU; both equal ``s
   mean, minimum, maximum and the intensity-weighted centroid.  The integer columns and the intensity range are exact; the
   float64 sums are atomic adds on the device (within ``n_k * 2^-53 * sum|terms|`` of the exact sum, not bit-reproducible).
 * :func:`filter_objects` -- drop small objects or keep the largest; the kept labels stay consecutive, in their old order.
-* :func:`segment_zyx` -- threshold (a number or multi-Otsu, after an optional Gaussian blur), label, measure, filter, and on
-  request grow the labels by a distance and measure each object's inscribed radius (``shrimpy_amd/distance.py``).
+* :func:`segment_zyx` -- threshold (a number or multi-Otsu, after an optional Gaussian blur), label, on request split the
+  touching objects by a watershed of their depth map (``shrimpy_amd/watershed.py``), measure, filter, and on request grow the
+  labels by a distance and measure each object's inscribed radius (``shrimpy_amd/distance.py``).
 
-Not built: watershed or any splitting of touching objects, multi-GPU or slab labelling, tracking across timepoints, label
-pyramids, volumes above ``2^31 - 1`` voxels.
+Not built: seeded watersheds, multi-GPU or slab labelling, tracking across timepoints, label pyramids, volumes above
+``2^31 - 1`` voxels.
 """
 
 from __future__ import annotations
@@ -179,7 +180,10 @@ def segment_zyx(vol, settings, sampling=(1, 1, 1)):
     ``(labels, table, n)``.  With ``sigma > 0`` the blurred volume is thresholded; with ``threshold: otsu`` the threshold is
     the multi-Otsu one of what is thresholded (a constant volume has no objects).  The table's intensities are ``vol``'s.
 
-    ``sampling = (sz, sy, sx)`` is the voxel spacing the two distance settings measure in (``shrimpy_amd/distance.py``).  With
+    ``sampling = (sz, sy, sx)`` is the voxel spacing the distance settings measure in (``shrimpy_amd/distance.py``).  With
+    ``split`` the labelled objects are split before anything else sees them (``watershed.split_touching``: the watershed of
+    each object's depth map, blurred by ``split_sigma`` voxels, basins shallower than ``split_min_depth`` merged), so the
+    table, ``min_volume`` and ``keep_largest`` act on the split objects.  With
     ``expand_distance > 0`` the labels that survive the filter grow into the background by at most that distance (a dropped
     speck claims no space) and the table is that of the grown labels.  With ``inscribed_radius`` the table gains the column
     ``inscribed_radius``: per object the greatest distance of one of its voxels to the nearest background voxel, of the final
@@ -195,6 +199,11 @@ def segment_zyx(vol, settings, sampling=(1, 1, 1)):
     else:
         threshold = float(settings.threshold)
     labels, n = label_volume(work, threshold, int(settings.connectivity))
+    if settings.split and n > 0:
+        from . import watershed
+
+        labels, n = watershed.split_touching(labels, sampling, float(settings.split_sigma), float(settings.split_min_depth),
+                                             int(settings.connectivity))
     table = region_table(labels, n, vol)
     if settings.min_volume > 0 or settings.keep_largest:
         labels, table, n = filter_objects(labels, table, int(settings.min_volume), bool(settings.keep_largest))

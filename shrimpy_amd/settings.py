@@ -559,7 +559,14 @@ class SegmentSettings(_StrictModel):
     that survive the filter into the background by at most that distance, without overlap (``skimage``'s ``expand_labels``
     rule on the exact Euclidean distance transform, ``shrimpy_amd/distance.py``); the table is then that of the grown labels.
     ``inscribed_radius`` adds a column of that name: per object the greatest distance from one of its voxels to the nearest
-    background voxel, of the final labels (``inscribed_radius_um`` in ``objects.csv``)."""
+    background voxel, of the final labels (``inscribed_radius_um`` in ``objects.csv``).
+
+    ``split`` splits touching objects after the labelling and before the size filter (``shrimpy_amd/watershed.py``): a
+    watershed by steepest ascent of each object's depth map -- the exact Euclidean distance to the background, blurred by a
+    Gaussian of ``split_sigma`` voxels -- whose basins are merged where the depth of the pass between them is at most
+    ``split_min_depth`` (in the units of ``expand_distance``: micrometres from the ``segment`` command).  The merge depth, not
+    the blur, is the knob that makes the result stable; no upstream is pinned for this step (its rule is the specification).
+    ``min_volume`` and ``keep_largest`` then act on the split objects."""
 
     channel_name: str
     threshold: Union[float, Literal["otsu"]]
@@ -570,6 +577,9 @@ class SegmentSettings(_StrictModel):
     keep_largest: bool = False
     inscribed_radius: bool = False
     expand_distance: NonNegativeFloat = 0.0
+    split: bool = False
+    split_sigma: NonNegativeFloat = 1.0
+    split_min_depth: NonNegativeFloat = 0.0
 
     @field_validator("threshold")
     @classmethod

@@ -69,6 +69,11 @@ def main():
                     "threshold, Bernoulli noise at p = 0.3 (connectivity 6) and an all-foreground volume, beside a device copy "
                     "and scipy.ndimage.label on this box's host at --label-host-grid; appended to profiles/label_config2.jsonl")
     ap.add_argument("--label-host-grid", default="43,512,568", help="Z,Y,X of the scipy.ndimage.label timing of --label")
+    ap.add_argument("--watershed", action="store_true", help="only: ms per launch of the watershed (csrc/watershed.hip: local, merge, "
+                    "flatten, count, scan, rank, final; HIP events between the launches, median of 3 calls after a warm-up) and of "
+                    "the saddle pass on --rl-grid, for the three scenes of --label -- the objects are the labelling's, the surface "
+                    "their depth map blurred with sigma 1 -- beside the labelling's seven launches on the same scene and a device "
+                    "copy in the same run; appended to profiles/watershed_config2.jsonl")
     ap.add_argument("--edt", action="store_true", help="only: ms per launch of the distance transform (csrc/edt.hip: x, y, z; HIP "
                     "events between the launches, median of 5 calls after a warm-up) on --rl-grid, for bench.synthetic_raw at its "
                     "multi-Otsu threshold, Bernoulli noise at p = 0.3 and an all-foreground volume with one background voxel, "
@@ -103,6 +108,9 @@ def main():
         return
     if args.mi:
         _mi(args, torch, dev, g, bench, tuple(int(v) for v in args.mi_grid.split(",")))
+        return
+    if args.watershed:
+        _watershed(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
         return
     if args.edt:
         _edt(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
@@ -674,6 +682,97 @@ def _label(args, torch, dev, g, bench, oshape):
                     "connectivity": 6, "objects": int(n_host), "ms": 1e3 * host_s, "Mvox_per_s": mask.size / host_s / 1e6})
     stamp = {"sources": _lib.kernel_source_sha16(), "device": torch.cuda.get_device_name(dev), "reps": reps, "warmups": 1}
     path = ROOT / "profiles" / "label_config2.jsonl"
+    with open(path, "a") as f:
+        for r in records:
+            line = json.dumps({**r, **stamp})
+            print(line, flush=True)
+            f.write(line + "\n")
+
+
+# algorithmic bytes per voxel of each launch of the watershed (csrc/watershed.hip): local reads objects and surface and writes a
+# parent word and a direction byte (the halo's re-reads aside), merge reads the direction bytes; the rest is the labelling's
+WATERSHED_BYTES_PER_VOXEL = {**LABEL_BYTES_PER_VOXEL, "local": 13.0, "merge": 1.0, "saddles": 12.0}
+
+
+def _watershed(args, torch, dev, g, bench, oshape):
+    """The watershed (csrc/watershed.hip) at the config-2 deskewed shape on the three scenes of --label: the objects are the
+    labelling's (connectivity 6), the surface is their depth map (distance.distance_transform_labels, invert) blurred with sigma
+    1 -- what SegmentSettings.split runs.  Every launch of lsr_watershed_f32 on its own (HIP events between them:
+    lsr_watershed_profile_f32), the labelling's seven launches on the same scene in the same run, and the saddle pass (the
+    table's memset included; no wave pre-reduction is built).  All foreground has no background voxel: its depth is +inf
+    everywhere, one plateau that the index rule alone orders -- the longest chains this rule can make."""
+    from shrimpy_amd import _lib, distance, dynatrack, watershed
+
+    reps = 3
+    z, y, x = oshape
+    n = z * y * x
+    labels = torch.empty(oshape, dtype=torch.int32, device=dev)
+    basins = torch.empty_like(labels)
+    copy_ms = _median_ms(lambda: basins.copy_(labels), reps, torch)
+    records = [{"kernel": "device copy (torch copy_)", "grid": list(oshape), "ms": copy_ms, "GBps": 8.0 * n / copy_ms / 1e6}]
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    scratch = torch.empty(_lib.call_value("lsr_watershed_scratch_bytes", z, y, x), dtype=torch.uint8, device=dev)
+    ms7 = (ctypes.c_float * 7)()
+
+    def scenes():
+        vol = bench.synthetic_raw(oshape, 1000, dev)
+        yield "bead scene (bench.synthetic_raw) at its multi-Otsu threshold", vol, float(dynatrack._multiotsu_threshold(vol, 0))
+        del vol
+        yield "Bernoulli noise, p = 0.3", torch.rand(oshape, device=dev, generator=g), 0.7
+        yield "all foreground", torch.ones(oshape, dtype=torch.float32, device=dev), 0.5
+
+    for name, vol, threshold in scenes():
+        times = []
+        for _ in range(reps + 1):
+            _lib.call("lsr_label_profile_f32", vol.data_ptr(), z, y, x, ctypes.c_float(threshold), 6, labels.data_ptr(),
+                      count.data_ptr(), scratch.data_ptr(), ms7, _lib.stream_ptr(dev))
+            times.append(list(ms7))
+        label_med = np.median(np.asarray(times[1:]), axis=0)
+        n_objects = int(count.item())
+        del vol
+        print(f"# {name}: {n_objects} objects, labelled in {float(label_med.sum()):.2f} ms", flush=True)
+        surface = dynatrack._gaussian_blur_3d(distance.distance_transform_labels(labels, (1, 1, 1), invert=True), 1.0)
+        torch.cuda.empty_cache()
+        times = []
+        for _ in range(reps + 1):
+            _lib.call("lsr_watershed_profile_f32", labels.data_ptr(), surface.data_ptr(), z, y, x, 6, basins.data_ptr(),
+                      count.data_ptr(), scratch.data_ptr(), ms7, _lib.stream_ptr(dev))
+            times.append(list(ms7))
+        med = np.median(np.asarray(times[1:]), axis=0)
+        n_basins = int(count.item())
+        print(f"# {name}: {n_basins} basins in {float(med.sum()):.2f} ms", flush=True)
+        base = {"input": name, "grid": list(oshape), "connectivity": 6, "objects": n_objects, "basins": n_basins,
+                "surface": "depth map (exact EDT), Gaussian sigma 1", "foreground_fraction": float((labels != 0).sum().item()) / n}
+        for launch, ms, lms in zip(LABEL_LAUNCHES, med, label_med):
+            bpv = WATERSHED_BYTES_PER_VOXEL[launch]
+            records.append({**base, "kernel": f"lsr_watershed_f32: {launch}", "ms": float(ms), "bytes_per_voxel": bpv,
+                            "algorithmic_GBps": bpv * n / float(ms) / 1e6, "lsr_label_f32_same_launch_ms": float(lms)})
+        records.append({**base, "kernel": "lsr_watershed_f32: all seven launches", "ms": float(med.sum()),
+                        "Mvox_per_s": n / float(med.sum()) / 1e3, "lsr_label_f32_all_seven_launches_ms": float(label_med.sum())})
+        if n_basins >= 2:
+            capacity = min(1 << int(4 * n_basins + 1024 - 1).bit_length(), 1 << 30)    # (watershed.basin_saddles' first capacity)
+            counts = torch.zeros(2, dtype=torch.int32, device=dev)
+            while True:
+                table = torch.zeros(capacity * watershed.SADDLE_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+
+                def saddles():
+                    table.zero_()
+                    _lib.call("lsr_watershed_saddles_f32", labels.data_ptr(), basins.data_ptr(), surface.data_ptr(), z, y, x, 6,
+                              capacity, table.data_ptr(), counts.data_ptr(), _lib.stream_ptr(dev))
+
+                ms = _median_ms(saddles, reps, torch)
+                claimed, lost = (int(v) for v in counts.cpu().tolist())
+                records.append({**base, "kernel": "lsr_watershed_saddles_f32 (the table's memset included; no wave pre-reduction)",
+                                "ms": ms, "capacity": capacity, "saddles": claimed, "pairs_without_a_slot": lost,
+                                "bytes_per_voxel": WATERSHED_BYTES_PER_VOXEL["saddles"], "algorithmic_GBps": 12.0 * n / ms / 1e6})
+                del table
+                if lost == 0 or capacity >= 1 << 30:
+                    break
+                capacity *= 2
+        del surface
+        torch.cuda.empty_cache()
+    stamp = {"sources": _lib.kernel_source_sha16(), "device": torch.cuda.get_device_name(dev), "reps": reps, "warmups": 1}
+    path = ROOT / "profiles" / "watershed_config2.jsonl"
     with open(path, "a") as f:
         for r in records:
             line = json.dumps({**r, **stamp})
