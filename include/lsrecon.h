@@ -1037,6 +1037,32 @@ int lsr_watershed_profile_f32(const int32_t* objects, const float* surface, int6
                               int32_t* basins, int32_t* n_basins, void* scratch, float* ms7, lsr_stream_t stream);
 
 /*
+ * The contingency table of two label volumes (csrc/overlap.hip; the rule is stated in csrc/overlap.hpp): what
+ * shrimpy_amd/track.py links the objects of consecutive timepoints by.  No upstream is pinned; tests/track_ref.py restates
+ * the rule with np.unique, and device, twin and restatement agree as sets of records, exactly.
+ *
+ * lsr_label_overlap_i32: a, b are int32 (Z, Y, X) volumes (device memory), shift_zyx three integers in HOST memory.  For
+ * every voxel v = (z, y, x) with u = v + shift inside the volume, a[v] > 0 and b[u] > 0, the pair (a[v], b[u]) gains 1;
+ * labels <= 0 are background.  `table` (device memory, WHICH THE CALLER HAS ZEROED) is an open-addressing hash table of
+ * `capacity` 16-byte records, capacity a power of two in 1 .. 2^30: uint64 pair = (uint32)a << 32 | (uint32)b (0: the slot
+ * is empty); uint64 count.  A pair starts probing where the saddle table's does (csrc/pair_hash.hpp) and probes linearly
+ * over at most min(capacity, 256) slots.  counts (int32[2], device memory, set by the entry): counts[0] = the slots claimed,
+ * counts[1] = the contributions (voxels) that found no slot -- if it is not zero the table holds partial counts: come back
+ * with a larger one.  Which slot a record lands in depends on the order of arrival: the contract is the set of records.
+ * max_blocks caps the grid (0: the default of lsr_label_overlap_geometry); the result does not depend on it.
+ * Everything wrong with a call is LSR_E_ARG, before any launch and with nothing written: a NULL pointer, a non-positive
+ * extent or more than 2^31 - 1 voxels, a capacity that is no power of two in range, max_blocks < 0, a table that overlaps
+ * a or b.  A shift at or beyond an extent leaves the table empty and counts zero.
+ * One launch (and the clearing of counts): each workgroup walks one contiguous span of the volume, reduces runs of equal
+ * pairs inside a wave by one ballot, accumulates in a table in LDS and flushes it once, so an all-foreground volume costs
+ * one global atomic pair per workgroup; shared words are touched by atomics only, nothing waits for anything.
+ * lsr_label_overlap_geometry: out[0] = the slots of one workgroup's LDS table, out[1] = the default cap of the grid.
+ */
+int lsr_label_overlap_geometry(int out[2]);
+int lsr_label_overlap_i32(const int32_t* a, const int32_t* b, int64_t Z, int64_t Y, int64_t X, const int32_t shift_zyx[3],
+                          int64_t capacity, void* table, int32_t* counts, int max_blocks, lsr_stream_t stream);
+
+/*
  * Host twins (csrc/host_twins.hip): the same signatures with HOST pointers, the same argument checks and the
  * same arithmetic in the same order, so the results equal the device entry points' bit for bit.  They serve
  * the boxes where the reference itself resolves to the CPU (shrimpy/preprocessing.py:78-82 -- its CI has no
@@ -1177,6 +1203,11 @@ int lsr_watershed_f32_cpu(const int32_t* objects, const float* surface, int64_t 
 int lsr_watershed_saddles_f32_cpu(const int32_t* objects, const int32_t* basins, const float* surface, int64_t Z, int64_t Y,
                                   int64_t X, int connectivity, int64_t capacity, void* table, int32_t* counts,
                                   lsr_stream_t stream);
+
+/* ... of the label-overlap table (csrc/overlap.hip): plain sequential code over the same rule, record, hash and probe bound
+ * (csrc/overlap.hpp): the kernel's set of records.  Every pointer HOST memory; max_blocks is checked and otherwise unused. */
+int lsr_label_overlap_i32_cpu(const int32_t* a, const int32_t* b, int64_t Z, int64_t Y, int64_t X, const int32_t shift_zyx[3],
+                              int64_t capacity, void* table, int32_t* counts, int max_blocks, lsr_stream_t stream);
 
 /* ... of the mutual-information metric (csrc/estimate_mi.hip): the per-sample rule of csrc/mi_sample.hpp on both sides.
  * The histogram and the count are the kernel's bits; the gradient rows are sums over lsr_affine_mi_gradient_blocks()

@@ -186,6 +186,9 @@ SIGNATURES: dict[str, list] = {
                                   ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), _stream],
     "lsr_watershed_saddles_f32": [ctypes.c_void_p, ctypes.c_void_p, _c_f32p, _i64, _i64, _i64, _int, _i64, ctypes.c_void_p,
                                   ctypes.c_void_p, _stream],
+    "lsr_label_overlap_geometry": [ctypes.POINTER(ctypes.c_int)],
+    "lsr_label_overlap_i32": [ctypes.c_void_p, ctypes.c_void_p, _i64, _i64, _i64, ctypes.POINTER(ctypes.c_int32), _i64,
+                              ctypes.c_void_p, ctypes.c_void_p, _int, _stream],
     "lsr_crc32c_host": [ctypes.c_void_p, _i64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)],
     "lsr_crc32c_host_portable": [ctypes.c_void_p, _i64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)],
     "lsr_average_slices_f32": [_c_f32p, _i64, _i64, _i64, _c_f32p, _i64, _int, _stream],
@@ -275,7 +278,9 @@ for _name in ("lsr_deskew_f32", "lsr_deskew_u16", "lsr_deskew_cval", "lsr_affine
               # ... and of the distance transform and the label expansion (csrc/edt.hip)
               "lsr_edt_f32", "lsr_edt_labels_i32", "lsr_label_expand_i32",
               # ... and of the watershed (csrc/watershed.hip)
-              "lsr_watershed_f32", "lsr_watershed_saddles_f32"):
+              "lsr_watershed_f32", "lsr_watershed_saddles_f32",
+              # ... and of the label-overlap table (csrc/overlap.hip)
+              "lsr_label_overlap_i32"):
     SIGNATURES[_name + "_cpu"] = SIGNATURES[_name]
 # entries whose answer is a byte count that can pass 2^31 (a negative value is a status)
 RETURNS_INT64 = ("lsr_edt_scratch_bytes", "lsr_watershed_scratch_bytes")

@@ -1615,6 +1615,143 @@ def run_segment(input_path, config, output_path, positions=(), zarr_version: str
             dist.destroy_process_group()
 
 
+TRACK_COLUMNS = ("track_id", "t_begin", "t_end", "parent_track_id")
+TRACK_OBJECT_COLUMNS = ("t", "label", "track_id", "parent_label", "overlap_voxels", "iou")
+
+
+@cli.command(cls=_eat_all_command("-i", "--input-position-dirpaths"))
+@click.option("-i", "--input-position-dirpaths", "input_path", required=True, multiple=True, type=click.UNPROCESSED,
+              help="Input OME-Zarr store of integer labels (HCS plate or single FOV), or the position directories of one plate.")
+@click.option("-c", "--config-filepath", "config", required=True, type=click.Path(exists=True, dir_okay=False, path_type=Path),
+              help="TrackSettings YAML.")
+@click.option("-o", "--output-dirpath", "output_path", required=True, type=click.Path(path_type=Path),
+              help="Output OME-Zarr store of int32 track ids (must not exist); tracks.csv and track_objects.csv are written "
+                   "beside each position's array.")
+@click.option("-p", "--position", "positions", multiple=True, help='Restrict to these position keys ("row/col/fov"); repeatable.')
+@click.option("--zarr-version", type=click.Choice(["0.4", "0.5"]), default="0.5", show_default=True,
+              help="NGFF version of the output store.")
+@click.option("--io", "io_backend", type=click.Choice(["auto", "native", "iohub"]), default="auto", show_default=True,
+              help="Store access for the input: this package's reader, iohub, or native with iohub as the fallback.")
+@click.option("--compression", type=click.Choice(["none", "gzip", "zstd", "blosc-zstd"]), default="blosc-zstd", show_default=True,
+              help="Chunk compression of the output.")
+def track(input_path, config, output_path, positions, zarr_version, io_backend, compression):
+    """Link the labelled objects of consecutive timepoints by their voxel overlap (config: a TrackSettings YAML).
+
+    Writes an int32 array "0" with the channel <channel_name>_tracks per position (every voxel's track id), tracks.csv
+    (track_id, t_begin, t_end, parent_track_id: tracks are contiguous in time, so this is the whole lineage) and
+    track_objects.csv (one row per object: its track, the label it was linked to, the shared voxels and their IoU).
+    Gap closing is not built: an object that is missing from one frame starts a new track when it comes back."""
+    input_path, positions = _inputs(input_path, positions)
+    _finish(run_track(input_path, config, output_path, positions, zarr_version, io_backend, compression))
+
+
+def run_track(input_path, config, output_path, positions=(), zarr_version: str = "0.5", io_backend: str = "auto",
+              compression=None) -> dict:
+    """``track``: the label volumes of ``channel_name`` of every position go through ``track.Tracker`` in order of ``t`` (each
+    is uploaded once; the overlap table of two consecutive frames is ``csrc/overlap.hip``'s, or its host twin's on a CPU-only
+    machine); the track ids are written as ``int32`` (the input's ``scale`` and ``translation`` copied), the track table as
+    ``<output>/<position>/tracks.csv`` (``TRACK_COLUMNS``) and the per-object links as ``track_objects.csv``
+    (``TRACK_OBJECT_COLUMNS``).  Everything is checked before the output store is created; with several ranks the positions are
+    dealt out in turn.  The output is written by this package's own writer."""
+    import csv
+
+    import torch
+
+    from .io.omezarr import as_volume_array, open_ome_zarr, position_scale
+    from .settings import TrackSettings
+    from .track import Tracker, relabel_by_track
+
+    try:
+        settings = TrackSettings.from_yaml(config)
+    except (ValueError, TypeError) as exc:
+        raise click.ClickException(f"{config}: {exc}") from exc
+    rank, world, device, created = _distributed()
+    try:
+        src, src_positions = _open_source(Path(input_path), io_backend)
+        try:
+            missing = [p for p in positions if p not in src_positions]
+            if missing:
+                raise click.ClickException(f"positions {missing} not found; available: {list(src_positions)}")
+            keys = [k for k in src_positions if not positions or k in positions]
+            if not keys:
+                raise click.ClickException("no positions to process")
+            arrays, channel, geometry = {}, {}, {}
+            for k in keys:
+                pos = src_positions[k]
+                names = list(pos.channel_names)
+                if settings.channel_name not in names:
+                    raise click.ClickException(f"channel_name {settings.channel_name!r} not in position {k} (it has {names})")
+                a = as_volume_array(pos["0"])
+                if len(a.shape) != 5:
+                    raise click.ClickException(f"position {k}: expected 5-D TCZYX data, got shape {tuple(a.shape)}")
+                if np.dtype(a.dtype).kind not in "iu":
+                    raise click.ClickException(f"position {k}: data type {a.dtype}; labels are integer data (int32 from segment)")
+                if int(np.prod(a.shape[2:], dtype=np.int64)) > 2 ** 31 - 1:
+                    raise click.ClickException(f"position {k}: a volume of {tuple(a.shape[2:])} has more than 2^31 - 1 voxels")
+                arrays[k], channel[k] = a, names.index(settings.channel_name)
+                geometry[k] = (list(position_scale(pos)), list(_position_translation(pos)))
+            out_channel = f"{settings.channel_name}_tracks"
+            error = None
+            if rank == 0:
+                try:
+                    if Path(output_path).exists() and any(Path(output_path).iterdir()):
+                        raise FileExistsError(f"{output_path} exists (never overwritten)")
+                    dst = open_ome_zarr(output_path, layout="hcs", mode="w", channel_names=[out_channel], version=zarr_version,
+                                        prefer_iohub=False)
+                    extra = {} if compression in (None, "none") else {"compress": compression}
+                    for k in keys:
+                        scale, translation = geometry[k]
+                        shape = (int(arrays[k].shape[0]), 1) + tuple(int(n) for n in arrays[k].shape[2:])
+                        dst.create_position(*k.split("/")).create_zeros("0", shape=shape, dtype="int32", scale=scale,
+                                                                        translation=translation if any(translation) else None,
+                                                                        **extra)
+                    dst.close()
+                except Exception as exc:  # noqa: BLE001 -- reported on every rank, see _agree
+                    error = f"{type(exc).__name__}: {exc}"
+            _agree(error)
+            dst = open_ome_zarr(output_path, layout="hcs", mode="a", channel_names=[out_channel], version=zarr_version,
+                                prefer_iohub=False)
+            dst_positions = dict(dst.positions())
+            counts = {}
+            t0 = time.perf_counter()
+            try:
+                for k in keys[rank::world]:
+                    out = as_volume_array(dst_positions[k]["0"])
+                    tracker = Tracker(settings)
+                    for t in range(int(arrays[k].shape[0])):
+                        vol = np.asarray(arrays[k].read_volume(t, channel[k]))
+                        if vol.size and (int(vol.max()) > 2 ** 31 - 1 or int(vol.min()) < -2 ** 31):
+                            raise click.ClickException(f"position {k}, t = {t}: a label does not fit int32")
+                        labels = torch.as_tensor(np.ascontiguousarray(vol, dtype=np.int32), device=device)
+                        out.write_volume(t, 0, relabel_by_track(labels, tracker.step(labels)).cpu().numpy())
+                    tracks = tracker.tracks()
+                    counts[k] = len(tracks["track_id"])
+                    with open(Path(output_path) / k / "tracks.csv", "w", newline="") as fh:
+                        w = csv.writer(fh)
+                        w.writerow(TRACK_COLUMNS)
+                        w.writerows(zip(*(tracks[c].tolist() for c in TRACK_COLUMNS)))
+                    with open(Path(output_path) / k / "track_objects.csv", "w", newline="") as fh:
+                        w = csv.writer(fh)
+                        w.writerow(TRACK_OBJECT_COLUMNS)
+                        rows = zip(*(tracks["objects"][c].tolist() for c in TRACK_OBJECT_COLUMNS))
+                        w.writerows([[repr(v) if isinstance(v, float) else v for v in row] for row in rows])
+            finally:
+                close = getattr(dst, "close", None)
+                if close:
+                    close()
+            return {"rank": rank, "world_size": world, "positions": len(keys[rank::world]), "tracks": counts,
+                    "seconds": time.perf_counter() - t0, "failed": []}
+        finally:
+            close = getattr(src, "close", None)
+            if close:
+                close()
+    finally:
+        if created:
+            import torch.distributed as dist
+
+            dist.destroy_process_group()
+
+
 @cli.command("pyramid", cls=_eat_all_command("-i", "--input-position-dirpaths"))
 @click.option("-i", "--input-position-dirpaths", "input_path", required=True, multiple=True, type=click.UNPROCESSED,
               help="The store to add levels to, IN PLACE (HCS plate or single FOV), or position directories of one plate.")

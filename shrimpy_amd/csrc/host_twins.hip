@@ -27,6 +27,7 @@
 //                                             <->  the same names without _cpu         (edt.hip)
 //   lsr_watershed_f32_cpu, lsr_watershed_saddles_f32_cpu
 //                                             <->  the same names without _cpu         (watershed.hip)
+//   lsr_label_overlap_i32_cpu                 <->  lsr_label_overlap_i32               (overlap.hip)
 //
 // Arithmetic (what "the same" means):
 //   resamplers -- the text the kernels compile (resample.hpp): coordinates, axis taps with their weights and the
@@ -1554,6 +1555,46 @@ extern "C" int lsr_watershed_saddles_f32_cpu(const int32_t* objects, const int32
             }
           }
         }
+      }
+    }
+  }
+  return LSR_OK;
+}
+
+// ---- label overlap (overlap.hip): plain sequential code over overlap.hpp's rule, record, hash and probe bound ----
+#include "overlap.hpp"
+
+extern "C" int lsr_label_overlap_i32_cpu(const int32_t* a, const int32_t* b, int64_t Z, int64_t Y, int64_t X,
+                                         const int32_t shift_zyx[3], int64_t capacity, void* table, int32_t* counts,
+                                         int max_blocks, lsr_stream_t) {
+  namespace ov = lsr::overlap;
+  if (int rc = ov::check_overlap(a, b, Z, Y, X, shift_zyx, capacity, table, counts, max_blocks)) return rc;
+  counts[0] = counts[1] = 0;
+  if (ov::shift_empties(Z, Y, X, shift_zyx)) return LSR_OK;
+  const int64_t sz = shift_zyx[0], sy = shift_zyx[1], sx = shift_zyx[2], plane = Y * X;
+  const uint32_t mask = static_cast<uint32_t>(capacity - 1);
+  const int probes = static_cast<int>(std::min<int64_t>(capacity, ov::kMaxProbes));
+  ov::Overlap* slots = static_cast<ov::Overlap*>(table);
+  for (int64_t z = std::max<int64_t>(0, -sz); z < std::min(Z, Z - sz); ++z) {
+    for (int64_t y = std::max<int64_t>(0, -sy); y < std::min(Y, Y - sy); ++y) {
+      for (int64_t x = std::max<int64_t>(0, -sx); x < std::min(X, X - sx); ++x) {
+        const int64_t v = z * plane + y * X + x;
+        const int32_t a0 = a[v], b0 = b[v + sz * plane + sy * X + sx];
+        if (a0 <= 0 || b0 <= 0) continue;
+        const unsigned long long pair = ov::pack(a0, b0);
+        uint32_t slot = lsr::pair_slot_of(pair, mask);
+        bool placed = false;
+        for (int p = 0; p < probes && !placed; ++p, slot = (slot + 1) & mask) {
+          if (slots[slot].pair == 0) {
+            slots[slot].pair = pair;
+            counts[0] += 1;
+          }
+          if (slots[slot].pair == pair) {
+            slots[slot].count += 1;
+            placed = true;
+          }
+        }
+        if (!placed) counts[1] += 1;
       }
     }
   }

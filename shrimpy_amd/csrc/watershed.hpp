@@ -15,6 +15,7 @@
 #pragma once
 
 #include "label.hpp"
+#include "pair_hash.hpp"
 
 namespace lsr {
 namespace watershed {
@@ -26,7 +27,7 @@ constexpr int kHaloY = kTileY + 2, kHaloX = kTileX + 2;
 constexpr int kHaloVoxels = (kTileZ + 2) * kHaloY * kHaloX;      // 6600: two words each, 52 800 B of LDS
 constexpr int kSelf = 13;                                        // the code of (0, 0, 0)
 constexpr int kMaxProbes = 256;                                  // a pair gives up after min(capacity, kMaxProbes) slots
-constexpr int64_t kMaxCapacity = int64_t(1) << 30;
+constexpr int64_t kMaxCapacity = kMaxPairCapacity;
 
 // The code of a direction: (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1), ascending in the linear index of the neighbour.
 __host__ __device__ inline int code_of(int dz, int dy, int dx) { return (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1); }
@@ -63,15 +64,8 @@ struct Saddle {
 };
 static_assert(sizeof(Saddle) == 16, "the saddle record's size is part of the ABI");
 
-// Where a pair starts probing (the finaliser of splitmix64).
-__host__ __device__ inline uint32_t slot_of(unsigned long long pair, uint32_t mask) {
-  pair ^= pair >> 30;
-  pair *= 0xbf58476d1ce4e5b9ull;
-  pair ^= pair >> 27;
-  pair *= 0x94d049bb133111ebull;
-  pair ^= pair >> 31;
-  return static_cast<uint32_t>(pair) & mask;
-}
+// Where a pair starts probing: pair_hash.hpp's, shared with the label-overlap table.
+__host__ __device__ inline uint32_t slot_of(unsigned long long pair, uint32_t mask) { return pair_slot_of(pair, mask); }
 
 // Is (dz, dy, dx) one of the neighbours that FOLLOW a voxel in raster order under `level`?
 __host__ __device__ inline bool forward_neighbour(int dz, int dy, int dx, int level) {

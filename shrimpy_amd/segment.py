@@ -14,8 +14,9 @@ numbering is a prefix count), ``csrc/host_twins.hip`` on the CPU; both equal ``s
   touching objects by a watershed of their depth map (``shrimpy_amd/watershed.py``), measure, filter, and on request grow the
   labels by a distance and measure each object's inscribed radius (``shrimpy_amd/distance.py``).
 
-Not built: seeded watersheds, multi-GPU or slab labelling, tracking across timepoints, label pyramids, volumes above
-``2^31 - 1`` voxels.
+Not built: seeded watersheds, multi-GPU or slab labelling, label pyramids, volumes above ``2^31 - 1`` voxels.  Labels are
+numbered from 1 at every timepoint; linking them over time is ``shrimpy_amd/track.py`` (the ``track`` command), where gap
+closing, motion models and a global assignment are not built.
 """
 
 from __future__ import annotations

@@ -589,6 +589,29 @@ class SegmentSettings(_StrictModel):
         return v
 
 
+class TrackSettings(_StrictModel):
+    """Tracking the objects of a label channel over time (``shrimpy_amd/track.py``, the ``track`` command).
+
+    ``channel_name`` is the label channel (``<name>_labels`` from the ``segment`` command).  An object of frame ``t + 1`` is
+    linked to the object of frame ``t`` it shares the most voxels with, among those that share at least ``min_overlap_voxels``
+    and whose intersection over union is at least ``min_iou``.  With ``divisions`` an object with two or more successors ends
+    and each successor starts a track that names it as its parent (the convention of the Cell Tracking Challenge); without,
+    the successor with the greatest overlap continues the track and the others start unrelated ones.  No upstream is pinned
+    for the linking rule (biahub's ``track`` runs ultrack); gap closing is not built."""
+
+    channel_name: str
+    min_overlap_voxels: PositiveInt = 1
+    min_iou: float = 0.0
+    divisions: bool = True
+
+    @field_validator("min_iou")
+    @classmethod
+    def _check_min_iou(cls, v):
+        if not 0.0 <= v <= 1.0:
+            raise ValueError("min_iou must be in 0 .. 1")
+        return v
+
+
 class ReconstructSettings(_StrictModel):
     """Whole per-volume pipeline: (flat-field) -> deskew -> (register) -> (deconvolve)."""
 

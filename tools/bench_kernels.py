@@ -74,6 +74,11 @@ def main():
                     "the saddle pass on --rl-grid, for the three scenes of --label -- the objects are the labelling's, the surface "
                     "their depth map blurred with sigma 1 -- beside the labelling's seven launches on the same scene and a device "
                     "copy in the same run; appended to profiles/watershed_config2.jsonl")
+    ap.add_argument("--overlap", action="store_true", help="only: ms of the label-overlap kernel (csrc/overlap.hip) on --rl-grid for "
+                    "the three scenes of --label, each taken as two frames (the second the first rolled by 2 voxels in x), over a "
+                    "sweep of the grid cap (HIP events, median of 3 calls after a warm-up), beside a device copy of one int32 "
+                    "volume and torch.unique of the packed pairs in the same run, with the global atomics per scene estimated "
+                    "from a sample of the workgroups' spans; appended to profiles/overlap_config2.jsonl")
     ap.add_argument("--edt", action="store_true", help="only: ms per launch of the distance transform (csrc/edt.hip: x, y, z; HIP "
                     "events between the launches, median of 5 calls after a warm-up) on --rl-grid, for bench.synthetic_raw at its "
                     "multi-Otsu threshold, Bernoulli noise at p = 0.3 and an all-foreground volume with one background voxel, "
@@ -108,6 +113,9 @@ def main():
         return
     if args.mi:
         _mi(args, torch, dev, g, bench, tuple(int(v) for v in args.mi_grid.split(",")))
+        return
+    if args.overlap:
+        _overlap(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
         return
     if args.watershed:
         _watershed(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
@@ -784,6 +792,108 @@ EDT_LAUNCHES = ("x", "y", "z")
 # algorithmic bytes per voxel of each launch (csrc/edt.hip) with both outputs asked for: what it must read and write once --
 # the x pass's second sweep over its own words and the envelope stacks of y and z aside
 EDT_BYTES_PER_VOXEL = {"x": 8.0, "y": 8.0, "z": 12.0}
+
+
+OVERLAP_STEP = 1024          # voxels one workgroup takes per stride of its span (csrc/overlap.hpp kStep)
+OVERLAP_CAPS = (256, 1024, 2048, 4096, 16384, 65536, 262144, 1048576)
+
+
+def _overlap(args, torch, dev, g, bench, oshape):
+    """The label-overlap kernel (csrc/overlap.hip) at the config-2 deskewed shape on the three scenes of --label, labelled under
+    connectivity 6; frame t + 1 is frame t rolled by 2 voxels in x.  Per scene: the kernel at every grid cap of OVERLAP_CAPS
+    (the table zeroed outside the timed region; 0 = the default is among them), torch.unique of the packed pairs (what a user
+    without the kernel would write), and the global atomics: each workgroup flushes one compare-and-swap + add per distinct
+    pair of its span, counted here by torch.unique on a sample of 16 spans and scaled to the grid.  The floor is two volume
+    reads, 8 bytes per voxel: the device copy of one int32 volume in the same run moves as much."""
+    from shrimpy_amd import _lib, dynatrack, segment, track
+
+    reps = 3
+    z, y, x = oshape
+    n = z * y * x
+    lds_slots, default_cap = track.overlap_geometry()
+    a = torch.empty(oshape, dtype=torch.int32, device=dev)
+    b = torch.empty_like(a)
+    copy_ms = _median_ms(lambda: b.copy_(a), reps, torch)
+    records = [{"kernel": "device copy of one int32 volume (torch copy_)", "grid": list(oshape), "ms": copy_ms,
+                "GBps": 8.0 * n / copy_ms / 1e6}]
+    del a, b
+    zero3 = (ctypes.c_int32 * 3)(0, 0, 0)
+
+    def scenes():
+        vol = bench.synthetic_raw(oshape, 1000, dev)
+        yield "bead scene (bench.synthetic_raw) at its multi-Otsu threshold", vol, float(dynatrack._multiotsu_threshold(vol, 0))
+        del vol
+        yield "Bernoulli noise, p = 0.3", torch.rand(oshape, device=dev, generator=g), 0.7
+        yield "all foreground", torch.ones(oshape, dtype=torch.float32, device=dev), 0.5
+
+    def geometry(cap):
+        steps = -(-n // OVERLAP_STEP)
+        span = -(-steps // min(steps, cap)) * OVERLAP_STEP
+        return span, -(-n // span)
+
+    for name, vol, threshold in scenes():
+        a, n_objects = segment.label_volume(vol, threshold, 6)
+        del vol
+        b = torch.roll(a, 2, dims=2).contiguous()
+        capacity = 1 << int(4 * min(2 * n_objects, n) + 1024 - 1).bit_length()
+        table = torch.zeros(capacity * track.OVERLAP_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        counts = torch.zeros(2, dtype=torch.int32, device=dev)
+        base = {"input": name, "grid": list(oshape), "objects": n_objects, "capacity": capacity, "lds_slots": lds_slots,
+                "foreground_fraction": float((a != 0).sum().item()) / n}
+        pairs = None
+        for cap in OVERLAP_CAPS:
+            times = []
+            for _ in range(reps + 1):
+                table.zero_()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                _lib.call("lsr_label_overlap_i32", a.data_ptr(), b.data_ptr(), z, y, x, zero3, capacity, table.data_ptr(),
+                          counts.data_ptr(), cap, _lib.stream_ptr(dev))
+                e1.record()
+                torch.cuda.synchronize()
+                times.append(e0.elapsed_time(e1))
+            ms = float(np.median(times[1:]))
+            claimed, lost = (int(v) for v in counts.cpu().tolist())
+            pairs = claimed
+            span, blocks = geometry(cap)
+            # distinct pairs per span on a sample of the spans: what each of those workgroups flushes
+            sample = sorted({int(k) for k in np.linspace(0, blocks - 1, 16)})
+            distinct = []
+            for k in sample:
+                sa, sb = a.view(-1)[k * span:(k + 1) * span], b.view(-1)[k * span:(k + 1) * span]
+                fg = (sa > 0) & (sb > 0)
+                distinct.append(int(torch.unique((sa[fg].long() << 32) | sb[fg].long()).numel()))
+            records.append({**base, "kernel": "lsr_label_overlap_i32", "max_blocks": cap, "default": cap == default_cap,
+                            "workgroups": blocks, "span_voxels": span, "ms": ms, "bytes_per_voxel": 8.0,
+                            "algorithmic_GBps": 8.0 * n / ms / 1e6, "times_the_copy": ms / copy_ms, "pairs": claimed, "lost": lost,
+                            "sampled_spans": len(sample), "distinct_pairs_per_span_mean": float(np.mean(distinct)),
+                            "distinct_pairs_per_span_max": int(max(distinct)),
+                            "spans_over_the_lds_table": int(sum(d > lds_slots for d in distinct)),
+                            "global_atomic_pairs_estimate": float(np.mean(distinct)) * blocks,
+                            "global_atomic_pairs_floor": claimed})
+        del table
+
+        def unique():
+            fg = (a > 0) & (b > 0)
+            return torch.unique((a.long() << 32 | b)[fg], return_counts=True)
+
+        keys, _ = unique()
+        assert int(keys.numel()) == pairs, "torch.unique and the kernel disagree on the number of pairs"
+        del keys
+        ms = _median_ms(unique, reps, torch)
+        records.append({**base, "kernel": "torch.unique((a.long() << 32 | b)[fg], return_counts=True)", "ms": ms, "pairs": pairs,
+                        "times_the_copy": ms / copy_ms})
+        del a, b
+        torch.cuda.empty_cache()
+    stamp = {"sources": _lib.kernel_source_sha16(), "device": torch.cuda.get_device_name(dev), "reps": reps, "warmups": 1,
+             "lds_probes": 16, "alternatives": "the grid cap is swept here; the LDS slot count (2048) and the LDS probe bound (16) "
+                                               "are compile-time constants of csrc/overlap.hpp and were not varied"}
+    path = ROOT / "profiles" / "overlap_config2.jsonl"
+    with open(path, "a") as f:
+        for r in records:
+            line = json.dumps({**r, **stamp})
+            print(line, flush=True)
+            f.write(line + "\n")
 
 
 def _edt(args, torch, dev, g, bench, oshape):
