@@ -18,19 +18,13 @@ import pytest
 from shrimpy_amd import _lib
 from shrimpy_amd.io import codecs
 from shrimpy_amd.io.device_codec import encode_frames_host, plan_frames
+from tests.encoder_cases import fibonacci_bytes as _fibonacci_bytes
 
 
 def _rl_like(n, seed=3):
     """float32 with the byte statistics of a deconvolved volume: few exponents, busy mantissas."""
     rng = np.random.default_rng(seed)
     return (100.0 + 30.0 * rng.standard_normal(n) ** 2 + (rng.random(n) < 1e-3) * rng.uniform(200, 4000, n)).astype(np.float32)
-
-
-def _fibonacci_bytes():
-    counts = [1, 1, 2, 3, 5, 8, 13, 21, 34, 55, 89, 144, 233, 377, 610, 987, 1597, 2584, 4181, 6765, 10946, 17711]
-    arr = np.concatenate([np.full(c, i, np.uint8) for i, c in enumerate(counts)])
-    np.random.default_rng(0).shuffle(arr)
-    return arr[:arr.size // 4 * 4].copy()
 
 
 def _cases():
