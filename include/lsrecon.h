@@ -1045,7 +1045,7 @@ int lsr_watershed_profile_f32(const int32_t* objects, const float* surface, int6
  * every voxel v = (z, y, x) with u = v + shift inside the volume, a[v] > 0 and b[u] > 0, the pair (a[v], b[u]) gains 1;
  * labels <= 0 are background.  `table` (device memory, WHICH THE CALLER HAS ZEROED) is an open-addressing hash table of
  * `capacity` 16-byte records, capacity a power of two in 1 .. 2^30: uint64 pair = (uint32)a << 32 | (uint32)b (0: the slot
- * is empty); uint64 count.  A pair starts probing where the saddle table's does (csrc/pair_hash.hpp) and probes linearly
+ * is empty); uint64 count.  A pair starts probing where the saddle table's does (csrc/pair_table.hpp) and probes linearly
  * over at most min(capacity, 256) slots.  counts (int32[2], device memory, set by the entry): counts[0] = the slots claimed,
  * counts[1] = the contributions (voxels) that found no slot -- if it is not zero the table holds partial counts: come back
  * with a larger one.  Which slot a record lands in depends on the order of arrival: the contract is the set of records.

@@ -1465,6 +1465,86 @@ def run_stitch(input_path, config, output_path, positions=(), zarr_version: str 
             dist.destroy_process_group()
 
 
+def _run_object_store(input_path, output_path, positions, zarr_version, io_backend, compression, channel_name: str, suffix: str,
+                      result_key: str, process, check_array=None) -> dict:
+    """What ``run_segment`` and ``run_track`` share: one channel of every selected position goes in, one int32 array per
+    position comes out.  Everything is checked before the output store is created (``check_array(key, array)`` adds a
+    command's own refusal); rank 0 creates the store (channel ``<channel_name><suffix>``, the input's ``scale`` and
+    ``translation`` copied); the positions are dealt out by rank, and ``process(key, array, channel, out, geometry, device,
+    directory)`` fills ``out`` from channel ``channel`` of ``array`` (``geometry``: the 5-D ``(scale, translation)``,
+    ``directory``: the position's, for its tables) and returns the position's entry of ``result[result_key]``."""
+    from .io.omezarr import as_volume_array, open_ome_zarr, position_scale
+
+    rank, world, device, created = _distributed()
+    try:
+        src, src_positions = _open_source(Path(input_path), io_backend)
+        try:
+            missing = [p for p in positions if p not in src_positions]
+            if missing:
+                raise click.ClickException(f"positions {missing} not found; available: {list(src_positions)}")
+            keys = [k for k in src_positions if not positions or k in positions]
+            if not keys:
+                raise click.ClickException("no positions to process")
+            arrays, channel, geometry = {}, {}, {}
+            for k in keys:
+                pos = src_positions[k]
+                names = list(pos.channel_names)
+                if channel_name not in names:
+                    raise click.ClickException(f"channel_name {channel_name!r} not in position {k} (it has {names})")
+                a = as_volume_array(pos["0"])
+                if len(a.shape) != 5:
+                    raise click.ClickException(f"position {k}: expected 5-D TCZYX data, got shape {tuple(a.shape)}")
+                if check_array is not None:
+                    check_array(k, a)
+                if int(np.prod(a.shape[2:], dtype=np.int64)) > 2 ** 31 - 1:
+                    raise click.ClickException(f"position {k}: a volume of {tuple(a.shape[2:])} has more than 2^31 - 1 voxels")
+                arrays[k], channel[k] = a, names.index(channel_name)
+                geometry[k] = (list(position_scale(pos)), list(_position_translation(pos)))
+            out_channel = f"{channel_name}{suffix}"
+            error = None
+            if rank == 0:
+                try:
+                    if Path(output_path).exists() and any(Path(output_path).iterdir()):
+                        raise FileExistsError(f"{output_path} exists (never overwritten)")
+                    dst = open_ome_zarr(output_path, layout="hcs", mode="w", channel_names=[out_channel], version=zarr_version,
+                                        prefer_iohub=False)
+                    extra = {} if compression in (None, "none") else {"compress": compression}
+                    for k in keys:
+                        scale, translation = geometry[k]
+                        shape = (int(arrays[k].shape[0]), 1) + tuple(int(n) for n in arrays[k].shape[2:])
+                        dst.create_position(*k.split("/")).create_zeros("0", shape=shape, dtype="int32", scale=scale,
+                                                                        translation=translation if any(translation) else None,
+                                                                        **extra)
+                    dst.close()
+                except Exception as exc:  # noqa: BLE001 -- reported on every rank, see _agree
+                    error = f"{type(exc).__name__}: {exc}"
+            _agree(error)
+            dst = open_ome_zarr(output_path, layout="hcs", mode="a", channel_names=[out_channel], version=zarr_version,
+                                prefer_iohub=False)
+            dst_positions = dict(dst.positions())
+            entries = {}
+            t0 = time.perf_counter()
+            try:
+                for k in keys[rank::world]:
+                    out = as_volume_array(dst_positions[k]["0"])
+                    entries[k] = process(k, arrays[k], channel[k], out, geometry[k], device, Path(output_path) / k)
+            finally:
+                close = getattr(dst, "close", None)
+                if close:
+                    close()
+            return {"rank": rank, "world_size": world, "positions": len(keys[rank::world]), result_key: entries,
+                    "seconds": time.perf_counter() - t0, "failed": []}
+        finally:
+            close = getattr(src, "close", None)
+            if close:
+                close()
+    finally:
+        if created:
+            import torch.distributed as dist
+
+            dist.destroy_process_group()
+
+
 OBJECT_COLUMNS = ("t", "label", "volume_voxels", "volume_um3", "bbox_z0", "bbox_y0", "bbox_x0", "bbox_z1", "bbox_y1", "bbox_x1",
                   "centroid_z", "centroid_y", "centroid_x", "centroid_z_um", "centroid_y_um", "centroid_x_um",
                   "intensity_sum", "intensity_mean", "intensity_min", "intensity_max",
@@ -1528,7 +1608,6 @@ def run_segment(input_path, config, output_path, positions=(), zarr_version: str
 
     import torch
 
-    from .io.omezarr import as_volume_array, open_ome_zarr, position_scale
     from .segment import segment_zyx
     from .settings import SegmentSettings
 
@@ -1536,83 +1615,24 @@ def run_segment(input_path, config, output_path, positions=(), zarr_version: str
         settings = SegmentSettings.from_yaml(config)
     except (ValueError, TypeError) as exc:
         raise click.ClickException(f"{config}: {exc}") from exc
-    rank, world, device, created = _distributed()
-    try:
-        src, src_positions = _open_source(Path(input_path), io_backend)
-        try:
-            missing = [p for p in positions if p not in src_positions]
-            if missing:
-                raise click.ClickException(f"positions {missing} not found; available: {list(src_positions)}")
-            keys = [k for k in src_positions if not positions or k in positions]
-            if not keys:
-                raise click.ClickException("no positions to process")
-            arrays, channel, geometry = {}, {}, {}
-            for k in keys:
-                pos = src_positions[k]
-                names = list(pos.channel_names)
-                if settings.channel_name not in names:
-                    raise click.ClickException(f"channel_name {settings.channel_name!r} not in position {k} (it has {names})")
-                a = as_volume_array(pos["0"])
-                if len(a.shape) != 5:
-                    raise click.ClickException(f"position {k}: expected 5-D TCZYX data, got shape {tuple(a.shape)}")
-                if int(np.prod(a.shape[2:], dtype=np.int64)) > 2 ** 31 - 1:
-                    raise click.ClickException(f"position {k}: a volume of {tuple(a.shape[2:])} has more than 2^31 - 1 voxels")
-                arrays[k], channel[k] = a, names.index(settings.channel_name)
-                geometry[k] = (list(position_scale(pos)), list(_position_translation(pos)))
-            out_channel = f"{settings.channel_name}_labels"
-            error = None
-            if rank == 0:
-                try:
-                    if Path(output_path).exists() and any(Path(output_path).iterdir()):
-                        raise FileExistsError(f"{output_path} exists (never overwritten)")
-                    dst = open_ome_zarr(output_path, layout="hcs", mode="w", channel_names=[out_channel], version=zarr_version,
-                                        prefer_iohub=False)
-                    extra = {} if compression in (None, "none") else {"compress": compression}
-                    for k in keys:
-                        scale, translation = geometry[k]
-                        shape = (int(arrays[k].shape[0]), 1) + tuple(int(n) for n in arrays[k].shape[2:])
-                        dst.create_position(*k.split("/")).create_zeros("0", shape=shape, dtype="int32", scale=scale,
-                                                                        translation=translation if any(translation) else None,
-                                                                        **extra)
-                    dst.close()
-                except Exception as exc:  # noqa: BLE001 -- reported on every rank, see _agree
-                    error = f"{type(exc).__name__}: {exc}"
-            _agree(error)
-            dst = open_ome_zarr(output_path, layout="hcs", mode="a", channel_names=[out_channel], version=zarr_version,
-                                prefer_iohub=False)
-            dst_positions = dict(dst.positions())
-            counts = {}
-            t0 = time.perf_counter()
-            try:
-                for k in keys[rank::world]:
-                    out = as_volume_array(dst_positions[k]["0"])
-                    scale, translation = geometry[k]
-                    rows = []
-                    for t in range(int(arrays[k].shape[0])):
-                        vol = np.ascontiguousarray(arrays[k].read_volume(t, channel[k]), dtype=np.float32)
-                        labels, table, n = segment_zyx(torch.as_tensor(vol, device=device), settings, sampling=scale[2:])
-                        out.write_volume(t, 0, labels.cpu().numpy())
-                        rows += object_rows(t, table, scale[2:], translation[2:])
-                        counts.setdefault(k, []).append(int(n))
-                    with open(Path(output_path) / k / "objects.csv", "w", newline="") as fh:
-                        w = csv.writer(fh)
-                        w.writerow(OBJECT_COLUMNS + (("inscribed_radius_um",) if settings.inscribed_radius else ()))
-                        w.writerows([[repr(v) if isinstance(v, float) else v for v in row] for row in rows])
-            finally:
-                close = getattr(dst, "close", None)
-                if close:
-                    close()
-            return {"rank": rank, "world_size": world, "positions": len(keys[rank::world]), "objects": counts,
-                    "seconds": time.perf_counter() - t0, "failed": []}
-        finally:
-            close = getattr(src, "close", None)
-            if close:
-                close()
-    finally:
-        if created:
-            import torch.distributed as dist
 
-            dist.destroy_process_group()
+    def position(key, array, channel, out, geometry, device, directory):
+        scale, translation = geometry
+        rows, counts = [], []
+        for t in range(int(array.shape[0])):
+            vol = np.ascontiguousarray(array.read_volume(t, channel), dtype=np.float32)
+            labels, table, n = segment_zyx(torch.as_tensor(vol, device=device), settings, sampling=scale[2:])
+            out.write_volume(t, 0, labels.cpu().numpy())
+            rows += object_rows(t, table, scale[2:], translation[2:])
+            counts.append(int(n))
+        with open(directory / "objects.csv", "w", newline="") as fh:
+            w = csv.writer(fh)
+            w.writerow(OBJECT_COLUMNS + (("inscribed_radius_um",) if settings.inscribed_radius else ()))
+            w.writerows([[repr(v) if isinstance(v, float) else v for v in row] for row in rows])
+        return counts
+
+    return _run_object_store(input_path, output_path, positions, zarr_version, io_backend, compression, settings.channel_name,
+                             "_labels", "objects", position)
 
 
 TRACK_COLUMNS = ("track_id", "t_begin", "t_end", "parent_track_id")
@@ -1657,7 +1677,6 @@ def run_track(input_path, config, output_path, positions=(), zarr_version: str =
 
     import torch
 
-    from .io.omezarr import as_volume_array, open_ome_zarr, position_scale
     from .settings import TrackSettings
     from .track import Tracker, relabel_by_track
 
@@ -1665,91 +1684,33 @@ def run_track(input_path, config, output_path, positions=(), zarr_version: str =
         settings = TrackSettings.from_yaml(config)
     except (ValueError, TypeError) as exc:
         raise click.ClickException(f"{config}: {exc}") from exc
-    rank, world, device, created = _distributed()
-    try:
-        src, src_positions = _open_source(Path(input_path), io_backend)
-        try:
-            missing = [p for p in positions if p not in src_positions]
-            if missing:
-                raise click.ClickException(f"positions {missing} not found; available: {list(src_positions)}")
-            keys = [k for k in src_positions if not positions or k in positions]
-            if not keys:
-                raise click.ClickException("no positions to process")
-            arrays, channel, geometry = {}, {}, {}
-            for k in keys:
-                pos = src_positions[k]
-                names = list(pos.channel_names)
-                if settings.channel_name not in names:
-                    raise click.ClickException(f"channel_name {settings.channel_name!r} not in position {k} (it has {names})")
-                a = as_volume_array(pos["0"])
-                if len(a.shape) != 5:
-                    raise click.ClickException(f"position {k}: expected 5-D TCZYX data, got shape {tuple(a.shape)}")
-                if np.dtype(a.dtype).kind not in "iu":
-                    raise click.ClickException(f"position {k}: data type {a.dtype}; labels are integer data (int32 from segment)")
-                if int(np.prod(a.shape[2:], dtype=np.int64)) > 2 ** 31 - 1:
-                    raise click.ClickException(f"position {k}: a volume of {tuple(a.shape[2:])} has more than 2^31 - 1 voxels")
-                arrays[k], channel[k] = a, names.index(settings.channel_name)
-                geometry[k] = (list(position_scale(pos)), list(_position_translation(pos)))
-            out_channel = f"{settings.channel_name}_tracks"
-            error = None
-            if rank == 0:
-                try:
-                    if Path(output_path).exists() and any(Path(output_path).iterdir()):
-                        raise FileExistsError(f"{output_path} exists (never overwritten)")
-                    dst = open_ome_zarr(output_path, layout="hcs", mode="w", channel_names=[out_channel], version=zarr_version,
-                                        prefer_iohub=False)
-                    extra = {} if compression in (None, "none") else {"compress": compression}
-                    for k in keys:
-                        scale, translation = geometry[k]
-                        shape = (int(arrays[k].shape[0]), 1) + tuple(int(n) for n in arrays[k].shape[2:])
-                        dst.create_position(*k.split("/")).create_zeros("0", shape=shape, dtype="int32", scale=scale,
-                                                                        translation=translation if any(translation) else None,
-                                                                        **extra)
-                    dst.close()
-                except Exception as exc:  # noqa: BLE001 -- reported on every rank, see _agree
-                    error = f"{type(exc).__name__}: {exc}"
-            _agree(error)
-            dst = open_ome_zarr(output_path, layout="hcs", mode="a", channel_names=[out_channel], version=zarr_version,
-                                prefer_iohub=False)
-            dst_positions = dict(dst.positions())
-            counts = {}
-            t0 = time.perf_counter()
-            try:
-                for k in keys[rank::world]:
-                    out = as_volume_array(dst_positions[k]["0"])
-                    tracker = Tracker(settings)
-                    for t in range(int(arrays[k].shape[0])):
-                        vol = np.asarray(arrays[k].read_volume(t, channel[k]))
-                        if vol.size and (int(vol.max()) > 2 ** 31 - 1 or int(vol.min()) < -2 ** 31):
-                            raise click.ClickException(f"position {k}, t = {t}: a label does not fit int32")
-                        labels = torch.as_tensor(np.ascontiguousarray(vol, dtype=np.int32), device=device)
-                        out.write_volume(t, 0, relabel_by_track(labels, tracker.step(labels)).cpu().numpy())
-                    tracks = tracker.tracks()
-                    counts[k] = len(tracks["track_id"])
-                    with open(Path(output_path) / k / "tracks.csv", "w", newline="") as fh:
-                        w = csv.writer(fh)
-                        w.writerow(TRACK_COLUMNS)
-                        w.writerows(zip(*(tracks[c].tolist() for c in TRACK_COLUMNS)))
-                    with open(Path(output_path) / k / "track_objects.csv", "w", newline="") as fh:
-                        w = csv.writer(fh)
-                        w.writerow(TRACK_OBJECT_COLUMNS)
-                        rows = zip(*(tracks["objects"][c].tolist() for c in TRACK_OBJECT_COLUMNS))
-                        w.writerows([[repr(v) if isinstance(v, float) else v for v in row] for row in rows])
-            finally:
-                close = getattr(dst, "close", None)
-                if close:
-                    close()
-            return {"rank": rank, "world_size": world, "positions": len(keys[rank::world]), "tracks": counts,
-                    "seconds": time.perf_counter() - t0, "failed": []}
-        finally:
-            close = getattr(src, "close", None)
-            if close:
-                close()
-    finally:
-        if created:
-            import torch.distributed as dist
 
-            dist.destroy_process_group()
+    def integer_data(key, array):
+        if np.dtype(array.dtype).kind not in "iu":
+            raise click.ClickException(f"position {key}: data type {array.dtype}; labels are integer data (int32 from segment)")
+
+    def position(key, array, channel, out, geometry, device, directory):
+        tracker = Tracker(settings)
+        for t in range(int(array.shape[0])):
+            vol = np.asarray(array.read_volume(t, channel))
+            if vol.size and (int(vol.max()) > 2 ** 31 - 1 or int(vol.min()) < -2 ** 31):
+                raise click.ClickException(f"position {key}, t = {t}: a label does not fit int32")
+            labels = torch.as_tensor(np.ascontiguousarray(vol, dtype=np.int32), device=device)
+            out.write_volume(t, 0, relabel_by_track(labels, tracker.step(labels)).cpu().numpy())
+        tracks = tracker.tracks()
+        with open(directory / "tracks.csv", "w", newline="") as fh:
+            w = csv.writer(fh)
+            w.writerow(TRACK_COLUMNS)
+            w.writerows(zip(*(tracks[c].tolist() for c in TRACK_COLUMNS)))
+        with open(directory / "track_objects.csv", "w", newline="") as fh:
+            w = csv.writer(fh)
+            w.writerow(TRACK_OBJECT_COLUMNS)
+            rows = zip(*(tracks["objects"][c].tolist() for c in TRACK_OBJECT_COLUMNS))
+            w.writerows([[repr(v) if isinstance(v, float) else v for v in row] for row in rows])
+        return len(tracks["track_id"])
+
+    return _run_object_store(input_path, output_path, positions, zarr_version, io_backend, compression, settings.channel_name,
+                             "_tracks", "tracks", position, check_array=integer_data)
 
 
 @cli.command("pyramid", cls=_eat_all_command("-i", "--input-position-dirpaths"))

@@ -24,6 +24,39 @@ inline int launch_status(const char* what) {
 
 inline hipStream_t as_stream(lsr_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
+// What a sequence of launches calls in front of each launch and behind the last.  A timing entry (profile_launches) hands in
+// its events and mark() records the next one on the stream; a plain entry hands in {} and mark() is a null check.
+struct LaunchMarks {
+  hipEvent_t* events = nullptr;
+  hipStream_t stream = nullptr;
+  int next = 0;
+  void mark() {
+    if (events != nullptr) (void)hipEventRecord(events[next++], stream);
+  }
+};
+
+// Measurement only: K launches with a HIP event between them.  launch(marks) issues them on `stream` and calls marks.mark()
+// K + 1 times; then this waits for the stream and writes the K times in milliseconds to ms (HOST memory).  The launches'
+// status goes before an event call's error.
+template <int K, class Launch>
+int profile_launches(float* ms, hipStream_t stream, const char* what, Launch&& launch) {
+  hipEvent_t events[K + 1];
+  int made = 0;
+  hipError_t e = hipSuccess;
+  for (; made <= K && e == hipSuccess; ++made) e = hipEventCreate(&events[made]);
+  if (e != hipSuccess) --made;
+  int rc = LSR_OK;
+  if (e == hipSuccess) {
+    rc = launch(LaunchMarks{events, stream});
+    e = hipEventSynchronize(events[K]);
+    for (int k = 0; k < K && e == hipSuccess; ++k) e = hipEventElapsedTime(&ms[k], events[k], events[k + 1]);
+  }
+  for (int k = 0; k < made; ++k) (void)hipEventDestroy(events[k]);
+  if (rc != LSR_OK) return rc;
+  if (e != hipSuccess) return fail(static_cast<int>(e), "%s: %s", what, hipGetErrorString(e));
+  return LSR_OK;
+}
+
 // Raise a kernel's dynamic-LDS ceiling above the 64 KB default.  The attribute belongs to the kernel's
 // code object on ONE device, so it is set once per (kernel, device): `done` is that kernel's bit mask of
 // devices already served (one static per call site; devices >= 64 are simply set every time).

@@ -143,28 +143,24 @@ __global__ __launch_bounds__(kThreads) void label_expand_kernel(const int32_t* _
 constexpr int64_t kMaxBlocks = 1 << 16;      // grid-stride launches: 256 per CU
 constexpr int kLaunches = 3;                 // x, y, z
 
-// The three launches; with `events` (kLaunches + 1 of them) one is recorded in front of each launch and one behind the last.
+// The three launches; a timing entry's marks (kLaunches + 1 events) get one in front of each launch and one behind the last.
 template <class Sites>
 int edt_launches(Sites sites, int64_t Z, int64_t Y, int64_t X, const double* sampling, float* dist, int32_t* nearest, void* scratch,
-                 hipStream_t q, hipEvent_t* events, const char* what) {
+                 hipStream_t q, lsr::LaunchMarks marks, const char* what) {
   const ed::Sampling s = ed::make_sampling(sampling);
   int32_t* work = nearest != nullptr ? nearest : reinterpret_cast<int32_t*>(dist);
   int32_t* stacks = static_cast<int32_t*>(scratch);
   const int iZ = static_cast<int>(Z), iY = static_cast<int>(Y), iX = static_cast<int>(X);
-  int k = 0;
-  auto mark = [&]() {
-    if (events != nullptr) (void)hipEventRecord(events[k++], q);
-  };
-  mark();
+  marks.mark();
   hipLaunchKernelGGL(edt_x_kernel<Sites>, dim3(static_cast<unsigned>(std::min(lsr::ceil_div(Z * Y, ed::kRowsPerBlock), ed::kMaxRowBlocks))),
                      dim3(kThreads), 0, q, sites, Z * Y, iX, work);
-  mark();
+  marks.mark();
   hipLaunchKernelGGL(edt_y_kernel, dim3(static_cast<unsigned>(ed::pass_lanes(Z * X) / kThreads)), dim3(kThreads), 0, q, work, iZ, iY,
                      iX, s.wy, s.wx, stacks);
-  mark();
+  marks.mark();
   hipLaunchKernelGGL(edt_z_kernel, dim3(static_cast<unsigned>(ed::pass_lanes(Y * X) / kThreads)), dim3(kThreads), 0, q, work, nearest,
                      reinterpret_cast<int32_t*>(dist), iZ, iY, iX, s, stacks);
-  mark();
+  marks.mark();
   return lsr::launch_status(what);
 }
 
@@ -172,21 +168,9 @@ int edt_launches(Sites sites, int64_t Z, int64_t Y, int64_t X, const double* sam
 template <class Sites>
 int edt_profile(Sites sites, int64_t Z, int64_t Y, int64_t X, const double* sampling, float* dist, int32_t* nearest, void* scratch,
                 float* ms3, hipStream_t q, const char* what) {
-  hipEvent_t events[kLaunches + 1];
-  int made = 0;
-  hipError_t e = hipSuccess;
-  for (; made <= kLaunches && e == hipSuccess; ++made) e = hipEventCreate(&events[made]);
-  if (e != hipSuccess) --made;
-  int rc = LSR_OK;
-  if (e == hipSuccess) {
-    rc = edt_launches(sites, Z, Y, X, sampling, dist, nearest, scratch, q, events, what);
-    e = hipEventSynchronize(events[kLaunches]);
-    for (int k = 0; k < kLaunches && e == hipSuccess; ++k) e = hipEventElapsedTime(&ms3[k], events[k], events[k + 1]);
-  }
-  for (int k = 0; k < made; ++k) (void)hipEventDestroy(events[k]);
-  if (rc != LSR_OK) return rc;
-  if (e != hipSuccess) return lsr::fail(static_cast<int>(e), "%s: %s", what, hipGetErrorString(e));
-  return LSR_OK;
+  return lsr::profile_launches<kLaunches>(ms3, q, what, [&](lsr::LaunchMarks marks) {
+    return edt_launches(sites, Z, Y, X, sampling, dist, nearest, scratch, q, marks, what);
+  });
 }
 
 }  // namespace
@@ -208,14 +192,14 @@ extern "C" int64_t lsr_edt_scratch_bytes(int64_t Z, int64_t Y, int64_t X) {
 extern "C" int lsr_edt_f32(const float* in, int64_t Z, int64_t Y, int64_t X, float threshold, int invert, const double* sampling,
                            float* dist, int32_t* nearest, void* scratch, lsr_stream_t stream) {
   if (int rc = ed::check_edt(in, Z, Y, X, sampling, dist, nearest, scratch)) return rc;
-  return edt_launches(FloatSites{in, threshold, invert != 0}, Z, Y, X, sampling, dist, nearest, scratch, lsr::as_stream(stream), nullptr,
+  return edt_launches(FloatSites{in, threshold, invert != 0}, Z, Y, X, sampling, dist, nearest, scratch, lsr::as_stream(stream), {},
                       "lsr_edt_f32");
 }
 
 extern "C" int lsr_edt_labels_i32(const int32_t* labels, int64_t Z, int64_t Y, int64_t X, int invert, const double* sampling,
                                   float* dist, int32_t* nearest, void* scratch, lsr_stream_t stream) {
   if (int rc = ed::check_edt(labels, Z, Y, X, sampling, dist, nearest, scratch)) return rc;
-  return edt_launches(LabelSites{labels, invert != 0}, Z, Y, X, sampling, dist, nearest, scratch, lsr::as_stream(stream), nullptr,
+  return edt_launches(LabelSites{labels, invert != 0}, Z, Y, X, sampling, dist, nearest, scratch, lsr::as_stream(stream), {},
                       "lsr_edt_labels_i32");
 }
 

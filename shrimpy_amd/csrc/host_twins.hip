@@ -1262,13 +1262,6 @@ extern "C" int lsr_label_f32_cpu(const float* in, int64_t Z, int64_t Y, int64_t 
   const int level = lb::level_of(connectivity);
   const int64_t n = Z * Y * X, plane = Y * X;
   int32_t* parent = labels;                    // a union-find rooted at the smallest index, as on the device
-  auto find = [&](int32_t a) {              // with path halving: a winding component stays near-linear
-    while (parent[a] != a) {
-      parent[a] = parent[parent[a]];
-      a = parent[a];
-    }
-    return a;
-  };
   for (int64_t z = 0; z < Z; ++z) {
     for (int64_t y = 0; y < Y; ++y) {
       for (int64_t x = 0; x < X; ++x) {
@@ -1286,7 +1279,7 @@ extern "C" int lsr_label_f32_cpu(const float* in, int64_t Z, int64_t Y, int64_t 
               if (z + dz < 0 || y + dy < 0 || y + dy >= Y || x + dx < 0 || x + dx >= X) continue;
               const int64_t t = v + dz * plane + dy * X + dx;
               if (parent[t] < 0) continue;
-              const int32_t other = find(static_cast<int32_t>(t));
+              const int32_t other = lb::find_host(parent, static_cast<int32_t>(t));
               if (other == root) continue;
               const int32_t lo = other < root ? other : root, hi = other < root ? root : other;
               parent[hi] = lo;
@@ -1298,21 +1291,7 @@ extern "C" int lsr_label_f32_cpu(const float* in, int64_t Z, int64_t Y, int64_t 
       }
     }
   }
-  // every chain is cut to its root, the roots are numbered in raster order (a numbered root holds -(label + 1), as on the
-  // device), and a root precedes every other voxel of its set
-  for (int64_t v = 0; v < n; ++v)
-    if (parent[v] >= 0) parent[v] = find(static_cast<int32_t>(v));
-  int32_t count = 0;
-  for (int64_t v = 0; v < n; ++v) {
-    const int32_t p = parent[v];
-    if (p < 0) continue;
-    if (p == v) parent[v] = -(++count) - 1;
-  }
-  for (int64_t v = 0; v < n; ++v) {
-    const int32_t p = labels[v];
-    labels[v] = p == -1 ? 0 : p < 0 ? -p - 1 : labels[p];       // (p < v is a root: it has its label already)
-  }
-  *n_objects = count;
+  *n_objects = lb::number_roots_host(labels, n);
   return LSR_OK;
 }
 
@@ -1466,13 +1445,6 @@ extern "C" int lsr_watershed_f32_cpu(const int32_t* objects, const float* surfac
   const int level = lb::level_of(connectivity);
   const int64_t n = Z * Y * X, plane = Y * X;
   int32_t* parent = basins;                    // a union-find rooted at the smallest index, as on the device
-  auto find = [&](int32_t a) {              // with path halving
-    while (parent[a] != a) {
-      parent[a] = parent[parent[a]];
-      a = parent[a];
-    }
-    return a;
-  };
   for (int64_t v = 0; v < n; ++v) parent[v] = objects[v] > 0 ? static_cast<int32_t>(v) : -1;
   for (int64_t z = 0; z < Z; ++z) {
     for (int64_t y = 0; y < Y; ++y) {
@@ -1489,22 +1461,12 @@ extern "C" int lsr_watershed_f32_cpu(const int32_t* objects, const float* surfac
         });
         if (code == ws::kSelf) continue;
         const int64_t t = v + (code / 9 - 1) * plane + (code / 3 % 3 - 1) * X + (code % 3 - 1);
-        const int32_t a = find(static_cast<int32_t>(v)), b = find(static_cast<int32_t>(t));
+        const int32_t a = lb::find_host(parent, static_cast<int32_t>(v)), b = lb::find_host(parent, static_cast<int32_t>(t));
         if (a != b) parent[a < b ? b : a] = a < b ? a : b;
       }
     }
   }
-  // the numbering of lsr_label_f32_cpu: chains cut, the roots numbered in raster order, a root before the rest of its set
-  for (int64_t v = 0; v < n; ++v)
-    if (parent[v] >= 0) parent[v] = find(static_cast<int32_t>(v));
-  int32_t count = 0;
-  for (int64_t v = 0; v < n; ++v)
-    if (parent[v] == v) parent[v] = -(++count) - 1;
-  for (int64_t v = 0; v < n; ++v) {
-    const int32_t p = basins[v];
-    basins[v] = p == -1 ? 0 : p < 0 ? -p - 1 : basins[p];
-  }
-  *n_basins = count;
+  *n_basins = lb::number_roots_host(basins, n);
   return LSR_OK;
 }
 
@@ -1517,7 +1479,7 @@ extern "C" int lsr_watershed_saddles_f32_cpu(const int32_t* objects, const int32
   const int level = lb::level_of(connectivity);
   const int64_t plane = Y * X;
   const uint32_t mask = static_cast<uint32_t>(capacity - 1);
-  const int probes = static_cast<int>(std::min<int64_t>(capacity, ws::kMaxProbes));
+  const int probes = lsr::pair_probes(capacity);
   ws::Saddle* slots = static_cast<ws::Saddle*>(table);
   counts[0] = counts[1] = 0;
   for (int64_t z = 0; z < Z; ++z) {
@@ -1539,18 +1501,8 @@ extern "C" int lsr_watershed_saddles_f32_cpu(const int32_t* objects, const int32
               const uint32_t ku = lb::float_key(surface[u]), pass = std::min(ku, kv);
               const unsigned long long a = static_cast<uint32_t>(std::min(a0, b0)), b = static_cast<uint32_t>(std::max(a0, b0));
               const unsigned long long pair = a << 32 | b;
-              uint32_t slot = ws::slot_of(pair, mask);
-              bool placed = false;
-              for (int p = 0; p < probes && !placed; ++p, slot = (slot + 1) & mask) {
-                if (slots[slot].pair == 0) {
-                  slots[slot].pair = pair;
-                  counts[0] += 1;
-                }
-                if (slots[slot].pair == pair) {
-                  slots[slot].key = std::max(slots[slot].key, pass);
-                  placed = true;
-                }
-              }
+              const bool placed = lsr::pair_insert_host(slots, mask, probes, pair, counts,
+                                                        [&](ws::Saddle& slot) { slot.key = std::max(slot.key, pass); });
               if (!placed) counts[1] += 1;
             }
           }
@@ -1573,7 +1525,7 @@ extern "C" int lsr_label_overlap_i32_cpu(const int32_t* a, const int32_t* b, int
   if (ov::shift_empties(Z, Y, X, shift_zyx)) return LSR_OK;
   const int64_t sz = shift_zyx[0], sy = shift_zyx[1], sx = shift_zyx[2], plane = Y * X;
   const uint32_t mask = static_cast<uint32_t>(capacity - 1);
-  const int probes = static_cast<int>(std::min<int64_t>(capacity, ov::kMaxProbes));
+  const int probes = lsr::pair_probes(capacity);
   ov::Overlap* slots = static_cast<ov::Overlap*>(table);
   for (int64_t z = std::max<int64_t>(0, -sz); z < std::min(Z, Z - sz); ++z) {
     for (int64_t y = std::max<int64_t>(0, -sy); y < std::min(Y, Y - sy); ++y) {
@@ -1582,19 +1534,7 @@ extern "C" int lsr_label_overlap_i32_cpu(const int32_t* a, const int32_t* b, int
         const int32_t a0 = a[v], b0 = b[v + sz * plane + sy * X + sx];
         if (a0 <= 0 || b0 <= 0) continue;
         const unsigned long long pair = ov::pack(a0, b0);
-        uint32_t slot = lsr::pair_slot_of(pair, mask);
-        bool placed = false;
-        for (int p = 0; p < probes && !placed; ++p, slot = (slot + 1) & mask) {
-          if (slots[slot].pair == 0) {
-            slots[slot].pair = pair;
-            counts[0] += 1;
-          }
-          if (slots[slot].pair == pair) {
-            slots[slot].count += 1;
-            placed = true;
-          }
-        }
-        if (!placed) counts[1] += 1;
+        if (!lsr::pair_insert_host(slots, mask, probes, pair, counts, [](ov::Overlap& slot) { slot.count += 1; })) counts[1] += 1;
       }
     }
   }

@@ -282,29 +282,25 @@ namespace {
 
 constexpr int kLaunches = 7;       // local, merge, flatten, count, scan, rank, final
 
-// The seven launches; with `events` (kLaunches + 1 of them) one is recorded in front of each launch and one behind the last.
+// The seven launches; a timing entry's marks (kLaunches + 1 events) get one in front of each launch and one behind the last.
 int label_launches(const float* in, int64_t Z, int64_t Y, int64_t X, float threshold, int connectivity, int32_t* labels,
-                   int32_t* n_objects, void* scratch, hipStream_t q, hipEvent_t* events) {
+                   int32_t* n_objects, void* scratch, hipStream_t q, lsr::LaunchMarks marks) {
   const int level = lb::level_of(connectivity);
   const Shape s{static_cast<int>(Z), static_cast<int>(Y), static_cast<int>(X)};
   const int64_t n = Z * Y * X;
   const int64_t tz = lsr::ceil_div(Z, lb::kTileZ), ty = lsr::ceil_div(Y, lb::kTileY), tx = lsr::ceil_div(X, lb::kTileX);
   const int64_t pieces = lsr::ceil_div(X, kThreads), units = Z * Y * pieces;
   int* counts = static_cast<int*>(scratch);
-  int k = 0;
-  auto mark = [&]() {
-    if (events != nullptr) (void)hipEventRecord(events[k++], q);
-  };
-  mark();
+  marks.mark();
   // (tz * ty * tx <= n < 2^31 tiles; at most kMaxTileBlocks workgroups walk them, one each at any shape met in practice)
   hipLaunchKernelGGL(label_local_kernel, dim3(static_cast<unsigned>(std::min(tz * ty * tx, kMaxTileBlocks))), dim3(kThreads), 0, q,
                      in, s, threshold, level, static_cast<int>(ty), static_cast<int>(tx), static_cast<unsigned>(tz * ty * tx),
                      labels);
-  mark();
+  marks.mark();
   hipLaunchKernelGGL(label_merge_kernel, dim3(static_cast<unsigned>(std::min(units, kMaxBlocks))), dim3(kThreads), 0, q, labels, s,
                      level, pieces, units);
-  number_launches(labels, n, counts, n_objects, q, mark);
-  mark();
+  number_launches(labels, n, counts, n_objects, q, marks);
+  marks.mark();
   return lsr::launch_status("lsr_label_f32");
 }
 
@@ -313,7 +309,7 @@ int label_launches(const float* in, int64_t Z, int64_t Y, int64_t X, float thres
 extern "C" int lsr_label_f32(const float* in, int64_t Z, int64_t Y, int64_t X, float threshold, int connectivity,
                              int32_t* labels, int32_t* n_objects, void* scratch, lsr_stream_t stream) {
   if (int rc = lb::check_label(in, Z, Y, X, connectivity, labels, n_objects, scratch)) return rc;
-  return label_launches(in, Z, Y, X, threshold, connectivity, labels, n_objects, scratch, lsr::as_stream(stream), nullptr);
+  return label_launches(in, Z, Y, X, threshold, connectivity, labels, n_objects, scratch, lsr::as_stream(stream), {});
 }
 
 // Measurement only (tools/bench_kernels.py --label): lsr_label_f32 with a HIP event between its launches; waits for the
@@ -322,21 +318,10 @@ extern "C" int lsr_label_profile_f32(const float* in, int64_t Z, int64_t Y, int6
                                      int32_t* labels, int32_t* n_objects, void* scratch, float* ms7, lsr_stream_t stream) {
   if (int rc = lb::check_label(in, Z, Y, X, connectivity, labels, n_objects, scratch)) return rc;
   LSR_REQUIRE_PTR(ms7);
-  hipEvent_t events[kLaunches + 1];
-  int made = 0;
-  hipError_t e = hipSuccess;
-  for (; made <= kLaunches && e == hipSuccess; ++made) e = hipEventCreate(&events[made]);
-  if (e != hipSuccess) --made;
-  int rc = LSR_OK;
-  if (e == hipSuccess) {
-    rc = label_launches(in, Z, Y, X, threshold, connectivity, labels, n_objects, scratch, lsr::as_stream(stream), events);
-    e = hipEventSynchronize(events[kLaunches]);
-    for (int k = 0; k < kLaunches && e == hipSuccess; ++k) e = hipEventElapsedTime(&ms7[k], events[k], events[k + 1]);
-  }
-  for (int k = 0; k < made; ++k) (void)hipEventDestroy(events[k]);
-  if (rc != LSR_OK) return rc;
-  if (e != hipSuccess) return lsr::fail(static_cast<int>(e), "lsr_label_profile_f32: %s", hipGetErrorString(e));
-  return LSR_OK;
+  hipStream_t q = lsr::as_stream(stream);
+  return lsr::profile_launches<kLaunches>(ms7, q, "lsr_label_profile_f32", [&](lsr::LaunchMarks marks) {
+    return label_launches(in, Z, Y, X, threshold, connectivity, labels, n_objects, scratch, q, marks);
+  });
 }
 
 extern "C" int lsr_label_regions_f32(const int32_t* labels, const float* intensity, int64_t Z, int64_t Y, int64_t X,

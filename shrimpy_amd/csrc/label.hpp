@@ -96,5 +96,32 @@ __host__ __device__ inline float key_float(uint32_t k) {
   return v;
 }
 
+// ---- the host twins' union-find (sequential; rooted at the smallest index, as on the device) ----
+
+// The root of a, with path halving: a winding component stays near-linear.
+inline int32_t find_host(int32_t* parent, int32_t a) {
+  while (parent[a] != a) {
+    parent[a] = parent[parent[a]];
+    a = parent[a];
+  }
+  return a;
+}
+
+// From parent words (-1 on the background) to labels, in place: every chain is cut to its root, the roots are numbered in
+// raster order (a numbered root holds -(label + 1), as on the device; a root precedes every other voxel of its set), and
+// every voxel takes its root's label, 0 on the background.  Returns the number of roots.
+inline int32_t number_roots_host(int32_t* words, int64_t n) {
+  for (int64_t v = 0; v < n; ++v)
+    if (words[v] >= 0) words[v] = find_host(words, static_cast<int32_t>(v));
+  int32_t count = 0;
+  for (int64_t v = 0; v < n; ++v)
+    if (words[v] == v) words[v] = -(++count) - 1;
+  for (int64_t v = 0; v < n; ++v) {
+    const int32_t p = words[v];
+    words[v] = p == -1 ? 0 : p < 0 ? -p - 1 : words[p];       // (p < v is a root: it has its label already)
+  }
+  return count;
+}
+
 }  // namespace label
 }  // namespace lsr

@@ -158,20 +158,19 @@ constexpr int64_t kMaxTileBlocks = 1 << 22;  // local: 2^22 * 256 threads < 2^32
 
 inline unsigned stride_grid(int64_t n) { return static_cast<unsigned>(std::min(lsr::ceil_div(n, kThreads), kMaxBlocks)); }
 
-// flatten, count, scan, rank, final on `stream`; `mark()` is called in front of each launch (the timing entries record an
-// event there).  counts: lsr::label::number_blocks(n) words.
-template <class Mark>
-inline void number_launches(int* parent, int64_t n, int* counts, int* n_objects, hipStream_t q, Mark&& mark) {
+// flatten, count, scan, rank, final on `stream`; `marks.mark()` is called in front of each launch (the timing entries record
+// an event there).  counts: lsr::label::number_blocks(n) words.
+inline void number_launches(int* parent, int64_t n, int* counts, int* n_objects, hipStream_t q, lsr::LaunchMarks& marks) {
   const int64_t blocks = lsr::label::number_blocks(n);
-  mark();
+  marks.mark();
   hipLaunchKernelGGL(label_flatten_kernel, dim3(stride_grid(n)), dim3(kThreads), 0, q, parent, n);
-  mark();
+  marks.mark();
   hipLaunchKernelGGL(label_count_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, q, parent, n, counts);
-  mark();
+  marks.mark();
   hipLaunchKernelGGL(label_scan_kernel, dim3(1), dim3(kScanThreads), 0, q, counts, blocks, n_objects);
-  mark();
+  marks.mark();
   hipLaunchKernelGGL(label_rank_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, q, parent, n, counts);
-  mark();
+  marks.mark();
   hipLaunchKernelGGL(label_final_kernel, dim3(stride_grid(n)), dim3(kThreads), 0, q, parent, n);
 }
 

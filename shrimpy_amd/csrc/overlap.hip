@@ -34,15 +34,9 @@ struct Shape {
 // One contribution to the global table: claim or find the pair's slot within `probes`, add the weight; count what is lost.
 __device__ __forceinline__ void global_add(ov::Overlap* table, unsigned mask, int probes, unsigned long long pair,
                                            unsigned weight, int* counts) {
-  unsigned slot = lsr::pair_slot_of(pair, mask);
-  for (int p = 0; p < probes; ++p, slot = (slot + 1) & mask) {      // bounded: nobody's progress is waited for
-    const unsigned long long old = atomicCAS(&table[slot].pair, 0ull, pair);
-    if (old == 0ull) atomicAdd(&counts[0], 1);
-    if (old == 0ull || old == pair) {
-      atomicAdd(&table[slot].count, static_cast<unsigned long long>(weight));
-      return;
-    }
-  }
+  if (lsr::pair_insert(table, mask, probes, pair, counts,
+                       [&](ov::Overlap& slot) { atomicAdd(&slot.count, static_cast<unsigned long long>(weight)); }))
+    return;
   atomicAdd(&counts[1], static_cast<int>(weight));
 }
 
@@ -137,6 +131,6 @@ extern "C" int lsr_label_overlap_i32(const int32_t* a, const int32_t* b, int64_t
   const Shape s{static_cast<int>(Z), static_cast<int>(Y), static_cast<int>(X)};
   hipLaunchKernelGGL(label_overlap_kernel, dim3(static_cast<unsigned>(blocks)), dim3(ov::kThreads), 0, q, a, b, s, shift_zyx[0],
                      shift_zyx[1], shift_zyx[2], n, span, static_cast<unsigned>(capacity - 1),
-                     static_cast<int>(std::min<int64_t>(capacity, ov::kMaxProbes)), static_cast<ov::Overlap*>(table), counts);
+                     lsr::pair_probes(capacity), static_cast<ov::Overlap*>(table), counts);
   return lsr::launch_status("lsr_label_overlap_i32");
 }

@@ -7,15 +7,15 @@
 //   (a[v], b[u]) gains 1.  Labels <= 0 are background; a u outside the volume contributes nothing.
 //   The table is `capacity` records of 16 bytes, capacity a power of two in 1 .. 2^30, zeroed by the caller:
 //   pair = (uint32)a << 32 | (uint32)b (0 = empty: both labels are positive, so no pair is 0) and its 64-bit count.
-//   A pair starts probing at pair_slot_of(pair, capacity - 1) and probes linearly over at most min(capacity, kMaxProbes)
-//   slots; a contribution that finds no slot adds its weight to counts[1] (the table then holds partial counts: come back
-//   with a larger one).  counts[0] = the slots claimed.  Both are set by the entry.
+//   A pair starts probing at pair_slot_of(pair, capacity - 1) and probes linearly over at most pair_probes(capacity)
+//   slots (pair_table.hpp); a contribution that finds no slot adds its weight to counts[1] (the table then holds partial
+//   counts: come back with a larger one).  counts[0] = the slots claimed.  Both are set by the entry.
 //   Pure integer arithmetic: the set of records does not depend on the order of execution (which slot holds which record
 //   does).
 #pragma once
 
 #include "label.hpp"
-#include "pair_hash.hpp"
+#include "pair_table.hpp"
 
 namespace lsr {
 namespace overlap {
@@ -32,7 +32,6 @@ constexpr int kChunks = 4;                          // wave steps of 64 voxels a
 constexpr int kStep = kThreads * kChunks;           // voxels one workgroup takes per stride of its span
 constexpr int kLdsSlots = 2048;                     // the per-workgroup table: 16 KiB of keys + 8 KiB of counts
 constexpr int kLdsProbes = 16;                      // a head gives up on LDS after this many slots and goes to global memory
-constexpr int kMaxProbes = 256;                     // ... and on the global table after min(capacity, kMaxProbes)
 // The grid's cap, chosen from profiles/overlap_config2.jsonl: on the config-2 shape it gives spans of 12 288 voxels, short enough
 // that the distinct pairs of a span of labelled NOISE (about 800) still fit the LDS table -- a span whose pairs do not fit pays
 // kLdsProbes failed probes per head and then a scattered global atomic -- while beads and an all-foreground volume take what
@@ -59,8 +58,7 @@ inline int check_overlap(const void* a, const void* b, int64_t Z, int64_t Y, int
   LSR_REQUIRE(Z > 0 && Y > 0 && X > 0, LSR_E_ARG, "shape (%lld,%lld,%lld) must be positive", (long long)Z, (long long)Y,
               (long long)X);
   if (label::check_volume(Z, Y, X) != LSR_OK) return LSR_E_ARG;        // (its message stands: at most 2^31 - 1 voxels)
-  LSR_REQUIRE(capacity > 0 && capacity <= kMaxPairCapacity && (capacity & (capacity - 1)) == 0, LSR_E_ARG,
-              "capacity %lld: a power of two, 1 .. 2^30", (long long)capacity);
+  if (int rc = check_pair_capacity(capacity)) return rc;
   LSR_REQUIRE(max_blocks >= 0, LSR_E_ARG, "max_blocks %d: 0 (the default) or a positive cap", max_blocks);
   const uintptr_t t0 = reinterpret_cast<uintptr_t>(table), t1 = t0 + static_cast<uintptr_t>(capacity) * sizeof(Overlap);
   const uintptr_t bytes = static_cast<uintptr_t>(Z * Y * X) * sizeof(int32_t);

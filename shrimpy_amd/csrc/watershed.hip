@@ -218,7 +218,8 @@ __global__ __launch_bounds__(kThreads) void watershed_saddles_kernel(const int* 
           const uint32_t ku = lb::float_key(surface[u]), pass = ku < kv ? ku : kv;
           const unsigned long long a = static_cast<unsigned>(a0 < b0 ? a0 : b0), b = static_cast<unsigned>(a0 < b0 ? b0 : a0);
           const unsigned long long pair = a << 32 | b;
-          unsigned slot = ws::slot_of(pair, mask);
+          // lsr::pair_insert spelled out: through the template hipcc gives this kernel 65 VGPRs where this loop takes 29
+          unsigned slot = lsr::pair_slot_of(pair, mask);
           bool placed = false;
           for (int p = 0; p < probes; ++p, slot = (slot + 1) & mask) {      // bounded: nobody's progress is waited for
             const unsigned long long old = atomicCAS(&table[slot].pair, 0ull, pair);
@@ -238,28 +239,24 @@ __global__ __launch_bounds__(kThreads) void watershed_saddles_kernel(const int* 
 
 constexpr int kLaunches = 7;       // local, merge, flatten, count, scan, rank, final
 
-// The seven launches; with `events` (kLaunches + 1 of them) one is recorded in front of each launch and one behind the last.
+// The seven launches; a timing entry's marks (kLaunches + 1 events) get one in front of each launch and one behind the last.
 int watershed_launches(const int32_t* objects, const float* surface, int64_t Z, int64_t Y, int64_t X, int connectivity,
-                       int32_t* basins, int32_t* n_basins, void* scratch, hipStream_t q, hipEvent_t* events) {
+                       int32_t* basins, int32_t* n_basins, void* scratch, hipStream_t q, lsr::LaunchMarks marks) {
   const int level = lb::level_of(connectivity);
   const Shape s{static_cast<int>(Z), static_cast<int>(Y), static_cast<int>(X)};
   const int64_t n = Z * Y * X;
   const int64_t tz = lsr::ceil_div(Z, ws::kTileZ), ty = lsr::ceil_div(Y, ws::kTileY), tx = lsr::ceil_div(X, ws::kTileX);
   int* counts = static_cast<int*>(scratch);
   unsigned char* dir = static_cast<unsigned char*>(scratch) + lb::number_blocks(n) * sizeof(int);
-  int k = 0;
-  auto mark = [&]() {
-    if (events != nullptr) (void)hipEventRecord(events[k++], q);
-  };
-  mark();
+  marks.mark();
   // (tz * ty * tx <= n < 2^31 tiles; at most kMaxTileBlocks workgroups walk them)
   hipLaunchKernelGGL(watershed_local_kernel, dim3(static_cast<unsigned>(std::min(tz * ty * tx, kMaxTileBlocks))), dim3(kThreads), 0, q,
                      objects, surface, s, level, static_cast<int>(ty), static_cast<int>(tx), static_cast<unsigned>(tz * ty * tx),
                      basins, dir);
-  mark();
+  marks.mark();
   hipLaunchKernelGGL(watershed_merge_kernel, dim3(stride_grid(lsr::ceil_div(n, 4))), dim3(kThreads), 0, q, basins, dir, s, n);
-  number_launches(basins, n, counts, n_basins, q, mark);
-  mark();
+  number_launches(basins, n, counts, n_basins, q, marks);
+  marks.mark();
   return lsr::launch_status("lsr_watershed_f32");
 }
 
@@ -281,7 +278,7 @@ extern "C" int64_t lsr_watershed_scratch_bytes(int64_t Z, int64_t Y, int64_t X) 
 extern "C" int lsr_watershed_f32(const int32_t* objects, const float* surface, int64_t Z, int64_t Y, int64_t X, int connectivity,
                                  int32_t* basins, int32_t* n_basins, void* scratch, lsr_stream_t stream) {
   if (int rc = ws::check_watershed(objects, surface, Z, Y, X, connectivity, basins, n_basins, scratch)) return rc;
-  return watershed_launches(objects, surface, Z, Y, X, connectivity, basins, n_basins, scratch, lsr::as_stream(stream), nullptr);
+  return watershed_launches(objects, surface, Z, Y, X, connectivity, basins, n_basins, scratch, lsr::as_stream(stream), {});
 }
 
 // Measurement only (tools/bench_kernels.py --watershed): lsr_watershed_f32 with a HIP event between its launches; waits for
@@ -291,21 +288,10 @@ extern "C" int lsr_watershed_profile_f32(const int32_t* objects, const float* su
                                          lsr_stream_t stream) {
   if (int rc = ws::check_watershed(objects, surface, Z, Y, X, connectivity, basins, n_basins, scratch)) return rc;
   LSR_REQUIRE_PTR(ms7);
-  hipEvent_t events[kLaunches + 1];
-  int made = 0;
-  hipError_t e = hipSuccess;
-  for (; made <= kLaunches && e == hipSuccess; ++made) e = hipEventCreate(&events[made]);
-  if (e != hipSuccess) --made;
-  int rc = LSR_OK;
-  if (e == hipSuccess) {
-    rc = watershed_launches(objects, surface, Z, Y, X, connectivity, basins, n_basins, scratch, lsr::as_stream(stream), events);
-    e = hipEventSynchronize(events[kLaunches]);
-    for (int k = 0; k < kLaunches && e == hipSuccess; ++k) e = hipEventElapsedTime(&ms7[k], events[k], events[k + 1]);
-  }
-  for (int k = 0; k < made; ++k) (void)hipEventDestroy(events[k]);
-  if (rc != LSR_OK) return rc;
-  if (e != hipSuccess) return lsr::fail(static_cast<int>(e), "lsr_watershed_profile_f32: %s", hipGetErrorString(e));
-  return LSR_OK;
+  hipStream_t q = lsr::as_stream(stream);
+  return lsr::profile_launches<kLaunches>(ms7, q, "lsr_watershed_profile_f32", [&](lsr::LaunchMarks marks) {
+    return watershed_launches(objects, surface, Z, Y, X, connectivity, basins, n_basins, scratch, q, marks);
+  });
 }
 
 extern "C" int lsr_watershed_saddles_f32(const int32_t* objects, const int32_t* basins, const float* surface, int64_t Z, int64_t Y,
@@ -319,6 +305,6 @@ extern "C" int lsr_watershed_saddles_f32(const int32_t* objects, const int32_t* 
   if (e != hipSuccess) return lsr::fail(static_cast<int>(e), "lsr_watershed_saddles_f32: %s", hipGetErrorString(e));
   hipLaunchKernelGGL(watershed_saddles_kernel, dim3(stride_grid(n)), dim3(kThreads), 0, q, objects, basins, surface, s, n,
                      lb::level_of(connectivity), static_cast<unsigned>(capacity - 1),
-                     static_cast<int>(std::min<int64_t>(capacity, ws::kMaxProbes)), static_cast<ws::Saddle*>(table), counts);
+                     lsr::pair_probes(capacity), static_cast<ws::Saddle*>(table), counts);
   return lsr::launch_status("lsr_watershed_saddles_f32");
 }

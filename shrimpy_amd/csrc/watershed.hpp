@@ -15,7 +15,7 @@
 #pragma once
 
 #include "label.hpp"
-#include "pair_hash.hpp"
+#include "pair_table.hpp"
 
 namespace lsr {
 namespace watershed {
@@ -26,8 +26,6 @@ constexpr int kTileVoxels = kTileZ * kTileY * kTileX;
 constexpr int kHaloY = kTileY + 2, kHaloX = kTileX + 2;
 constexpr int kHaloVoxels = (kTileZ + 2) * kHaloY * kHaloX;      // 6600: two words each, 52 800 B of LDS
 constexpr int kSelf = 13;                                        // the code of (0, 0, 0)
-constexpr int kMaxProbes = 256;                                  // a pair gives up after min(capacity, kMaxProbes) slots
-constexpr int64_t kMaxCapacity = kMaxPairCapacity;
 
 // The code of a direction: (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1), ascending in the linear index of the neighbour.
 __host__ __device__ inline int code_of(int dz, int dy, int dx) { return (dz + 1) * 9 + (dy + 1) * 3 + (dx + 1); }
@@ -64,9 +62,6 @@ struct Saddle {
 };
 static_assert(sizeof(Saddle) == 16, "the saddle record's size is part of the ABI");
 
-// Where a pair starts probing: pair_hash.hpp's, shared with the label-overlap table.
-__host__ __device__ inline uint32_t slot_of(unsigned long long pair, uint32_t mask) { return pair_slot_of(pair, mask); }
-
 // Is (dz, dy, dx) one of the neighbours that FOLLOW a voxel in raster order under `level`?
 __host__ __device__ inline bool forward_neighbour(int dz, int dy, int dx, int level) {
   return label::backward_neighbour(-dz, -dy, -dx, level);
@@ -98,9 +93,7 @@ inline int check_saddles(const void* objects, const void* basins, const void* su
   LSR_REQUIRE_PTR(counts);
   if (int rc = label::check_volume(Z, Y, X)) return rc;
   LSR_REQUIRE(label::level_of(connectivity) != 0, LSR_E_ARG, "connectivity %d: 6, 18 or 26", connectivity);
-  LSR_REQUIRE(capacity > 0 && capacity <= kMaxCapacity && (capacity & (capacity - 1)) == 0, LSR_E_ARG,
-              "capacity %lld: a power of two, 1 .. 2^30", (long long)capacity);
-  return LSR_OK;
+  return check_pair_capacity(capacity);
 }
 
 }  // namespace watershed

@@ -24,7 +24,7 @@ from __future__ import annotations
 import ctypes
 
 from . import _lib
-from .segment import _check_volume, _run
+from .segment import _check_volume, _run, _scratch, _shape3
 
 __all__ = ["tiling", "distance_transform", "distance_transform_labels", "expand_labels"]
 
@@ -51,24 +51,14 @@ def _sampling(sampling):
     return s, (ctypes.c_double * 3)(*s)
 
 
-def _shape(t, name: str):
-    z, y, x = (int(v) for v in t.shape)
-    if min(z, y, x) <= 0:
-        raise ValueError(f"{name} must not be empty, got shape {(z, y, x)}")
-    return z, y, x
-
-
 def _transform(entry: str, vol, head: tuple, invert: bool, sampling, return_indices: bool, want_dist: bool = True):
     import torch
 
-    z, y, x = _shape(vol, "the volume")
+    z, y, x = _shape3(vol, "the volume")
     _, c_sampling = _sampling(sampling)
-    scratch_bytes = _lib.call_value("lsr_edt_scratch_bytes", z, y, x)
-    if scratch_bytes < 0:
-        _lib.call("lsr_edt_scratch_bytes", z, y, x)       # (raises with the library's message)
+    scratch = _scratch("lsr_edt_scratch_bytes", z, y, x, vol.device)
     dist = torch.empty((z, y, x), dtype=torch.float32, device=vol.device) if want_dist else None
     nearest = torch.empty((z, y, x), dtype=torch.int32, device=vol.device) if return_indices else None
-    scratch = torch.empty((max(scratch_bytes, 4),), dtype=torch.uint8, device=vol.device)
     _run(vol.device, entry, vol.data_ptr(), z, y, x, *head, int(bool(invert)), c_sampling,
          None if dist is None else dist.data_ptr(), None if nearest is None else nearest.data_ptr(), scratch.data_ptr())
     return (dist, nearest) if return_indices else dist
@@ -102,7 +92,7 @@ def expand_labels(labels, distance: float, sampling=(1, 1, 1)):
     import torch
 
     labels = _check_volume(labels, "labels", torch.int32)
-    z, y, x = _shape(labels, "labels")
+    z, y, x = _shape3(labels, "labels")
     distance = float(distance)
     if math.isnan(distance) or distance < 0.0:
         raise ValueError(f"distance must not be negative, got {distance}")

@@ -35,11 +35,15 @@ REGION_DTYPE = np.dtype([("volume", "<i8"), ("sum_zyx", "<i8", (3,)), ("sum_v", 
 assert REGION_DTYPE.itemsize == 96
 
 
+def _tile_shape(entry: str) -> tuple[int, int, int]:
+    zyx = (ctypes.c_int * 3)()
+    _lib.call(entry, zyx)
+    return tuple(zyx)
+
+
 def tile_shape() -> tuple[int, int, int]:
     """The ``(z, y, x)`` tile one workgroup labels in LDS (``lsr_label_tile_shape``)."""
-    zyx = (ctypes.c_int * 3)()
-    _lib.call("lsr_label_tile_shape", zyx)
-    return tuple(zyx)
+    return _tile_shape("lsr_label_tile_shape")
 
 
 def _run(device, entry: str, *args) -> None:
@@ -68,6 +72,63 @@ def _check_volume(t, name: str, dtype):
     return t
 
 
+# ---- shared with distance.py, watershed.py and track.py --------------------------------------------------------------------------
+
+def _shape3(t, name: str) -> tuple[int, int, int]:
+    """``(z, y, x)`` of a checked volume that must not be empty."""
+    z, y, x = (int(v) for v in t.shape)
+    if min(z, y, x) <= 0:
+        raise ValueError(f"{name} must not be empty, got shape {(z, y, x)}")
+    return z, y, x
+
+
+def _same_volume(a, b, name_a: str, name_b: str) -> None:
+    """``b`` has ``a``'s shape and sits on ``a``'s device."""
+    if b.shape != a.shape or b.device != a.device:
+        raise ValueError(f"{name_b} {tuple(b.shape)} on {b.device} does not match {name_a} {tuple(a.shape)} on {a.device}")
+
+
+def _connectivity(connectivity) -> int:
+    if connectivity not in (6, 18, 26):
+        raise ValueError(f"connectivity must be 6, 18 or 26, got {connectivity!r}")
+    return int(connectivity)
+
+
+def _scratch(entry: str, z: int, y: int, x: int, device):
+    """The scratch buffer ``entry`` (a ``*_scratch_bytes``) asks for at this shape, as a uint8 tensor on ``device``."""
+    import torch
+
+    scratch_bytes = _lib.call_value(entry, z, y, x)
+    if scratch_bytes < 0:
+        _lib.call(entry, z, y, x)       # (raises with the library's message)
+    return torch.empty((max(scratch_bytes, 4),), dtype=torch.uint8, device=device)
+
+
+def _fill_pair_table(device, dtype: np.dtype, capacity: int, ceiling: int, what: str, launch) -> np.ndarray:
+    """The claimed records of an open-addressing pair table (``csrc/pair_table.hpp``) as a host array of ``dtype``, sorted by
+    ``pair``.  ``launch(capacity, table_ptr, counts_ptr)`` fills a zeroed table of ``capacity`` records and sets ``counts =
+    (claimed, lost)``; while a contribution is lost the capacity doubles and the pass runs again, up to ``ceiling`` slots
+    (then :class:`RuntimeError`, which begins with ``what.format(lost)``: the caller's name and what was lost)."""
+    import torch
+
+    while True:
+        table = torch.zeros((capacity * dtype.itemsize,), dtype=torch.uint8, device=device)   # the host zeroes it
+        counts = torch.empty((2,), dtype=torch.int32, device=device)
+        launch(capacity, table.data_ptr(), counts.data_ptr())
+        claimed, lost = (int(v) for v in counts.cpu().tolist())
+        if lost == 0:
+            break
+        del table
+        if capacity >= ceiling:
+            raise RuntimeError(f"{what.format(lost)} found no slot in a table of {capacity} slots ({claimed} claimed), the ceiling")
+        capacity *= 2
+    rows = table.cpu().numpy().view(dtype)
+    rows = rows[rows["pair"] != 0]
+    rows = rows[np.argsort(rows["pair"], kind="stable")]
+    assert len(rows) == claimed
+    return rows
+
+
 def label_volume(vol, threshold: float, connectivity: int = 6):
     """Label the components of ``vol > threshold`` ((Z, Y, X) float32): ``(labels, n)``.
 
@@ -77,18 +138,12 @@ def label_volume(vol, threshold: float, connectivity: int = 6):
     import torch
 
     vol = _check_volume(vol, "vol", torch.float32)
-    z, y, x = (int(v) for v in vol.shape)
-    if connectivity not in (6, 18, 26):
-        raise ValueError(f"connectivity must be 6, 18 or 26, got {connectivity!r}")
-    if min(z, y, x) <= 0:
-        raise ValueError(f"vol must not be empty, got shape {(z, y, x)}")
-    scratch_bytes = _lib.call_value("lsr_label_scratch_bytes", z, y, x)
-    if scratch_bytes < 0:
-        _lib.call("lsr_label_scratch_bytes", z, y, x)       # (raises with the library's message)
+    connectivity = _connectivity(connectivity)
+    z, y, x = _shape3(vol, "vol")
+    scratch = _scratch("lsr_label_scratch_bytes", z, y, x, vol.device)
     labels = torch.empty((z, y, x), dtype=torch.int32, device=vol.device)
     count = torch.empty((1,), dtype=torch.int32, device=vol.device)
-    scratch = torch.empty((max(scratch_bytes, 4),), dtype=torch.uint8, device=vol.device)
-    _run(vol.device, "lsr_label_f32", vol.data_ptr(), z, y, x, ctypes.c_float(float(threshold)), int(connectivity),
+    _run(vol.device, "lsr_label_f32", vol.data_ptr(), z, y, x, ctypes.c_float(float(threshold)), connectivity,
          labels.data_ptr(), count.data_ptr(), scratch.data_ptr())
     return labels, int(count.cpu().item())
 
@@ -103,9 +158,7 @@ def _raw_table(labels, n: int, intensity=None) -> np.ndarray:
         raise ValueError(f"n must not be negative, got {n}")
     if intensity is not None:
         intensity = _check_volume(intensity, "intensity", torch.float32)
-        if intensity.shape != labels.shape or intensity.device != labels.device:
-            raise ValueError(f"intensity {tuple(intensity.shape)} on {intensity.device} does not match labels "
-                             f"{tuple(labels.shape)} on {labels.device}")
+        _same_volume(labels, intensity, "labels", "intensity")
     if n == 0:
         return np.zeros((0,), dtype=REGION_DTYPE)
     z, y, x = (int(v) for v in labels.shape)

@@ -36,7 +36,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .segment import _check_volume, _run
+from .segment import _check_volume, _fill_pair_table, _run, _same_volume, _shape3
 
 __all__ = ["OVERLAP_DTYPE", "MAX_CAPACITY", "overlap_geometry", "label_overlaps", "label_volumes", "link_frames", "Tracker",
            "track_frames", "relabel_by_track"]
@@ -60,12 +60,8 @@ def _frames(a, b):
 
     a = _check_volume(a, "a", torch.int32)
     b = _check_volume(b, "b", torch.int32)
-    if a.shape != b.shape or a.device != b.device:
-        raise ValueError(f"b {tuple(b.shape)} on {b.device} does not match a {tuple(a.shape)} on {a.device}")
-    z, y, x = (int(v) for v in a.shape)
-    if min(z, y, x) <= 0:
-        raise ValueError(f"a must not be empty, got shape {(z, y, x)}")
-    return a, b, (z, y, x)
+    _same_volume(a, b, "a", "b")
+    return a, b, _shape3(a, "a")
 
 
 def _shift(shift):
@@ -86,8 +82,6 @@ def label_overlaps(a, b, shift=(0, 0, 0), _capacity: int | None = None, _max_blo
     ``bound = min(max(a) + max(b), voxels)``, and while a contribution finds no slot the capacity doubles and the pass runs
     again, up to ``MAX_CAPACITY`` slots (then :class:`RuntimeError`).  ``_capacity`` sets the first capacity (a power of two;
     tests force the retry with it), ``_max_blocks`` caps the grid (0: the kernel's default; the result does not depend on it)."""
-    import torch
-
     a, b, (z, y, x) = _frames(a, b)
     c_shift = _shift(shift)
     if _capacity is not None:
@@ -97,23 +91,12 @@ def label_overlaps(a, b, shift=(0, 0, 0), _capacity: int | None = None, _max_blo
         capacity = 1 << int(4 * bound + 1024 - 1).bit_length()
     if capacity <= 0 or capacity & (capacity - 1) or capacity > MAX_CAPACITY:
         raise ValueError(f"_capacity must be a power of two up to 2^30, got {capacity}")
-    while True:
-        table = torch.zeros((capacity * OVERLAP_DTYPE.itemsize,), dtype=torch.uint8, device=a.device)   # the host zeroes it
-        counts = torch.empty((2,), dtype=torch.int32, device=a.device)
-        _run(a.device, "lsr_label_overlap_i32", a.data_ptr(), b.data_ptr(), z, y, x, c_shift, capacity, table.data_ptr(),
-             counts.data_ptr(), int(_max_blocks))
-        claimed, lost = (int(v) for v in counts.cpu().tolist())
-        if lost == 0:
-            break
-        del table
-        if capacity >= MAX_CAPACITY:
-            raise RuntimeError(f"label_overlaps: {lost} voxels found no slot in a table of {capacity} slots ({claimed} claimed), "
-                               "the ceiling")
-        capacity *= 2
-    rows = table.cpu().numpy().view(OVERLAP_DTYPE)
-    rows = rows[rows["pair"] != 0]
-    rows = rows[np.argsort(rows["pair"], kind="stable")]
-    assert len(rows) == claimed
+
+    def launch(capacity, table_ptr, counts_ptr):
+        _run(a.device, "lsr_label_overlap_i32", a.data_ptr(), b.data_ptr(), z, y, x, c_shift, capacity, table_ptr, counts_ptr,
+             int(_max_blocks))
+
+    rows = _fill_pair_table(a.device, OVERLAP_DTYPE, capacity, MAX_CAPACITY, "label_overlaps: {} voxels", launch)
     return {"a": (rows["pair"] >> np.uint64(32)).astype(np.int64), "b": (rows["pair"] & np.uint64(0xFFFFFFFF)).astype(np.int64),
             "count": rows["count"].astype(np.int64)}
 

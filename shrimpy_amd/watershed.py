@@ -36,12 +36,11 @@ Not built: seeded (marker) watersheds, a compact-watershed term, watershed lines
 
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 
 from . import _lib
-from .segment import _check_volume, _run, region_table
+from .segment import (_check_volume, _connectivity, _fill_pair_table, _run, _same_volume, _scratch, _shape3, _tile_shape,
+                      region_table)
 
 __all__ = ["SADDLE_DTYPE", "MAX_CAPACITY", "tile_shape", "watershed_basins", "basin_saddles", "merge_map", "split_labels",
            "split_touching"]
@@ -55,9 +54,7 @@ MAX_CAPACITY = 1 << 28
 
 def tile_shape() -> tuple[int, int, int]:
     """The ``(z, y, x)`` tile one workgroup stages in LDS (``lsr_watershed_tile_shape``)."""
-    zyx = (ctypes.c_int * 3)()
-    _lib.call("lsr_watershed_tile_shape", zyx)
-    return tuple(zyx)
+    return _tile_shape("lsr_watershed_tile_shape")
 
 
 def _key_to_float(keys: np.ndarray) -> np.ndarray:
@@ -77,19 +74,8 @@ def _pair(objects, surface):
 
     objects = _check_volume(objects, "objects", torch.int32)
     surface = _check_volume(surface, "surface", torch.float32)
-    if surface.shape != objects.shape or surface.device != objects.device:
-        raise ValueError(f"surface {tuple(surface.shape)} on {surface.device} does not match objects {tuple(objects.shape)} on "
-                         f"{objects.device}")
-    z, y, x = (int(v) for v in objects.shape)
-    if min(z, y, x) <= 0:
-        raise ValueError(f"objects must not be empty, got shape {(z, y, x)}")
-    return objects, surface, (z, y, x)
-
-
-def _connectivity(connectivity) -> int:
-    if connectivity not in (6, 18, 26):
-        raise ValueError(f"connectivity must be 6, 18 or 26, got {connectivity!r}")
-    return int(connectivity)
+    _same_volume(objects, surface, "objects", "surface")
+    return objects, surface, _shape3(objects, "objects")
 
 
 def watershed_basins(objects, surface, connectivity: int = 6):
@@ -100,12 +86,9 @@ def watershed_basins(objects, surface, connectivity: int = 6):
 
     objects, surface, (z, y, x) = _pair(objects, surface)
     connectivity = _connectivity(connectivity)
-    scratch_bytes = _lib.call_value("lsr_watershed_scratch_bytes", z, y, x)
-    if scratch_bytes < 0:
-        _lib.call("lsr_watershed_scratch_bytes", z, y, x)       # (raises with the library's message)
+    scratch = _scratch("lsr_watershed_scratch_bytes", z, y, x, objects.device)
     basins = torch.empty((z, y, x), dtype=torch.int32, device=objects.device)
     count = torch.empty((1,), dtype=torch.int32, device=objects.device)
-    scratch = torch.empty((max(scratch_bytes, 4),), dtype=torch.uint8, device=objects.device)
     _run(objects.device, "lsr_watershed_f32", objects.data_ptr(), surface.data_ptr(), z, y, x, connectivity, basins.data_ptr(),
          count.data_ptr(), scratch.data_ptr())
     return basins, int(count.cpu().item())
@@ -121,9 +104,7 @@ def basin_saddles(objects, basins, n_basins: int, surface, connectivity: int = 6
 
     objects, surface, (z, y, x) = _pair(objects, surface)
     basins = _check_volume(basins, "basins", torch.int32)
-    if basins.shape != objects.shape or basins.device != objects.device:
-        raise ValueError(f"basins {tuple(basins.shape)} on {basins.device} does not match objects {tuple(objects.shape)} on "
-                         f"{objects.device}")
+    _same_volume(objects, basins, "objects", "basins")
     connectivity = _connectivity(connectivity)
     empty = {"a": np.zeros((0,), np.int32), "b": np.zeros((0,), np.int32), "saddle": np.zeros((0,), np.float32)}
     if int(n_basins) < 2:
@@ -131,23 +112,12 @@ def basin_saddles(objects, basins, n_basins: int, surface, connectivity: int = 6
     capacity = int(_capacity) if _capacity is not None else 1 << int(4 * int(n_basins) + 1024 - 1).bit_length()
     if capacity <= 0 or capacity & (capacity - 1):
         raise ValueError(f"_capacity must be a power of two, got {capacity}")
-    while True:
-        table = torch.zeros((capacity * SADDLE_DTYPE.itemsize,), dtype=torch.uint8, device=objects.device)   # the host zeroes it
-        counts = torch.empty((2,), dtype=torch.int32, device=objects.device)
+
+    def launch(capacity, table_ptr, counts_ptr):
         _run(objects.device, "lsr_watershed_saddles_f32", objects.data_ptr(), basins.data_ptr(), surface.data_ptr(), z, y, x,
-             connectivity, capacity, table.data_ptr(), counts.data_ptr())
-        claimed, lost = (int(v) for v in counts.cpu().tolist())
-        if lost == 0:
-            break
-        del table
-        if capacity >= MAX_CAPACITY:
-            raise RuntimeError(f"basin_saddles: {lost} neighbour pairs found no slot in a table of {capacity} slots "
-                               f"({claimed} claimed), the ceiling")
-        capacity *= 2
-    rows = table.cpu().numpy().view(SADDLE_DTYPE)
-    rows = rows[rows["pair"] != 0]
-    rows = rows[np.argsort(rows["pair"], kind="stable")]
-    assert len(rows) == claimed
+             connectivity, capacity, table_ptr, counts_ptr)
+
+    rows = _fill_pair_table(objects.device, SADDLE_DTYPE, capacity, MAX_CAPACITY, "basin_saddles: {} neighbour pairs", launch)
     return {"a": (rows["pair"] >> np.uint64(32)).astype(np.int32), "b": (rows["pair"] & np.uint64(0xFFFFFFFF)).astype(np.int32),
             "saddle": _key_to_float(rows["key"])}
 
