@@ -997,6 +997,32 @@ int lsr_edt_profile_f32(const float* in, int64_t Z, int64_t Y, int64_t X, float 
                         float* dist, int32_t* nearest, void* scratch, float* ms3, lsr_stream_t stream);
 
 /*
+ * Flat grey-scale morphology under a box (csrc/morphology.hip, shrimpy_amd/morphology.py).  The rule is stated in
+ * csrc/morphology.hpp; PINNED to scipy.ndimage.grey_erosion / grey_dilation / grey_opening / grey_closing / white_tophat /
+ * black_tophat with size = 2r + 1, element for element on NaN-free volumes:
+ *   in, out are contiguous (Z, Y, X) float32 volumes; the window is 2r + 1 wide per axis, half-widths (rz, ry, rx).
+ *   erode(v)(p) is the least and dilate(v)(p) the greatest v(q) over the in-volume q of the box around p: voxels outside the
+ *   volume do not compete, and a half-width may exceed the axis.  Values compare by the order-preserving integer image of a
+ *   float (-0.0 below +0.0, +-inf ordinary values); the result is the bit pattern of the chosen element.  A window that holds
+ *   a NaN gives the canonical quiet NaN 0x7fc00000, for erosion and dilation alike.
+ *   op: 0 erode, 1 dilate, 2 open = dilate(erode), 3 close = erode(dilate), 4 white top-hat = in - open, 5 black top-hat =
+ *   close - in; the top-hats are one IEEE float32 subtraction per voxel, fused into the last pass (a NaN it produces may carry
+ *   any payload).  An axis with half-width 0 gets no pass; all three at 0 make ops 0 .. 3 a copy and ops 4, 5 in - in.
+ * out must not alias in (LSR_E_ARG); a negative half-width or an unknown op is LSR_E_ARG, a half-width above the cap
+ * LSR_E_UNSUPPORTED, a NULL pointer LSR_E_NULL, a non-positive extent LSR_E_SHAPE; nothing is launched or written then.  One
+ * launch per axis with a half-width > 0 and per erosion or dilation (an opening: up to six); every launch reads each voxel of
+ * its source once and writes each voxel of its target once, no launch communicates between workgroups.  `scratch` (device
+ * memory, lsr_grey_morph_scratch_bytes(Z, Y, X) bytes -- two float volumes -- or a negative status; its contents on entry do
+ * not matter) holds the results between the passes; `in` is never written and `out` exactly once.
+ * lsr_grey_morph_tiling: {the greatest half-width per axis, columns per workgroup of the y and z passes, outputs per staged
+ * row segment of the x pass, threads per workgroup of the x pass}.
+ */
+int lsr_grey_morph_tiling(int tiling[4]);
+int64_t lsr_grey_morph_scratch_bytes(int64_t Z, int64_t Y, int64_t X);
+int lsr_grey_morph_f32(const float* in, float* out, int64_t Z, int64_t Y, int64_t X, int rz, int ry, int rx, int op,
+                       void* scratch, lsr_stream_t stream);
+
+/*
  * Splitting touching objects: a watershed by steepest ascent (csrc/watershed.hip, shrimpy_amd/watershed.py).  PARITY
  * UNPINNED: no upstream is pinned, the rule IS the specification (csrc/watershed.hpp; tests/watershed_ref.py restates it).
  *   objects (int32, Z * Y * X): values <= 0 are background.  surface (float32): its values compare by the order-preserving
@@ -1208,6 +1234,12 @@ int lsr_watershed_saddles_f32_cpu(const int32_t* objects, const int32_t* basins,
  * (csrc/overlap.hpp): the kernel's set of records.  Every pointer HOST memory; max_blocks is checked and otherwise unused. */
 int lsr_label_overlap_i32_cpu(const int32_t* a, const int32_t* b, int64_t Z, int64_t Y, int64_t X, const int32_t shift_zyx[3],
                               int64_t capacity, void* table, int32_t* counts, int max_blocks, lsr_stream_t stream);
+
+/* ... of the grey morphology (csrc/morphology.hip): the same plan of passes and the same walk along a line
+ * (csrc/morphology.hpp), so `out` is the kernels' bits.  Every pointer HOST memory; `scratch` holds the results between the
+ * passes, as on the device. */
+int lsr_grey_morph_f32_cpu(const float* in, float* out, int64_t Z, int64_t Y, int64_t X, int rz, int ry, int rx, int op,
+                           void* scratch, lsr_stream_t stream);
 
 /* ... of the mutual-information metric (csrc/estimate_mi.hip): the per-sample rule of csrc/mi_sample.hpp on both sides.
  * The histogram and the count are the kernel's bits; the gradient rows are sums over lsr_affine_mi_gradient_blocks()

@@ -179,6 +179,9 @@ SIGNATURES: dict[str, list] = {
     "lsr_edt_profile_f32": [_c_f32p, _i64, _i64, _i64, _f32, _int, _f64p, _c_f32p, ctypes.c_void_p, ctypes.c_void_p,
                             ctypes.POINTER(ctypes.c_float), _stream],
     "lsr_label_expand_i32": [ctypes.c_void_p, ctypes.c_void_p, _i64, _i64, _i64, _f64p, ctypes.c_double, ctypes.c_void_p, _stream],
+    "lsr_grey_morph_tiling": [ctypes.POINTER(ctypes.c_int)],
+    "lsr_grey_morph_scratch_bytes": [_i64, _i64, _i64],
+    "lsr_grey_morph_f32": [_c_f32p, _c_f32p, _i64, _i64, _i64, _int, _int, _int, _int, ctypes.c_void_p, _stream],
     "lsr_watershed_tile_shape": [ctypes.POINTER(ctypes.c_int)],
     "lsr_watershed_scratch_bytes": [_i64, _i64, _i64],
     "lsr_watershed_f32": [ctypes.c_void_p, _c_f32p, _i64, _i64, _i64, _int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _stream],
@@ -280,10 +283,12 @@ for _name in ("lsr_deskew_f32", "lsr_deskew_u16", "lsr_deskew_cval", "lsr_affine
               # ... and of the watershed (csrc/watershed.hip)
               "lsr_watershed_f32", "lsr_watershed_saddles_f32",
               # ... and of the label-overlap table (csrc/overlap.hip)
-              "lsr_label_overlap_i32"):
+              "lsr_label_overlap_i32",
+              # ... and of the grey morphology (csrc/morphology.hip)
+              "lsr_grey_morph_f32"):
     SIGNATURES[_name + "_cpu"] = SIGNATURES[_name]
 # entries whose answer is a byte count that can pass 2^31 (a negative value is a status)
-RETURNS_INT64 = ("lsr_edt_scratch_bytes", "lsr_watershed_scratch_bytes")
+RETURNS_INT64 = ("lsr_edt_scratch_bytes", "lsr_watershed_scratch_bytes", "lsr_grey_morph_scratch_bytes")
 SIGNATURES["lsr_rl_tv_scale_f32_cpu"] = SIGNATURES["lsr_rl_tv_scale_f32"][:-1]     # (this twin takes no stream)
 for _name in ("lsr_rl_accel_dots_f32", "lsr_rl_accel_predict_f32",                     # (nor do these)
               # ... nor those of the mutual-information metric (csrc/estimators_host.hip)

@@ -17,6 +17,7 @@ CPU path (biahub's; the reference's own CLI has only ``acquire`` and ``gui``,
     python -m shrimpy_amd.cli pyramid     -i store.zarr --levels 4        (adds levels to the store in place)
     python -m shrimpy_amd.cli estimate-stitch -i tiles.zarr -c estimate.yml -o stitch.yml
     python -m shrimpy_amd.cli stitch      -i tiles.zarr -c stitch.yml    -o stitched.zarr
+    python -m shrimpy_amd.cli subtract-background -i store.zarr -c background.yml -o flat.zarr
 
 Every (position, timepoint, channel) volume is an independent unit.  Launched under
 ``python -m torch.distributed.run --nproc-per-node N`` each rank takes the units
@@ -1202,6 +1203,99 @@ def run_stabilize(input_path, config, output_path, positions=(), zarr_version: s
                      levels=levels, level_factor_z=level_factor_z)
 
 
+class _BackgroundStep:
+    """``run_store``'s step of the ``subtract-background`` command: ``for_unit`` hands out the top-hat at the half-widths of
+    the unit's position (``named`` channels) or a plain copy (every other channel); the volume keeps its shape."""
+
+    def __init__(self, half_widths_of, op: str, named: bool, raw_shape, _settings, device):
+        self.device = device
+        self.output_shape = tuple(int(n) for n in raw_shape)
+        self._half_widths_of, self._op, self._named = half_widths_of, op, named
+
+    def for_unit(self, unit):
+        import torch
+
+        from . import morphology
+
+        half_widths = self._half_widths_of(unit.position) if self._named else None
+        tophat = getattr(morphology, self._op)
+
+        def step(raw):
+            vol = torch.as_tensor(raw, device=self.device).to(torch.float32).contiguous()
+            return vol if half_widths is None else tophat(vol, half_widths)
+
+        return step
+
+
+@cli.command("subtract-background", cls=_eat_all_command("-i", "--input-position-dirpaths"))
+@_common
+def subtract_background(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error,
+                        levels, level_factor_z):
+    """Subtract a slowly varying background: the top-hat of whole channels (config: a BackgroundSettings YAML).
+
+    Every volume of the channels channel_names is replaced by its white top-hat (v - opening(v); op: black_tophat gives
+    closing(v) - v) under a box of `radius` micrometres (a number or [z, y, x]; 0 on an axis: no window there) at the
+    position's scale; the other channels are copied.  The window has to be wider than the objects that are to stay."""
+    input_path, positions = _inputs(input_path, positions)
+    _finish(run_subtract_background(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression,
+                                    on_error, **_pyramid_options(levels, level_factor_z)))
+
+
+def run_subtract_background(input_path, config, output_path, positions=(), zarr_version: str = "0.5", resume: bool = False,
+                            io_backend: str = "auto", compression=None, on_error: str = "raise", levels: int = 1,
+                            level_factor_z: int = 2) -> dict:
+    """``subtract-background``: every ``(position, t, c)`` volume of a named channel is replaced by its top-hat
+    (``shrimpy_amd/morphology.py``) at the half-widths ``radius`` comes to at the position's ``(z, y, x)`` scale, the other
+    channels are copied.  Everything is checked before the output store is created: the settings, the channels, and the
+    half-widths of every position against the kernels' cap."""
+    from .io.omezarr import position_scale
+    from .morphology import half_widths_of
+    from .settings import BackgroundSettings
+
+    try:
+        settings = BackgroundSettings.from_yaml(config)
+    except (ValueError, TypeError) as exc:
+        raise click.ClickException(f"{config}: {exc}") from exc
+    channels = list(settings.channel_names)
+    src, src_positions = _open_source(Path(input_path), io_backend)
+    try:
+        missing = [p for p in positions if p not in src_positions]
+        if missing:
+            raise click.ClickException(f"positions {missing} not found; available: {list(src_positions)}")
+        keys = [k for k in src_positions if not positions or k in positions]
+        if not keys:
+            raise click.ClickException("no positions to process")
+        names = list(src_positions[keys[0]].channel_names)
+        unknown = [n for n in channels if n not in names]
+        if unknown:
+            raise click.ClickException(f"channel_names {unknown} not in the store (it has {names})")
+        half_widths = {}
+        for key in keys:
+            scale = tuple(float(v) for v in position_scale(src_positions[key])[-3:])
+            try:
+                half_widths[key] = half_widths_of(settings.radius, scale)
+            except ValueError as exc:
+                raise click.ClickException(f"position {key}: {exc}") from exc
+    finally:
+        close = getattr(src, "close", None)
+        if close:
+            close()
+    # run_store's channel plan: the named channels take the first step, the others the second
+    plan = ReconstructSettings(registration=RegisterSettings(source_channel_names=channels,
+                                                             affine_transform_zyx=np.eye(4).tolist()))
+
+    def factory(raw_shape, plan_settings, device):
+        return _BackgroundStep(half_widths.__getitem__, settings.op, plan_settings.registration is not None, raw_shape,
+                               plan_settings, device)
+
+    return run_store(input_path, output_path, plan, tuple(keys) if positions else (), zarr_version,
+                     reconstructor_factory=factory, resume=resume, io_backend=io_backend, compression=compression,
+                     on_error=on_error,
+                     fingerprint_extra={"subtract_background": {"settings": settings.model_dump(mode="json"),
+                                                                "half_widths": {k: list(v) for k, v in half_widths.items()}}},
+                     levels=levels, level_factor_z=level_factor_z)
+
+
 def _position_translation(position) -> tuple[float, ...]:
     """(T, C, Z, Y, X) NGFF ``translation`` of a position's level 0 (zeros when absent)."""
     ms = position.zattrs.get("multiscales", [{}])
@@ -1466,10 +1560,10 @@ def run_stitch(input_path, config, output_path, positions=(), zarr_version: str 
 
 
 def _run_object_store(input_path, output_path, positions, zarr_version, io_backend, compression, channel_name: str, suffix: str,
-                      result_key: str, process, check_array=None) -> dict:
+                      result_key: str, process, check_array=None, check_geometry=None) -> dict:
     """What ``run_segment`` and ``run_track`` share: one channel of every selected position goes in, one int32 array per
-    position comes out.  Everything is checked before the output store is created (``check_array(key, array)`` adds a
-    command's own refusal); rank 0 creates the store (channel ``<channel_name><suffix>``, the input's ``scale`` and
+    position comes out.  Everything is checked before the output store is created (``check_array(key, array)`` and
+    ``check_geometry(key, (scale, translation))`` add a command's own refusals); rank 0 creates the store (channel ``<channel_name><suffix>``, the input's ``scale`` and
     ``translation`` copied); the positions are dealt out by rank, and ``process(key, array, channel, out, geometry, device,
     directory)`` fills ``out`` from channel ``channel`` of ``array`` (``geometry``: the 5-D ``(scale, translation)``,
     ``directory``: the position's, for its tables) and returns the position's entry of ``result[result_key]``."""
@@ -1500,6 +1594,8 @@ def _run_object_store(input_path, output_path, positions, zarr_version, io_backe
                     raise click.ClickException(f"position {k}: a volume of {tuple(a.shape[2:])} has more than 2^31 - 1 voxels")
                 arrays[k], channel[k] = a, names.index(channel_name)
                 geometry[k] = (list(position_scale(pos)), list(_position_translation(pos)))
+                if check_geometry is not None:
+                    check_geometry(k, geometry[k])
             out_channel = f"{channel_name}{suffix}"
             error = None
             if rank == 0:
@@ -1591,7 +1687,11 @@ def segment(input_path, config, output_path, positions, zarr_version, io_backend
 
     expand_distance (micrometres, the position's scale) grows the filtered labels without overlap; inscribed_radius adds
     the column inscribed_radius_um to objects.csv.  split: true splits touching objects before the size filter: a watershed
-    of each object's depth map blurred by split_sigma voxels, basins shallower than split_min_depth (micrometres) merged."""
+    of each object's depth map blurred by split_sigma voxels, basins shallower than split_min_depth (micrometres) merged.
+
+    background_radius (micrometres, a number or [z, y, x]; 0 on an axis: no window there) thresholds the white top-hat of the
+    volume under a box of that radius instead of the volume: a slowly varying background goes, objects narrower than the
+    window stay.  fill_holes: true fills the holes of the thresholded mask before it is labelled."""
     input_path, positions = _inputs(input_path, positions)
     _finish(run_segment(input_path, config, output_path, positions, zarr_version, io_backend, compression))
 
@@ -1631,8 +1731,17 @@ def run_segment(input_path, config, output_path, positions=(), zarr_version: str
             w.writerows([[repr(v) if isinstance(v, float) else v for v in row] for row in rows])
         return counts
 
+    def check_radius(key, geometry):
+        """``background_radius`` at the position's scale stays within the kernels' cap."""
+        from .morphology import half_widths_of
+
+        try:
+            half_widths_of(settings.background_radius, geometry[0][2:])
+        except ValueError as exc:
+            raise click.ClickException(f"position {key}: background_radius: {exc}") from exc
+
     return _run_object_store(input_path, output_path, positions, zarr_version, io_backend, compression, settings.channel_name,
-                             "_labels", "objects", position)
+                             "_labels", "objects", position, check_geometry=check_radius)
 
 
 TRACK_COLUMNS = ("track_id", "t_begin", "t_end", "parent_track_id")

@@ -28,6 +28,7 @@
 //   lsr_watershed_f32_cpu, lsr_watershed_saddles_f32_cpu
 //                                             <->  the same names without _cpu         (watershed.hip)
 //   lsr_label_overlap_i32_cpu                 <->  lsr_label_overlap_i32               (overlap.hip)
+//   lsr_grey_morph_f32_cpu                    <->  lsr_grey_morph_f32                  (morphology.hip)
 //
 // Arithmetic (what "the same" means):
 //   resamplers -- the text the kernels compile (resample.hpp): coordinates, axis taps with their weights and the
@@ -1537,6 +1538,45 @@ extern "C" int lsr_label_overlap_i32_cpu(const int32_t* a, const int32_t* b, int
         if (!lsr::pair_insert_host(slots, mask, probes, pair, counts, [](ov::Overlap& slot) { slot.count += 1; })) counts[1] += 1;
       }
     }
+  }
+  return LSR_OK;
+}
+
+// ---- grey morphology (morphology.hip): the same plan of passes and the same walk (morphology.hpp), a tile of columns per step ----
+#include "morphology.hpp"
+
+extern "C" int lsr_grey_morph_f32_cpu(const float* in, float* out, int64_t Z, int64_t Y, int64_t X, int rz, int ry, int rx, int op,
+                                      void* scratch, lsr_stream_t) {
+  namespace mo = lsr::morph;
+  if (int rc = mo::check_morph(in, out, Z, Y, X, rz, ry, rx, op, scratch)) return rc;
+  const int64_t voxels = Z * Y * X;
+  mo::Pass passes[mo::kMaxPasses];
+  const int n = mo::plan(rz, ry, rx, op, passes);
+  const int fuse = mo::fuse_of(op);
+  if (n == 0) {
+    for (int64_t e = 0; e < voxels; ++e) out[e] = mo::fused(in[e], in[e], fuse);
+    return LSR_OK;
+  }
+  float* work = static_cast<float*>(scratch);
+  std::atomic<bool> failed{false};
+  for (int k = 0; k < n; ++k) {
+    const mo::Pass ps = passes[k];
+    const float* src = mo::pass_source(k, in, work, voxels);
+    float* dst = mo::pass_target(k, n, out, work, voxels);
+    const int f = k == n - 1 ? fuse : static_cast<int>(mo::kPlain);
+    const float* orig = f != mo::kPlain ? in : nullptr;
+    const mo::Lines lines = mo::lines_of(ps.axis, Z, Y, X);
+    const int64_t tiles_per_slab = lsr::ceil_div(lines.columns, mo::kColumns);
+    lsr::parallel_ranges(lines.outer * tiles_per_slab, [&](int64_t first, int64_t last) {
+      std::vector<uint32_t> strip(static_cast<size_t>(2 * ps.r + 1) * mo::kColumns);
+      for (int64_t tile = first; tile < last; ++tile) {
+        const int64_t slab = tile / tiles_per_slab, c0 = (tile - slab * tiles_per_slab) * mo::kColumns;
+        const int lanes = static_cast<int>(std::min<int64_t>(mo::kColumns, lines.columns - c0));
+        mo::walk_host(src, dst, orig, slab * lines.ostep + c0 * lines.cstep, lanes, lines.cstep, lines.L, lines.step, ps.r,
+                      ps.least, f, strip.data());
+      }
+    }, failed);
+    if (failed.load()) return lsr::fail(LSR_E_ARG, "lsr_grey_morph_f32_cpu: out of memory for the block strip");
   }
   return LSR_OK;
 }

@@ -10,11 +10,13 @@ numbering is a prefix count), ``csrc/host_twins.hip`` on the CPU; both equal ``s
   mean, minimum, maximum and the intensity-weighted centroid.  The integer columns and the intensity range are exact; the
   float64 sums are atomic adds on the device (within ``n_k * 2^-53 * sum|terms|`` of the exact sum, not bit-reproducible).
 * :func:`filter_objects` -- drop small objects or keep the largest; the kept labels stay consecutive, in their old order.
-* :func:`segment_zyx` -- threshold (a number or multi-Otsu, after an optional Gaussian blur), label, on request split the
+* :func:`segment_zyx` -- on request subtract the background (the white top-hat of ``shrimpy_amd/morphology.py``), threshold (a
+  number or multi-Otsu, after an optional Gaussian blur), on request fill the holes of the mask, label, on request split the
   touching objects by a watershed of their depth map (``shrimpy_amd/watershed.py``), measure, filter, and on request grow the
   labels by a distance and measure each object's inscribed radius (``shrimpy_amd/distance.py``).
 
-Not built: seeded watersheds, multi-GPU or slab labelling, label pyramids, volumes above ``2^31 - 1`` voxels.  Labels are
+Not built: seeded watersheds, multi-GPU or slab labelling, label pyramids, volumes above ``2^31 - 1`` voxels, ball-shaped or
+rolling-ball background windows (the window is a box), background-subtracted intensity columns in the table.  Labels are
 numbered from 1 at every timepoint; linking them over time is ``shrimpy_amd/track.py`` (the ``track`` command), where gap
 closing, motion models and a global assignment are not built.
 """
@@ -233,6 +235,9 @@ def segment_zyx(vol, settings, sampling=(1, 1, 1)):
     """Threshold, label, measure and filter one (Z, Y, X) float32 volume by a :class:`~shrimpy_amd.settings.SegmentSettings`:
     ``(labels, table, n)``.  With ``sigma > 0`` the blurred volume is thresholded; with ``threshold: otsu`` the threshold is
     the multi-Otsu one of what is thresholded (a constant volume has no objects).  The table's intensities are ``vol``'s.
+    With ``background_radius > 0`` the white top-hat of ``vol`` under a box of that radius (in the units of ``sampling``,
+    ``shrimpy_amd/morphology.py``) is what is blurred and thresholded; with ``fill_holes`` the mask ``work > threshold`` is
+    filled (``scipy.ndimage.binary_fill_holes``) before it is labelled, for every ``connectivity``.
 
     ``sampling = (sz, sy, sx)`` is the voxel spacing the distance settings measure in (``shrimpy_amd/distance.py``).  With
     ``split`` the labelled objects are split before anything else sees them (``watershed.split_touching``: the watershed of
@@ -247,12 +252,24 @@ def segment_zyx(vol, settings, sampling=(1, 1, 1)):
     from . import dynatrack as D
 
     vol = _check_volume(vol, "vol", torch.float32)
-    work = D._gaussian_blur_3d(vol, float(settings.sigma)) if settings.sigma > 0 else vol
+    work = vol
+    radius = settings.background_radius
+    if any(float(r) > 0 for r in (radius if isinstance(radius, (tuple, list)) else (radius,))):
+        from . import morphology
+
+        work = morphology.subtract_background(work, radius, sampling)
+    work = D._gaussian_blur_3d(work, float(settings.sigma)) if settings.sigma > 0 else work
     if settings.threshold == "otsu":
         threshold = D._multiotsu_threshold(work, int(settings.otsu_component))
     else:
         threshold = float(settings.threshold)
-    labels, n = label_volume(work, threshold, int(settings.connectivity))
+    if settings.fill_holes:
+        from . import morphology
+
+        # (the filled mask as a volume of 0 and 1: its components under `connectivity` are the filled objects)
+        labels, n = label_volume(morphology.fill_holes(work > threshold).to(torch.float32), 0.5, int(settings.connectivity))
+    else:
+        labels, n = label_volume(work, threshold, int(settings.connectivity))
     if settings.split and n > 0:
         from . import watershed
 

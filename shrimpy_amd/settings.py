@@ -566,10 +566,21 @@ class SegmentSettings(_StrictModel):
     Gaussian of ``split_sigma`` voxels -- whose basins are merged where the depth of the pass between them is at most
     ``split_min_depth`` (in the units of ``expand_distance``: micrometres from the ``segment`` command).  The merge depth, not
     the blur, is the knob that makes the result stable; no upstream is pinned for this step (its rule is the specification).
-    ``min_volume`` and ``keep_largest`` then act on the split objects."""
+    ``min_volume`` and ``keep_largest`` then act on the split objects.
+
+    ``background_radius`` (a number or ``[z, y, x]``, in the units of ``expand_distance``: micrometres from the ``segment``
+    command) takes a slowly varying background away before anything else: the volume is replaced by its white top-hat under a
+    box of that radius (``shrimpy_amd/morphology.py``; per axis ``floor(radius / scale + 0.5)`` voxels to each side), then
+    blurred and thresholded -- a number, or the multi-Otsu value of what is thresholded.  The window has to be wider than
+    the objects.  A component 0 means no window on that axis (``[0, r, r]`` works plane by plane); 0, the default, leaves the
+    volume alone.  ``fill_holes`` fills the holes of the thresholded mask before it is labelled
+    (``scipy.ndimage.binary_fill_holes``: background that no path of face neighbours joins to the border of the volume), for
+    every ``connectivity``.  The table's intensities stay the input's."""
 
     channel_name: str
     threshold: Union[float, Literal["otsu"]]
+    background_radius: Union[NonNegativeFloat, tuple[NonNegativeFloat, NonNegativeFloat, NonNegativeFloat]] = 0.0
+    fill_holes: bool = False
     sigma: NonNegativeFloat = 0.0
     otsu_component: NonNegativeInt = 0
     connectivity: Literal[6, 18, 26] = 6
@@ -586,6 +597,41 @@ class SegmentSettings(_StrictModel):
     def _check_threshold(cls, v):
         if not isinstance(v, str) and not np.isfinite(float(v)):
             raise ValueError("threshold must be a finite number or \"otsu\"")
+        return v
+
+    @field_validator("background_radius")
+    @classmethod
+    def _check_background_radius(cls, v):
+        if not all(np.isfinite(float(r)) for r in (v if isinstance(v, tuple) else (v,))):
+            raise ValueError("background_radius must be finite")
+        return v
+
+
+class BackgroundSettings(_StrictModel):
+    """Top-hat background subtraction of whole channels (``shrimpy_amd/morphology.py``, the ``subtract-background`` command).
+
+    Every volume of the channels ``channel_names`` is replaced by its top-hat under a box of ``radius`` -- a number or
+    ``[z, y, x]`` in the units of the position's scale (micrometres), per axis ``floor(radius / scale + 0.5)`` voxels to each
+    side, a component 0 meaning no window on that axis.  ``op`` ``"white_tophat"`` (``v - opening(v)``) keeps bright
+    structures narrower than the window, ``"black_tophat"`` (``closing(v) - v``) dark ones.  The other channels are copied."""
+
+    channel_names: list[str]
+    radius: Union[NonNegativeFloat, tuple[NonNegativeFloat, NonNegativeFloat, NonNegativeFloat]]
+    op: Literal["white_tophat", "black_tophat"] = "white_tophat"
+
+    @field_validator("channel_names")
+    @classmethod
+    def _check_channels(cls, v):
+        if not v:
+            raise ValueError("channel_names is empty: nothing to subtract a background from")
+        return v
+
+    @field_validator("radius")
+    @classmethod
+    def _check_radius(cls, v):
+        values = v if isinstance(v, tuple) else (v,)
+        if not all(np.isfinite(float(r)) for r in values) or not any(float(r) > 0 for r in values):
+            raise ValueError("radius must be finite and positive on at least one axis")
         return v
 
 

@@ -83,6 +83,11 @@ def main():
                     "events between the launches, median of 5 calls after a warm-up) on --rl-grid, for bench.synthetic_raw at its "
                     "multi-Otsu threshold, Bernoulli noise at p = 0.3 and an all-foreground volume with one background voxel, "
                     "beside a device copy of an int32 volume in the same run; appended to profiles/edt_config2.jsonl")
+    ap.add_argument("--morphology", action="store_true", help="only: ms of the grey-morphology kernels (csrc/morphology.hip: erosion, "
+                    "opening, white top-hat) on --rl-grid for the bench's bead scene at half-widths 5, 25, 50 and 128 (HIP events, "
+                    "median of 3 calls after a warm-up), beside a device copy of one volume and the three launches of "
+                    "lsr_local_max_candidates_f32 at the same half-width (up to 64) in the same run; appended to "
+                    "profiles/morphology_config2.jsonl")
     ap.add_argument("--mi", action="store_true", help="only: ms per launch of the mutual-information kernels (csrc/estimate_mi.hip: "
                     "joint histogram, gradient) on --mi-grid at strides 1 and 4, 32 and 64 bins, on bench.synthetic_raw "
                     "(background-dominated) and on uniform noise (spread over all cells), beside a torch formulation "
@@ -122,6 +127,9 @@ def main():
         return
     if args.edt:
         _edt(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
+        return
+    if args.morphology:
+        _morphology(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
         return
     if args.label:
         _label(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
@@ -950,6 +958,73 @@ def _edt(args, torch, dev, g, bench, oshape):
     with open(path, "a") as f:
         for r in records:
             line = json.dumps({**r, **stamp})
+            print(line, flush=True)
+            f.write(line + "\n")
+
+
+def _morphology(args, torch, dev, g, bench, oshape):
+    """Grey morphology (csrc/morphology.hip) at the config-2 deskewed shape on the bench's bead scene: erosion (3 launches),
+    opening (6) and white top-hat (6, the subtraction fused into the last) at cubic half-widths 5, 25, 50 and, if the cap allows,
+    128, and the erosion along z, y and x alone (one launch each); a launch moves 8 algorithmic bytes per voxel (one read, one
+    write; the top-hat's last one 12).  Beside them, in the same
+    run, the floor -- a device copy of one volume, the same 8 bytes per voxel -- and, where the half-width is at most 64, the
+    three launches of lsr_local_max_candidates_f32 at the same half-width: the running maximum the bead detection has (two
+    volumes written, the third pass fused with the peak test)."""
+    from shrimpy_amd import _lib, morphology
+
+    reps = 3
+    z, y, x = oshape
+    n = z * y * x
+    vol = bench.synthetic_raw(oshape, 1000, dev)
+    out = torch.empty_like(vol)
+    copy_ms = _median_ms(lambda: out.copy_(vol), reps, torch)
+    records = [{"kernel": "device copy of a float32 volume (torch copy_)", "grid": list(oshape), "ms": copy_ms,
+                "GBps": 8.0 * n / copy_ms / 1e6}]
+    cap = morphology.max_half_width()
+    scratch = torch.empty(_lib.call_value("lsr_grey_morph_scratch_bytes", z, y, x), dtype=torch.uint8, device=dev)
+    nbytes = ctypes.c_int64(0)
+    _lib.call("lsr_local_max_scratch_bytes", z, y, x, ctypes.byref(nbytes))
+    assert nbytes.value <= scratch.numel()                  # (two float volumes as well: the same buffer serves)
+    capacity = 1 << 20
+    index = torch.empty(capacity, dtype=torch.int64, device=dev)
+    value = torch.empty(capacity, dtype=torch.float32, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    for r in (5, 25, 50, 128):
+        if r > cap:
+            continue
+        base = {"input": "bead scene (bench.synthetic_raw)", "grid": list(oshape), "half_widths": [r, r, r]}
+        for name, launches in (("grey_erosion", 3), ("grey_opening", 6), ("white_tophat", 6)):
+            def launch(op=morphology.OPS[name]):
+                _lib.call("lsr_grey_morph_f32", vol.data_ptr(), out.data_ptr(), z, y, x, r, r, r, op, scratch.data_ptr(),
+                          _lib.stream_ptr(dev))
+            ms = _median_ms(launch, reps, torch)
+            bpv = 8.0 * launches + (4.0 if name == "white_tophat" else 0.0)
+            records.append({**base, "kernel": f"lsr_grey_morph_f32: {name} ({launches} launches)", "ms": ms,
+                            "ms_per_launch": ms / launches, "bytes_per_voxel": bpv, "algorithmic_GBps": bpv * n / ms / 1e6,
+                            "copy_time_ratio_per_launch": ms / launches / copy_ms})
+        for axis, name in enumerate("zyx"):                 # one launch each: the window on one axis only
+            rr = [r if a == axis else 0 for a in range(3)]
+
+            def one(rr=rr):
+                _lib.call("lsr_grey_morph_f32", vol.data_ptr(), out.data_ptr(), z, y, x, *rr, 0, scratch.data_ptr(),
+                          _lib.stream_ptr(dev))
+            ms = _median_ms(one, reps, torch)
+            records.append({**base, "half_widths": rr, "kernel": f"lsr_grey_morph_f32: grey_erosion along {name} (1 launch)",
+                            "ms": ms, "bytes_per_voxel": 8.0, "algorithmic_GBps": 8.0 * n / ms / 1e6,
+                            "copy_time_ratio_per_launch": ms / copy_ms})
+        if r <= 64:
+            def detect():
+                _lib.call("lsr_local_max_candidates_f32", vol.data_ptr(), z, y, x, r, r, r, ctypes.c_float(3.0e38), index.data_ptr(),
+                          value.data_ptr(), capacity, count.data_ptr(), scratch.data_ptr(), _lib.stream_ptr(dev))
+            ms = _median_ms(detect, reps, torch)
+            records.append({**base, "kernel": "lsr_local_max_candidates_f32 (3 launches, 2 volumes written)", "ms": ms,
+                            "ms_per_launch": ms / 3, "ms_per_volume_written": ms / 2,
+                            "copy_time_ratio_per_launch": ms / 3 / copy_ms})
+    stamp = {"sources": _lib.kernel_source_sha16(), "device": torch.cuda.get_device_name(dev), "reps": reps, "warmups": 1}
+    path = ROOT / "profiles" / "morphology_config2.jsonl"
+    with open(path, "a") as f:
+        for rec in records:
+            line = json.dumps({**rec, **stamp})
             print(line, flush=True)
             f.write(line + "\n")
 
