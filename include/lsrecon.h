@@ -1023,6 +1023,32 @@ int lsr_grey_morph_f32(const float* in, float* out, int64_t Z, int64_t Y, int64_
                        void* scratch, lsr_stream_t stream);
 
 /*
+ * Rank filters under a box: rank, median, percentile and outlier removal (csrc/rank.hip, shrimpy_amd/rank.py).  The rule is
+ * stated in csrc/rank.hpp; PINNED to scipy.ndimage.rank_filter / median_filter / percentile_filter with size = 2r + 1 and
+ * mode = "reflect", by value on NaN-free volumes:
+ *   in, out are contiguous (Z, Y, X) float32 volumes; half-widths (rz, ry, rx), each in 0 .. 3, window 2r + 1 per axis, n
+ *   elements; `rank` in 0 .. n - 1 (the median is n / 2).  The border is scipy's `reflect` (d c b a | a b c d): index i of an
+ *   axis of length L reads m = i mod 2L, then m < L ? m : 2L - 1 - m; a half-width may exceed the axis, and reflected voxels
+ *   count as often as they fall in the window.  m(p) is the rank-th smallest (from 0) of the window's values under the
+ *   order-preserving integer image of a float (-0.0 below +0.0, +-inf ordinary values, a NaN the greatest and returned as
+ *   the canonical quiet NaN 0x7fc00000); the result is the bit pattern of the chosen element.
+ *   op, fused into the store (t = threshold, v the voxel, each difference one IEEE float32 subtraction, a comparison with a
+ *   NaN false): 0 value: m; 1 remove_bright: (v - m > t) ? m : v; 2 remove_dark: (m - v > t) ? m : v; 3 remove_both: m where
+ *   either holds, else v.  All half-widths 0: every op copies v, except that a NaN becomes the canonical one under op 0.
+ *   variant: 0 dispatches the half-width triples of {0, 1}^3 to kernels that hold the window in registers and every other
+ *   window to the generic kernel, 1 forces the generic kernel; both give the same bytes.
+ * out must not alias in (LSR_E_ARG); a negative half-width, a rank outside 0 .. n - 1, an unknown op or variant and a NaN
+ * threshold under ops 1 .. 3 are LSR_E_ARG, a half-width above the cap LSR_E_UNSUPPORTED, a NULL pointer LSR_E_NULL, a
+ * non-positive extent LSR_E_SHAPE; nothing is launched or written then.  One launch, no scratch, no atomics, nothing between
+ * workgroups: a workgroup stages the codes of its tile and a halo of r per side in LDS, the border resolved at load time;
+ * `in` is never written and every voxel of `out` exactly once.
+ * lsr_rank_filter_tiling: {the greatest half-width per axis, the tile's z, y and x extent}.
+ */
+int lsr_rank_filter_tiling(int tiling[4]);
+int lsr_rank_filter_f32(const float* in, float* out, int64_t Z, int64_t Y, int64_t X, int rz, int ry, int rx, int rank, int op,
+                        float threshold, int variant, lsr_stream_t stream);
+
+/*
  * Splitting touching objects: a watershed by steepest ascent (csrc/watershed.hip, shrimpy_amd/watershed.py).  PARITY
  * UNPINNED: no upstream is pinned, the rule IS the specification (csrc/watershed.hpp; tests/watershed_ref.py restates it).
  *   objects (int32, Z * Y * X): values <= 0 are background.  surface (float32): its values compare by the order-preserving
@@ -1240,6 +1266,11 @@ int lsr_label_overlap_i32_cpu(const int32_t* a, const int32_t* b, int64_t Z, int
  * passes, as on the device. */
 int lsr_grey_morph_f32_cpu(const float* in, float* out, int64_t Z, int64_t Y, int64_t X, int rz, int ry, int rx, int op,
                            void* scratch, lsr_stream_t stream);
+
+/* ... of the rank filters (csrc/rank.hip): the same fold, codes, bisection and fused op (csrc/rank.hpp), so `out` is the
+ * kernel's bits.  Every pointer HOST memory; `variant` is accepted and ignored. */
+int lsr_rank_filter_f32_cpu(const float* in, float* out, int64_t Z, int64_t Y, int64_t X, int rz, int ry, int rx, int rank, int op,
+                            float threshold, int variant, lsr_stream_t stream);
 
 /* ... of the mutual-information metric (csrc/estimate_mi.hip): the per-sample rule of csrc/mi_sample.hpp on both sides.
  * The histogram and the count are the kernel's bits; the gradient rows are sums over lsr_affine_mi_gradient_blocks()

@@ -18,6 +18,7 @@ CPU path (biahub's; the reference's own CLI has only ``acquire`` and ``gui``,
     python -m shrimpy_amd.cli estimate-stitch -i tiles.zarr -c estimate.yml -o stitch.yml
     python -m shrimpy_amd.cli stitch      -i tiles.zarr -c stitch.yml    -o stitched.zarr
     python -m shrimpy_amd.cli subtract-background -i store.zarr -c background.yml -o flat.zarr
+    python -m shrimpy_amd.cli despeckle   -i store.zarr -c despeckle.yml -o clean.zarr
 
 Every (position, timepoint, channel) volume is an independent unit.  Launched under
 ``python -m torch.distributed.run --nproc-per-node N`` each rank takes the units
@@ -1296,6 +1297,112 @@ def run_subtract_background(input_path, config, output_path, positions=(), zarr_
                      levels=levels, level_factor_z=level_factor_z)
 
 
+class _DespeckleStep:
+    """``run_store``'s step of the ``despeckle`` command: ``for_unit`` hands out the rank filter at the half-widths of the
+    unit's position (``named`` channels) or a plain copy (every other channel); the volume keeps its shape."""
+
+    def __init__(self, half_widths_of, settings, named: bool, raw_shape, _settings, device):
+        self.device = device
+        self.output_shape = tuple(int(n) for n in raw_shape)
+        self._half_widths_of, self._despeckle, self._named = half_widths_of, settings, named
+
+    def for_unit(self, unit):
+        import torch
+
+        from . import rank
+
+        half_widths = self._half_widths_of(unit.position) if self._named else None
+        s = self._despeckle
+
+        def step(raw):
+            vol = torch.as_tensor(raw, device=self.device).to(torch.float32).contiguous()
+            if half_widths is None:
+                return vol
+            if s.percentile is not None:
+                return rank.percentile_filter(vol, s.percentile, half_widths)
+            if s.op == "median":
+                return rank.median_filter(vol, half_widths)
+            return rank.remove_outliers(vol, half_widths, s.threshold, s.op[len("remove_"):])
+
+        return step
+
+
+@cli.command("despeckle", cls=_eat_all_command("-i", "--input-position-dirpaths"))
+@_common
+def despeckle(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error, levels,
+              level_factor_z):
+    """Remove hot pixels and speckle: a median / outlier-removal filter of whole channels (config: a DespeckleSettings YAML).
+
+    Every volume of the channels channel_names is filtered under a box of `radius` micrometres (a number or [z, y, x]) at the
+    position's scale, or of `half_widths` voxels ([z, y, x]; hot pixels of a raw stack: [0, 1, 1]); at most 3 voxels to each
+    side.  op: median replaces every voxel by the median of its box (or, with `percentile`, by that percentile);
+    remove_bright (the default), remove_dark and remove_both replace only the voxels that differ from the median by more than
+    `threshold` and leave the others as they are.  The other channels are copied."""
+    input_path, positions = _inputs(input_path, positions)
+    _finish(run_despeckle(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error,
+                          **_pyramid_options(levels, level_factor_z)))
+
+
+def run_despeckle(input_path, config, output_path, positions=(), zarr_version: str = "0.5", resume: bool = False,
+                  io_backend: str = "auto", compression=None, on_error: str = "raise", levels: int = 1,
+                  level_factor_z: int = 2) -> dict:
+    """``despeckle``: every ``(position, t, c)`` volume of a named channel goes through the rank filter
+    (``shrimpy_amd/rank.py``) at ``half_widths``, or at the half-widths ``radius`` comes to at the position's ``(z, y, x)``
+    scale; the other channels are copied.  Everything is checked before the output store is created: the settings, the
+    channels, and the half-widths of every position against the kernel's cap."""
+    from . import rank
+    from .io.omezarr import position_scale
+    from .settings import DespeckleSettings
+
+    try:
+        settings = DespeckleSettings.from_yaml(config)
+    except (ValueError, TypeError) as exc:
+        raise click.ClickException(f"{config}: {exc}") from exc
+    channels = list(settings.channel_names)
+    src, src_positions = _open_source(Path(input_path), io_backend)
+    try:
+        missing = [p for p in positions if p not in src_positions]
+        if missing:
+            raise click.ClickException(f"positions {missing} not found; available: {list(src_positions)}")
+        keys = [k for k in src_positions if not positions or k in positions]
+        if not keys:
+            raise click.ClickException("no positions to process")
+        names = list(src_positions[keys[0]].channel_names)
+        unknown = [n for n in channels if n not in names]
+        if unknown:
+            raise click.ClickException(f"channel_names {unknown} not in the store (it has {names})")
+        half_widths = {}
+        for key in keys:
+            scale = tuple(float(v) for v in position_scale(src_positions[key])[-3:])
+            try:
+                if settings.half_widths is not None:
+                    half_widths[key] = rank._half_widths(settings.half_widths)
+                else:
+                    half_widths[key] = rank.half_widths_of(settings.radius, scale)
+                if settings.percentile is not None:
+                    rank.rank_of_percentile(settings.percentile, rank.window_size(half_widths[key]))
+            except ValueError as exc:
+                raise click.ClickException(f"position {key}: {exc}") from exc
+    finally:
+        close = getattr(src, "close", None)
+        if close:
+            close()
+    # run_store's channel plan: the named channels take the first step, the others the second
+    plan = ReconstructSettings(registration=RegisterSettings(source_channel_names=channels,
+                                                             affine_transform_zyx=np.eye(4).tolist()))
+
+    def factory(raw_shape, plan_settings, device):
+        return _DespeckleStep(half_widths.__getitem__, settings, plan_settings.registration is not None, raw_shape,
+                              plan_settings, device)
+
+    return run_store(input_path, output_path, plan, tuple(keys) if positions else (), zarr_version,
+                     reconstructor_factory=factory, resume=resume, io_backend=io_backend, compression=compression,
+                     on_error=on_error,
+                     fingerprint_extra={"despeckle": {"settings": settings.model_dump(mode="json"),
+                                                      "half_widths": {k: list(v) for k, v in half_widths.items()}}},
+                     levels=levels, level_factor_z=level_factor_z)
+
+
 def _position_translation(position) -> tuple[float, ...]:
     """(T, C, Z, Y, X) NGFF ``translation`` of a position's level 0 (zeros when absent)."""
     ms = position.zattrs.get("multiscales", [{}])
@@ -1691,7 +1798,9 @@ def segment(input_path, config, output_path, positions, zarr_version, io_backend
 
     background_radius (micrometres, a number or [z, y, x]; 0 on an axis: no window there) thresholds the white top-hat of the
     volume under a box of that radius instead of the volume: a slowly varying background goes, objects narrower than the
-    window stay.  fill_holes: true fills the holes of the thresholded mask before it is labelled."""
+    window stay.  fill_holes: true fills the holes of the thresholded mask before it is labelled.  median_radius
+    (micrometres, a number or [z, y, x]; at most 3 voxels to each side) takes the median of the volume under a box of that
+    radius before anything else: speckle goes, edges stay."""
     input_path, positions = _inputs(input_path, positions)
     _finish(run_segment(input_path, config, output_path, positions, zarr_version, io_backend, compression))
 
@@ -1732,13 +1841,18 @@ def run_segment(input_path, config, output_path, positions=(), zarr_version: str
         return counts
 
     def check_radius(key, geometry):
-        """``background_radius`` at the position's scale stays within the kernels' cap."""
+        """``background_radius`` and ``median_radius`` at the position's scale stay within their kernels' caps."""
+        from . import rank
         from .morphology import half_widths_of
 
         try:
             half_widths_of(settings.background_radius, geometry[0][2:])
         except ValueError as exc:
             raise click.ClickException(f"position {key}: background_radius: {exc}") from exc
+        try:
+            rank.half_widths_of(settings.median_radius, geometry[0][2:])
+        except ValueError as exc:
+            raise click.ClickException(f"position {key}: median_radius: {exc}") from exc
 
     return _run_object_store(input_path, output_path, positions, zarr_version, io_backend, compression, settings.channel_name,
                              "_labels", "objects", position, check_geometry=check_radius)

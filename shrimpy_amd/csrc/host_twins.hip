@@ -29,6 +29,7 @@
 //                                             <->  the same names without _cpu         (watershed.hip)
 //   lsr_label_overlap_i32_cpu                 <->  lsr_label_overlap_i32               (overlap.hip)
 //   lsr_grey_morph_f32_cpu                    <->  lsr_grey_morph_f32                  (morphology.hip)
+//   lsr_rank_filter_f32_cpu                   <->  lsr_rank_filter_f32                 (rank.hip)
 //
 // Arithmetic (what "the same" means):
 //   resamplers -- the text the kernels compile (resample.hpp): coordinates, axis taps with their weights and the
@@ -1578,5 +1579,21 @@ extern "C" int lsr_grey_morph_f32_cpu(const float* in, float* out, int64_t Z, in
     }, failed);
     if (failed.load()) return lsr::fail(LSR_E_ARG, "lsr_grey_morph_f32_cpu: out of memory for the block strip");
   }
+  return LSR_OK;
+}
+
+// ---- rank filters (rank.hip): the same fold, codes, bisection and fused op (rank.hpp), a row of voxels per step ----
+#include "rank.hpp"
+
+extern "C" int lsr_rank_filter_f32_cpu(const float* in, float* out, int64_t Z, int64_t Y, int64_t X, int rz, int ry, int rx, int rank,
+                                       int op, float threshold, int variant, lsr_stream_t) {
+  namespace rk = lsr::rank;
+  if (int rc = rk::check_rank(in, out, Z, Y, X, rz, ry, rx, rank, op, threshold, variant)) return rc;
+  lsr::parallel_ranges(Z * Y, [&](int64_t first, int64_t last) {
+    for (int64_t row = first; row < last; ++row) {
+      const int64_t z = row / Y, y = row - z * Y;
+      for (int64_t x = 0; x < X; ++x) out[row * X + x] = rk::voxel_host(in, Z, Y, X, z, y, x, rz, ry, rx, rank, op, threshold);
+    }
+  });
   return LSR_OK;
 }

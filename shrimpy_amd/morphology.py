@@ -49,7 +49,7 @@ def max_half_width() -> int:
     return tiling()[0]
 
 
-def _half_widths(half_widths) -> tuple[int, int, int]:
+def _half_widths(half_widths, cap=None) -> tuple[int, int, int]:
     try:
         r = tuple(half_widths)
     except TypeError as exc:
@@ -59,7 +59,7 @@ def _half_widths(half_widths) -> tuple[int, int, int]:
     r = tuple(int(v) for v in r)
     if min(r) < 0:
         raise ValueError(f"half_widths must not be negative, got {r}")
-    cap = max_half_width()
+    cap = max_half_width() if cap is None else cap
     if max(r) > cap:
         raise ValueError(f"half_widths {r}: at most {cap} per axis")
     return r
@@ -108,10 +108,11 @@ def black_tophat(vol, half_widths):
     return _morph("black_tophat", vol, half_widths)
 
 
-def half_widths_of(radius, sampling=(1, 1, 1)) -> tuple[int, int, int]:
+def half_widths_of(radius, sampling=(1, 1, 1), cap=None) -> tuple[int, int, int]:
     """Half-widths in voxels of a ``radius`` in the units of ``sampling = (sz, sy, sx)``: ``floor(radius / s + 0.5)`` per axis.
     ``radius`` is one number for every axis or a ``(z, y, x)`` triple; a component 0 means no window on that axis.  A
-    half-width above the kernels' cap is a ``ValueError`` that names the cap."""
+    half-width above the kernels' cap (``cap``: another family's, ``shrimpy_amd/rank.py``) is a ``ValueError`` that names the
+    cap."""
     try:
         s = tuple(float(v) for v in sampling)
     except TypeError as exc:
@@ -125,7 +126,7 @@ def half_widths_of(radius, sampling=(1, 1, 1)) -> tuple[int, int, int]:
     if len(r) != 3 or not all(math.isfinite(v) and v >= 0.0 for v in r):
         raise ValueError(f"radius must be a non-negative finite number or three of them (z, y, x), got {radius!r}")
     quotients = tuple(a / b for a, b in zip(r, s))
-    cap = max_half_width()
+    cap = max_half_width() if cap is None else cap
     if any(q + 0.5 >= cap + 1 for q in quotients):
         raise ValueError(f"radius {radius!r} at sampling {s} is a half-width of {tuple(round(q, 3) for q in quotients)} voxels: "
                          f"at most {cap} per axis")

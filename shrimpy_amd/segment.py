@@ -10,7 +10,7 @@ numbering is a prefix count), ``csrc/host_twins.hip`` on the CPU; both equal ``s
   mean, minimum, maximum and the intensity-weighted centroid.  The integer columns and the intensity range are exact; the
   float64 sums are atomic adds on the device (within ``n_k * 2^-53 * sum|terms|`` of the exact sum, not bit-reproducible).
 * :func:`filter_objects` -- drop small objects or keep the largest; the kept labels stay consecutive, in their old order.
-* :func:`segment_zyx` -- on request subtract the background (the white top-hat of ``shrimpy_amd/morphology.py``), threshold (a
+* :func:`segment_zyx` -- on request take the median under a small box (``shrimpy_amd/rank.py``), subtract the background (the white top-hat of ``shrimpy_amd/morphology.py``), threshold (a
   number or multi-Otsu, after an optional Gaussian blur), on request fill the holes of the mask, label, on request split the
   touching objects by a watershed of their depth map (``shrimpy_amd/watershed.py``), measure, filter, and on request grow the
   labels by a distance and measure each object's inscribed radius (``shrimpy_amd/distance.py``).
@@ -237,7 +237,8 @@ def segment_zyx(vol, settings, sampling=(1, 1, 1)):
     the multi-Otsu one of what is thresholded (a constant volume has no objects).  The table's intensities are ``vol``'s.
     With ``background_radius > 0`` the white top-hat of ``vol`` under a box of that radius (in the units of ``sampling``,
     ``shrimpy_amd/morphology.py``) is what is blurred and thresholded; with ``fill_holes`` the mask ``work > threshold`` is
-    filled (``scipy.ndimage.binary_fill_holes``) before it is labelled, for every ``connectivity``.
+    filled (``scipy.ndimage.binary_fill_holes``) before it is labelled, for every ``connectivity``.  With ``median_radius > 0``
+    the median of ``vol`` under a box of that radius (``shrimpy_amd/rank.py``) takes ``vol``'s place before all of that.
 
     ``sampling = (sz, sy, sx)`` is the voxel spacing the distance settings measure in (``shrimpy_amd/distance.py``).  With
     ``split`` the labelled objects are split before anything else sees them (``watershed.split_touching``: the watershed of
@@ -253,6 +254,11 @@ def segment_zyx(vol, settings, sampling=(1, 1, 1)):
 
     vol = _check_volume(vol, "vol", torch.float32)
     work = vol
+    radius = settings.median_radius
+    if any(float(r) > 0 for r in (radius if isinstance(radius, (tuple, list)) else (radius,))):
+        from . import rank
+
+        work = rank.median_filter(work, rank.half_widths_of(radius, sampling))
     radius = settings.background_radius
     if any(float(r) > 0 for r in (radius if isinstance(radius, (tuple, list)) else (radius,))):
         from . import morphology

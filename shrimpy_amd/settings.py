@@ -575,10 +575,16 @@ class SegmentSettings(_StrictModel):
     the objects.  A component 0 means no window on that axis (``[0, r, r]`` works plane by plane); 0, the default, leaves the
     volume alone.  ``fill_holes`` fills the holes of the thresholded mask before it is labelled
     (``scipy.ndimage.binary_fill_holes``: background that no path of face neighbours joins to the border of the volume), for
-    every ``connectivity``.  The table's intensities stay the input's."""
+    every ``connectivity``.  The table's intensities stay the input's.
+
+    ``median_radius`` (a number or ``[z, y, x]``, the same units) replaces the volume by its median under a box of that radius
+    (``shrimpy_amd/rank.py``; at most 3 voxels to each side) before all of the above: speckle and hot pixels go, edges and the
+    contacts between objects stay where a Gaussian ``sigma`` would round them off.  0, the default, leaves the volume
+    alone."""
 
     channel_name: str
     threshold: Union[float, Literal["otsu"]]
+    median_radius: Union[NonNegativeFloat, tuple[NonNegativeFloat, NonNegativeFloat, NonNegativeFloat]] = 0.0
     background_radius: Union[NonNegativeFloat, tuple[NonNegativeFloat, NonNegativeFloat, NonNegativeFloat]] = 0.0
     fill_holes: bool = False
     sigma: NonNegativeFloat = 0.0
@@ -604,6 +610,13 @@ class SegmentSettings(_StrictModel):
     def _check_background_radius(cls, v):
         if not all(np.isfinite(float(r)) for r in (v if isinstance(v, tuple) else (v,))):
             raise ValueError("background_radius must be finite")
+        return v
+
+    @field_validator("median_radius")
+    @classmethod
+    def _check_median_radius(cls, v):
+        if not all(np.isfinite(float(r)) for r in (v if isinstance(v, tuple) else (v,))):
+            raise ValueError("median_radius must be finite")
         return v
 
 
@@ -633,6 +646,53 @@ class BackgroundSettings(_StrictModel):
         if not all(np.isfinite(float(r)) for r in values) or not any(float(r) > 0 for r in values):
             raise ValueError("radius must be finite and positive on at least one axis")
         return v
+
+
+class DespeckleSettings(_StrictModel):
+    """Median, percentile and outlier-removal filtering of whole channels (``shrimpy_amd/rank.py``, the ``despeckle`` command).
+
+    Every volume of the channels ``channel_names`` is filtered under a box given by exactly one of ``radius`` -- a number or
+    ``[z, y, x]`` in the units of the position's scale (micrometres), per axis ``floor(radius / scale + 0.5)`` voxels to each
+    side -- and ``half_widths`` -- ``[z, y, x]`` in voxels (hot pixels of a raw stack: ``[0, 1, 1]``); a component 0 means no
+    window on that axis, and a half-width is at most 3.  ``op``: ``"median"`` replaces every voxel by the median of its box;
+    ``"remove_bright"`` (the default), ``"remove_dark"`` and ``"remove_both"`` replace only the voxels that stand out from that
+    median by more than ``threshold`` (``v - m > threshold``, ``m - v > threshold``, either) and leave every other voxel as it
+    is -- ImageJ's "Remove Outliers"; ``threshold`` is required for them.  With ``percentile`` set (``op`` must be ``"median"``)
+    the filter is that percentile of the box instead (``scipy.ndimage.percentile_filter``'s convention).  The other channels
+    are copied."""
+
+    channel_names: list[str]
+    radius: Optional[Union[NonNegativeFloat, tuple[NonNegativeFloat, NonNegativeFloat, NonNegativeFloat]]] = None
+    half_widths: Optional[tuple[NonNegativeInt, NonNegativeInt, NonNegativeInt]] = None
+    op: Literal["median", "remove_bright", "remove_dark", "remove_both"] = "remove_bright"
+    threshold: Optional[NonNegativeFloat] = None
+    percentile: Optional[float] = None
+
+    @field_validator("channel_names")
+    @classmethod
+    def _check_channels(cls, v):
+        if not v:
+            raise ValueError("channel_names is empty: nothing to filter")
+        return v
+
+    @model_validator(mode="after")
+    def _check_consistency(self):
+        if (self.radius is None) == (self.half_widths is None):
+            raise ValueError("exactly one of radius and half_widths must be given")
+        values = self.half_widths if self.radius is None else (self.radius if isinstance(self.radius, tuple) else (self.radius,))
+        if not all(np.isfinite(float(r)) for r in values) or not any(float(r) > 0 for r in values):
+            raise ValueError("radius / half_widths must be finite and positive on at least one axis")
+        if self.op == "median":
+            if self.threshold is not None:
+                raise ValueError("threshold has no meaning for op: median")
+        elif self.threshold is None or not np.isfinite(self.threshold):
+            raise ValueError(f"op: {self.op} needs a finite threshold >= 0")
+        if self.percentile is not None:
+            if self.op != "median":
+                raise ValueError("percentile is set: op must be median")
+            if not -100.0 <= self.percentile <= 100.0:           # (a NaN too)
+                raise ValueError("percentile must be in -100 .. 100")
+        return self
 
 
 class TrackSettings(_StrictModel):

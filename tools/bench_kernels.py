@@ -88,6 +88,11 @@ def main():
                     "median of 3 calls after a warm-up), beside a device copy of one volume and the three launches of "
                     "lsr_local_max_candidates_f32 at the same half-width (up to 64) in the same run; appended to "
                     "profiles/morphology_config2.jsonl")
+    ap.add_argument("--rank", action="store_true", help="only: ms of the rank-filter kernel (csrc/rank.hip) on --rl-grid for the "
+                    "bench's bead scene: the median at half-widths (0, 1, 1), (1, 1, 1), (2, 2, 2) and (3, 3, 3), the first two "
+                    "again on the generic path (variant = 1), and remove_bright at (0, 1, 1) (HIP events, median of 3 calls after a "
+                    "warm-up), beside a device copy of one volume and grey_erosion at the same half-widths in the same run; "
+                    "appended to profiles/rank_config2.jsonl")
     ap.add_argument("--mi", action="store_true", help="only: ms per launch of the mutual-information kernels (csrc/estimate_mi.hip: "
                     "joint histogram, gradient) on --mi-grid at strides 1 and 4, 32 and 64 bins, on bench.synthetic_raw "
                     "(background-dominated) and on uniform noise (spread over all cells), beside a torch formulation "
@@ -127,6 +132,9 @@ def main():
         return
     if args.edt:
         _edt(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
+        return
+    if args.rank:
+        _rank(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
         return
     if args.morphology:
         _morphology(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
@@ -1022,6 +1030,65 @@ def _morphology(args, torch, dev, g, bench, oshape):
                             "copy_time_ratio_per_launch": ms / 3 / copy_ms})
     stamp = {"sources": _lib.kernel_source_sha16(), "device": torch.cuda.get_device_name(dev), "reps": reps, "warmups": 1}
     path = ROOT / "profiles" / "morphology_config2.jsonl"
+    with open(path, "a") as f:
+        for rec in records:
+            line = json.dumps({**rec, **stamp})
+            print(line, flush=True)
+            f.write(line + "\n")
+
+
+def _rank(args, torch, dev, g, bench, oshape):
+    """Rank filters (csrc/rank.hip) at the config-2 deskewed shape on the bench's bead scene: one launch that moves 8 algorithmic
+    bytes per voxel (one read, one write; remove_bright 12).  The median at half-widths (0, 1, 1) and (1, 1, 1) -- kernels that
+    sort the window in registers -- and at (2, 2, 2) and (3, 3, 3) -- the generic kernel, which reads the window from LDS on
+    each of the 32 sweeps of its bisection --, the first two again with variant = 1 (the generic kernel), and remove_bright at (0, 1, 1).  Beside
+    them, in the same run, the floor -- a device copy of one volume, the same 8 bytes per voxel -- and grey_erosion at the same
+    half-widths: rank 0 is the same function away from the borders, which is asserted on the interior before anything is timed."""
+    from shrimpy_amd import _lib
+
+    reps = 3
+    z, y, x = oshape
+    n = z * y * x
+    vol = bench.synthetic_raw(oshape, 1000, dev)
+    out = torch.empty_like(vol)
+    copy_ms = _median_ms(lambda: out.copy_(vol), reps, torch)
+    records = [{"kernel": "device copy of a float32 volume (torch copy_)", "grid": list(oshape), "ms": copy_ms,
+                "GBps": 8.0 * n / copy_ms / 1e6}]
+    scratch = torch.empty(_lib.call_value("lsr_grey_morph_scratch_bytes", z, y, x), dtype=torch.uint8, device=dev)
+    eroded = torch.empty_like(vol)
+
+    def rank_call(r, rank, op, threshold, variant):
+        _lib.call("lsr_rank_filter_f32", vol.data_ptr(), out.data_ptr(), z, y, x, *r, rank, op, ctypes.c_float(threshold), variant,
+                  _lib.stream_ptr(dev))
+
+    def erode(r):
+        _lib.call("lsr_grey_morph_f32", vol.data_ptr(), eroded.data_ptr(), z, y, x, *r, 0, scratch.data_ptr(), _lib.stream_ptr(dev))
+
+    for r in ((0, 1, 1), (1, 1, 1), (2, 2, 2), (3, 3, 3)):
+        window = (2 * r[0] + 1) * (2 * r[1] + 1) * (2 * r[2] + 1)
+        base = {"input": "bead scene (bench.synthetic_raw)", "grid": list(oshape), "half_widths": list(r), "window": window}
+        rank_call(r, 0, 0, 0.0, 0)
+        erode(r)
+        inner = tuple(slice(k, -k) if k else slice(None) for k in r)
+        assert torch.equal(out[inner], eroded[inner]), f"rank 0 and grey_erosion differ in the interior at {r}"
+        variants = (0, 1) if max(r) <= 1 else (0,)
+        for variant in variants:
+            ms = _median_ms(lambda: rank_call(r, window // 2, 0, 0.0, variant), reps, torch)
+            path = "registers" if variant == 0 and max(r) <= 1 else "generic"
+            records.append({**base, "kernel": f"lsr_rank_filter_f32: median ({path} path, variant = {variant})", "variant": variant,
+                            "path": path, "ms": ms, "bytes_per_voxel": 8.0, "algorithmic_GBps": 8.0 * n / ms / 1e6,
+                            "copy_time_ratio": ms / copy_ms})
+        if r == (0, 1, 1):
+            ms = _median_ms(lambda: rank_call(r, window // 2, 1, 200.0, 0), reps, torch)
+            records.append({**base, "kernel": "lsr_rank_filter_f32: remove_bright, threshold 200 (registers path, variant = 0)",
+                            "variant": 0, "path": "registers", "ms": ms, "bytes_per_voxel": 12.0,
+                            "algorithmic_GBps": 12.0 * n / ms / 1e6, "copy_time_ratio": ms / copy_ms})
+        launches = sum(1 for k in r if k)
+        ms = _median_ms(lambda: erode(r), reps, torch)
+        records.append({**base, "kernel": f"lsr_grey_morph_f32: grey_erosion ({launches} launches)", "ms": ms,
+                        "bytes_per_voxel": 8.0 * launches, "copy_time_ratio": ms / copy_ms})
+    stamp = {"sources": _lib.kernel_source_sha16(), "device": torch.cuda.get_device_name(dev), "reps": reps, "warmups": 1}
+    path = ROOT / "profiles" / "rank_config2.jsonl"
     with open(path, "a") as f:
         for rec in records:
             line = json.dumps({**rec, **stamp})
