@@ -303,9 +303,14 @@ int lsr_average_slices_f32(const float* in, int64_t Zd, int64_t Y, int64_t X, fl
 /*
  * Bright-field flat-field correction -- replaces _LabelfreePreprocessor._flat_field_BF
  * (shrimpy/preprocessing.py:385-404): pattern = median over Z per (y, x) pixel with
- * torch.quantile(0.5) semantics (exact middle elements; b - (b - a) * 0.5 between the two of an
- * even count; NaN if the column holds one), out = in / pattern * mean(pattern).
+ * torch.quantile(0.5) semantics (the exact middle elements a <= b under the order-preserving integer
+ * image of a float, -0.0 below +0.0 and +-inf ordinary values; fma(-(b - a), 0.5, b) -- the
+ * difference rounded to float32, the rest rounded once, as torch's lerp on the host -- between the two
+ * of an even count; the canonical NaN 0x7fc00000 if the column holds one; a pixel's bits depend on its
+ * own column alone), out = in / pattern * mean(pattern), the division first, each rounded to float32.
  *
+ * lsr_flatfield_tiling: {pixels per workgroup, z phases per pixel, loads in flight per thread, the
+ *   first Z that is refused} of the median kernel.
  * lsr_flatfield_pattern_f32: `pattern` (Y*X floats) and `mean_out` (one float) are device
  *   outputs; `scratch` = lsr_flatfield_scratch_bytes() bytes of device memory. Z < 65536.
  *   Reads `in` at most four times (radix select, csrc/flatfield.hip), writes nothing else.
@@ -314,6 +319,7 @@ int lsr_average_slices_f32(const float* in, int64_t Zd, int64_t Y, int64_t X, fl
  *   way into the kernel -- bit-identical to apply followed by deskew, without the corrected
  *   volume's round trip through HBM.
  */
+int lsr_flatfield_tiling(int tiling[4]);
 int lsr_flatfield_scratch_bytes(void);
 int lsr_flatfield_pattern_f32(const float* in, int64_t Z, int64_t Y, int64_t X, float* pattern,
                               float* mean_out, void* scratch, lsr_stream_t stream);

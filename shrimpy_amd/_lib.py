@@ -61,6 +61,7 @@ SIGNATURES: dict[str, list] = {
     "lsr_flatfield_pattern_u16": [ctypes.c_void_p, _i64, _i64, _i64, _c_f32p, _c_f32p, ctypes.c_void_p, _stream],
     "lsr_flatfield_apply_u16": [ctypes.c_void_p, _c_f32p, _c_f32p, _c_f32p, _i64, _i64, _i64, _stream],
     "lsr_flatfield_scratch_bytes": [],
+    "lsr_flatfield_tiling": [ctypes.POINTER(ctypes.c_int)],
     "lsr_flatfield_pattern_f32": [_c_f32p, _i64, _i64, _i64, _c_f32p, _c_f32p, ctypes.c_void_p, _stream],
     "lsr_flatfield_apply_f32": [_c_f32p, _c_f32p, _c_f32p, _c_f32p, _i64, _i64, _i64, _stream],
     "lsr_affine_f32": [_c_f32p, _i64, _i64, _i64, _c_f32p, _i64, _i64, _i64, _f64p, _f32, _int, _stream],

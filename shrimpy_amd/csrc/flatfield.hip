@@ -16,8 +16,13 @@
 // is the MAXIMUM of its bin and rank k the MINIMUM of its own, so the next pass is a min/max
 // reduction and the pixel is done.  No pass is ever added: <= 4 reads of the volume (2 for stacks
 // of integer camera counts, whose keys are 16-bit integers -- see the kernel), nothing else
-// is written but the (Y, X) pattern.  Results are the exact middle elements; the interpolation
-// between them is torch's: lerp(a, b, 0.5) = b - (b - a) * 0.5 in f32.
+// is written but the (Y, X) pattern.  Results are the exact middle elements a <= b UNDER THE KEY
+// ORDER (-0.0 below +0.0, +-inf ordinary values); the interpolation between them is the one
+// torch.quantile computes on the host: lerp(a, b, 0.5) = fma(-(b - a), 0.5, b) -- the difference
+// rounded to f32, the rest rounded ONCE.  The fused multiply-add is explicit (the library is built
+// with -ffp-contract=off); an unfused b - (b - a) * 0.5 drops a bit of (b - a) * 0.5 among the
+// denormals.  A pixel's pattern bits depend on its own column alone (tests/flatfield_ref.py
+// restates the rule, tests/flatfield_cases.py aims at every pass and edge below).
 //
 // Algorithmic HBM bytes: 4 * N_in per pass, <= 4 passes (median) + 4 * N_in + 4 * N_in (apply,
 // when it is not fused into the deskew kernel's staging, deskew.hip).
@@ -72,8 +77,12 @@ __global__ __launch_bounds__(kThreads) void flat_median_kernel(MedianArgs p) {
   // Camera stacks are integer counts below 65536 stored as f32: their keys are 16-bit integers
   // and the select needs two passes, not four.  The workgroup tries that when its first samples
   // look like counts and falls back to the float keys (from scratch) should any sample of its 128
-  // pixels turn out not to be one.
-  auto is_count = [](float v) { return v >= 0.0f && v < 65536.0f && v == truncf(v); };
+  // pixels turn out not to be one.  A count is an integer in [+0, 65536): the bits of a
+  // non-negative float order as the values do, so one unsigned compare against the bits of 65536.0f
+  // refuses the negatives, -0.0 (its integer key would come back as +0.0: the sign of a zero median
+  // would depend on the other pixels of the workgroup), +inf, the NaNs and everything >= 65536.
+  // A uint16 is a count by its type (the compiler does not see that through the compare on the bits).
+  auto is_count = [](float v) { return U16 || (__float_as_uint(v) < 0x47800000u && v == truncf(v)); };
   bool int_mode = U16 || __syncthreads_and(is_count(static_cast<float>(src[static_cast<int64_t>(min(g, Z - 1)) * p.plane])) ? 1 : 0) != 0;
 
   auto reset_state = [&]() {
@@ -208,8 +217,9 @@ __global__ __launch_bounds__(kThreads) void flat_median_kernel(MedianArgs p) {
     const float a = int_mode ? static_cast<float>(s_prefix0[tid]) : value_of(s_prefix0[tid]);
     const float b = int_mode ? static_cast<float>(s_prefix1[tid]) : value_of(s_prefix1[tid]);
     // torch.quantile(0.5): lerp(a, b, w) with w = 0.5 for an even count (the branch of
-    // at::native::lerp for |w| >= 0.5), w = 0 for an odd one
-    float med = (Z & 1) ? a : b - (b - a) * 0.5f;
+    // at::native::lerp for |w| >= 0.5: b - (b - a) * (1 - w), contracted to one fma on the host),
+    // w = 0 for an odd one
+    float med = (Z & 1) ? a : __fmaf_rn(-(b - a), 0.5f, b);
     if (s_nan[tid]) med = __uint_as_float(0x7fc00000u);  // quantile propagates NaN
     p.pattern[col0 + tid] = med;
   }
@@ -282,6 +292,17 @@ __global__ __launch_bounds__(256) void flat_apply_kernel(const float* __restrict
 
 extern "C" int lsr_flatfield_scratch_bytes(void) { return kReduceBlocks * static_cast<int>(sizeof(double)); }
 
+constexpr int64_t kFirstRefusedZ = 65536;  // the per-pixel histograms count in 16 bits
+
+extern "C" int lsr_flatfield_tiling(int tiling[4]) {
+  LSR_REQUIRE_PTR(tiling);
+  tiling[0] = kCols;
+  tiling[1] = kZGroups;
+  tiling[2] = kUnroll;
+  tiling[3] = static_cast<int>(kFirstRefusedZ);
+  return LSR_OK;
+}
+
 namespace {
 int flatfield_pattern(const char* what, const void* in, bool u16, int64_t Z, int64_t Y, int64_t X,
                       float* pattern, float* mean_out, void* scratch, lsr_stream_t stream) {
@@ -292,7 +313,7 @@ int flatfield_pattern(const char* what, const void* in, bool u16, int64_t Z, int
   LSR_REQUIRE(Z > 0 && Y > 0 && X > 0, LSR_E_SHAPE, "shape (%lld,%lld,%lld) must be positive",
               (long long)Z, (long long)Y, (long long)X);
   LSR_REQUIRE_VOLUME(Z, Y, X);
-  LSR_REQUIRE(Z < 65536, LSR_E_UNSUPPORTED, "Z = %lld: the per-pixel histograms count in 16 bits",
+  LSR_REQUIRE(Z < kFirstRefusedZ, LSR_E_UNSUPPORTED, "Z = %lld: the per-pixel histograms count in 16 bits",
               (long long)Z);
   const int64_t plane = Y * X;
   const int64_t tiles = lsr::ceil_div(plane, static_cast<int64_t>(kCols));

@@ -550,8 +550,9 @@ extern "C" int lsr_rl_dense_stats_f32_cpu(const float* y, float* x, float* ratio
 }
 
 // ---- bright-field flat-field (shrimpy/preprocessing.py:385-404): pattern = volume.quantile(0.5, dim=0), its
-// mean, out = in / pattern * mean.  The median as flatfield.hip forms it: the two middle order statistics a <= b,
-// torch's lerp b - (b - a) * 0.5 for an even count, a for an odd one, NaN if the column holds one; the mean in f64.
+// mean, out = in / pattern * mean.  The median as flatfield.hip forms it: the two middle order statistics a <= b under
+// the order of the keys (-0.0 below +0.0), torch's lerp fma(-(b - a), 0.5, b) -- one explicit fused multiply-add -- for an
+// even count, a for an odd one, the canonical NaN if the column holds one; the mean in f64.
 
 namespace {
 
@@ -567,26 +568,39 @@ int flat_pattern_cpu(const T* in, int64_t Z, int64_t Y, int64_t X, float* patter
   const int64_t plane = Y * X;
   std::atomic<bool> failed{false};
   parallel_ranges(plane, [&](int64_t first, int64_t last) {
-    std::vector<float> col(static_cast<size_t>(Z));
+    // the column as keys (the order-preserving unsigned image of a float, as flatfield.hip): selecting by the keys tells
+    // -0.0 from +0.0, which operator< on floats does not
+    auto key_of = [](float v) {
+      uint32_t u;
+      std::memcpy(&u, &v, sizeof u);
+      return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+    };
+    auto value_of = [](uint32_t k) {
+      const uint32_t u = k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu);
+      float v;
+      std::memcpy(&v, &u, sizeof v);
+      return v;
+    };
+    std::vector<uint32_t> col(static_cast<size_t>(Z));
     for (int64_t i = first; i < last; ++i) {
       bool nan = false;
       for (int64_t z = 0; z < Z; ++z) {
         const float v = static_cast<float>(in[z * plane + i]);
-        col[static_cast<size_t>(z)] = v;
+        col[static_cast<size_t>(z)] = key_of(v);
         nan |= v != v;
       }
       if (nan) {
-        pattern[i] = std::nanf("");
+        pattern[i] = value_of(0xffc00000u);  // the key of the canonical quiet NaN, bits 0x7fc00000, as the kernel writes it
         continue;
       }
       const int64_t hi = Z / 2;
       std::nth_element(col.begin(), col.begin() + hi, col.end());
-      const float b = col[static_cast<size_t>(hi)];
+      const float b = value_of(col[static_cast<size_t>(hi)]);
       if (Z & 1) {
         pattern[i] = b;
       } else {
-        const float a = *std::max_element(col.begin(), col.begin() + hi);
-        pattern[i] = b - (b - a) * 0.5f;
+        const float a = value_of(*std::max_element(col.begin(), col.begin() + hi));
+        pattern[i] = std::fmaf(-(b - a), 0.5f, b);
       }
     }
   }, failed);

@@ -6,15 +6,30 @@ The median runs as a streaming radix select (``csrc/flatfield.hip``: at most fou
 volume); the division is either its own launch or fused into the deskew kernel's staging pass
 (``deskew_with_matrix(..., flat_field=pattern)``).  Bright field only -- see the reference's note.
 CPU tensors run the native host twins (``lsr_flatfield_*_cpu``, same median rule, f64 mean).
+
+The median rule: the two middle elements ``a <= b`` of a column under the order-preserving integer image of a float (``-0.0``
+below ``+0.0``, ``+-inf`` ordinary values); ``a`` for an odd ``Z``, ``fma(-(b - a), 0.5, b)`` for an even one -- what
+``torch.quantile`` computes on the host, one rounding after the difference --; the canonical NaN for a column that holds one.
+A pixel's bits depend on its own column alone (``tests/flatfield_ref.py`` restates the rule).
 """
 
 from __future__ import annotations
+
+import ctypes
 
 from dataclasses import dataclass
 
 from . import _lib
 
-__all__ = ["FlatFieldPattern", "flat_field_pattern", "flat_field_bf", "flat_field_correction"]
+__all__ = ["FlatFieldPattern", "flat_field_pattern", "flat_field_bf", "flat_field_correction", "tiling"]
+
+
+def tiling() -> tuple[int, int, int, int]:
+    """``(pixels per workgroup, z phases per pixel, loads in flight per thread, first refused Z)`` of the median kernel
+    (``lsr_flatfield_tiling``)."""
+    out = (ctypes.c_int * 4)()
+    _lib.call("lsr_flatfield_tiling", out)
+    return tuple(out)
 
 
 @dataclass

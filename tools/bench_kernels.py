@@ -93,6 +93,13 @@ def main():
                     "again on the generic path (variant = 1), and remove_bright at (0, 1, 1) (HIP events, median of 3 calls after a "
                     "warm-up), beside a device copy of one volume and grey_erosion at the same half-widths in the same run; "
                     "appended to profiles/rank_config2.jsonl")
+    ap.add_argument("--flatfield", action="store_true", help="only: ms of the flat-field median (csrc/flatfield.hip, + mean) on the "
+                    "config-2 raw shape for its three variants -- integer counts as float32, float values, uint16 counts --, each "
+                    "timed --flatfield-repeats times (a repetition: the mean of --reps calls between HIP events after a warm-up), "
+                    "so that the spread between repetitions stands beside a before/after difference; appended with --tag to "
+                    "profiles/flatfield_pin.jsonl")
+    ap.add_argument("--flatfield-repeats", type=int, default=5)
+    ap.add_argument("--tag", default="", help="with --flatfield: what the lines are tagged with (the commit measured)")
     ap.add_argument("--mi", action="store_true", help="only: ms per launch of the mutual-information kernels (csrc/estimate_mi.hip: "
                     "joint histogram, gradient) on --mi-grid at strides 1 and 4, 32 and 64 bins, on bench.synthetic_raw "
                     "(background-dominated) and on uniform noise (spread over all cells), beside a torch formulation "
@@ -120,6 +127,9 @@ def main():
 
     if args.psf_fit:
         _psf_fit(args, torch, dev)
+        return
+    if args.flatfield:
+        _flatfield(args, torch, dev, g, bench)
         return
     if args.mi:
         _mi(args, torch, dev, g, bench, tuple(int(v) for v in args.mi_grid.split(",")))
@@ -1035,6 +1045,35 @@ def _morphology(args, torch, dev, g, bench, oshape):
             line = json.dumps({**rec, **stamp})
             print(line, flush=True)
             f.write(line + "\n")
+
+
+def _flatfield(args, torch, dev, g, bench):
+    """The three median variants of the affine-and-deskew section (same stacks, same generator), each repeated."""
+    from shrimpy_amd import _lib
+    from shrimpy_amd.flatfield import flat_field_pattern
+
+    raw_shape = bench.WORKLOADS["config2"][1]
+    counts = torch.randint(80, 600, raw_shape, device=dev, generator=g).to(torch.float32)
+    records = []
+    stamp = {"label": args.tag, "sources": _lib.kernel_source_sha16(), "device": torch.cuda.get_device_name(dev),
+             "reps": args.reps, "warmups": 1}
+
+    def measure(name, stack, passes, itemsize):
+        for rep in range(args.flatfield_repeats):
+            ms = timed(lambda: flat_field_pattern(stack), args.reps)
+            records.append({"kernel": name, "raw": list(raw_shape), "repetition": rep, "ms": ms,
+                            "passes_GBps": passes * itemsize * stack.numel() / ms / 1e6, **stamp})
+            print(json.dumps(records[-1]), flush=True)
+
+    measure("flat_median_kernel (+ mean), integer counts", counts, 2, 4.0)
+    raw16 = counts.to(torch.uint16)
+    counts += torch.rand(raw_shape, device=dev, generator=g)              # continuous values: 4 passes
+    measure("flat_median_kernel (+ mean), float values", counts, 4, 4.0)
+    del counts
+    measure("flat_median_kernel<U16> (+ mean)", raw16, 2, 2.0)
+    with open(ROOT / "profiles" / "flatfield_pin.jsonl", "a") as f:
+        for rec in records:
+            f.write(json.dumps(rec) + "\n")
 
 
 def _rank(args, torch, dev, g, bench, oshape):
