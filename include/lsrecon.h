@@ -827,8 +827,9 @@ int lsr_peak_abs_shifted_f32(const float* in, int64_t Z, int64_t Y, int64_t X, l
  *   no peak within their reach.  Every peak is appended, in no particular order, as (linear index, value) to cand_index /
  *   cand_value (`capacity` entries each, device) through *count (one device counter, zeroed by the call); the counter
  *   keeps counting past the capacity while nothing is stored there, so *count > capacity afterwards means the buffers were
- *   too small.  `scratch`: lsr_local_max_scratch_bytes(Z, Y, X, &bytes) bytes of device memory (two volumes: the separable
- *   box maximum's partial results).  Three launches, no host synchronisation.
+ *   too small.  `scratch`: lsr_local_max_scratch_bytes(Z, Y, X, &bytes) bytes of device memory (two volumes: s dilated
+ *   along x, and that along y -- the passes of lsr_grey_morph_f32; the z pass carries the test and stores no volume).  One
+ *   launch per axis with a half-width > 0 and always the z one: at most three, no host synchronisation.
  * lsr_psf_accumulate_f32: psf (pz * py * px float32, odd extents <= 129) = the mean over the contributing beads of
  *   (patch - B) / S, patches centred on the linear indices `centres` (n_beads, device), B = the float64 mean of the patch's
  *   outer shell (its six faces), S = sum(patch - B) in float64 in a fixed order; bead_stats (n_beads x {B, S}, float64,
@@ -1208,7 +1209,7 @@ int lsr_peak_abs_shifted_f32_cpu(const float* in, int64_t Z, int64_t Y, int64_t 
                                  void* scratch, lsr_stream_t stream);
 
 /* ... of the bead detection and the PSF average (csrc/peaks.hip): the same peaks (callers sort them) and the same bits of
- * bead_stats and psf; every pointer HOST memory, `scratch` unused (the twin allocates its three volumes itself) */
+ * bead_stats and psf; every pointer HOST memory, `scratch` unused (the twins allocate their two volumes themselves) */
 int lsr_box_smooth_f32_cpu(const float* in, float* out, int64_t Z, int64_t Y, int64_t X, int taps, float tap, void* scratch,
                            lsr_stream_t stream);
 int lsr_local_max_candidates_f32_cpu(const float* s, int64_t Z, int64_t Y, int64_t X, int rz, int ry, int rx,

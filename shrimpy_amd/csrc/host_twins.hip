@@ -717,29 +717,43 @@ extern "C" int lsr_rl_accel_predict_f32_cpu(const float* x1, int64_t x1_pitch, i
 }
 
 // ---- bead detection and PSF averaging (peaks.hip): the same rule, the same sums in the same order ----
+#include "morphology.hpp"
 #include "peaks.hpp"
 
 namespace {
 
-// out(i) = max of in over [i - r, i + r] within [0, L) along one line (van Herk / Gil-Werman on the -inf padded line);
-// `pad`, `g`, `h` are the worker's buffers of at least L + 4 r + 1 floats
-void line_max(const float* in, float* out, int64_t L, int64_t stride, int r, float* pad, float* g, float* h) {
-  using lsr::peaks::nmax;
-  const float ninf = -std::numeric_limits<float>::infinity();
-  const int64_t w = 2 * r + 1, total = lsr::ceil_div(L + 2 * r, w) * w;
-  for (int64_t j = 0; j < total; ++j) pad[j] = (j >= r && j < L + r) ? in[(j - r) * stride] : ninf;
-  for (int64_t b = 0; b < total; b += w) {
-    g[b] = pad[b];
-    for (int64_t t = 1; t < w; ++t) g[b + t] = nmax(g[b + t - 1], pad[b + t]);
-    h[b + w - 1] = pad[b + w - 1];
-    for (int64_t t = w - 2; t >= 0; --t) h[b + t] = nmax(h[b + t + 1], pad[b + t]);
-  }
-  for (int64_t i = 0; i < L; ++i) out[i * stride] = nmax(h[i], g[i + w - 1]);
+// One pass of the morphology's walk (morphology.hpp) over the workers: tiles of kColumns lines per step, a strip per worker
+// range, sink_of(rank) the range's sink.  Returns the number of ranges.  The grey morphology's twin below runs its passes here
+// as well.
+template <typename SinkOf>
+int walk_pass(const float* src, const lsr::morph::Lines& lines, int r, bool least, std::atomic<bool>& failed, SinkOf&& sink_of) {
+  namespace mo = lsr::morph;
+  const int64_t tiles_per_slab = lsr::ceil_div(lines.columns, mo::kColumns);
+  return lsr::parallel_ranges_indexed(lines.outer * tiles_per_slab, [&](int rank, int64_t first, int64_t last) {
+    std::vector<uint32_t> strip(static_cast<size_t>(2 * r + 1) * mo::kColumns);
+    const auto sink = sink_of(rank);
+    for (int64_t tile = first; tile < last; ++tile) {
+      const int64_t slab = tile / tiles_per_slab, c0 = (tile - slab * tiles_per_slab) * mo::kColumns;
+      const int lanes = static_cast<int>(std::min<int64_t>(mo::kColumns, lines.columns - c0));
+      mo::walk_host(src, slab * lines.ostep + c0 * lines.cstep, lanes, lines.cstep, lines.L, lines.step, r, least, strip.data(),
+                    sink);
+    }
+  }, failed);
 }
 
 struct Candidate {
   long long index;
   float value;
+};
+
+// the sink of the twin's z walk: the test, and the append to the worker's own list
+struct PeakSink {
+  const lsr::peaks::PeakTest* test;
+  std::vector<Candidate>* mine;
+  bool operator()(int64_t lin, float m) const { return test->maximum(lin, m); }
+  void late(int64_t lin) const {
+    if (test->first(lin)) mine->push_back(Candidate{static_cast<long long>(lin), test->s[lin]});
+  }
 };
 
 }  // namespace
@@ -781,46 +795,25 @@ extern "C" int lsr_local_max_candidates_f32_cpu(const float* s, int64_t Z, int64
                                                 lsr_stream_t) {
   if (int rc = lsr::peaks::check_local_max(s, Z, Y, X, rz, ry, rx, threshold, cand_index, cand_value, capacity, count))
     return rc;
-  const int64_t n = Z * Y * X, plane = Y * X;
+  namespace mo = lsr::morph;
+  const int64_t n = Z * Y * X;
   std::atomic<bool> failed{false};
-  std::vector<float> a, b, m;
+  std::vector<float> va, vb;                     // A = s dilated along x, B = A dilated along y; an axis without a window: no pass
   try {
-    a.resize(static_cast<size_t>(n));
-    b.resize(static_cast<size_t>(n));
-    m.resize(static_cast<size_t>(n));
+    if (rx > 0) va.resize(static_cast<size_t>(n));
+    if (ry > 0) vb.resize(static_cast<size_t>(n));
   } catch (const std::bad_alloc&) {
-    return lsr::fail(LSR_E_ARG, "lsr_local_max_candidates_f32_cpu: out of memory for three volumes of %lld voxels", (long long)n);
+    return lsr::fail(LSR_E_ARG, "lsr_local_max_candidates_f32_cpu: out of memory for two volumes of %lld voxels", (long long)n);
   }
-  const int64_t longest = std::max(Z, std::max(Y, X)) + 4 * lsr::peaks::kMaxHalfWidth + 1;
-  auto pass = [&](const float* in, float* out, int64_t lines, int64_t L, int64_t stride, int r, auto&& base_of) {
-    parallel_ranges(lines, [&](int64_t first, int64_t last) {
-      std::vector<float> buf(static_cast<size_t>(3 * longest));
-      for (int64_t ln = first; ln < last; ++ln) {
-        const int64_t base = base_of(ln);
-        line_max(in + base, out + base, L, stride, r, buf.data(), buf.data() + longest, buf.data() + 2 * longest);
-      }
-    }, failed);
-  };
-  pass(s, a.data(), Z * Y, X, 1, rx, [&](int64_t ln) { return ln * X; });
-  pass(a.data(), b.data(), Z * X, Y, X, ry, [&](int64_t ln) { return (ln / X) * plane + ln % X; });
-  pass(b.data(), m.data(), plane, Z, plane, rz, [&](int64_t ln) { return ln; });
+  const float* a = rx > 0 ? va.data() : s;
+  const float* b = ry > 0 ? vb.data() : a;
+  const mo::StoreSink to_a{va.data(), nullptr, mo::kPlain}, to_b{vb.data(), nullptr, mo::kPlain};
+  if (rx > 0) walk_pass(s, mo::lines_of(2, Z, Y, X), rx, false, failed, [&](int) { return to_a; });
+  if (ry > 0) walk_pass(a, mo::lines_of(1, Z, Y, X), ry, false, failed, [&](int) { return to_b; });
+  // the z walk carries the test (at rz == 0 too: w = 1, every voxel of B its own maximum); M is never stored
+  const lsr::peaks::PeakTest test{s, a, b, X, Y * X, rz, ry, rx, threshold};
   std::vector<std::vector<Candidate>> found(1024);
-  const int used = lsr::parallel_ranges_indexed(Z * Y, [&](int rank, int64_t first, int64_t last) {
-    std::vector<Candidate>& mine = found[rank];
-    for (int64_t row = first; row < last; ++row) {
-      const int64_t z = row / Y, y = row - z * Y;
-      for (int64_t x = 0; x < X; ++x) {
-        const int64_t lin = row * X + x;
-        const float sv = s[lin];
-        if (!(sv == m[lin] && sv >= threshold)) continue;
-        bool tie = false;
-        for (int64_t d = std::min<int64_t>(rx, x); d > 0 && !tie; --d) tie = s[lin - d] >= sv;
-        for (int64_t d = std::min<int64_t>(ry, y); d > 0 && !tie; --d) tie = a[lin - d * X] >= sv;
-        for (int64_t d = std::min<int64_t>(rz, z); d > 0 && !tie; --d) tie = b[lin - d * plane] >= sv;
-        if (!tie) mine.push_back(Candidate{static_cast<long long>(lin), sv});
-      }
-    }
-  }, failed);
+  const int used = walk_pass(b, mo::lines_of(0, Z, Y, X), rz, false, failed, [&](int rank) { return PeakSink{&test, &found[rank]}; });
   LSR_REQUIRE(!failed.load(), LSR_E_ARG, "lsr_local_max_candidates_f32_cpu: out of memory in a worker");
   unsigned long long total = 0;
   for (int k = 0; k < used; ++k)
@@ -1557,8 +1550,8 @@ extern "C" int lsr_label_overlap_i32_cpu(const int32_t* a, const int32_t* b, int
   return LSR_OK;
 }
 
-// ---- grey morphology (morphology.hip): the same plan of passes and the same walk (morphology.hpp), a tile of columns per step ----
-#include "morphology.hpp"
+// ---- grey morphology (morphology.hip): the same plan of passes and the same walk (morphology.hpp), a tile of columns per step
+// (walk_pass above) ----
 
 extern "C" int lsr_grey_morph_f32_cpu(const float* in, float* out, int64_t Z, int64_t Y, int64_t X, int rz, int ry, int rx, int op,
                                       void* scratch, lsr_stream_t) {
@@ -1576,21 +1569,10 @@ extern "C" int lsr_grey_morph_f32_cpu(const float* in, float* out, int64_t Z, in
   std::atomic<bool> failed{false};
   for (int k = 0; k < n; ++k) {
     const mo::Pass ps = passes[k];
-    const float* src = mo::pass_source(k, in, work, voxels);
-    float* dst = mo::pass_target(k, n, out, work, voxels);
     const int f = k == n - 1 ? fuse : static_cast<int>(mo::kPlain);
-    const float* orig = f != mo::kPlain ? in : nullptr;
-    const mo::Lines lines = mo::lines_of(ps.axis, Z, Y, X);
-    const int64_t tiles_per_slab = lsr::ceil_div(lines.columns, mo::kColumns);
-    lsr::parallel_ranges(lines.outer * tiles_per_slab, [&](int64_t first, int64_t last) {
-      std::vector<uint32_t> strip(static_cast<size_t>(2 * ps.r + 1) * mo::kColumns);
-      for (int64_t tile = first; tile < last; ++tile) {
-        const int64_t slab = tile / tiles_per_slab, c0 = (tile - slab * tiles_per_slab) * mo::kColumns;
-        const int lanes = static_cast<int>(std::min<int64_t>(mo::kColumns, lines.columns - c0));
-        mo::walk_host(src, dst, orig, slab * lines.ostep + c0 * lines.cstep, lanes, lines.cstep, lines.L, lines.step, ps.r,
-                      ps.least, f, strip.data());
-      }
-    }, failed);
+    const mo::StoreSink sink{mo::pass_target(k, n, out, work, voxels), f != mo::kPlain ? in : nullptr, f};
+    walk_pass(mo::pass_source(k, in, work, voxels), mo::lines_of(ps.axis, Z, Y, X), ps.r, ps.least, failed,
+              [&](int) { return sink; });
     if (failed.load()) return lsr::fail(LSR_E_ARG, "lsr_grey_morph_f32_cpu: out of memory for the block strip");
   }
   return LSR_OK;

@@ -3,21 +3,23 @@
 // scipy.ndimage element for element (tests/morphology_ref.py).
 //
 // One launch per axis with a half-width > 0 (an opening: up to six), nothing between workgroups, no atomics; every launch
-// reads each voxel of its source once and writes each voxel of its target once.
+// reads each voxel of its source once and writes each voxel of its target once.  The bead detection (peaks.hip) runs its box
+// maximum through the same launches (launch_pass, launch_strided of morphology.hpp), its z pass with a sink of its own.
 //   x       morph_rows_kernel: a workgroup walks a row in equal segments of at most kRowSegment outputs.  The codes of the
 //           segment and of the window's reach on both sides sit in LDS; the 2r codes the next segment shares with this one are
 //           MOVED inside LDS, not read again.  Window maxima by doubling spans (1, 2, 4, ... <= w): log2 w LDS sweeps per
 //           voxel.  The values of the segment to come -- of this row or of the workgroup's next one -- are read into registers
 //           before the sweeps begin, so the reads of global memory run under the LDS work.
-//   y, z    morph_strided_kernel: one wavefront per workgroup owns kColumns = 64 neighbouring columns -- every row it touches
-//           is one 256-byte access -- and walks them block by block (blocks of w positions) over the whole line.  LDS holds w
+//   y, z    morph_strided_kernel (morphology.hpp, a template of the sink): one wavefront per workgroup owns kColumns = 64
+//           neighbouring columns -- every row it touches is one 256-byte access -- and walks them block by block (blocks of w positions) over the whole line.  LDS holds w
 //           codes per column: the suffix maxima of the previous block, overwritten in place by the current block's codes as
 //           the forward sweep consumes them (slot t is free once h(t) has been used), then turned into its suffix maxima by a
 //           backward sweep.  The prefix maximum runs in a register.  No barrier: a lane touches its own column only.  The
 //           line is read as one stream, 8, 16 or 32 rows ahead of the walk (the wider the window, the fewer wavefronts its
 //           strip leaves on a compute unit, the more each has in flight).
 //           w * 256 bytes of LDS: 2.8 KB at r = 5, 25.9 KB at r = 50, 131.3 KB at the cap r = 256.
-// The top-hats' subtraction is fused into the last pass (it reads the caller's volume at the voxel it writes).
+// What a pass does with a window maximum is its sink: here StoreSink, which also fuses the top-hats' subtraction into the last
+// pass (it reads the caller's volume at the voxel it writes).
 
 #include <algorithm>
 
@@ -31,9 +33,7 @@ using mo::encode;
 using mo::umax;
 
 constexpr int kRowBuf = mo::kRowSegment + 2 * mo::kMaxHalfWidth;
-constexpr int64_t kMaxBlocks = int64_t(1) << 20;
 constexpr int64_t kMaxRowBlocks = 256 * 16;      // x pass: workgroups at most (they stride over the rows, reading ahead)
-constexpr int kNarrow = 12;                      // half-widths up to here: 8 rows ahead per lane (registers, not LDS, limit the waves)
 
 constexpr int kRowRegs = (kRowBuf + mo::kRowThreads - 1) / mo::kRowThreads;   // values of one segment per thread
 
@@ -54,9 +54,9 @@ __device__ __forceinline__ RowItem row_item(int64_t row, int sgi, int seg, int64
   return it;
 }
 
-__global__ __launch_bounds__(mo::kRowThreads) void morph_rows_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                                                      const float* __restrict__ orig, int64_t rows, int64_t X,
-                                                                      int r, int least_i, int fuse, int seg, int nsegs) {
+__global__ __launch_bounds__(mo::kRowThreads) void morph_rows_kernel(const float* __restrict__ in, mo::StoreSink sink,
+                                                                      int64_t rows, int64_t X, int r, int least_i, int seg,
+                                                                      int nsegs) {
   __shared__ uint32_t raw[kRowBuf], ping[kRowBuf], pong[kRowBuf];
   const bool least = least_i != 0;
   const int tid = threadIdx.x, w = 2 * r + 1;
@@ -102,10 +102,7 @@ __global__ __launch_bounds__(mo::kRowThreads) void morph_rows_kernel(const float
       nxt = nxt == ping ? pong : ping;
     }
     const int64_t at = row * X + it.x0;
-    for (int t = tid; t < it.len; t += mo::kRowThreads) {
-      const float m = decode(umax(cur[t], cur[t + w - span]), least);
-      out[at + t] = mo::fused(m, fuse != mo::kPlain ? orig[at + t] : 0.0f, fuse);
-    }
+    for (int t = tid; t < it.len; t += mo::kRowThreads) sink(at + t, decode(umax(cur[t], cur[t + w - span]), least));
     if (next_sgi != 0) {                         // the 2r codes the next segment starts with (len = seg >= 2r: no overlap)
       for (int i = tid; i < 2 * r; i += mo::kRowThreads) raw[i] = raw[it.len + i];
     }
@@ -113,66 +110,6 @@ __global__ __launch_bounds__(mo::kRowThreads) void morph_rows_kernel(const float
     if (!more) break;
     row = next_row;
     sgi = next_sgi;
-  }
-}
-
-template <int U>
-__global__ __launch_bounds__(mo::kColumns) void morph_strided_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                                                      const float* __restrict__ orig, mo::Lines p, int r,
-                                                                      int least_i, int fuse) {
-  extern __shared__ uint32_t strip[];            // [w][kColumns]
-  const bool least = least_i != 0;
-  const int lane = threadIdx.x, w = 2 * r + 1;
-  const int64_t tiles_per_slab = (p.columns + mo::kColumns - 1) / mo::kColumns, tiles = p.outer * tiles_per_slab;
-  const int64_t blocks = (p.L - 1 + r) / w + 1;
-  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    const int64_t slab = tile / tiles_per_slab, col = (tile - slab * tiles_per_slab) * mo::kColumns + lane;
-    if (col >= p.columns) continue;              // (no barrier anywhere below)
-    const int64_t base = slab * p.ostep + col * p.cstep;
-    for (int t = 0; t < w; ++t) strip[t * mo::kColumns + lane] = mo::kNoCode;
-    // The line as one stream of positions j = 0 .. blocks * w, U at a time; the loads of the next U are issued before
-    // this U is walked, so a lane has U .. 2U rows in flight whatever w is.
-    const int64_t total = blocks * w;
-    float ahead[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) ahead[u] = u < p.L ? in[base + u * p.step] : 0.0f;
-    uint32_t g = mo::kNoCode;
-    int t = 0;
-    for (int64_t j0 = 0; j0 < total; j0 += U) {
-      uint32_t c[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) c[u] = j0 + u < p.L ? encode(ahead[u], least) : mo::kNoCode;
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int64_t j = j0 + U + u;
-        ahead[u] = j < p.L ? in[base + j * p.step] : 0.0f;
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int64_t j = j0 + u;
-        if (j < total) {
-          g = umax(g, c[u]);
-          const uint32_t m = t < w - 1 ? umax(strip[(t + 1) * mo::kColumns + lane], g) : g;
-          strip[t * mo::kColumns + lane] = c[u];
-          const int64_t i = j - r;
-          if (i >= 0 && i < p.L) {
-            const int64_t at = base + i * p.step;
-            out[at] = mo::fused(decode(m, least), fuse != mo::kPlain ? orig[at] : 0.0f, fuse);
-          }
-          if (++t == w) {                          // the block is complete: its codes become its suffix maxima
-            t = 0;
-            g = mo::kNoCode;
-            if (j + 1 < total) {
-              uint32_t run = mo::kNoCode;
-              for (int s = w - 1; s >= 0; --s) {
-                run = umax(run, strip[s * mo::kColumns + lane]);
-                strip[s * mo::kColumns + lane] = run;
-              }
-            }
-          }
-        }
-      }
-    }
   }
 }
 
@@ -186,9 +123,18 @@ __global__ __launch_bounds__(256) void morph_pointwise_kernel(const float* __res
   }
 }
 
-std::atomic<uint64_t> g_lds_allowed{0};
-
 }  // namespace
+
+int mo::launch_pass(const float* src, const mo::StoreSink& sink, int64_t Z, int64_t Y, int64_t X, const mo::Pass& ps,
+                    const char* who, hipStream_t st) {
+  if (ps.axis != 2) return mo::launch_strided(src, mo::lines_of(ps.axis, Z, Y, X), ps.r, ps.least, sink, who, st);
+  // segments of equal length (a multiple of the wavefront), at most kRowSegment outputs each
+  const int64_t want = lsr::ceil_div(X, mo::kRowSegment);
+  const int seg = static_cast<int>(lsr::ceil_div(lsr::ceil_div(X, want), lsr::kWave) * lsr::kWave);
+  hipLaunchKernelGGL(morph_rows_kernel, dim3(static_cast<unsigned>(std::min(Z * Y, kMaxRowBlocks))), dim3(mo::kRowThreads), 0, st,
+                     src, sink, Z * Y, X, ps.r, ps.least ? 1 : 0, seg, static_cast<int>(lsr::ceil_div(X, seg)));
+  return LSR_OK;
+}
 
 extern "C" int lsr_grey_morph_tiling(int tiling[4]) {
   LSR_REQUIRE_PTR(tiling);
@@ -216,41 +162,15 @@ extern "C" int lsr_grey_morph_f32(const float* in, float* out, int64_t Z, int64_
   const int fuse = mo::fuse_of(op);
   if (n == 0) {
     const int64_t want = lsr::ceil_div(voxels, 256);
-    hipLaunchKernelGGL(morph_pointwise_kernel, dim3(static_cast<unsigned>(std::min(want, kMaxBlocks))), dim3(256), 0, st, in, out,
+    hipLaunchKernelGGL(morph_pointwise_kernel, dim3(static_cast<unsigned>(std::min(want, mo::kMaxBlocks))), dim3(256), 0, st, in, out,
                        voxels, fuse);
     return lsr::launch_status("lsr_grey_morph_f32");
   }
-  constexpr int kMaxLds = (2 * mo::kMaxHalfWidth + 1) * mo::kColumns * static_cast<int>(sizeof(uint32_t));
   float* work = static_cast<float*>(scratch);
   for (int k = 0; k < n; ++k) {
-    const mo::Pass& ps = passes[k];
-    const float* src = mo::pass_source(k, in, work, voxels);
-    float* dst = mo::pass_target(k, n, out, work, voxels);
     const int f = k == n - 1 ? fuse : static_cast<int>(mo::kPlain);
-    const float* orig = f != mo::kPlain ? in : nullptr;
-    if (ps.axis == 2) {
-      // segments of equal length (a multiple of the wavefront), at most kRowSegment outputs each
-      const int64_t want = lsr::ceil_div(X, mo::kRowSegment);
-      const int seg = static_cast<int>(lsr::ceil_div(lsr::ceil_div(X, want), lsr::kWave) * lsr::kWave);
-      hipLaunchKernelGGL(morph_rows_kernel, dim3(static_cast<unsigned>(std::min(Z * Y, kMaxRowBlocks))), dim3(mo::kRowThreads), 0, st,
-                         src, dst, orig, Z * Y, X, ps.r, ps.least ? 1 : 0, f, seg, static_cast<int>(lsr::ceil_div(X, seg)));
-    } else {
-      const mo::Lines lines = mo::lines_of(ps.axis, Z, Y, X);
-      const int64_t tiles = lines.outer * lsr::ceil_div(lines.columns, mo::kColumns);
-      const size_t lds = sizeof(uint32_t) * (2 * ps.r + 1) * mo::kColumns;
-      const dim3 grid(static_cast<unsigned>(std::min(tiles, kMaxBlocks)));
-      // rows in flight per lane: the wider the window, the fewer wavefronts its LDS strip leaves on a compute unit
-      if (ps.r <= kNarrow) {
-        hipLaunchKernelGGL(morph_strided_kernel<8>, grid, dim3(mo::kColumns), lds, st, src, dst, orig, lines, ps.r, ps.least ? 1 : 0, f);
-      } else if (lds <= 64 * 1024) {
-        hipLaunchKernelGGL(morph_strided_kernel<16>, grid, dim3(mo::kColumns), lds, st, src, dst, orig, lines, ps.r, ps.least ? 1 : 0, f);
-      } else {
-        if (int rc = lsr::allow_dynamic_lds(reinterpret_cast<const void*>(morph_strided_kernel<32>), kMaxLds, g_lds_allowed,
-                                            "lsr_grey_morph_f32"))
-          return rc;
-        hipLaunchKernelGGL(morph_strided_kernel<32>, grid, dim3(mo::kColumns), lds, st, src, dst, orig, lines, ps.r, ps.least ? 1 : 0, f);
-      }
-    }
+    const mo::StoreSink sink{mo::pass_target(k, n, out, work, voxels), f != mo::kPlain ? in : nullptr, f};
+    if (int rc = mo::launch_pass(mo::pass_source(k, in, work, voxels), sink, Z, Y, X, passes[k], "lsr_grey_morph_f32", st)) return rc;
   }
   return lsr::launch_status("lsr_grey_morph_f32");
 }

@@ -1,5 +1,6 @@
 // What the grey-morphology kernels (morphology.hip) and their host twin (host_twins.hip) share: the rule, the entry check, the
-// order, the plan of passes and the walk along a line -- ONE definition, so that the two sides choose the same element.
+// order, the plan of passes and the walk along a line -- ONE definition, so that the two sides choose the same element.  The
+// bead detection (peaks.hip and its twin) runs the same passes: its box maximum is a dilation, and its test is the walk's sink.
 //
 // Rule.  A flat box of half-widths (rz, ry, rx), window 2r + 1 per axis, over a contiguous (Z, Y, X) float32 volume v.
 //   erode(v)(p)   the least    v(q) over the in-volume q of the box around p
@@ -7,7 +8,7 @@
 //   Voxels outside the volume do not compete (for centred odd boxes that is scipy.ndimage's default `reflect` border); a
 //   half-width may exceed the axis.  Values compare by label::float_key (-0.0 below +0.0, +-inf ordinary values) and the
 //   result is the bit pattern of the chosen element: no order of evaluation can change it.  A window that holds a NaN gives
-//   the canonical quiet NaN 0x7fc00000, for erosion and dilation alike (the rule of peaks::nmax).
+//   the canonical quiet NaN 0x7fc00000, for erosion and dilation alike: such a window has no least and no greatest element.
 //   open = dilate(erode), close = erode(dilate); white top-hat = v - open(v), black top-hat = close(v) - v: one IEEE float32
 //   subtraction per voxel (a NaN it produces may carry any payload).
 //   An axis with half-width 0 gets no pass; with all three at 0, erode .. close copy v and the top-hats are v - v.
@@ -18,7 +19,11 @@
 // maximum of a code (encode below): the float's key for a maximum, its complement for a minimum, NaN the greatest code and 0
 // "does not compete".  A pass is a van Herk / Gil-Werman walk: the line is cut into blocks of w = 2r + 1; with h the suffix
 // maxima of the previous block and g the running prefix maximum of the current one, out(j - r) = max(h(t + 1), g(t)) at
-// offset t of the block that holds j.  About three comparisons per voxel at any w.
+// offset t of the block that holds j.  About three comparisons per voxel at any w.  What is done with out(i) is the walk's
+// SINK, sink(at, m) with `at` the voxel's linear index and m the decoded element: StoreSink below writes it (minus or from the
+// caller's volume for the top-hats), the bead detection's (peaks.hpp) tests it against the smoothed volume and never stores it.
+// A sink that answers true is handed the voxel again, sink.late(at): its rare and long path, which the kernel keeps out of its
+// unrolled steps.
 #pragma once
 
 #include "common.hpp"
@@ -59,6 +64,17 @@ __host__ __device__ inline uint32_t umax(uint32_t a, uint32_t b) { return a > b 
 __host__ __device__ inline float fused(float m, float orig, int fuse) {
   return fuse == kInMinus ? orig - m : (fuse == kMinusIn ? m - orig : m);
 }
+
+struct StoreSink {
+  float* out;
+  const float* orig;        // read at the voxel written, unless fuse == kPlain
+  int fuse;
+  __host__ __device__ bool operator()(int64_t at, float m) const {
+    out[at] = fused(m, fuse != kPlain ? orig[at] : 0.0f, fuse);
+    return false;
+  }
+  __host__ __device__ void late(int64_t) const {}
+};
 
 inline int check_morph(const float* in, const float* out, int64_t Z, int64_t Y, int64_t X, int rz, int ry, int rx, int op,
                        const void* scratch) {
@@ -118,10 +134,11 @@ inline float* pass_target(int k, int n, float* out, float* scratch, int64_t voxe
 }
 
 // The walk of `lanes` (<= kColumns) neighbouring lines at once, as a wavefront takes it: strip[t * kColumns + lane] holds the
-// suffix maxima of the previous block.  The host twin runs exactly this; the kernel runs it with a lane per thread and the
-// loads of a block issued ahead of their use (morphology.hip).
-inline void walk_host(const float* in, float* out, const float* orig, int64_t base, int lanes, int64_t cstep, int64_t L,
-                      int64_t step, int r, bool least, int fuse, uint32_t* strip) {
+// suffix maxima of the previous block.  The host twins run exactly this; morph_strided_kernel below runs it with a lane per
+// thread and the loads of a block issued ahead of their use.
+template <typename Sink>
+inline void walk_host(const float* in, int64_t base, int lanes, int64_t cstep, int64_t L, int64_t step, int r, bool least,
+                      uint32_t* strip, const Sink& sink) {
   const int w = 2 * r + 1;
   for (int64_t i = 0; i < int64_t(w) * kColumns; ++i) strip[i] = kNoCode;
   const int64_t blocks = (L - 1 + r) / w + 1;
@@ -136,7 +153,7 @@ inline void walk_host(const float* in, float* out, const float* orig, int64_t ba
         g[lane] = umax(g[lane], c);
         const uint32_t m = t < w - 1 ? umax(strip[(t + 1) * kColumns + lane], g[lane]) : g[lane];
         strip[t * kColumns + lane] = c;
-        if (i >= 0 && i < L) out[at + i * step] = fused(decode(m, least), orig != nullptr ? orig[at + i * step] : 0.0f, fuse);
+        if (i >= 0 && i < L && sink(at + i * step, decode(m, least))) sink.late(at + i * step);
       }
     }
     for (int lane = 0; lane < lanes; ++lane) {
@@ -148,6 +165,95 @@ inline void walk_host(const float* in, float* out, const float* orig, int64_t ba
     }
   }
 }
+
+// y, z (and any axis but x) on the device: one wavefront per workgroup owns kColumns neighbouring columns and walks them over
+// the whole line; U rows are read ahead of the walk.  See morphology.hip.
+template <int U, typename Sink>
+__global__ __launch_bounds__(kColumns) void morph_strided_kernel(const float* __restrict__ in, Lines p, int r, int least_i,
+                                                                  Sink sink) {
+  extern __shared__ uint32_t strip[];            // [w][kColumns]
+  const bool least = least_i != 0;
+  const int lane = threadIdx.x, w = 2 * r + 1;
+  const int64_t tiles_per_slab = (p.columns + kColumns - 1) / kColumns, tiles = p.outer * tiles_per_slab;
+  const int64_t blocks = (p.L - 1 + r) / w + 1;
+  for (int64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const int64_t slab = tile / tiles_per_slab, col = (tile - slab * tiles_per_slab) * kColumns + lane;
+    if (col >= p.columns) continue;              // (no barrier anywhere below)
+    const int64_t base = slab * p.ostep + col * p.cstep;
+    for (int t = 0; t < w; ++t) strip[t * kColumns + lane] = kNoCode;
+    // The line as one stream of positions j = 0 .. blocks * w, U at a time; the loads of the next U are issued before
+    // this U is walked, so a lane has U .. 2U rows in flight whatever w is.
+    const int64_t total = blocks * w;
+    float ahead[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) ahead[u] = u < p.L ? in[base + u * p.step] : 0.0f;
+    uint32_t g = kNoCode;
+    int t = 0;
+    for (int64_t j0 = 0; j0 < total; j0 += U) {
+      uint32_t c[U];
+      unsigned late = 0;                           // bit u: the sink wants the voxel of step u again, after the U steps
+#pragma unroll
+      for (int u = 0; u < U; ++u) c[u] = j0 + u < p.L ? encode(ahead[u], least) : kNoCode;
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t j = j0 + U + u;
+        ahead[u] = j < p.L ? in[base + j * p.step] : 0.0f;
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t j = j0 + u;
+        if (j < total) {
+          g = umax(g, c[u]);
+          const uint32_t m = t < w - 1 ? umax(strip[(t + 1) * kColumns + lane], g) : g;
+          strip[t * kColumns + lane] = c[u];
+          const int64_t i = j - r;
+          if (i >= 0 && i < p.L && sink(base + i * p.step, decode(m, least))) late |= 1u << u;
+          if (++t == w) {                          // the block is complete: its codes become its suffix maxima
+            t = 0;
+            g = kNoCode;
+            if (j + 1 < total) {
+              uint32_t run = kNoCode;
+              for (int s = w - 1; s >= 0; --s) {
+                run = umax(run, strip[s * kColumns + lane]);
+                strip[s * kColumns + lane] = run;
+              }
+            }
+          }
+        }
+      }
+      for (; late != 0; late &= late - 1) sink.late(base + (j0 + __ffs(late) - 1 - r) * p.step);
+    }
+  }
+}
+
+// Launches the walk over `lines` on `st`, sink by sink.  Rows in flight per lane: the wider the window, the fewer wavefronts
+// its LDS strip (w * kColumns codes) leaves on a compute unit, the more each has in flight; up to kNarrow registers, not LDS,
+// limit the waves.
+constexpr int kNarrow = 12;
+constexpr int64_t kMaxBlocks = int64_t(1) << 20;
+template <typename Sink>
+inline int launch_strided(const float* src, const Lines& lines, int r, bool least, const Sink& sink, const char* who,
+                          hipStream_t st) {
+  constexpr int kMaxLds = (2 * kMaxHalfWidth + 1) * kColumns * static_cast<int>(sizeof(uint32_t));
+  static std::atomic<uint64_t> lds_allowed{0};   // (one per sink: one per kernel)
+  const int64_t tiles = lines.outer * ceil_div(lines.columns, kColumns);
+  const size_t lds = sizeof(uint32_t) * (2 * r + 1) * kColumns;
+  const dim3 grid(static_cast<unsigned>(tiles < kMaxBlocks ? tiles : kMaxBlocks));
+  if (r <= kNarrow) {
+    hipLaunchKernelGGL((morph_strided_kernel<8, Sink>), grid, dim3(kColumns), lds, st, src, lines, r, least ? 1 : 0, sink);
+  } else if (lds <= 64 * 1024) {
+    hipLaunchKernelGGL((morph_strided_kernel<16, Sink>), grid, dim3(kColumns), lds, st, src, lines, r, least ? 1 : 0, sink);
+  } else {
+    if (int rc = allow_dynamic_lds(reinterpret_cast<const void*>(morph_strided_kernel<32, Sink>), kMaxLds, lds_allowed, who))
+      return rc;
+    hipLaunchKernelGGL((morph_strided_kernel<32, Sink>), grid, dim3(kColumns), lds, st, src, lines, r, least ? 1 : 0, sink);
+  }
+  return LSR_OK;
+}
+
+// One pass of lsr_grey_morph_f32 on `st` (morphology.hip): the x pass by rows, any other through launch_strided<StoreSink>.
+int launch_pass(const float* src, const StoreSink& sink, int64_t Z, int64_t Y, int64_t X, const Pass& ps, const char* who,
+                hipStream_t st);
 
 }  // namespace morph
 }  // namespace lsr

@@ -7,16 +7,17 @@
 // with a smaller linear index (of tied maxima in reach of each other the first in C order wins).  A NaN compares false
 // with everything: it is never a peak, and neither is a voxel with a NaN in its window.
 //
-// The box maximum is separable -- three passes, one per axis, each a van Herk / Gil-Werman running maximum (about three
-// comparisons per voxel at ANY window width; the (2r+1)^3 gather of the definition is 10^5..10^6 reads per voxel at the
+// The box maximum is separable, and it is the grey dilation of morphology.hpp: the same passes, kernels and launches (about
+// three comparisons per voxel at ANY window width; the (2r+1)^3 gather of the definition is 10^5..10^6 reads per voxel at the
 // reference's min_distance of 20..50):
-//     A = max of s over the x window      rows staged in LDS, window maxima by doubling spans (1, 2, 4, ... <= w)
-//     B = max of A over the y window      one thread per (column, block of w = 2r + 1 rows): the suffix maxima h of its
-//     M = max of B over the z window        block go into a private LDS strip, the prefix maxima g of the next block run
-//                                           in a register, out(i) = max(h(i), g(i + w - 1)); no barrier, rows of 64
-//                                           consecutive floats per wave, every input read twice (once per side)
-// Voxels outside the volume do not compete (-inf).  The z pass is fused with the test: M is never written; a voxel with
-// s == M and s >= threshold (rare) then checks the tie rule along the three half-windows BELOW it in C order,
+//     A = s dilated along x      morph::launch_pass: the row kernel
+//     B = A dilated along y      morph::launch_pass: the strided walk with the plain store
+//     M = B dilated along z      the strided walk with the test below as its sink: M is never written
+// An axis with half-width 0 gets no launch (A is s, B is A); the z walk always runs -- at w = 1 it hands every voxel of B to
+// the sink -- because it carries the test.  Voxels outside the volume do not compete.  The passes compare codes, not floats:
+// A, B and M may hold +0.0 where a -0.0 was the first of the two in the window, and the canonical NaN for a window with any
+// NaN; the test only ever COMPARES them with s, so neither shows.  A voxel with s == M and s >= threshold (rare) then checks
+// the tie rule along the three half-windows BELOW it in C order (peaks::PeakTest),
 //     s(z, y, x') x' in [x - rx, x)      A(z, y', x) y' in [y - ry, y)      B(z', y, x) z' in [z - rz, z)
 // -- together exactly the window's voxels of smaller linear index -- and appends (linear index, value) to the caller's
 // buffer through ONE integer atomic counter.  The counter keeps counting past the capacity (nothing is stored there), so
@@ -27,15 +28,10 @@
 // outer shell, S = sum(patch - B).  Then one thread per PSF voxel adds (v - B) / S over the beads with S > 0 in list
 // order in float64 and stores the mean as float32: the same bits on every run, and the host twin's.
 
+#include "morphology.hpp"
 #include "peaks.hpp"
 
 namespace {
-
-using lsr::peaks::nmax;
-constexpr float kNegInf = -__builtin_inff();
-constexpr int kRowThreads = 256;
-constexpr int kRowSeg = 1024;                                      // outputs per staged row segment
-constexpr int kRowBuf = kRowSeg + 2 * lsr::peaks::kMaxHalfWidth;   // + the window's reach on both sides
 
 // ---- box smoothing: one axis per launch, float64 between the passes ----
 // out(i) = sum_k tap * in(mirror(i - r + k)) along one axis, accumulated in float64 in tap order (the host twin's order:
@@ -54,120 +50,23 @@ __global__ __launch_bounds__(256) void box_pass_kernel(const TIn* __restrict__ i
   }
 }
 
-// ---- x: rows in LDS, doubling spans ----
-__global__ __launch_bounds__(kRowThreads) void max_rows_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                                               int64_t rows, int X, int r, int seg, int nsegs) {
-  __shared__ float buf[2][kRowBuf];
-  const int tid = threadIdx.x, w = 2 * r + 1;
-  for (int64_t item = blockIdx.x; item < rows * nsegs; item += gridDim.x) {
-    const int64_t row = item / nsegs;
-    const int x0 = static_cast<int>(item - row * nsegs) * seg;
-    const int len = min(seg, X - x0), n = len + 2 * r;
-    const float* src = in + row * X;
-    for (int i = tid; i < n; i += kRowThreads) {
-      const int x = x0 - r + i;
-      buf[0][i] = (x >= 0 && x < X) ? src[x] : kNegInf;
-    }
-    __syncthreads();
-    int cur = 0, span = 1;                  // buf[cur][i] = max over [i, i + span)
-    for (; span * 2 <= w; span *= 2) {
-      for (int i = tid; i + span < n; i += kRowThreads) buf[cur ^ 1][i] = nmax(buf[cur][i], buf[cur][i + span]);
-      __syncthreads();
-      cur ^= 1;
-    }
-    float* dst = out + row * X + x0;
-    for (int t = tid; t < len; t += kRowThreads) dst[t] = nmax(buf[cur][t], buf[cur][t + w - span]);
-    __syncthreads();                        // the next item overwrites both buffers
-  }
-}
-
-// ---- y and z: one thread per (column, block of w positions) ----
-struct MaxArgs {
-  const float* in;
-  float* out;              // not written by the fused pass
-  int64_t L, inner;        // axis length, distance between its positions (outer index: blockIdx.z)
-  int r;
-  // the fused pass (axis z: L = Z, inner = Y * X, in = B)
-  const float* s;
-  const float* a;
-  int X, ry, rx;
-  float threshold;
+// ---- the sink of the z walk: the test, and the append ----
+struct PeakSink {
+  lsr::peaks::PeakTest test;
   long long* cand_index;
   float* cand_value;
-  long long capacity;
+  unsigned long long capacity;
   unsigned long long* count;
+  __device__ bool operator()(int64_t lin, float m) const { return test.maximum(lin, m); }
+  __device__ void late(int64_t lin) const {
+    if (!test.first(lin)) return;
+    const unsigned long long slot = atomicAdd(count, 1ull);
+    if (slot < capacity) {
+      cand_index[slot] = lin;
+      cand_value[slot] = test.s[lin];
+    }
+  }
 };
-
-template <bool FUSED>
-__global__ void max_strided_kernel(MaxArgs p) {
-  extern __shared__ float strip[];          // [w][blockDim.x]: this thread's suffix maxima
-  const int nt = blockDim.x, tid = threadIdx.x;
-  const int64_t col = static_cast<int64_t>(blockIdx.x) * nt + tid;
-  if (col >= p.inner) return;               // (no barrier below)
-  const int w = 2 * p.r + 1;
-  const int64_t base = static_cast<int64_t>(blockIdx.z) * p.L * p.inner + col;
-  const float* in = p.in + base;
-  const int64_t i0 = static_cast<int64_t>(blockIdx.y) * w;   // first output of this block; its window starts at i0 - r
-  const int64_t j0 = i0 - p.r;
-  float run = kNegInf;
-#pragma unroll 4
-  for (int t = w - 1; t >= 0; --t) {
-    const int64_t j = j0 + t;
-    const float v = (j >= 0 && j < p.L) ? in[j * p.inner] : kNegInf;
-    run = nmax(run, v);
-    strip[t * nt + tid] = run;
-  }
-  float g = kNegInf;
-#pragma unroll 4
-  for (int t = 0; t < w; ++t) {
-    const int64_t i = i0 + t;
-    if (i >= p.L) break;
-    if (t > 0) {
-      const int64_t j = j0 + w + t - 1;
-      g = nmax(g, j < p.L ? in[j * p.inner] : kNegInf);
-    }
-    const float m = nmax(strip[t * nt + tid], g);
-    if constexpr (!FUSED) {
-      p.out[base + i * p.inner] = m;
-    } else {
-      const int64_t lin = i * p.inner + col;
-      const float sv = p.s[lin];
-      if (sv == m && sv >= p.threshold) {
-        // the window's voxels of smaller linear index, through the three partial maxima
-        const int64_t y = col / p.X, x = col - y * p.X;
-        bool tie = false;
-        for (int64_t d = min(static_cast<int64_t>(p.rx), x); d > 0 && !tie; --d) tie = p.s[lin - d] >= sv;
-        for (int64_t d = min(static_cast<int64_t>(p.ry), y); d > 0 && !tie; --d) tie = p.a[lin - d * p.X] >= sv;
-        for (int64_t d = min(static_cast<int64_t>(p.r), i); d > 0 && !tie; --d) tie = p.in[lin - d * p.inner] >= sv;
-        if (!tie) {
-          const unsigned long long slot = atomicAdd(p.count, 1ull);
-          if (slot < static_cast<unsigned long long>(p.capacity)) {
-            p.cand_index[slot] = lin;
-            p.cand_value[slot] = sv;
-          }
-        }
-      }
-    }
-  }
-}
-
-// threads per workgroup of the strided passes: the LDS strip is w floats per thread, kept within 33 KB
-int strided_threads(int r) {
-  const int w = 2 * r + 1;
-  return w <= 32 ? 256 : (w <= 64 ? 128 : 64);
-}
-
-int launch_strided(bool fused, MaxArgs p, int64_t outer, hipStream_t s) {
-  const int nt = strided_threads(p.r), w = 2 * p.r + 1;
-  const int64_t gx = lsr::ceil_div(p.inner, nt), gy = lsr::ceil_div(p.L, w);
-  LSR_REQUIRE(gx < (int64_t(1) << 31) && gy < 65536 && outer < 65536, LSR_E_SHAPE,
-              "grid (%lld, %lld, %lld) is too large", (long long)gx, (long long)gy, (long long)outer);
-  const dim3 grid(static_cast<unsigned>(gx), static_cast<unsigned>(gy), static_cast<unsigned>(outer));
-  const size_t lds = sizeof(float) * w * nt;
-  if (fused) hipLaunchKernelGGL(max_strided_kernel<true>, grid, dim3(nt), lds, s, p);
-  else hipLaunchKernelGGL(max_strided_kernel<false>, grid, dim3(nt), lds, s, p);
-  return LSR_OK;
-}
 
 // ---- PSF averaging ----
 constexpr int kTree = lsr::peaks::kTreeThreads;
@@ -278,27 +177,22 @@ extern "C" int lsr_local_max_candidates_f32(const float* s, int64_t Z, int64_t Y
   LSR_REQUIRE(X < (int64_t(1) << 30) && Y * X < (int64_t(1) << 40), LSR_E_UNSUPPORTED, "plane of %lld x %lld is too large",
               (long long)Y, (long long)X);
   hipStream_t st = lsr::as_stream(stream);
-  float* a = static_cast<float*>(scratch);
-  float* b = a + Z * Y * X;
-  if (hipMemsetAsync(count, 0, sizeof(unsigned long long), st) != hipSuccess)
-    return lsr::launch_status("lsr_local_max_candidates_f32");
-  {
-    const int64_t nsegs = lsr::ceil_div(X, kRowSeg);
-    const int seg = static_cast<int>(lsr::ceil_div(lsr::ceil_div(X, nsegs), 4) * 4);
-    const int64_t items = Z * Y * nsegs;
-    const int64_t blocks = items < 256 * 64 ? items : 256 * 64;
-    hipLaunchKernelGGL(max_rows_kernel, dim3(static_cast<unsigned>(blocks)), dim3(kRowThreads), 0, st, s, a, Z * Y,
-                       static_cast<int>(X), rx, seg, static_cast<int>(lsr::ceil_div(X, seg)));
-  }
-  MaxArgs p{};
-  p.in = a; p.out = b; p.L = Y; p.inner = X; p.r = ry;
-  if (int rc = launch_strided(false, p, Z, st)) return rc;
-  p.in = b; p.out = nullptr; p.L = Z; p.inner = Y * X; p.r = rz;
-  p.s = s; p.a = a; p.X = static_cast<int>(X); p.ry = ry; p.rx = rx;
-  p.threshold = threshold;
-  p.cand_index = cand_index; p.cand_value = cand_value; p.capacity = capacity; p.count = count;
-  if (int rc = launch_strided(true, p, 1, st)) return rc;
-  return lsr::launch_status("lsr_local_max_candidates_f32");
+  namespace mo = lsr::morph;
+  const char* who = "lsr_local_max_candidates_f32";
+  float* scratch_a = static_cast<float*>(scratch);
+  float* scratch_b = scratch_a + Z * Y * X;
+  if (hipMemsetAsync(count, 0, sizeof(unsigned long long), st) != hipSuccess) return lsr::launch_status(who);
+  const float* a = rx > 0 ? scratch_a : s;
+  const float* b = ry > 0 ? scratch_b : a;
+  const mo::StoreSink to_a{scratch_a, nullptr, mo::kPlain}, to_b{scratch_b, nullptr, mo::kPlain};
+  if (rx > 0)
+    if (int rc = mo::launch_pass(s, to_a, Z, Y, X, mo::Pass{2, rx, false}, who, st)) return rc;
+  if (ry > 0)
+    if (int rc = mo::launch_pass(a, to_b, Z, Y, X, mo::Pass{1, ry, false}, who, st)) return rc;
+  const PeakSink sink{lsr::peaks::PeakTest{s, a, b, X, Y * X, rz, ry, rx, threshold}, cand_index, cand_value,
+                      static_cast<unsigned long long>(capacity), count};
+  if (int rc = mo::launch_strided(b, mo::lines_of(0, Z, Y, X), rz, false, sink, who, st)) return rc;
+  return lsr::launch_status(who);
 }
 
 extern "C" int lsr_psf_accumulate_f32(const float* vol, int64_t Z, int64_t Y, int64_t X, const long long* centres,

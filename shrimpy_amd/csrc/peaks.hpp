@@ -1,5 +1,6 @@
 // What the bead-detection / PSF-averaging kernels (peaks.hip) and their host twins (host_twins.hip) share: the
-// argument checks, the NaN-propagating maximum and the fixed reduction tree of the per-bead sums.
+// argument checks, the peak test (the sink of the morphology's walk, morphology.hpp) and the fixed reduction tree of the
+// per-bead sums.
 #pragma once
 
 #include <cmath>
@@ -13,8 +14,34 @@ constexpr int kMaxHalfWidth = 64;      // window half-widths per axis (as the bl
 constexpr int kTreeThreads = 256;      // the per-bead sums: 256 strided partial sums, then a binary tree
 constexpr int kMaxPatch = 129;         // PSF patch extent per axis (what DeconvolveSettings.psf_shape_zyx takes)
 
-// max(a, b) that keeps a NaN from either side: a window that holds a NaN has no maximum, so no voxel equals it
-__host__ __device__ inline float nmax(float a, float b) { return (a >= b || a != a) ? a : b; }
+// The test at voxel `lin` of the smoothed volume s, given the maximum m of its window (a NaN where the window holds one: no
+// voxel equals it): s == m, s >= threshold, and no voxel of the window with a smaller linear index reaches s.  Those voxels
+// are exactly the three half-windows BELOW the voxel in C order of s along x, of A (s dilated along x) along y and of B (A
+// dilated along y) along z; an axis with half-width 0 has none, and A or B may then be the volume before it.  Rarely true
+// past the first line, so the division is behind it.
+struct PeakTest {
+  const float* s;
+  const float* a;
+  const float* b;
+  int64_t X, plane;
+  int rz, ry, rx;
+  float threshold;
+  // at every voxel
+  __host__ __device__ bool maximum(int64_t lin, float m) const {
+    const float sv = s[lin];
+    return sv == m && sv >= threshold;
+  }
+  // the tie rule, at a voxel that passed maximum()
+  __host__ __device__ bool first(int64_t lin) const {
+    const float sv = s[lin];
+    const int64_t z = lin / plane, rem = lin - z * plane, y = rem / X, x = rem - y * X;
+    bool tie = false;
+    for (int64_t d = rx < x ? rx : x; d > 0 && !tie; --d) tie = s[lin - d] >= sv;
+    for (int64_t d = ry < y ? ry : y; d > 0 && !tie; --d) tie = a[lin - d * X] >= sv;
+    for (int64_t d = rz < z ? rz : z; d > 0 && !tie; --d) tie = b[lin - d * plane] >= sv;
+    return !tie;
+  }
+};
 
 inline int check_local_max(const float* s, int64_t Z, int64_t Y, int64_t X, int rz, int ry, int rx, float threshold,
                            const long long* cand_index, const float* cand_value, int64_t capacity,

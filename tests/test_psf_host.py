@@ -26,7 +26,7 @@ import torch
 import yaml
 
 from oracle import cpu_ref as o
-from shrimpy_amd import _lib, psf
+from shrimpy_amd import _lib, morphology, psf
 from shrimpy_amd.io.omezarr import open_ome_zarr
 from shrimpy_amd.settings import CharacterizeSettings, DeconvolveSettings
 from tests import psf_ref as r
@@ -78,8 +78,10 @@ def engineered(shape=(12, 14, 16)):
 
 
 def boundary_ties(r3=(3, 3, 3)):
-    """Equal pairs that straddle the kernels' tile boundaries: the x pass stages rows in two segments of 552 columns at
-    X = 1100, the y and z passes work in blocks of w = 2 r + 1 positions, threads in groups of 256 columns."""
+    """Equal pairs that straddle the tile boundaries of the FORMER kernels (bead detection had a sliding maximum of its own
+    until it moved onto the morphology passes): the x pass staged rows in two segments of 552 columns at X = 1100, the y and z
+    passes worked in blocks of w = 2 r + 1 positions, threads in groups of 256 columns.  ``walk_ties`` is the same
+    construction at the edges of the passes that run now."""
     w = 2 * r3[1] + 1
     v = np.zeros((2 * w + 2, 2 * w + 3, 1100), dtype=np.float32)
     v[2, 3, 551] = v[2, 3, 552] = 8.0            # x segment boundary
@@ -87,6 +89,56 @@ def boundary_ties(r3=(3, 3, 3)):
     v[w - 1, 12, 700] = v[w, 12, 700] = 5.0      # z block boundary
     v[w, 1, 30] = v[w - 1, 2, 29] = 4.0          # the smaller index is on the previous plane
     return v
+
+
+def row_segments():
+    """(X, segment): a row just over one staged segment of the x pass, and the equal segments it is cut into -- from the
+    exported tiling (``lsr_grey_morph_tiling``), as ``tests/morphology_cases.py`` sizes its shapes."""
+    _, columns, segment, _ = morphology.tiling()
+    x = segment + 52
+    parts = -(-x // segment)
+    return x, -(-(-(-x // parts)) // columns) * columns
+
+
+def walk_ties(r3=(3, 3, 3)):
+    """``boundary_ties`` at the edges of the morphology passes: the x pass stages a row of X = 2100 in two segments of 1088
+    (at a segment of 2048), the y and z walks cut a line into blocks of w = 2 r + 1 positions, a wavefront owns 64 columns."""
+    _, columns, _, _ = morphology.tiling()
+    x, seg = row_segments()
+    w = 2 * r3[1] + 1
+    v = np.zeros((2 * w + 2, 2 * w + 3, x), dtype=np.float32)
+    v[2, 3, seg - 1] = v[2, 3, seg] = 8.0                      # x segment boundary
+    v[4, w - 1, columns - 1] = v[4, w, columns] = 6.0          # y block boundary and a column-group boundary
+    v[w - 1, 12, 700] = v[w, 12, 700] = 5.0                    # z block boundary
+    v[w, 1, 30] = v[w - 1, 2, 29] = 4.0                        # the smaller index is on the previous plane
+    return v
+
+
+# Half-widths at which the composition of the passes changes: an axis without a window gets no pass (A is s, B is A) and the z
+# walk still runs at w = 1 -- every axis in turn, and all; a window wider than every axis; one inside every axis.
+COMPOSITION_TRIPLES = [(0, 0, 0), (0, 2, 3), (2, 0, 3), (2, 3, 0), (0, 0, 2), (1, 0, 0), (6, 8, 12), (1, 2, 3)]
+ZERO_TRIPLES = COMPOSITION_TRIPLES[:6]
+
+
+def composition_cases():
+    """(label, volume, min_distance, threshold) on one (5, 7, 11) volume of small integers and three value classes of it:
+    signed zeros (the passes may hand back +0.0 for -0.0: equal), +inf (a tied pair in reach of each other, and a lone
+    one) and a NaN.  No -inf: the restatement pads with it."""
+    base = tied((5, 7, 11), 1, levels=3)
+    zeros = base.copy()
+    at = zeros == 0.0
+    zeros[at] = np.where(np.random.default_rng(21).integers(0, 2, int(at.sum())) == 1, -0.0, 0.0).astype(np.float32)
+    assert np.signbit(zeros).any() and (at & ~np.signbit(zeros)).any()
+    inf = base.copy()
+    inf[1, 2, 3] = inf[1, 2, 5] = inf[3, 3, 3] = np.inf
+    nan = base.copy()
+    nan[2, 3, 4] = np.nan
+    for md in COMPOSITION_TRIPLES:
+        kind = "zero half-width" if md in ZERO_TRIPLES else "half-widths"
+        yield f"{kind} {md}", base, md, 1.0
+        yield f"signed zeros {md}", zeros, md, -1.0
+        yield f"+inf {md}", inf, md, 1.0
+        yield f"a NaN in reach {md}", nan, md, 0.0
 
 
 # (label, volume, blur, min_distance, threshold, exclude_border, max_num_peaks)
@@ -106,6 +158,11 @@ def detection_cases(big=False):
     nan[4, 10, 17] = np.nan
     yield "a NaN", nan, 1, 3, 100.0, (0, 0, 0), None
     yield "a NaN, smoothed", nan, 3, 3, 100.0, (0, 0, 0), None
+    for label, v, md, thr in composition_cases():
+        yield label, v, 1, md, thr, (0, 0, 0), None
+    two_segments = tied((9, 17, row_segments()[0]), 8)
+    yield "morphology tiling: ties everywhere, two row segments", two_segments, 1, (1, 3, 5), 2.0, (0, 0, 0), None
+    yield "morphology tiling: ties across tile boundaries", walk_ties(), 1, 3, 1.0, (0, 0, 0), None
     if big:
         yield "64 x 512 x 600", noisy((64, 512, 600), 10), 3, (5, 20, 50), 300.0, (5, 5, 5), 500
         yield "64 x 512 x 600, ties", tied((64, 512, 600), 11, levels=1000), 1, (3, 10, 24), 990.0, (0, 0, 0), None
@@ -126,6 +183,9 @@ def hold_detection(device, big=False):
         assert np.array_equal(got_c.numpy(), want_c), label
         assert np.array_equal(got_v.numpy(), want_v), label
     assert counts["engineered"] > 0 and counts["a NaN"] > 0 and counts["r = 64"] > 0
+    for label, n in counts.items():
+        if label.startswith(("zero half-width", "+inf", "morphology tiling")):
+            assert n > 0, label
     return counts
 
 
@@ -182,13 +242,15 @@ def test_twin_smoothing_against_scipy_in_float64():
 
 def test_twin_detection_does_not_depend_on_the_thread_count():
     v = _t(tied((9, 17, 300), 12))
-    lists = []
-    for n in (1, 3, 7):
-        torch.set_num_threads(n)
-        lists.append(psf.local_maxima(v, (1, 3, 5), 2.0))
-    torch.set_num_threads(1)
-    for idx, val in lists[1:]:
-        assert np.array_equal(np.sort(idx), np.sort(lists[0][0]))
+    for md in ((1, 3, 5), (0, 3, 5)):
+        lists = []
+        for n in (1, 3, 7):
+            torch.set_num_threads(n)
+            lists.append(psf.local_maxima(v, md, 2.0))
+        torch.set_num_threads(1)
+        assert len(lists[0][0]) > 0
+        for idx, val in lists[1:]:
+            assert np.array_equal(np.sort(idx), np.sort(lists[0][0])), md
 
 
 def test_candidate_overflow_is_a_value_error_naming_the_threshold():

@@ -49,7 +49,7 @@ def main():
                     "accelerated iteration and the wall time of 9 / 10 / 15 accelerated beside 20 plain iterations on the "
                     "fused separable, ky (x) kzx and Fourier routes, on --rl-grid")
     ap.add_argument("--peaks", action="store_true", help="only: ms of the bead-detection launches (csrc/peaks.hip) at "
-                    "min_distance 10 and 50 and of the box smoothing in front of them, on --rl-grid")
+                    "min_distance 5, 10, 25 and 50 and of the box smoothing in front of them, on --rl-grid")
     ap.add_argument("--peaks-host", action="store_true", help="with --peaks: also time scipy.ndimage.maximum_filter for "
                     "the same windows on this box's host cores")
     ap.add_argument("--phase", action="store_true", help="only: one application of the phase reconstruction (yaml optics) on "
@@ -986,8 +986,8 @@ def _morphology(args, torch, dev, g, bench, oshape):
     128, and the erosion along z, y and x alone (one launch each); a launch moves 8 algorithmic bytes per voxel (one read, one
     write; the top-hat's last one 12).  Beside them, in the same
     run, the floor -- a device copy of one volume, the same 8 bytes per voxel -- and, where the half-width is at most 64, the
-    three launches of lsr_local_max_candidates_f32 at the same half-width: the running maximum the bead detection has (two
-    volumes written, the third pass fused with the peak test)."""
+    three launches of lsr_local_max_candidates_f32 at the same half-width: the same x and y passes (two volumes written) and
+    the z walk with the peak test as its sink."""
     from shrimpy_amd import _lib, morphology
 
     reps = 3
@@ -1252,10 +1252,10 @@ def _mi(args, torch, dev, g, bench, shape):
 
 
 def _peaks(args, torch, dev, g, oshape):
-    """Bead detection (csrc/peaks.hip): the three launches of lsr_local_max_candidates_f32 -- x, y and the fused z pass
-    of the separable box maximum -- on a smoothed Poisson volume with a few hundred beads, per min_distance; 24 algorithmic
-    bytes per voxel (s, A and B each written or read once per pass; the marching passes read every input twice, the
-    second time from cache).  --peaks-host: scipy's maximum_filter over the same window on the host, the step a user
+    """Bead detection (csrc/peaks.hip): the three launches of lsr_local_max_candidates_f32 -- the grey morphology's x and y
+    dilation passes and its z walk with the peak test as the sink -- on a smoothed Poisson volume with a few hundred beads,
+    per min_distance; 24 algorithmic bytes per voxel (x reads s and writes A, y reads A and writes B, z reads B and s: every
+    pass reads its source once, as one stream).  --peaks-host: scipy's maximum_filter over the same window on the host, the step a user
     without this kernel would run."""
     import ctypes
     import time
@@ -1279,7 +1279,7 @@ def _peaks(args, torch, dev, g, oshape):
     index = torch.empty(capacity, dtype=torch.int64, device=dev)
     value = torch.empty(capacity, dtype=torch.float32, device=dev)
     count = torch.zeros(1, dtype=torch.int64, device=dev)
-    for r in (10, 50):
+    for r in (5, 10, 25, 50):
         def launch():
             _lib.call("lsr_local_max_candidates_f32", s.data_ptr(), z, y, x, r, r, r, ctypes.c_float(200.0), index.data_ptr(),
                       value.data_ptr(), capacity, count.data_ptr(), scratch.data_ptr(), _lib.stream_ptr(dev))
