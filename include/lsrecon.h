@@ -128,6 +128,12 @@ int lsr_deskew_cval(const void* in, int in_u16, int64_t Z, int64_t Y, int64_t X,
 int lsr_deskew_cval_cpu(const void* in, int in_u16, int64_t Z, int64_t Y, int64_t X, float* out, int64_t Zo, int64_t Yo,
                         int64_t Xo, int64_t out_pitch, int64_t out_plane, int64_t Zd, const double M[12], int avg_n,
                         int mode, const float* flat_pattern, const float* flat_mean, const float* cval, lsr_stream_t stream);
+/* The launch the deskew entries above make for this output shape and matrix -- host code, no device call; the status is
+ * the one those entries return for the same shape and matrix.  out = {X' per workgroup (64 halved until the tile's scan
+ * range fits the slab), Y' per workgroup, LDS slab rows, slab rows staged per pass, tiles along X', tiles along Y',
+ * workgroups with work, workgroups launched (padded to a multiple of 8 unless LSR_DESKEW_SWIZZLE=0)}.  The entries launch
+ * from the same function: what the tests count from it is what runs. */
+int lsr_deskew_plan(int64_t Zo, int64_t Yo, int64_t Xo, const double M[12], int64_t out[8]);
 /* min / max of uint16 camera counts as two floats (exact), scratch as lsr_minmax_f32 */
 int lsr_minmax_u16(const uint16_t* in, int64_t n, float* out2, void* scratch, lsr_stream_t stream);
 

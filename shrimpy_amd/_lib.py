@@ -52,6 +52,7 @@ SIGNATURES: dict[str, list] = {
                           _int, _int, ctypes.c_void_p, ctypes.c_void_p, _stream],
     "lsr_deskew_cval": [ctypes.c_void_p, _int, _i64, _i64, _i64, _c_f32p, _i64, _i64, _i64, _i64, _i64, _i64, _f64p,
                         _int, _int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _stream],
+    "lsr_deskew_plan": [_i64, _i64, _i64, _f64p, ctypes.POINTER(ctypes.c_int64)],
     "lsr_minmax_u16": [ctypes.c_void_p, _i64, _c_f32p, ctypes.c_void_p, _stream],
     "lsr_deskew_u16": [ctypes.c_void_p, _i64, _i64, _i64, _c_f32p, _i64, _i64, _i64, _i64, _i64, _i64, _f64p, _int, _stream],
     "lsr_deskew_flat_f32": [_c_f32p, _i64, _i64, _i64, _c_f32p, _i64, _i64, _i64, _i64, _i64, _i64, _f64p, _int,

@@ -30,7 +30,9 @@ constexpr int kSlabRows = 68; // LDS rows (input z) a workgroup can stage
 constexpr int kPitch = kTileY + 1;  // +1 float: lanes walk z at ~b rows/lane -> distinct banks
 constexpr int kThreads = 256;
 constexpr int kRowsPerThread = kTileY * kTileX / kThreads;  // 16 output points per thread
-constexpr int kMaxAvg = 4096;  // sanity bound only
+constexpr int kMaxAvg = lsr::kMaxAvgSlices;  // sanity bound only (shared with the host twin)
+constexpr int kStageStep = kThreads / 64;  // slab rows per pass over the workgroup
+constexpr int kStageBatch = 6;             // loads in flight per thread
 
 struct DeskewArgs {
   const void* in;           // raw stack: float32, or (U16) uint16 camera counts
@@ -135,8 +137,8 @@ __global__ __launch_bounds__(kThreads) void deskew_kernel(DeskewArgs p) {
         pat = p.flat_pattern[y_in * p.X + x_safe];
         mean = p.flat_mean[0];
       }
-      constexpr int kStep = kThreads / 64;   // slab rows per pass over the workgroup
-      constexpr int kBatch = 6;              // loads in flight per thread
+      constexpr int kStep = kStageStep;
+      constexpr int kBatch = kStageBatch;
       for (int zl0 = tid >> 6; zl0 < n_rows; zl0 += kStep * kBatch) {
         float v[kBatch];
 #pragma unroll
@@ -220,9 +222,48 @@ __global__ __launch_bounds__(256) void average_slices_kernel(const float* __rest
 
 bool is_integer(double v) { return v == static_cast<double>(static_cast<int64_t>(v)); }
 
-}  // namespace
+// The launch of one deskew call: everything the host decides from the output shape and the matrix.  deskew_impl launches
+// from it and lsr_deskew_plan reports it, so what the tests count is what runs.
+struct DeskewPlan {
+  int tile_x;                // X' per workgroup: halved from kTileX until the slab holds the tile's z range
+  int64_t tiles_x, tiles_y;
+  int64_t blocks;            // tiles_x * tiles_y * Zo
+  int xcd_swizzle;
+  int64_t grid;              // workgroups launched: `blocks`, padded to a multiple of 8 under the swizzle
+};
 
-namespace {
+int deskew_plan(int64_t Zo, int64_t Yo, int64_t Xo, const double M[12], DeskewPlan* plan) {
+  LSR_REQUIRE_PTR(M);
+  LSR_REQUIRE(Zo > 0 && Yo > 0 && Xo > 0, LSR_E_SHAPE, "output shape (%lld,%lld,%lld) must be positive", (long long)Zo,
+              (long long)Yo, (long long)Xo);
+  LSR_REQUIRE_VOLUME(Zo, Yo, Xo);
+  if (int rc = lsr::check_matrix(M)) return rc;
+
+  // deskew structure: only z_in is fractional
+  const bool structured = M[1] == 0.0 && (M[4] == 1.0 || M[4] == -1.0) && M[5] == 0.0 &&
+                          M[6] == 0.0 && is_integer(M[7]) && M[8] == 0.0 &&
+                          (M[9] == 1.0 || M[9] == -1.0) && M[10] == 0.0 && is_integer(M[11]);
+  LSR_REQUIRE(structured, LSR_E_UNSUPPORTED,
+              "matrix is not a deskew shear (rows 1,2 must be signed unit axes with integer "
+              "offsets, M[0][1] == 0): use lsr_affine_f32 + lsr_average_slices_f32");
+
+  // slab rows needed by a tile of w X' values: floor span of |b|*(w-1) plus the +1 neighbour
+  const double ab = M[2] < 0 ? -M[2] : M[2];
+  int tile_x = kTileX;
+  while (tile_x > 1 && ab * (tile_x - 1) + 3.0 > static_cast<double>(kSlabRows)) tile_x >>= 1;
+  LSR_REQUIRE(ab * (tile_x - 1) + 3.0 <= static_cast<double>(kSlabRows), LSR_E_UNSUPPORTED,
+              "scan step per output voxel |b| = %g is too large for the LDS slab", ab);
+  plan->tile_x = tile_x;
+  plan->tiles_x = lsr::ceil_div(Xo, tile_x);
+  plan->tiles_y = lsr::ceil_div(Yo, kTileY);
+  plan->blocks = plan->tiles_x * plan->tiles_y * Zo;
+  LSR_REQUIRE(plan->blocks < (int64_t(1) << 31), LSR_E_SHAPE, "grid of %lld workgroups is too large",
+              (long long)plan->blocks);
+  plan->xcd_swizzle = 1;
+  if (const char* e = std::getenv("LSR_DESKEW_SWIZZLE")) plan->xcd_swizzle = e[0] != '0';   // measurement override
+  plan->grid = plan->xcd_swizzle ? 8 * ((plan->blocks + 7) / 8) : plan->blocks;
+  return LSR_OK;
+}
 
 int deskew_impl(const char* what, const void* in, bool u16, int64_t Z, int64_t Y, int64_t X, float* out,
                 int64_t Zo, int64_t Yo, int64_t Xo, int64_t out_pitch, int64_t out_plane,
@@ -249,15 +290,8 @@ int deskew_impl(const char* what, const void* in, bool u16, int64_t Z, int64_t Y
   LSR_REQUIRE(out_pitch >= Xo && out_plane >= Yo * out_pitch, LSR_E_SHAPE,
               "output strides (%lld, %lld) are smaller than the output plane (%lld x %lld)",
               (long long)out_pitch, (long long)out_plane, (long long)Yo, (long long)Xo);
-  if (int rc = lsr::check_matrix(M)) return rc;
-
-  // deskew structure: only z_in is fractional
-  const bool structured = M[1] == 0.0 && (M[4] == 1.0 || M[4] == -1.0) && M[5] == 0.0 &&
-                          M[6] == 0.0 && is_integer(M[7]) && M[8] == 0.0 &&
-                          (M[9] == 1.0 || M[9] == -1.0) && M[10] == 0.0 && is_integer(M[11]);
-  LSR_REQUIRE(structured, LSR_E_UNSUPPORTED,
-              "matrix is not a deskew shear (rows 1,2 must be signed unit axes with integer "
-              "offsets, M[0][1] == 0): use lsr_affine_f32 + lsr_average_slices_f32");
+  DeskewPlan plan;
+  if (int rc = deskew_plan(Zo, Yo, Xo, M, &plan)) return rc;   // the matrix, the shear's structure, the tile, the grid
 
   DeskewArgs p;
   p.in = in;
@@ -270,27 +304,15 @@ int deskew_impl(const char* what, const void* in, bool u16, int64_t Z, int64_t Y
   p.sx = static_cast<int>(M[9]); p.ox = static_cast<int64_t>(M[11]);
   p.avg_n = avg_n;
   p.grid = mode == LSR_MODE_GRID_CONSTANT ? 1 : 0;
-
-  // slab rows needed by a tile of w X' values: floor span of |b|*(w-1) plus the +1 neighbour
-  const double ab = p.b < 0 ? -p.b : p.b;
-  int tile_x = kTileX;
-  while (tile_x > 1 && ab * (tile_x - 1) + 3.0 > static_cast<double>(kSlabRows)) tile_x >>= 1;
-  LSR_REQUIRE(ab * (tile_x - 1) + 3.0 <= static_cast<double>(kSlabRows), LSR_E_UNSUPPORTED,
-              "scan step per output voxel |b| = %g is too large for the LDS slab", ab);
-  p.tile_x = tile_x;
-  p.tiles_x = lsr::ceil_div(Xo, tile_x);
-  p.tiles_y = lsr::ceil_div(Yo, kTileY);
-  const int64_t blocks = p.tiles_x * p.tiles_y * Zo;
-  LSR_REQUIRE(blocks < (int64_t(1) << 31), LSR_E_SHAPE, "grid of %lld workgroups is too large",
-              (long long)blocks);
-
+  p.tile_x = plan.tile_x;
+  p.tiles_x = plan.tiles_x;
+  p.tiles_y = plan.tiles_y;
   p.flat_pattern = flat_pattern;
   p.flat_mean = flat_mean;
   p.cval = cval;
-  p.blocks = blocks;
-  p.xcd_swizzle = 1;
-  if (const char* e = std::getenv("LSR_DESKEW_SWIZZLE")) p.xcd_swizzle = e[0] != '0';   // measurement override
-  const dim3 grid(static_cast<unsigned>(p.xcd_swizzle ? 8 * ((blocks + 7) / 8) : blocks)), block(kThreads);
+  p.blocks = plan.blocks;
+  p.xcd_swizzle = plan.xcd_swizzle;
+  const dim3 grid(static_cast<unsigned>(plan.grid)), block(kThreads);
   hipStream_t s = lsr::as_stream(stream);
   if (u16 && flat_pattern != nullptr) hipLaunchKernelGGL((deskew_kernel<true, true>), grid, block, 0, s, p);
   else if (u16) hipLaunchKernelGGL((deskew_kernel<false, true>), grid, block, 0, s, p);
@@ -357,6 +379,21 @@ extern "C" int lsr_deskew_cval(const void* in, int in_u16, int64_t Z, int64_t Y,
               "flat_pattern and flat_mean come together (both NULL: no flat-field correction)");
   return deskew_impl("lsr_deskew_cval", in, in_u16 != 0, Z, Y, X, out, Zo, Yo, Xo, out_pitch, out_plane, Zd, M,
                      avg_n, flat_pattern, flat_mean, stream, mode, cval);
+}
+
+extern "C" int lsr_deskew_plan(int64_t Zo, int64_t Yo, int64_t Xo, const double M[12], int64_t out[8]) {
+  LSR_REQUIRE_PTR(out);
+  DeskewPlan plan;
+  if (int rc = deskew_plan(Zo, Yo, Xo, M, &plan)) return rc;
+  out[0] = plan.tile_x;
+  out[1] = kTileY;
+  out[2] = kSlabRows;
+  out[3] = kStageStep * kStageBatch;
+  out[4] = plan.tiles_x;
+  out[5] = plan.tiles_y;
+  out[6] = plan.blocks;
+  out[7] = plan.grid;
+  return LSR_OK;
 }
 
 extern "C" int lsr_average_slices_f32(const float* in, int64_t Zd, int64_t Y, int64_t X,

@@ -63,7 +63,7 @@ namespace {
 
 using lsr::parallel_ranges;
 std::atomic<int>& g_threads = lsr::g_host_threads;
-constexpr int kMaxAvg = 16;    // as deskew.hip
+constexpr int kMaxAvg = lsr::kMaxAvgSlices;
 // the stencil kernels hold 15 taps per axis (31 along z, correlate_z.hip); larger dense PSFs run in the Fourier
 // domain on the device (deconvolve_fft.py, up to 129 taps per axis) -- the twins' loops take any count
 constexpr int kMaxTaps = 129;

@@ -128,6 +128,8 @@ inline int require_border(int mode, bool* grid, bool* f32 = nullptr) {
               f32 != nullptr ? ", with or without LSR_MODE_F32_INTERP" : " (the f32-interpolation flag has no host twin)");
   return LSR_OK;
 }
+// the most slices one output plane may average: what deskew.hip and its twin in host_twins.hip both accept
+constexpr int kMaxAvgSlices = 4096;
 inline int check_matrix(const double M[12]) {
   LSR_REQUIRE_PTR(M);
   for (int i = 0; i < 12; ++i) LSR_REQUIRE(M[i] == M[i] && M[i] - M[i] == 0.0, LSR_E_ARG, "M[%d] is not finite", i);
