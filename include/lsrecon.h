@@ -1128,6 +1128,35 @@ int lsr_label_overlap_i32(const int32_t* a, const int32_t* b, int64_t Z, int64_t
                           int64_t capacity, void* table, int32_t* counts, int max_blocks, lsr_stream_t stream);
 
 /*
+ * The volume, first and second moments of every object of a label volume (csrc/moments.hip; the rule is stated in
+ * csrc/moments.hpp): what shrimpy_amd/segment.py derives axis lengths and orientations from.  No upstream is pinned;
+ * tests/moments_ref.py restates the rule with np.add.at on int64, and device, twin and restatement are equal byte for byte.
+ *
+ * lsr_label_moments_i32: labels is an int32 (Z, Y, X) volume (device memory).  For every voxel (z, y, x) with
+ * 1 <= labels[v] <= n_objects, record labels[v] - 1 of `table` gains 1 (volume), z, y, x (s_z, s_y, s_x) and z^2, y^2, x^2,
+ * zy, zx, yx (m_zz, m_yy, m_xx, m_zy, m_zx, m_yx), in absolute voxel indices.  `table` (device memory, WHICH THE CALLER HAS
+ * ZEROED) is n_objects records of ten int64 in that order, 80 bytes each.  Labels outside 1 .. n_objects are ignored; a label
+ * that no voxel carries keeps a zero record.  Pure integer arithmetic: the records do not depend on the order of execution.
+ * max_blocks caps the grid (0: the default of lsr_label_moments_geometry); the result does not depend on it.
+ * Refused before any launch and with nothing read or written: LSR_E_ARG for a NULL pointer, a non-positive extent,
+ * n_objects < 0, max_blocks < 0 or a table that overlaps labels; LSR_E_UNSUPPORTED for more than 2^31 - 1 voxels or for
+ * Z*Y*X * max(Z, Y, X)^2 >= 2^63, where a sum could wrap.  n_objects == 0 returns at once.
+ * One launch: each workgroup walks one contiguous span of the volume, finds the runs of equal labels inside a row by one
+ * ballot, takes a run's ten sums in closed form from (z, y, x0, length), accumulates in a table in LDS and flushes it once, so
+ * an all-foreground volume costs ten global atomics per workgroup; shared words are touched by atomics only, nothing waits
+ * for anything.
+ * lsr_label_moments_geometry: out[0] = the slots of one workgroup's LDS table, out[1] = the default cap of the grid.
+ */
+int lsr_label_moments_geometry(int out[2]);
+int lsr_label_moments_i32(const int32_t* labels, int64_t Z, int64_t Y, int64_t X, int64_t n_objects, void* table,
+                          int max_blocks, lsr_stream_t stream);
+/* measurement only (tools/bench_kernels.py --moments): the same kernel with lds_slots slots in the LDS table (a power of two
+ * up to 512) probed over at most lds_probes (1 .. 512) slots, or with lds_slots == 0 the plain form in which every run head
+ * adds to the global record directly */
+int lsr_label_moments_variant_i32(const int32_t* labels, int64_t Z, int64_t Y, int64_t X, int64_t n_objects, void* table,
+                                  int max_blocks, int lds_slots, int lds_probes, lsr_stream_t stream);
+
+/*
  * Host twins (csrc/host_twins.hip): the same signatures with HOST pointers, the same argument checks and the
  * same arithmetic in the same order, so the results equal the device entry points' bit for bit.  They serve
  * the boxes where the reference itself resolves to the CPU (shrimpy/preprocessing.py:78-82 -- its CI has no
@@ -1273,6 +1302,12 @@ int lsr_watershed_saddles_f32_cpu(const int32_t* objects, const int32_t* basins,
  * (csrc/overlap.hpp): the kernel's set of records.  Every pointer HOST memory; max_blocks is checked and otherwise unused. */
 int lsr_label_overlap_i32_cpu(const int32_t* a, const int32_t* b, int64_t Z, int64_t Y, int64_t X, const int32_t shift_zyx[3],
                               int64_t capacity, void* table, int32_t* counts, int max_blocks, lsr_stream_t stream);
+
+/* ... of the label moments (csrc/moments.hip): plain sequential code over the same rule, record and checks
+ * (csrc/moments.hpp), voxel by voxel: the kernel's records byte for byte.  Every pointer HOST memory; max_blocks is checked
+ * and otherwise unused. */
+int lsr_label_moments_i32_cpu(const int32_t* labels, int64_t Z, int64_t Y, int64_t X, int64_t n_objects, void* table,
+                              int max_blocks, lsr_stream_t stream);
 
 /* ... of the grey morphology (csrc/morphology.hip): the same plan of passes and the same walk along a line
  * (csrc/morphology.hpp), so `out` is the kernels' bits.  Every pointer HOST memory; `scratch` holds the results between the

@@ -196,6 +196,9 @@ SIGNATURES: dict[str, list] = {
     "lsr_label_overlap_geometry": [ctypes.POINTER(ctypes.c_int)],
     "lsr_label_overlap_i32": [ctypes.c_void_p, ctypes.c_void_p, _i64, _i64, _i64, ctypes.POINTER(ctypes.c_int32), _i64,
                               ctypes.c_void_p, ctypes.c_void_p, _int, _stream],
+    "lsr_label_moments_geometry": [ctypes.POINTER(ctypes.c_int)],
+    "lsr_label_moments_i32": [ctypes.c_void_p, _i64, _i64, _i64, _i64, ctypes.c_void_p, _int, _stream],
+    "lsr_label_moments_variant_i32": [ctypes.c_void_p, _i64, _i64, _i64, _i64, ctypes.c_void_p, _int, _int, _int, _stream],
     "lsr_crc32c_host": [ctypes.c_void_p, _i64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)],
     "lsr_crc32c_host_portable": [ctypes.c_void_p, _i64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)],
     "lsr_average_slices_f32": [_c_f32p, _i64, _i64, _i64, _c_f32p, _i64, _int, _stream],
@@ -288,6 +291,8 @@ for _name in ("lsr_deskew_f32", "lsr_deskew_u16", "lsr_deskew_cval", "lsr_affine
               "lsr_watershed_f32", "lsr_watershed_saddles_f32",
               # ... and of the label-overlap table (csrc/overlap.hip)
               "lsr_label_overlap_i32",
+              # ... and of the label moments (csrc/moments.hip)
+              "lsr_label_moments_i32",
               # ... and of the grey morphology (csrc/morphology.hip)
               "lsr_grey_morph_f32",
               # ... and of the rank filters (csrc/rank.hip)

@@ -1757,7 +1757,8 @@ OBJECT_COLUMNS = ("t", "label", "volume_voxels", "volume_um3", "bbox_z0", "bbox_
 def object_rows(t: int, table: dict, scale_zyx, translation_zyx) -> list[list]:
     """The ``objects.csv`` rows of one timepoint's table (``segment.region_table`` with intensities), in
     ``OBJECT_COLUMNS`` order.  Physical centroids are ``translation + centroid * scale`` of the position's level 0.  A table
-    with an ``inscribed_radius`` column (``SegmentSettings.inscribed_radius``) gets it appended as the last value."""
+    with an ``inscribed_radius`` column (``SegmentSettings.inscribed_radius``) gets it appended behind them, a table with the
+    shape columns (``SegmentSettings.shape``) the values of ``SHAPE_OBJECT_COLUMNS`` behind that."""
     sz, sy, sx = (float(v) for v in scale_zyx)
     rows = []
     for k in range(len(table["label"])):
@@ -1769,7 +1770,17 @@ def object_rows(t: int, table: dict, scale_zyx, translation_zyx) -> list[list]:
                      float(table["intensity_max"][k]), *(float(v) for v in table["weighted_centroid"][k])])
         if "inscribed_radius" in table:
             rows[-1].append(float(table["inscribed_radius"][k]))
+        if "axis_lengths" in table:
+            rows[-1] += [*(float(v) for v in table["axis_lengths"][k]), *(float(v) for v in table["major_axis"][k]),
+                         float(table["surface_area"][k]), float(table["contact_area"][k]), int(table["n_neighbours"][k]),
+                         int(table["touches_border"][k])]
     return rows
+
+
+# what `shape: true` appends to objects.csv, behind every other column
+SHAPE_OBJECT_COLUMNS = ("axis_length_major_um", "axis_length_mid_um", "axis_length_minor_um", "major_axis_z", "major_axis_y",
+                        "major_axis_x", "surface_area_um2", "contact_area_um2", "n_neighbours", "touches_border")
+CONTACT_COLUMNS = ("t", "label_a", "label_b", "faces_z", "faces_y", "faces_x", "area_um2")
 
 
 @cli.command(cls=_eat_all_command("-i", "--input-position-dirpaths"))
@@ -1800,7 +1811,13 @@ def segment(input_path, config, output_path, positions, zarr_version, io_backend
     volume under a box of that radius instead of the volume: a slowly varying background goes, objects narrower than the
     window stay.  fill_holes: true fills the holes of the thresholded mask before it is labelled.  median_radius
     (micrometres, a number or [z, y, x]; at most 3 voxels to each side) takes the median of the volume under a box of that
-    radius before anything else: speckle goes, edges stay."""
+    radius before anything else: speckle goes, edges stay.
+
+    shape: true measures the final labels and appends to objects.csv the three axis lengths of the ellipsoid with each
+    object's second moments and its major axis, the surface area (the staircase area of the voxel faces, about 1.5 times a
+    smooth sphere's), the contact area with other labels, the number of neighbours and touches_border.  contacts: true
+    writes contacts.csv beside objects.csv: one row per timepoint and pair of labels that share a face, with the shared
+    faces per axis and their area.  Plain labels under connectivity 6 never share a face; split and grown labels do."""
     input_path, positions = _inputs(input_path, positions)
     _finish(run_segment(input_path, config, output_path, positions, zarr_version, io_backend, compression))
 
@@ -1810,14 +1827,16 @@ def run_segment(input_path, config, output_path, positions=(), zarr_version: str
     """``segment``: every (position, t) volume of ``channel_name`` goes through ``segment.segment_zyx``; the labels are written
     as ``int32`` (the input's ``scale`` and ``translation`` copied), the object tables of a position's timepoints as
     ``<output>/<position>/objects.csv`` (``OBJECT_COLUMNS``, and ``inscribed_radius_um`` behind them where the setting is on;
-    the position's ``(z, y, x)`` scale is the sampling of ``expand_distance`` and of the radius).  Everything is checked before
-    the output store is created; with several ranks the positions are dealt out in turn.  The output is written by this
-    package's own writer."""
+    the position's ``(z, y, x)`` scale is the sampling of ``expand_distance`` and of the radius).  With ``shape: true``
+    ``SHAPE_OBJECT_COLUMNS`` follow behind every other column; with ``contacts: true`` the touching pairs of every timepoint go
+    to ``<output>/<position>/contacts.csv`` (``CONTACT_COLUMNS``; the header alone where nothing touches).  Everything is
+    checked before the output store is created; with several ranks the positions are dealt out in turn.  The output is
+    written by this package's own writer."""
     import csv
 
     import torch
 
-    from .segment import segment_zyx
+    from .segment import contact_table, segment_zyx
     from .settings import SegmentSettings
 
     try:
@@ -1827,17 +1846,28 @@ def run_segment(input_path, config, output_path, positions=(), zarr_version: str
 
     def position(key, array, channel, out, geometry, device, directory):
         scale, translation = geometry
-        rows, counts = [], []
+        rows, counts, touching = [], [], []
         for t in range(int(array.shape[0])):
             vol = np.ascontiguousarray(array.read_volume(t, channel), dtype=np.float32)
             labels, table, n = segment_zyx(torch.as_tensor(vol, device=device), settings, sampling=scale[2:])
             out.write_volume(t, 0, labels.cpu().numpy())
             rows += object_rows(t, table, scale[2:], translation[2:])
             counts.append(int(n))
-        with open(directory / "objects.csv", "w", newline="") as fh:
-            w = csv.writer(fh)
-            w.writerow(OBJECT_COLUMNS + (("inscribed_radius_um",) if settings.inscribed_radius else ()))
-            w.writerows([[repr(v) if isinstance(v, float) else v for v in row] for row in rows])
+            if settings.contacts:
+                c = contact_table(labels, scale[2:])
+                touching += [[int(t), int(a), int(b), *(int(v) for v in f), float(area)]
+                             for a, b, f, area in zip(c["a"], c["b"], c["faces_zyx"], c["area"])]
+
+        def write(name, header, lines):
+            with open(directory / name, "w", newline="") as fh:
+                w = csv.writer(fh)
+                w.writerow(header)
+                w.writerows([[repr(v) if isinstance(v, float) else v for v in row] for row in lines])
+
+        write("objects.csv", OBJECT_COLUMNS + (("inscribed_radius_um",) if settings.inscribed_radius else ())
+              + (SHAPE_OBJECT_COLUMNS if settings.shape else ()), rows)
+        if settings.contacts:
+            write("contacts.csv", CONTACT_COLUMNS, touching)
         return counts
 
     def check_radius(key, geometry):

@@ -28,6 +28,7 @@
 //   lsr_watershed_f32_cpu, lsr_watershed_saddles_f32_cpu
 //                                             <->  the same names without _cpu         (watershed.hip)
 //   lsr_label_overlap_i32_cpu                 <->  lsr_label_overlap_i32               (overlap.hip)
+//   lsr_label_moments_i32_cpu                 <->  lsr_label_moments_i32               (moments.hip)
 //   lsr_grey_morph_f32_cpu                    <->  lsr_grey_morph_f32                  (morphology.hip)
 //   lsr_rank_filter_f32_cpu                   <->  lsr_rank_filter_f32                 (rank.hip)
 //
@@ -1544,6 +1545,39 @@ extern "C" int lsr_label_overlap_i32_cpu(const int32_t* a, const int32_t* b, int
         if (a0 <= 0 || b0 <= 0) continue;
         const unsigned long long pair = ov::pack(a0, b0);
         if (!lsr::pair_insert_host(slots, mask, probes, pair, counts, [](ov::Overlap& slot) { slot.count += 1; })) counts[1] += 1;
+      }
+    }
+  }
+  return LSR_OK;
+}
+
+// ---- label moments (moments.hip): plain sequential code over moments.hpp's rule, record and checks, voxel by voxel (the kernel
+// adds the closed-form sums of whole runs: the two must agree byte for byte) ----
+#include "moments.hpp"
+
+extern "C" int lsr_label_moments_i32_cpu(const int32_t* labels, int64_t Z, int64_t Y, int64_t X, int64_t n_objects, void* table,
+                                         int max_blocks, lsr_stream_t) {
+  namespace mo = lsr::moments;
+  if (int rc = mo::check_moments(labels, Z, Y, X, n_objects, table, max_blocks)) return rc;
+  if (n_objects == 0) return LSR_OK;
+  mo::Moments* rows = static_cast<mo::Moments*>(table);
+  for (int64_t z = 0; z < Z; ++z) {
+    for (int64_t y = 0; y < Y; ++y) {
+      const int32_t* line = labels + (z * Y + y) * X;
+      for (int64_t x = 0; x < X; ++x) {
+        const int32_t l = line[x];
+        if (l < 1 || l > n_objects) continue;
+        mo::Moments& m = rows[l - 1];
+        m.volume += 1;
+        m.s_z += z;
+        m.s_y += y;
+        m.s_x += x;
+        m.m_zz += z * z;
+        m.m_yy += y * y;
+        m.m_xx += x * x;
+        m.m_zy += z * y;
+        m.m_zx += z * x;
+        m.m_yx += y * x;
       }
     }
   }

@@ -10,6 +10,12 @@ numbering is a prefix count), ``csrc/host_twins.hip`` on the CPU; both equal ``s
   mean, minimum, maximum and the intensity-weighted centroid.  The integer columns and the intensity range are exact; the
   float64 sums are atomic adds on the device (within ``n_k * 2^-53 * sum|terms|`` of the exact sum, not bit-reproducible).
 * :func:`filter_objects` -- drop small objects or keep the largest; the kept labels stay consecutive, in their old order.
+* :func:`moment_table` -- per label the exact integer sums of the coordinates and of their products (``csrc/moments.hip``: one
+  launch, runs of equal labels reduced in closed form, a table in LDS per workgroup; the twin in ``csrc/host_twins.hip``).
+* :func:`shape_table` -- axis lengths and the major axis from those moments, exposed faces, staircase surface area, contact
+  area, neighbours and ``touches_border``; :func:`contact_table` -- the pairs of labels that share a face.  PARITY UNPINNED
+  (skimage is not a dependency): the rules in :func:`shape_table`'s docstring are the specification,
+  ``tests/moments_ref.py`` restates them in plain numpy.
 * :func:`segment_zyx` -- on request take the median under a small box (``shrimpy_amd/rank.py``), subtract the background (the white top-hat of ``shrimpy_amd/morphology.py``), threshold (a
   number or multi-Otsu, after an optional Gaussian blur), on request fill the holes of the mask, label, on request split the
   touching objects by a watershed of their depth map (``shrimpy_amd/watershed.py``), measure, filter, and on request grow the
@@ -29,12 +35,17 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["REGION_DTYPE", "tile_shape", "label_volume", "region_table", "filter_objects", "segment_zyx"]
+__all__ = ["REGION_DTYPE", "MOMENTS_DTYPE", "tile_shape", "label_volume", "region_table", "filter_objects", "moments_geometry",
+           "moment_table", "shape_table", "contact_table", "segment_zyx"]
 
 # one record of the object table (csrc/label.hpp ``Region``)
 REGION_DTYPE = np.dtype([("volume", "<i8"), ("sum_zyx", "<i8", (3,)), ("sum_v", "<f8"), ("sum_vzyx", "<f8", (3,)),
                          ("lo", "<i4", (3,)), ("hi", "<i4", (3,)), ("v_min", "<f4"), ("v_max", "<f4")])
 assert REGION_DTYPE.itemsize == 96
+# one record of the moment table (csrc/moments.hpp ``Moments``)
+MOMENT_FIELDS = ("volume", "s_z", "s_y", "s_x", "m_zz", "m_yy", "m_xx", "m_zy", "m_zx", "m_yx")
+MOMENTS_DTYPE = np.dtype([(f, "<i8") for f in MOMENT_FIELDS])
+assert MOMENTS_DTYPE.itemsize == 80
 
 
 def _tile_shape(entry: str) -> tuple[int, int, int]:
@@ -231,6 +242,201 @@ def filter_objects(labels, table: dict, min_volume: int = 0, keep_largest: bool 
     return labels, out, int(kept.sum())
 
 
+def moments_geometry() -> tuple[int, int]:
+    """``(LDS table slots per workgroup, default cap of the grid)`` of the moment kernel (``lsr_label_moments_geometry``)."""
+    out = (ctypes.c_int * 2)()
+    _lib.call("lsr_label_moments_geometry", out)
+    return int(out[0]), int(out[1])
+
+
+def _raw_moments(labels, n: int, _max_blocks: int = 0) -> np.ndarray:
+    """The ``n`` records of ``lsr_label_moments_i32`` as a host structured array (``MOMENTS_DTYPE``)."""
+    import torch
+
+    labels = _check_volume(labels, "labels", torch.int32)
+    n = int(n)
+    if n < 0:
+        raise ValueError(f"n must not be negative, got {n}")
+    z, y, x = _shape3(labels, "labels")
+    if n == 0:
+        return np.zeros((0,), dtype=MOMENTS_DTYPE)
+    table = torch.zeros((n * MOMENTS_DTYPE.itemsize,), dtype=torch.uint8, device=labels.device)     # the host zeroes it
+    _run(labels.device, "lsr_label_moments_i32", labels.data_ptr(), z, y, x, n, table.data_ptr(), int(_max_blocks))
+    return table.cpu().numpy().view(MOMENTS_DTYPE).copy()
+
+
+def moment_table(labels, n: int, _max_blocks: int = 0) -> dict:
+    """The integer moments of the labels ``1 .. n`` of a (Z, Y, X) int32 tensor (CPU or HIP), as a dict of int64 numpy arrays of
+    length ``n``: ``volume``, ``s_z``, ``s_y``, ``s_x`` (sums of the coordinates) and ``m_zz``, ``m_yy``, ``m_xx``, ``m_zy``,
+    ``m_zx``, ``m_yx`` (sums of their products), in absolute voxel indices.  Exact: pure integer arithmetic on the device and in
+    the host twin (``csrc/moments.hpp``).  Labels outside ``1 .. n`` are ignored, a label that no voxel carries has a zero row.
+    ``_max_blocks`` caps the grid (0: the kernel's default; the result does not depend on it)."""
+    raw = _raw_moments(labels, n, _max_blocks)
+    return {f: np.ascontiguousarray(raw[f], dtype=np.int64) for f in MOMENT_FIELDS}
+
+
+def _sampling3(sampling) -> tuple[float, float, float]:
+    s = tuple(float(v) for v in sampling)
+    if len(s) != 3 or not all(np.isfinite(v) and v > 0 for v in s):
+        raise ValueError(f"sampling must be three positive numbers (z, y, x), got {sampling!r}")
+    return s
+
+
+def _face_areas(sampling) -> np.ndarray:
+    """The area of one face perpendicular to z, to y and to x."""
+    sz, sy, sx = sampling
+    return np.asarray([sy * sx, sz * sx, sz * sy], dtype=np.float64)
+
+
+def _self_overlaps(labels, n: int) -> list[dict]:
+    """Per axis ``c`` the overlap table of ``labels`` with itself under the unit shift along ``c`` (``track.label_overlaps``),
+    restricted to the labels ``1 .. n``: every face-adjacent pair of voxels of the volume, once."""
+    from . import track         # (track imports this module)
+
+    tables = []
+    for c in range(3):
+        shift = [0, 0, 0]
+        shift[c] = 1
+        t = track.label_overlaps(labels, labels, tuple(shift))
+        keep = (t["a"] <= n) & (t["b"] <= n)
+        tables.append({k: v[keep] for k, v in t.items()})
+    return tables
+
+
+def _pair_faces(overlaps: list[dict]):
+    """``(a, b, faces_zyx)`` of the pairs ``a < b`` that share a face, sorted by ``(a, b)``: the contact of ``a < b`` along ``c``
+    is ``n_ab(c) + n_ba(c)``."""
+    keys, counts, axes = [], [], []
+    for c, t in enumerate(overlaps):
+        off = t["a"] != t["b"]
+        a, b = t["a"][off], t["b"][off]
+        keys.append(np.minimum(a, b) << 32 | np.maximum(a, b))
+        counts.append(t["count"][off])
+        axes.append(np.full((int(off.sum()),), c, dtype=np.int64))
+    pairs, inverse = np.unique(np.concatenate(keys), return_inverse=True)
+    faces = np.zeros((len(pairs), 3), dtype=np.int64)
+    np.add.at(faces, (inverse.reshape(-1), np.concatenate(axes)), np.concatenate(counts))
+    return (pairs >> 32).astype(np.int64), (pairs & 0xFFFFFFFF).astype(np.int64), faces
+
+
+def contact_table(labels, sampling=(1, 1, 1)) -> dict:
+    """The pairs of labels that share a face: ``{"a", "b", "faces_zyx", "area"}`` with ``a < b``, sorted by ``(a, b)`` --
+    ``faces_zyx`` ((P, 3) int64) counts the shared faces perpendicular to z, to y and to x, exactly; ``area`` (float64) is
+    ``faces_z * sy * sx + faces_y * sz * sx + faces_x * sz * sy`` under ``sampling = (sz, sy, sx)``.  Labels ``<= 0`` are
+    background.  Built from three :func:`shrimpy_amd.track.label_overlaps` calls, on the device the labels are on."""
+    import torch
+
+    labels = _check_volume(labels, "labels", torch.int32)
+    _shape3(labels, "labels")
+    sampling = _sampling3(sampling)
+    a, b, faces = _pair_faces(_self_overlaps(labels, 2 ** 31 - 1))
+    return {"a": a, "b": b, "faces_zyx": faces, "area": faces.astype(np.float64) @ _face_areas(sampling)}
+
+
+def _covariances(m: dict, sampling) -> np.ndarray:
+    """``(n, 3, 3)`` float64: ``C_ab = s_a s_b (N m_ab - S_a S_b) / N^2`` with the numerator in exact integers (int64 where
+    ``N * m`` stays below 2^62, Python integers otherwise) and rounded once, plus ``s_a^2 / 12`` on the diagonal; NaN where
+    ``N == 0``."""
+    vol = m["volume"]
+    n = len(vol)
+    sums = (m["s_z"], m["s_y"], m["s_x"])
+    second = {(0, 0): m["m_zz"], (1, 1): m["m_yy"], (2, 2): m["m_xx"], (0, 1): m["m_zy"], (0, 2): m["m_zx"], (1, 2): m["m_yx"]}
+    # (S_a^2 <= N m_aa, so the diagonal bounds every term of every numerator)
+    wide = n > 0 and max(float(np.max(vol.astype(np.float64) * second[(a, a)].astype(np.float64))) for a in range(3)) >= 2.0 ** 62
+    as_int = (lambda v: v.astype(object)) if wide else (lambda v: v)
+    cov = np.full((n, 3, 3), np.nan, dtype=np.float64)
+    live = vol > 0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        inv_n2 = 1.0 / (vol.astype(np.float64) * vol.astype(np.float64))
+        for (a, b), mab in second.items():
+            numerator = as_int(vol) * as_int(mab) - as_int(sums[a]) * as_int(sums[b])
+            value = numerator.astype(np.float64) * (sampling[a] * sampling[b]) * inv_n2
+            if a == b:
+                value = value + sampling[a] * sampling[a] / 12.0
+            cov[:, a, b] = cov[:, b, a] = np.where(live, value, np.nan)
+    return cov
+
+
+def shape_table(labels, n: int, sampling=(1, 1, 1), bbox=None) -> dict:
+    """The shape and the contacts of the labels ``1 .. n`` ((Z, Y, X) int32, CPU or HIP), one row per label, as a dict of numpy
+    arrays.  ``sampling = (sz, sy, sx)`` is the voxel spacing; lengths and areas are in its units.
+
+    The rules.
+
+    * Moments: :func:`moment_table` (exact integers); its ten columns are returned as they are.
+    * ``covariance`` ((n, 3, 3) float64): ``C_ab = s_a s_b (N m_ab - S_a S_b) / N^2``, the numerator in exact integers and
+      rounded once, plus ``s_a^2 / 12`` on the diagonal -- a voxel counts as a uniform cell, so that a box of ``L`` voxels has
+      exactly the continuous box's variance ``(L s)^2 / 12`` and a single voxel is not degenerate.
+    * ``eigenvalues`` ((n, 3), ``l0 >= l1 >= l2``): ``numpy.linalg.eigh`` of ``C``, clipped at 0.  ``axis_lengths`` ((n, 3):
+      major, mid, minor) ``= 2 sqrt(5 l)``: the full axes of the solid ellipsoid with these second moments.
+    * ``major_axis`` ((n, 3), z y x): the unit eigenvector of ``l0``, its first non-zero component positive (a component of
+      magnitude below ``1e-12`` counts as zero and is returned as 0).
+    * Faces: for the axis ``c`` let ``n_ab(c)`` be the overlap table of the labels with themselves under the unit shift along
+      ``c`` (``track.label_overlaps``).  The exposed faces of ``k`` perpendicular to ``c`` are ``2 volume_k - 2 n_kk(c)``
+      (``faces_zyx``, (n, 3) int64): faces against the background, against another label and against the border of the volume
+      alike.  The contact of ``a < b`` along ``c`` is ``n_ab(c) + n_ba(c)``; ``contact_faces_zyx`` sums a label's contacts,
+      ``n_neighbours`` counts the distinct labels it touches.  All exact.
+    * ``surface_area = faces_z sy sx + faces_y sz sx + faces_x sz sy``: the STAIRCASE area of the voxel surface, which does not
+      converge to a smooth surface's (it is about 1.5 times a sphere's), so no sphericity is derived from it.
+      ``contact_area`` is the same sum over ``contact_faces_zyx``.
+    * ``touches_border`` (bool): the bounding box reaches a face of the volume.  ``bbox`` ((n, 6), :func:`region_table`'s) is
+      measured here unless it is handed in.
+
+    A label that no voxel carries has zero counts, NaN lengths and ``touches_border`` False.
+
+    Not built: intensity-weighted moments, a smoothed (Crofton-weight) area estimator and sphericity, a stand-alone ``measure``
+    command for label stores that ``segment`` did not write, ``label_regions_kernel`` on the moment kernel's form, multi-GPU
+    tables."""
+    import torch
+
+    labels = _check_volume(labels, "labels", torch.int32)
+    shape = _shape3(labels, "labels")
+    sampling = _sampling3(sampling)
+    n = int(n)
+    moments = moment_table(labels, n)
+    vol = moments["volume"]
+    cov = _covariances(moments, sampling)
+    live = vol > 0
+    eigenvalues = np.full((n, 3), np.nan, dtype=np.float64)
+    major = np.full((n, 3), np.nan, dtype=np.float64)
+    if live.any():
+        w, v = np.linalg.eigh(cov[live])                           # ascending
+        eigenvalues[live] = np.clip(w[:, ::-1], 0.0, None)
+        axis = v[:, :, 2]
+        axis = np.where(np.abs(axis) < 1e-12, 0.0, axis)
+        first = np.take_along_axis(axis, np.argmax(axis != 0.0, axis=1)[:, None], axis=1)
+        major[live] = axis * np.where(first < 0.0, -1.0, 1.0)
+    overlaps = _self_overlaps(labels, n)
+    faces = np.zeros((n, 3), dtype=np.int64)
+    for c, t in enumerate(overlaps):
+        same = t["a"] == t["b"]
+        inner = np.zeros((n,), dtype=np.int64)
+        inner[t["a"][same] - 1] = t["count"][same]
+        faces[:, c] = 2 * vol - 2 * inner
+    a, b, pair_faces = _pair_faces(overlaps)
+    contact_faces = np.zeros((n, 3), dtype=np.int64)
+    np.add.at(contact_faces, a - 1, pair_faces)
+    np.add.at(contact_faces, b - 1, pair_faces)
+    neighbours = np.bincount(np.concatenate([a, b]) - 1, minlength=n).astype(np.int64) if n > 0 else np.zeros((0,), np.int64)
+    if bbox is None:
+        bbox = region_table(labels, n)["bbox"]
+    bbox = np.asarray(bbox).reshape(n, 6)
+    areas = _face_areas(sampling)
+    return {
+        "label": np.arange(1, n + 1, dtype=np.int32), **moments,
+        "covariance": cov, "eigenvalues": eigenvalues, "axis_lengths": 2.0 * np.sqrt(5.0 * eigenvalues), "major_axis": major,
+        "faces_zyx": faces, "contact_faces_zyx": contact_faces,
+        "surface_area": faces.astype(np.float64) @ areas, "contact_area": contact_faces.astype(np.float64) @ areas,
+        "n_neighbours": neighbours,
+        "touches_border": live & ((bbox[:, :3] <= 0).any(axis=1) | (bbox[:, 3:] >= np.asarray(shape)).any(axis=1)),
+    }
+
+
+# what `shape: true` adds to segment_zyx's table
+SHAPE_COLUMNS = ("axis_lengths", "major_axis", "surface_area", "contact_area", "n_neighbours", "touches_border", "faces_zyx",
+                 "contact_faces_zyx", "eigenvalues", "covariance") + MOMENT_FIELDS[1:]
+
+
 def segment_zyx(vol, settings, sampling=(1, 1, 1)):
     """Threshold, label, measure and filter one (Z, Y, X) float32 volume by a :class:`~shrimpy_amd.settings.SegmentSettings`:
     ``(labels, table, n)``.  With ``sigma > 0`` the blurred volume is thresholded; with ``threshold: otsu`` the threshold is
@@ -247,7 +453,9 @@ def segment_zyx(vol, settings, sampling=(1, 1, 1)):
     ``expand_distance > 0`` the labels that survive the filter grow into the background by at most that distance (a dropped
     speck claims no space) and the table is that of the grown labels.  With ``inscribed_radius`` the table gains the column
     ``inscribed_radius``: per object the greatest distance of one of its voxels to the nearest background voxel, of the final
-    labels (``+inf`` where the volume has no background)."""
+    labels (``+inf`` where the volume has no background).  With ``shape`` the final labels -- after the filter and the
+    expansion, where ``inscribed_radius`` is measured -- go through :func:`shape_table` and the table gains its columns
+    (``SHAPE_COLUMNS``).  ``contacts`` is the ``segment`` command's: it writes :func:`contact_table` of the returned labels."""
     import torch
 
     from . import dynatrack as D
@@ -294,4 +502,7 @@ def segment_zyx(vol, settings, sampling=(1, 1, 1)):
             depth = distance.distance_transform_labels(labels, sampling, invert=True)
             table["inscribed_radius"] = (region_table(labels, n, depth)["intensity_max"] if n > 0
                                          else np.zeros((0,), dtype=np.float32))
+    if settings.shape:
+        measured = shape_table(labels, n, sampling, bbox=table["bbox"])
+        table.update({k: measured[k] for k in SHAPE_COLUMNS})
     return labels, table, n

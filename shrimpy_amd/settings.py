@@ -580,7 +580,13 @@ class SegmentSettings(_StrictModel):
     ``median_radius`` (a number or ``[z, y, x]``, the same units) replaces the volume by its median under a box of that radius
     (``shrimpy_amd/rank.py``; at most 3 voxels to each side) before all of the above: speckle and hot pixels go, edges and the
     contacts between objects stay where a Gaussian ``sigma`` would round them off.  0, the default, leaves the volume
-    alone."""
+    alone.
+
+    ``shape`` measures the final labels' second moments, faces and contacts (``segment.shape_table``) and adds the axis
+    lengths, the major axis, the staircase surface area, the contact area, the number of neighbours and ``touches_border`` to
+    the table and to ``objects.csv``.  ``contacts`` makes the ``segment`` command write ``contacts.csv``: one row per pair of
+    labels that share a face, with the shared faces per axis and their area.  Under connectivity 6 plain labels never share a
+    face; split (``split``) and grown (``expand_distance``) labels do."""
 
     channel_name: str
     threshold: Union[float, Literal["otsu"]]
@@ -597,6 +603,8 @@ class SegmentSettings(_StrictModel):
     split: bool = False
     split_sigma: NonNegativeFloat = 1.0
     split_min_depth: NonNegativeFloat = 0.0
+    shape: bool = False
+    contacts: bool = False
 
     @field_validator("threshold")
     @classmethod

@@ -79,6 +79,10 @@ def main():
                     "sweep of the grid cap (HIP events, median of 3 calls after a warm-up), beside a device copy of one int32 "
                     "volume and torch.unique of the packed pairs in the same run, with the global atomics per scene estimated "
                     "from a sample of the workgroups' spans; appended to profiles/overlap_config2.jsonl")
+    ap.add_argument("--moments", action="store_true", help="only: ms of the label-moment kernel (csrc/moments.hip) on --rl-grid for "
+                    "the three scenes of --label: as shipped, over a sweep of LDS slots and grid caps, and in the plain form without "
+                    "an LDS table, beside a device copy, lsr_label_regions_f32 without intensities and the three overlap launches of "
+                    "segment.contact_table in the same run; appended to profiles/moments_config2.jsonl")
     ap.add_argument("--edt", action="store_true", help="only: ms per launch of the distance transform (csrc/edt.hip: x, y, z; HIP "
                     "events between the launches, median of 5 calls after a warm-up) on --rl-grid, for bench.synthetic_raw at its "
                     "multi-Otsu threshold, Bernoulli noise at p = 0.3 and an all-foreground volume with one background voxel, "
@@ -136,6 +140,9 @@ def main():
         return
     if args.overlap:
         _overlap(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
+        return
+    if args.moments:
+        _moments(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
         return
     if args.watershed:
         _watershed(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
@@ -915,6 +922,114 @@ def _overlap(args, torch, dev, g, bench, oshape):
              "lds_probes": 16, "alternatives": "the grid cap is swept here; the LDS slot count (2048) and the LDS probe bound (16) "
                                                "are compile-time constants of csrc/overlap.hpp and were not varied"}
     path = ROOT / "profiles" / "overlap_config2.jsonl"
+    with open(path, "a") as f:
+        for r in records:
+            line = json.dumps({**r, **stamp})
+            print(line, flush=True)
+            f.write(line + "\n")
+
+
+MOMENTS_STEP = 1024          # voxels one workgroup takes per stride of its span (csrc/moments.hpp kStep)
+MOMENTS_SLOTS = (64, 128, 256, 512)
+MOMENTS_CAPS = (1024, 4096, 8192, 16384, 65536, 262144)
+MOMENTS_PROBES = 8           # the LDS probe bound (csrc/moments.hpp kLdsProbes)
+MOMENTS_PROBE_SWEEP = (1, 2, 4, 16, 32)
+
+
+def _moments(args, torch, dev, g, bench, oshape):
+    """The label-moment kernel (csrc/moments.hip) at the config-2 deskewed shape on the three scenes of --label, labelled under
+    connectivity 6.  Per scene, each the median of 3 calls after a warm-up between HIP events (the tables zeroed outside the timed
+    region): the kernel as shipped; the sweep of LDS slots and grid caps through the measurement entry, and once the plain form
+    without an LDS table (every run head straight to global atomics); lsr_label_regions_f32 without intensities in the same run;
+    the three overlap launches of segment.contact_table.  The floor is one volume read, 4 bytes per voxel: the device copy of one
+    int32 volume moves twice as much."""
+    from shrimpy_amd import _lib, dynatrack, segment, track
+
+    reps = 3
+    z, y, x = oshape
+    n = z * y * x
+    lds_slots, default_cap = segment.moments_geometry()
+    a = torch.empty(oshape, dtype=torch.int32, device=dev)
+    b = torch.empty_like(a)
+    copy_ms = _median_ms(lambda: b.copy_(a), reps, torch)
+    records = [{"kernel": "device copy of one int32 volume (torch copy_)", "grid": list(oshape), "ms": copy_ms,
+                "GBps": 8.0 * n / copy_ms / 1e6}]
+    del a, b
+    stream = _lib.stream_ptr(dev)
+
+    def scenes():
+        vol = bench.synthetic_raw(oshape, 1000, dev)
+        yield "bead scene (bench.synthetic_raw) at its multi-Otsu threshold", vol, float(dynatrack._multiotsu_threshold(vol, 0))
+        del vol
+        yield "Bernoulli noise, p = 0.3", torch.rand(oshape, device=dev, generator=g), 0.7
+        yield "all foreground", torch.ones(oshape, dtype=torch.float32, device=dev), 0.5
+
+    def timed(launch, clear):
+        times = []
+        for _ in range(reps + 1):
+            clear()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            launch()
+            e1.record()
+            torch.cuda.synchronize()
+            times.append(e0.elapsed_time(e1))
+        return float(np.median(times[1:]))
+
+    def geometry(cap):
+        steps = -(-n // MOMENTS_STEP)
+        span = -(-steps // min(steps, cap)) * MOMENTS_STEP
+        return span, -(-n // span)
+
+    for name, vol, threshold in scenes():
+        labels, n_objects = segment.label_volume(vol, threshold, 6)
+        del vol
+        torch.cuda.empty_cache()
+        base = {"input": name, "grid": list(oshape), "objects": n_objects, "foreground_fraction": float((labels != 0).sum().item()) / n}
+        print(f"# {name}: {n_objects} objects", flush=True)
+        table = torch.zeros(max(n_objects, 1) * segment.MOMENTS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        ms = timed(lambda: _lib.call("lsr_label_moments_i32", labels.data_ptr(), z, y, x, n_objects, table.data_ptr(), 0, stream),
+                   table.zero_)
+        want = table.clone()
+        span, blocks = geometry(default_cap)
+        records.append({**base, "kernel": "lsr_label_moments_i32", "lds_slots": lds_slots, "lds_probes": MOMENTS_PROBES,
+                        "max_blocks": default_cap, "default": True,
+                        "workgroups": blocks, "span_voxels": span, "ms": ms, "bytes_per_voxel": 4.0,
+                        "algorithmic_GBps": 4.0 * n / ms / 1e6, "times_the_copy": ms / copy_ms})
+        forms = [(0, default_cap, 1)] + [(slots, cap, MOMENTS_PROBES) for slots in MOMENTS_SLOTS for cap in MOMENTS_CAPS]
+        forms += [(lds_slots, default_cap, probes) for probes in MOMENTS_PROBE_SWEEP]
+        for slots, cap, probes in forms:
+            ms = timed(lambda: _lib.call("lsr_label_moments_variant_i32", labels.data_ptr(), z, y, x, n_objects, table.data_ptr(),
+                                         cap, slots, probes, stream), table.zero_)
+            assert torch.equal(table, want), "a form of the kernel disagrees with the shipped one"
+            span, blocks = geometry(cap)
+            records.append({**base, "kernel": "lsr_label_moments_variant_i32" + (" (plain form: no LDS table)" if slots == 0 else ""),
+                            "lds_slots": slots, "lds_probes": probes if slots else 0, "max_blocks": cap,
+                            "default": (slots, cap, probes) == (lds_slots, default_cap, MOMENTS_PROBES),
+                            "workgroups": blocks, "span_voxels": span, "ms": ms, "times_the_copy": ms / copy_ms})
+        del table, want
+        regions = torch.zeros(max(n_objects, 1) * segment.REGION_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        ms = timed(lambda: _lib.call("lsr_label_regions_f32", labels.data_ptr(), None, z, y, x, n_objects, regions.data_ptr(), stream),
+                   regions.zero_)
+        records.append({**base, "kernel": "lsr_label_regions_f32 (intensity = NULL)", "ms": ms, "times_the_copy": ms / copy_ms})
+        del regions
+        capacity = 1 << int(4 * min(2 * n_objects, n) + 1024 - 1).bit_length()
+        pairs = torch.zeros(capacity * track.OVERLAP_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        counts = torch.zeros(2, dtype=torch.int32, device=dev)
+        shifts = [(ctypes.c_int32 * 3)(*s) for s in ((1, 0, 0), (0, 1, 0), (0, 0, 1))]
+
+        def contacts():
+            for s in shifts:
+                _lib.call("lsr_label_overlap_i32", labels.data_ptr(), labels.data_ptr(), z, y, x, s, capacity, pairs.data_ptr(),
+                          counts.data_ptr(), 0, stream)
+
+        ms = timed(contacts, pairs.zero_)
+        records.append({**base, "kernel": "the three lsr_label_overlap_i32 launches of segment.contact_table (one table)",
+                        "capacity": capacity, "lost": int(counts.cpu()[1]), "ms": ms, "times_the_copy": ms / copy_ms})
+        del pairs, labels
+        torch.cuda.empty_cache()
+    stamp = {"sources": _lib.kernel_source_sha16(), "device": torch.cuda.get_device_name(dev), "reps": reps, "warmups": 1}
+    path = ROOT / "profiles" / "moments_config2.jsonl"
     with open(path, "a") as f:
         for r in records:
             line = json.dumps({**r, **stamp})
