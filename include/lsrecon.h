@@ -1062,6 +1062,32 @@ int lsr_rank_filter_f32(const float* in, float* out, int64_t Z, int64_t Y, int64
                         float threshold, int variant, lsr_stream_t stream);
 
 /*
+ * Ridge, sheet and blob filters on the eigenvalues of the Hessian (csrc/hessian.hip, shrimpy_amd/hessian.py).  The rule is
+ * stated in csrc/hessian.hpp; PINNED to numpy -- np.gradient twice and np.linalg.eigvalsh, what
+ * skimage.feature.hessian_matrix(use_gaussian_derivatives=False) and hessian_matrix_eigvals compute (tests/hessian_ref.py):
+ *   g, out are contiguous (Z, Y, X) float32 volumes, g already smoothed; (sz, sy, sx) the sampling; `scale` multiplies the
+ *   eigenvalues (the Python layer passes sigma^2).  D_a f along an axis of length n is np.gradient's: the central difference
+ *   over 2 s_a inside, the one-sided difference over s_a at i = 0 and i = n - 1, 0 for n = 1 (numpy raises there).  H_ab =
+ *   D_b (D_a g) for a <= b in float64 from the float32 g (the divisions are multiplications by the float64 reciprocals); at
+ *   the faces the one-sided forms compose as numpy composes them, chosen from the voxel's index, and no position outside the
+ *   volume is read.  l1 <= l2 <= l3 are the eigenvalues of H, with dark = 1 of -H (float64, cyclic Jacobi, within 2^-31.5
+ *   ||H||_F); e_k = float32(scale * l_k).  With m_k = (-e_k > 0) ? -e_k : 0, every measure is a bit-exact float32 function of
+ *   (e1, e2, e3): 0, 1, 2 e1, e2, e3; 3 ridge m1; 4 tube sqrtf(m1 * m2); 5 sheet m1 - m2; 6 blob m3; 7 log -((e1 + e2) + e3).
+ *   A voxel whose stencil -- the voxels its six entries read: itself, two steps along each axis, the in-plane diagonals, as
+ *   the faces allow -- holds a non-finite value gives the canonical quiet NaN 0x7fc00000 under every measure.
+ *   accumulate: 0 stores the response r; 1 stores max(out, r) -- NaN if either is a NaN, else (out >= r) ? out : r -- so that
+ *   calls at several sigmas leave the running maximum.
+ * out must not alias g (LSR_E_ARG); a sampling that is not positive and finite, a non-finite scale and an unknown measure,
+ * dark or accumulate are LSR_E_ARG, a NULL pointer LSR_E_NULL, a non-positive extent LSR_E_SHAPE, more than 2^31 - 1 voxels
+ * LSR_E_UNSUPPORTED; nothing is launched or written then.  One launch, no scratch, no atomics, nothing between workgroups: a
+ * workgroup stages its tile of g and a halo of 2 per side in LDS; g is never written and every voxel of `out` exactly once.
+ * lsr_hessian_tiling: {the halo, the tile's z, y and x extent}.
+ */
+int lsr_hessian_tiling(int tiling[4]);
+int lsr_hessian_response_f32(const float* g, float* out, int64_t Z, int64_t Y, int64_t X, double sz, double sy, double sx,
+                             double scale, int measure, int dark, int accumulate, lsr_stream_t stream);
+
+/*
  * Splitting touching objects: a watershed by steepest ascent (csrc/watershed.hip, shrimpy_amd/watershed.py).  PARITY
  * UNPINNED: no upstream is pinned, the rule IS the specification (csrc/watershed.hpp; tests/watershed_ref.py restates it).
  *   objects (int32, Z * Y * X): values <= 0 are background.  surface (float32): its values compare by the order-preserving
@@ -1319,6 +1345,11 @@ int lsr_grey_morph_f32_cpu(const float* in, float* out, int64_t Z, int64_t Y, in
  * kernel's bits.  Every pointer HOST memory; `variant` is accepted and ignored. */
 int lsr_rank_filter_f32_cpu(const float* in, float* out, int64_t Z, int64_t Y, int64_t X, int rz, int ry, int rx, int rank, int op,
                             float threshold, int variant, lsr_stream_t stream);
+
+/* ... of the Hessian eigenvalue responses (csrc/hessian.hip): the same derivative, entries, Jacobi sweeps, responses and
+ * store (csrc/hessian.hpp), so `out` is the kernel's bits.  Every pointer HOST memory. */
+int lsr_hessian_response_f32_cpu(const float* g, float* out, int64_t Z, int64_t Y, int64_t X, double sz, double sy, double sx,
+                                 double scale, int measure, int dark, int accumulate, lsr_stream_t stream);
 
 /* ... of the mutual-information metric (csrc/estimate_mi.hip): the per-sample rule of csrc/mi_sample.hpp on both sides.
  * The histogram and the count are the kernel's bits; the gradient rows are sums over lsr_affine_mi_gradient_blocks()

@@ -186,6 +186,9 @@ SIGNATURES: dict[str, list] = {
     "lsr_grey_morph_f32": [_c_f32p, _c_f32p, _i64, _i64, _i64, _int, _int, _int, _int, ctypes.c_void_p, _stream],
     "lsr_rank_filter_tiling": [ctypes.POINTER(ctypes.c_int)],
     "lsr_rank_filter_f32": [_c_f32p, _c_f32p, _i64, _i64, _i64, _int, _int, _int, _int, _int, _f32, _int, _stream],
+    "lsr_hessian_tiling": [ctypes.POINTER(ctypes.c_int)],
+    "lsr_hessian_response_f32": [_c_f32p, _c_f32p, _i64, _i64, _i64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                 ctypes.c_double, _int, _int, _int, _stream],
     "lsr_watershed_tile_shape": [ctypes.POINTER(ctypes.c_int)],
     "lsr_watershed_scratch_bytes": [_i64, _i64, _i64],
     "lsr_watershed_f32": [ctypes.c_void_p, _c_f32p, _i64, _i64, _i64, _int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _stream],
@@ -296,7 +299,9 @@ for _name in ("lsr_deskew_f32", "lsr_deskew_u16", "lsr_deskew_cval", "lsr_affine
               # ... and of the grey morphology (csrc/morphology.hip)
               "lsr_grey_morph_f32",
               # ... and of the rank filters (csrc/rank.hip)
-              "lsr_rank_filter_f32"):
+              "lsr_rank_filter_f32",
+              # ... and of the Hessian eigenvalue responses (csrc/hessian.hip)
+              "lsr_hessian_response_f32"):
     SIGNATURES[_name + "_cpu"] = SIGNATURES[_name]
 # entries whose answer is a byte count that can pass 2^31 (a negative value is a status)
 RETURNS_INT64 = ("lsr_edt_scratch_bytes", "lsr_watershed_scratch_bytes", "lsr_grey_morph_scratch_bytes")

@@ -19,6 +19,7 @@ CPU path (biahub's; the reference's own CLI has only ``acquire`` and ``gui``,
     python -m shrimpy_amd.cli stitch      -i tiles.zarr -c stitch.yml    -o stitched.zarr
     python -m shrimpy_amd.cli subtract-background -i store.zarr -c background.yml -o flat.zarr
     python -m shrimpy_amd.cli despeckle   -i store.zarr -c despeckle.yml -o clean.zarr
+    python -m shrimpy_amd.cli enhance     -i store.zarr -c enhance.yml   -o tubes.zarr
 
 Every (position, timepoint, channel) volume is an independent unit.  Launched under
 ``python -m torch.distributed.run --nproc-per-node N`` each rank takes the units
@@ -1403,6 +1404,106 @@ def run_despeckle(input_path, config, output_path, positions=(), zarr_version: s
                      levels=levels, level_factor_z=level_factor_z)
 
 
+class _EnhanceStep:
+    """``run_store``'s step of the ``enhance`` command: ``for_unit`` hands out the multi-scale Hessian response at the scales
+    of the unit's position (``named`` channels) or a plain copy (every other channel); the volume keeps its shape."""
+
+    def __init__(self, scales_of, settings, named: bool, raw_shape, _settings, device):
+        self.device = device
+        self.output_shape = tuple(int(n) for n in raw_shape)
+        self._scales_of, self._enhance, self._named = scales_of, settings, named
+
+    def for_unit(self, unit):
+        import torch
+
+        from . import hessian
+
+        scales = self._scales_of(unit.position) if self._named else None
+        s = self._enhance
+
+        def step(raw):
+            vol = torch.as_tensor(raw, device=self.device).to(torch.float32).contiguous()
+            if scales is None:
+                return vol
+            return hessian.enhance(vol, s.measure, scales[0], scales[1], s.dark)
+
+        return step
+
+
+@cli.command("enhance", cls=_eat_all_command("-i", "--input-position-dirpaths"))
+@_common
+def enhance(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error, levels,
+            level_factor_z):
+    """Enhance tubes, sheets or blobs: a filter on the eigenvalues of the smoothed Hessian (config: an EnhanceSettings YAML).
+
+    Every volume of the channels `channels` is replaced by its `measure` -- ridge, tube (Sato's tubeness), sheet, blob, log
+    (the scale-normalised Laplacian) or an eigenvalue e1 <= e2 <= e3 --, the maximum over the scales `sigmas_um`
+    (micrometres, at the position's scale) or `sigmas` (voxels); dark: true looks for dark structures.  The other channels
+    are copied."""
+    input_path, positions = _inputs(input_path, positions)
+    _finish(run_enhance(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error,
+                        **_pyramid_options(levels, level_factor_z)))
+
+
+def run_enhance(input_path, config, output_path, positions=(), zarr_version: str = "0.5", resume: bool = False,
+                io_backend: str = "auto", compression=None, on_error: str = "raise", levels: int = 1,
+                level_factor_z: int = 2) -> dict:
+    """``enhance``: every ``(position, t, c)`` volume of a named channel goes through ``hessian.enhance`` at the settings'
+    scales -- ``sigmas_um`` at the position's ``(z, y, x)`` scale, ``sigmas`` on the voxel grid --; the other channels are
+    copied.  Everything is checked before the output store is created: the settings, the channels, and the blur radius of
+    every scale of every position against the blur's cap."""
+    from . import hessian
+    from .io.omezarr import position_scale
+    from .settings import EnhanceSettings
+
+    try:
+        settings = EnhanceSettings.from_yaml(config)
+    except (ValueError, TypeError) as exc:
+        raise click.ClickException(f"{config}: {exc}") from exc
+    channels = list(settings.channels)
+    if not channels:
+        raise click.ClickException(f"{config}: channels is empty: nothing to filter")
+    src, src_positions = _open_source(Path(input_path), io_backend)
+    try:
+        missing = [p for p in positions if p not in src_positions]
+        if missing:
+            raise click.ClickException(f"positions {missing} not found; available: {list(src_positions)}")
+        keys = [k for k in src_positions if not positions or k in positions]
+        if not keys:
+            raise click.ClickException("no positions to process")
+        names = list(src_positions[keys[0]].channel_names)
+        unknown = [n for n in channels if n not in names]
+        if unknown:
+            raise click.ClickException(f"channels {unknown} not in the store (it has {names})")
+        scales = {}
+        for key in keys:
+            scale = tuple(float(v) for v in position_scale(src_positions[key])[-3:])
+            try:
+                scales[key] = settings.scales(scale)
+                for sigma in scales[key][0]:
+                    hessian.blur_radii(sigma, scales[key][1])
+            except ValueError as exc:
+                raise click.ClickException(f"position {key}: {exc}") from exc
+    finally:
+        close = getattr(src, "close", None)
+        if close:
+            close()
+    # run_store's channel plan: the named channels take the first step, the others the second
+    plan = ReconstructSettings(registration=RegisterSettings(source_channel_names=channels,
+                                                             affine_transform_zyx=np.eye(4).tolist()))
+
+    def factory(raw_shape, plan_settings, device):
+        return _EnhanceStep(scales.__getitem__, settings, plan_settings.registration is not None, raw_shape, plan_settings,
+                            device)
+
+    return run_store(input_path, output_path, plan, tuple(keys) if positions else (), zarr_version,
+                     reconstructor_factory=factory, resume=resume, io_backend=io_backend, compression=compression,
+                     on_error=on_error,
+                     fingerprint_extra={"enhance": {"settings": settings.model_dump(mode="json"),
+                                                    "scales": {k: [list(v[0]), list(v[1])] for k, v in scales.items()}}},
+                     levels=levels, level_factor_z=level_factor_z)
+
+
 def _position_translation(position) -> tuple[float, ...]:
     """(T, C, Z, Y, X) NGFF ``translation`` of a position's level 0 (zeros when absent)."""
     ms = position.zattrs.get("multiscales", [{}])
@@ -1811,7 +1912,9 @@ def segment(input_path, config, output_path, positions, zarr_version, io_backend
     volume under a box of that radius instead of the volume: a slowly varying background goes, objects narrower than the
     window stay.  fill_holes: true fills the holes of the thresholded mask before it is labelled.  median_radius
     (micrometres, a number or [z, y, x]; at most 3 voxels to each side) takes the median of the volume under a box of that
-    radius before anything else: speckle goes, edges stay.
+    radius before anything else: speckle goes, edges stay.  enhance ({measure: ridge | tube | sheet | blob | log, sigmas_um:
+    [...] or sigmas: [...] in voxels, dark: false}) thresholds a ridge, sheet or blob response of the smoothed Hessian's
+    eigenvalues, the maximum over the sigmas, instead of the intensity: tubes, membranes and puncta on an uneven background.
 
     shape: true measures the final labels and appends to objects.csv the three axis lengths of the ellipsoid with each
     object's second moments and its major axis, the surface area (the staircase area of the voxel faces, about 1.5 times a
@@ -1883,6 +1986,15 @@ def run_segment(input_path, config, output_path, positions=(), zarr_version: str
             rank.half_widths_of(settings.median_radius, geometry[0][2:])
         except ValueError as exc:
             raise click.ClickException(f"position {key}: median_radius: {exc}") from exc
+        if settings.enhance is not None:
+            from . import hessian
+
+            sigmas, grid = settings.enhance.scales(geometry[0][2:])
+            try:
+                for sigma in sigmas:
+                    hessian.blur_radii(sigma, grid)
+            except ValueError as exc:
+                raise click.ClickException(f"position {key}: enhance: {exc}") from exc
 
     return _run_object_store(input_path, output_path, positions, zarr_version, io_backend, compression, settings.channel_name,
                              "_labels", "objects", position, check_geometry=check_radius)

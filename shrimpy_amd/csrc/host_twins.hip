@@ -31,6 +31,7 @@
 //   lsr_label_moments_i32_cpu                 <->  lsr_label_moments_i32               (moments.hip)
 //   lsr_grey_morph_f32_cpu                    <->  lsr_grey_morph_f32                  (morphology.hip)
 //   lsr_rank_filter_f32_cpu                   <->  lsr_rank_filter_f32                 (rank.hip)
+//   lsr_hessian_response_f32_cpu              <->  lsr_hessian_response_f32            (hessian.hip)
 //
 // Arithmetic (what "the same" means):
 //   resamplers -- the text the kernels compile (resample.hpp): coordinates, axis taps with their weights and the
@@ -1623,6 +1624,27 @@ extern "C" int lsr_rank_filter_f32_cpu(const float* in, float* out, int64_t Z, i
     for (int64_t row = first; row < last; ++row) {
       const int64_t z = row / Y, y = row - z * Y;
       for (int64_t x = 0; x < X; ++x) out[row * X + x] = rk::voxel_host(in, Z, Y, X, z, y, x, rz, ry, rx, rank, op, threshold);
+    }
+  });
+  return LSR_OK;
+}
+
+// ---- Hessian eigenvalue responses (hessian.hip): the same derivative, entries, Jacobi sweeps, responses and store (hessian.hpp),
+// a row of voxels per step; the loads go to the volume itself ----
+#include "hessian.hpp"
+
+extern "C" int lsr_hessian_response_f32_cpu(const float* g, float* out, int64_t Z, int64_t Y, int64_t X, double sz, double sy,
+                                            double sx, double scale, int measure, int dark, int accumulate, lsr_stream_t) {
+  namespace hs = lsr::hessian;
+  if (int rc = hs::check_hessian(g, out, Z, Y, X, sz, sy, sx, scale, measure, dark, accumulate)) return rc;
+  const hs::Recip recip = hs::recip_of(sz, sy, sx);
+  lsr::parallel_ranges(Z * Y, [&](int64_t first, int64_t last) {
+    for (int64_t row = first; row < last; ++row) {
+      const int64_t z = row / Y, y = row - z * Y;
+      for (int64_t x = 0; x < X; ++x) {
+        const float r = hs::voxel_host(g, Z, Y, X, z, y, x, recip, scale, measure, dark);
+        out[row * X + x] = accumulate ? hs::greater_of(out[row * X + x], r) : r;
+      }
     }
   });
   return LSR_OK;

@@ -444,7 +444,9 @@ def segment_zyx(vol, settings, sampling=(1, 1, 1)):
     With ``background_radius > 0`` the white top-hat of ``vol`` under a box of that radius (in the units of ``sampling``,
     ``shrimpy_amd/morphology.py``) is what is blurred and thresholded; with ``fill_holes`` the mask ``work > threshold`` is
     filled (``scipy.ndimage.binary_fill_holes``) before it is labelled, for every ``connectivity``.  With ``median_radius > 0``
-    the median of ``vol`` under a box of that radius (``shrimpy_amd/rank.py``) takes ``vol``'s place before all of that.
+    the median of ``vol`` under a box of that radius (``shrimpy_amd/rank.py``) takes ``vol``'s place before all of that.  With
+    ``enhance`` the multi-scale Hessian response of what those two left (``shrimpy_amd/hessian.py``) is what is blurred and
+    thresholded.
 
     ``sampling = (sz, sy, sx)`` is the voxel spacing the distance settings measure in (``shrimpy_amd/distance.py``).  With
     ``split`` the labelled objects are split before anything else sees them (``watershed.split_touching``: the watershed of
@@ -472,6 +474,11 @@ def segment_zyx(vol, settings, sampling=(1, 1, 1)):
         from . import morphology
 
         work = morphology.subtract_background(work, radius, sampling)
+    if settings.enhance is not None:
+        from . import hessian
+
+        sigmas, grid = settings.enhance.scales(sampling)
+        work = hessian.enhance(work, settings.enhance.measure, sigmas, grid, settings.enhance.dark)
     work = D._gaussian_blur_3d(work, float(settings.sigma)) if settings.sigma > 0 else work
     if settings.threshold == "otsu":
         threshold = D._multiotsu_threshold(work, int(settings.otsu_component))

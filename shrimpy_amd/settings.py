@@ -544,6 +544,41 @@ class StitchSettings(_StrictModel):
         return v
 
 
+class EnhanceSettings(_StrictModel):
+    """Ridge, sheet and blob filters on the eigenvalues of the Gaussian-smoothed Hessian (``shrimpy_amd/hessian.py``; the
+    ``enhance`` command and ``SegmentSettings.enhance``).
+
+    ``measure``: ``ridge`` (the strongest negative curvature: sheets, tubes and blobs), ``tube`` (Sato's tubeness), ``sheet``
+    (a bright plate), ``blob`` (negative curvature in every direction), ``log`` (the scale-normalised Laplacian, bright
+    positive), or an eigenvalue itself, ``e1 <= e2 <= e3``.  The response is the maximum over the scales given by exactly one
+    of ``sigmas_um`` -- in the units of the position's scale (micrometres), blurred and differentiated at that scale -- and
+    ``sigmas`` -- in voxels, on the voxel grid.  ``dark: true`` looks for dark structures on a bright background.  ``channels``
+    names the channels the ``enhance`` command filters (the others are copied); ``segment`` ignores it."""
+
+    channels: list[str] = []
+    measure: Literal["e1", "e2", "e3", "ridge", "tube", "sheet", "blob", "log"]
+    sigmas_um: Optional[list[PositiveFloat]] = None
+    sigmas: Optional[list[PositiveFloat]] = None
+    dark: bool = False
+
+    @model_validator(mode="after")
+    def _check_sigmas(self):
+        if (self.sigmas_um is None) == (self.sigmas is None):
+            raise ValueError("exactly one of sigmas_um and sigmas must be given")
+        values = self.sigmas if self.sigmas_um is None else self.sigmas_um
+        if not values:
+            raise ValueError("sigmas is empty: no scale to filter at")
+        if not all(np.isfinite(v) for v in values):
+            raise ValueError("sigmas must be finite")
+        return self
+
+    def scales(self, sampling) -> tuple[list[float], tuple[float, float, float]]:
+        """``(sigmas, sampling)`` for ``hessian.enhance``: ``sigmas_um`` at ``sampling``, ``sigmas`` on the voxel grid."""
+        if self.sigmas_um is not None:
+            return [float(v) for v in self.sigmas_um], tuple(float(s) for s in sampling)
+        return [float(v) for v in self.sigmas], (1.0, 1.0, 1.0)
+
+
 class SegmentSettings(_StrictModel):
     """Connected-component segmentation of one channel (``shrimpy_amd/segment.py``, the ``segment`` command).
 
@@ -582,6 +617,12 @@ class SegmentSettings(_StrictModel):
     contacts between objects stay where a Gaussian ``sigma`` would round them off.  0, the default, leaves the volume
     alone.
 
+    ``enhance`` (an :class:`EnhanceSettings` without ``channels``) replaces what is thresholded by a ridge, sheet or blob
+    response of the Hessian's eigenvalues (``shrimpy_amd/hessian.py``), after ``median_radius`` and ``background_radius`` and
+    before ``sigma`` and the threshold: tubes, membranes and puncta that no threshold of the intensity separates from an
+    uneven background.  ``threshold`` -- a number or ``otsu`` -- then applies to the response.  Unset, the default, nothing
+    changes.
+
     ``shape`` measures the final labels' second moments, faces and contacts (``segment.shape_table``) and adds the axis
     lengths, the major axis, the staircase surface area, the contact area, the number of neighbours and ``touches_border`` to
     the table and to ``objects.csv``.  ``contacts`` makes the ``segment`` command write ``contacts.csv``: one row per pair of
@@ -592,6 +633,7 @@ class SegmentSettings(_StrictModel):
     threshold: Union[float, Literal["otsu"]]
     median_radius: Union[NonNegativeFloat, tuple[NonNegativeFloat, NonNegativeFloat, NonNegativeFloat]] = 0.0
     background_radius: Union[NonNegativeFloat, tuple[NonNegativeFloat, NonNegativeFloat, NonNegativeFloat]] = 0.0
+    enhance: Optional[EnhanceSettings] = None
     fill_holes: bool = False
     sigma: NonNegativeFloat = 0.0
     otsu_component: NonNegativeInt = 0

@@ -97,6 +97,12 @@ def main():
                     "again on the generic path (variant = 1), and remove_bright at (0, 1, 1) (HIP events, median of 3 calls after a "
                     "warm-up), beside a device copy of one volume and grey_erosion at the same half-widths in the same run; "
                     "appended to profiles/rank_config2.jsonl")
+    ap.add_argument("--hessian", action="store_true", help="only: ms of the Hessian-eigenvalue kernel (csrc/hessian.hip) on --rl-grid "
+                    "for the bench's bead scene blurred at sigma 1.5: e1, tube and log with and without accumulate, the three blur "
+                    "launches of one scale, enhance at three sigmas end to end (HIP events, median of 3 calls after a warm-up), "
+                    "beside a device copy of one volume, the torch fallback (torch.gradient + torch.linalg.eigvalsh) on a shape it "
+                    "fits in memory, and the worst eigenvalue error against numpy on a crop; appended to "
+                    "profiles/hessian_config2.jsonl")
     ap.add_argument("--flatfield", action="store_true", help="only: ms of the flat-field median (csrc/flatfield.hip, + mean) on the "
                     "config-2 raw shape for its three variants -- integer counts as float32, float values, uint16 counts --, each "
                     "timed --flatfield-repeats times (a repetition: the mean of --reps calls between HIP events after a warm-up), "
@@ -149,6 +155,9 @@ def main():
         return
     if args.edt:
         _edt(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
+        return
+    if args.hessian:
+        _hessian(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
         return
     if args.rank:
         _rank(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
@@ -1243,6 +1252,103 @@ def _rank(args, torch, dev, g, bench, oshape):
                         "bytes_per_voxel": 8.0 * launches, "copy_time_ratio": ms / copy_ms})
     stamp = {"sources": _lib.kernel_source_sha16(), "device": torch.cuda.get_device_name(dev), "reps": reps, "warmups": 1}
     path = ROOT / "profiles" / "rank_config2.jsonl"
+    with open(path, "a") as f:
+        for rec in records:
+            line = json.dumps({**rec, **stamp})
+            print(line, flush=True)
+            f.write(line + "\n")
+
+
+def _hessian(args, torch, dev, g, bench, oshape):
+    """Hessian-eigenvalue responses (csrc/hessian.hip) at the config-2 deskewed shape on the bench's bead scene blurred at sigma
+    1.5: one launch that moves 8 algorithmic bytes per voxel (one read, one write; 12 with accumulate) and does its arithmetic in
+    float64.  Beside it, in the same run, the floor -- a device copy of one volume --, the three blur launches of one scale,
+    enhance at three sigmas end to end (three blurs and three launches, two blur buffers and the output allocated inside), the
+    torch fallback (torch.gradient nine times, torch.linalg.eigvalsh on float64 matrices) on a shape it fits in memory, and the
+    worst eigenvalue error of the device against np.gradient / np.linalg.eigvalsh in float64 on a crop of the scene, in units
+    of the bound 2^-23 scale ||H||_F."""
+    from shrimpy_amd import _lib, hessian
+
+    reps = 3
+    z, y, x = oshape
+    n = z * y * x
+    vol = bench.synthetic_raw(oshape, 1000, dev)
+    out = torch.empty_like(vol)
+    copy_ms = _median_ms(lambda: out.copy_(vol), reps, torch)
+    records = [{"kernel": "device copy of a float32 volume (torch copy_)", "grid": list(oshape), "ms": copy_ms,
+                "GBps": 8.0 * n / copy_ms / 1e6}]
+    sigma, sampling = 1.5, (1.0, 1.0, 1.0)
+    buffers = hessian._buffers(vol)
+    blur_ms = _median_ms(lambda: hessian._blur(vol, sigma, sampling, buffers), reps, torch)
+    records.append({"kernel": "lsr_blur_reflect_f32: the three launches of one scale (taps made inside)", "grid": list(oshape),
+                    "sigma": sigma, "radii": list(hessian.blur_radii(sigma, sampling)), "ms": blur_ms, "bytes_per_voxel": 24.0,
+                    "copy_time_ratio": blur_ms / copy_ms})
+    blurred = hessian._blur(vol, sigma, sampling, buffers)
+
+    def respond(measure, accumulate):
+        _lib.call("lsr_hessian_response_f32", blurred.data_ptr(), out.data_ptr(), z, y, x, *(ctypes.c_double(s) for s in sampling),
+                  ctypes.c_double(sigma * sigma), hessian.MEASURES[measure], 0, accumulate, _lib.stream_ptr(dev))
+
+    base = {"input": "bead scene (bench.synthetic_raw) blurred at sigma 1.5", "grid": list(oshape)}
+    for measure in ("e1", "tube", "log"):
+        for accumulate in (0, 1):
+            out.zero_()
+            ms = _median_ms(lambda: respond(measure, accumulate), reps, torch)
+            bytes_per_voxel = 12.0 if accumulate else 8.0
+            records.append({**base, "kernel": f"lsr_hessian_response_f32: {measure}, accumulate = {accumulate}", "measure": measure,
+                            "accumulate": accumulate, "ms": ms, "bytes_per_voxel": bytes_per_voxel,
+                            "algorithmic_GBps": bytes_per_voxel * n / ms / 1e6, "copy_time_ratio": ms / copy_ms})
+    sigmas = (1.0, 1.5, 2.0)
+    ms = _median_ms(lambda: hessian.enhance(vol, "tube", sigmas, sampling), reps, torch)
+    records.append({"kernel": "hessian.enhance: tube at three sigmas end to end (9 blur launches, 3 kernel launches)",
+                    "input": "bead scene (bench.synthetic_raw)", "grid": list(oshape), "sigmas": list(sigmas), "ms": ms,
+                    "copy_time_ratio": ms / copy_ms})
+    # the torch fallback, on a crop it fits in memory (the (Z, Y, X, 3, 3) float64 matrices of the whole volume are 57 GB)
+    small = (64, 256, 256)
+    crop = blurred[:small[0], :small[1], :small[2]].contiguous()
+
+    def fallback():
+        g64 = crop.double()
+        first = torch.gradient(g64)
+        H = torch.empty(small + (3, 3), dtype=torch.float64, device=dev)
+        for a in range(3):
+            for b in range(a, 3):
+                H[..., a, b] = H[..., b, a] = torch.gradient(first[a], dim=b)[0]
+        return (sigma * sigma * torch.linalg.eigvalsh(H)).float()
+
+    small_out = torch.empty_like(crop)
+
+    def small_kernel():
+        _lib.call("lsr_hessian_response_f32", crop.data_ptr(), small_out.data_ptr(), *small, *(ctypes.c_double(s) for s in sampling),
+                  ctypes.c_double(sigma * sigma), 0, 0, 0, _lib.stream_ptr(dev))
+
+    records.append({"kernel": "torch fallback: torch.gradient x 9 + torch.linalg.eigvalsh (float64), all three eigenvalues",
+                    "grid": list(small), "ms": _median_ms(fallback, reps, torch)})
+    records.append({"kernel": "lsr_hessian_response_f32: e1, accumulate = 0 (one of the three launches the fallback stands for)",
+                    "grid": list(small), "ms": _median_ms(small_kernel, reps, torch)})
+    # the worst eigenvalue error against numpy in float64, in units of 2^-23 scale ||H||_F, on a crop
+    tiny = (40, 48, 56)
+    g = blurred[:tiny[0], :tiny[1], :tiny[2]].contiguous()
+    g64 = g.cpu().numpy().astype(np.float64)
+    first = np.gradient(g64)
+    H = np.empty(tiny + (3, 3))
+    for a in range(3):
+        for b in range(a, 3):
+            H[..., a, b] = H[..., b, a] = np.gradient(first[a], axis=b)
+    want, norm = sigma * sigma * np.linalg.eigvalsh(H), sigma * sigma * np.sqrt((H * H).sum(axis=(-1, -2)))
+    worst = 0.0
+    tiny_out = torch.empty_like(g)
+    for k in range(3):
+        _lib.call("lsr_hessian_response_f32", g.data_ptr(), tiny_out.data_ptr(), *tiny, *(ctypes.c_double(s) for s in sampling),
+                  ctypes.c_double(sigma * sigma), k, 0, 0, _lib.stream_ptr(dev))
+        err = np.abs(tiny_out.cpu().numpy().astype(np.float64) - want[..., k])
+        keep = norm > 0
+        worst = max(worst, float(np.max(err[keep] / (2.0 ** -23 * norm[keep]))))
+        assert np.all(err <= 2.0 ** -23 * norm), "the eigenvalue bound"
+    records.append({"kernel": "lsr_hessian_response_f32: worst eigenvalue error against np.gradient / np.linalg.eigvalsh (float64)",
+                    "grid": list(tiny), "worst_error_over_bound": worst, "bound": "2^-23 scale ||H||_F"})
+    stamp = {"sources": _lib.kernel_source_sha16(), "device": torch.cuda.get_device_name(dev), "reps": reps, "warmups": 1}
+    path = ROOT / "profiles" / "hessian_config2.jsonl"
     with open(path, "a") as f:
         for rec in records:
             line = json.dumps({**rec, **stamp})
