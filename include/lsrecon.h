@@ -1183,6 +1183,43 @@ int lsr_label_moments_variant_i32(const int32_t* labels, int64_t Z, int64_t Y, i
                                   int max_blocks, int lds_slots, int lds_probes, lsr_stream_t stream);
 
 /*
+ * The intensities every object of a label volume holds in another volume (csrc/intensity.hip; the rule is stated in
+ * csrc/intensity.hpp): what shrimpy_amd/segment.py: intensity_table and the `measure` command read.  No upstream is pinned;
+ * tests/intensity_ref.py restates the rule in numpy.
+ *
+ * lsr_label_intensity_f32 / _u16: labels is an int32 (Z, Y, X) volume, v a float32 / uint16 volume of the same shape (device
+ * memory).  For every voxel (z, y, x) with 1 <= labels[i] <= n_objects, record labels[i] - 1 of `table` gains 1 (count), v,
+ * v^2, v z, v y, v x (sum_v, sum_vv, sum_vz, sum_vy, sum_vx; absolute voxel indices) and v (v_min, v_max).  `table` (device
+ * memory, WHICH THE CALLER HAS ZEROED) is n_objects records of 64 bytes: count (int64), the five sums (float64 for float32
+ * values, uint64 for uint16 values), v_min and v_max (float32, or uint32 holding the value), 8 bytes of padding that stay zero.
+ * Labels outside 1 .. n_objects are ignored; a label that no voxel carries keeps a zero record.
+ * float32: count, v_min and v_max are exact; the extremes are ordered as lsr_label_regions_f32 orders them (-0.0 below +0.0; a
+ * NaN outside the infinities on the side of its sign bit).  Every float64 sum is within 2 n_k 2^-53 sum|terms| of the exact sum
+ * of its exact terms (n_k: the object's voxels), in atomic adds whose order is not fixed; a non-finite voxel follows IEEE
+ * arithmetic into its own object's sums only.  uint16: pure integer arithmetic, independent of the order of execution.
+ * max_blocks caps the grid (0: the default of lsr_label_intensity_geometry); only the order of the float64 adds depends on it.
+ * Refused before any launch and with nothing read or written: LSR_E_ARG for a NULL pointer, a non-positive extent,
+ * n_objects < 0, max_blocks < 0 or a table that overlaps labels or v; LSR_E_UNSUPPORTED for more than 2^31 - 1 voxels and, for
+ * uint16 values, for 65535 * Z*Y*X * max(Z, Y, X) >= 2^64, where a sum could wrap.  n_objects == 0 returns at once.
+ * Two launches: each workgroup walks one contiguous span of both volumes, finds the runs of equal labels inside a row by one
+ * ballot, reduces a run's sums and extremes by shuffles restricted to the run, accumulates in a table in LDS (64-bit LDS
+ * atomic adds, the hardware's float64 add among them) and flushes it once; a finishing launch over the records decodes the
+ * extremes.  Shared words are touched by atomics only, nothing waits for anything.
+ * lsr_label_intensity_geometry: out[0] = the slots of one workgroup's LDS table, out[1] = the default cap of the grid.
+ */
+int lsr_label_intensity_geometry(int out[2]);
+int lsr_label_intensity_f32(const int32_t* labels, const float* v, int64_t Z, int64_t Y, int64_t X, int64_t n_objects, void* table,
+                            int max_blocks, lsr_stream_t stream);
+int lsr_label_intensity_u16(const int32_t* labels, const uint16_t* v, int64_t Z, int64_t Y, int64_t X, int64_t n_objects,
+                            void* table, int max_blocks, lsr_stream_t stream);
+/* measurement only (tools/bench_kernels.py --intensity): the same kernel (v is uint16 where value_is_u16 != 0, float32
+ * otherwise) with lds_slots slots in the LDS table (a power of two up to 512) probed over at most lds_probes (1 .. 512) slots,
+ * or with lds_slots == 0 the plain form in which every run head goes to the global record directly */
+int lsr_label_intensity_variant(const int32_t* labels, const void* v, int value_is_u16, int64_t Z, int64_t Y, int64_t X,
+                                int64_t n_objects, void* table, int max_blocks, int lds_slots, int lds_probes,
+                                lsr_stream_t stream);
+
+/*
  * Host twins (csrc/host_twins.hip): the same signatures with HOST pointers, the same argument checks and the
  * same arithmetic in the same order, so the results equal the device entry points' bit for bit.  They serve
  * the boxes where the reference itself resolves to the CPU (shrimpy/preprocessing.py:78-82 -- its CI has no
@@ -1334,6 +1371,15 @@ int lsr_label_overlap_i32_cpu(const int32_t* a, const int32_t* b, int64_t Z, int
  * and otherwise unused. */
 int lsr_label_moments_i32_cpu(const int32_t* labels, int64_t Z, int64_t Y, int64_t X, int64_t n_objects, void* table,
                               int max_blocks, lsr_stream_t stream);
+
+/* ... of the label intensities (csrc/intensity.hip): plain sequential code over the same rule, records and checks
+ * (csrc/intensity.hpp), voxel by voxel.  uint16: the kernel's records byte for byte.  float32: the kernel's count and extremes;
+ * the float64 sums add the same terms in raster order, inside the same bound.  Every pointer HOST memory; max_blocks is checked
+ * and otherwise unused. */
+int lsr_label_intensity_f32_cpu(const int32_t* labels, const float* v, int64_t Z, int64_t Y, int64_t X, int64_t n_objects,
+                                void* table, int max_blocks, lsr_stream_t stream);
+int lsr_label_intensity_u16_cpu(const int32_t* labels, const uint16_t* v, int64_t Z, int64_t Y, int64_t X, int64_t n_objects,
+                                void* table, int max_blocks, lsr_stream_t stream);
 
 /* ... of the grey morphology (csrc/morphology.hip): the same plan of passes and the same walk along a line
  * (csrc/morphology.hpp), so `out` is the kernels' bits.  Every pointer HOST memory; `scratch` holds the results between the

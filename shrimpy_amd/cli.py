@@ -20,6 +20,13 @@ CPU path (biahub's; the reference's own CLI has only ``acquire`` and ``gui``,
     python -m shrimpy_amd.cli subtract-background -i store.zarr -c background.yml -o flat.zarr
     python -m shrimpy_amd.cli despeckle   -i store.zarr -c despeckle.yml -o clean.zarr
     python -m shrimpy_amd.cli enhance     -i store.zarr -c enhance.yml   -o tubes.zarr
+    python -m shrimpy_amd.cli segment     -i store.zarr -c segment.yml   -o labels.zarr
+    python -m shrimpy_amd.cli track       -i labels.zarr -c track.yml    -o tracks.zarr
+    python -m shrimpy_amd.cli measure     -l tracks.zarr -i store.zarr -c measure.yml -o measurements/
+
+``measure`` reads two stores and writes tables only: per position ``measurements.csv``, one row per timepoint and label (or
+track id) with its volume and, per channel of the intensity store, the sum, mean, standard deviation, extremes and weighted
+centroid -- on request beside the mean of a ring of local background around each object.
 
 Every (position, timepoint, channel) volume is an independent unit.  Launched under
 ``python -m torch.distributed.run --nproc-per-node N`` each rank takes the units
@@ -2076,6 +2083,193 @@ def run_track(input_path, config, output_path, positions=(), zarr_version: str =
 
     return _run_object_store(input_path, output_path, positions, zarr_version, io_backend, compression, settings.channel_name,
                              "_tracks", "tracks", position, check_array=integer_data)
+
+
+MEASURE_COLUMNS = ("t", "label", "volume_voxels", "volume_um3")
+# per measured channel `c`: c_sum, c_mean, ...; with a background distance also c_background_voxels, ...
+MEASURE_CHANNEL_COLUMNS = ("sum", "mean", "std", "min", "max", "weighted_centroid_z_um", "weighted_centroid_y_um",
+                           "weighted_centroid_x_um")
+MEASURE_BACKGROUND_COLUMNS = ("background_voxels", "background_mean", "mean_minus_background")
+
+
+@cli.command(cls=_eat_all_command("-i", "--input-position-dirpaths"))
+@click.option("-l", "--labels-dirpath", "labels_path", required=True, type=click.Path(exists=True, file_okay=False, path_type=Path),
+              help="OME-Zarr store of integer labels: the output of segment or track, or anything else that wrote integer data.")
+@click.option("-i", "--input-position-dirpaths", "input_path", required=True, multiple=True, type=click.UNPROCESSED,
+              help="The OME-Zarr store whose channels are measured (HCS plate or single FOV), or the position directories of one plate.")
+@click.option("-c", "--config-filepath", "config", required=True, type=click.Path(exists=True, dir_okay=False, path_type=Path),
+              help="MeasureSettings YAML.")
+@click.option("-o", "--output-dirpath", "output_path", required=True, type=click.Path(path_type=Path),
+              help="Output directory (must not exist); measurements.csv is written into <output>/<position>/.")
+@click.option("-p", "--position", "positions", multiple=True, help='Restrict to these position keys ("row/col/fov"); repeatable.')
+@click.option("--io", "io_backend", type=click.Choice(["auto", "native", "iohub"]), default="auto", show_default=True,
+              help="Store access for the inputs: this package's reader, iohub, or native with iohub as the fallback.")
+def measure(labels_path, input_path, config, output_path, positions, io_backend):
+    """Measure the objects of a label store in the channels of another store (config: a MeasureSettings YAML).
+
+    Writes <output>/<position>/measurements.csv: one row per timepoint and label that has voxels, with the volume and, per
+    measured channel c, c_sum, c_mean, c_std, c_min, c_max and the intensity-weighted centroid in micrometres.  uint16 and
+    float32 channels are measured as they are stored.  Measuring the output of track gives one row per track id and
+    timepoint: the intensity curve of every lineage.
+
+    background_distance (micrometres) adds, per channel, the voxels and the mean of a ring of local background around every
+    object -- farther than background_gap from it, within background_gap + background_distance, nearer to it than to any
+    other object -- and c_mean_minus_background."""
+    input_path, positions = _inputs(input_path, positions)
+    _finish(run_measure(labels_path, input_path, config, output_path, positions, io_backend))
+
+
+def run_measure(labels_path, input_path, config, output_path, positions=(), io_backend: str = "auto") -> dict:
+    """``measure``: per (position, t) the label volume of ``label_channel_name`` is uploaded once, ``n`` is its greatest label,
+    and every measured channel is uploaded once and goes through ``segment.intensity_table`` (``csrc/intensity.hip``, or its
+    host twin on a CPU-only machine) -- uint16 data through the uint16 entry, float32 data through the float32 entry, nothing
+    converted; with ``background_distance > 0`` the ring volume (``segment.shell_labels``) is built once per (position, t) and
+    every channel takes a second launch on it.  The rows go to ``<output>/<position>/measurements.csv``: ``MEASURE_COLUMNS``,
+    then per channel ``c`` the columns ``c_<name>`` of ``MEASURE_CHANNEL_COLUMNS`` (and of ``MEASURE_BACKGROUND_COLUMNS``),
+    one row per ``(t, label)`` with voxels, in order of ``t``, then ``label``; physical coordinates are ``translation + index *
+    scale`` of the label store's position.  Everything is checked before the output directory is created: the positions exist
+    in both stores, the channels exist, the label data is integer and fits int32, ``(T, Z, Y, X)`` and the ``(z, y, x)`` scale
+    of the two stores agree per position, the intensity data is uint16 or float32.  With several ranks the positions are dealt
+    out in turn."""
+    import csv
+
+    import torch
+
+    from .io.omezarr import as_volume_array, position_scale
+    from .segment import intensity_table, shell_labels
+    from .settings import MeasureSettings
+
+    try:
+        settings = MeasureSettings.from_yaml(config)
+    except (ValueError, TypeError) as exc:
+        raise click.ClickException(f"{config}: {exc}") from exc
+    ring = float(settings.background_distance) > 0
+
+    rank, world, device, created = _distributed()
+    try:
+        label_store, label_positions = _open_source(Path(labels_path), io_backend)
+        try:
+            src, src_positions = _open_source(Path(input_path), io_backend)
+            try:
+                missing = [p for p in positions if p not in src_positions]
+                if missing:
+                    raise click.ClickException(f"positions {missing} not found in {input_path}; available: {list(src_positions)}")
+                keys = [k for k in src_positions if not positions or k in positions]
+                if not keys:
+                    raise click.ClickException("no positions to process")
+                plan = {}
+                for k in keys:
+                    if k not in label_positions:
+                        raise click.ClickException(f"position {k} not found in {labels_path}; available: {list(label_positions)}")
+                    lpos, pos = label_positions[k], src_positions[k]
+                    label_names, names = list(lpos.channel_names), list(pos.channel_names)
+                    if settings.label_channel_name not in label_names:
+                        raise click.ClickException(f"label_channel_name {settings.label_channel_name!r} not in position {k} of "
+                                                   f"{labels_path} (it has {label_names})")
+                    measured = list(names) if settings.channels is None else list(settings.channels)
+                    absent = [c for c in measured if c not in names]
+                    if absent:
+                        raise click.ClickException(f"channels {absent} not in position {k} of {input_path} (it has {names})")
+                    la, a = as_volume_array(lpos["0"]), as_volume_array(pos["0"])
+                    if len(la.shape) != 5 or len(a.shape) != 5:
+                        raise click.ClickException(f"position {k}: expected 5-D TCZYX data, got shapes {tuple(la.shape)} and "
+                                                   f"{tuple(a.shape)}")
+                    if np.dtype(la.dtype).kind not in "iu":
+                        raise click.ClickException(f"position {k}: label data type {la.dtype}; labels are integer data")
+                    if np.dtype(a.dtype) not in (np.dtype(np.uint16), np.dtype(np.float32)):
+                        raise click.ClickException(f"position {k}: intensity data type {a.dtype}; uint16 or float32 is measured")
+                    shape, other = (int(la.shape[0]),) + tuple(int(v) for v in la.shape[2:]), (int(a.shape[0]),) + tuple(
+                        int(v) for v in a.shape[2:])
+                    if shape != other:
+                        raise click.ClickException(f"position {k}: the labels are (T, Z, Y, X) = {shape}, the intensities {other}")
+                    if int(np.prod(shape[1:], dtype=np.int64)) > 2 ** 31 - 1:
+                        raise click.ClickException(f"position {k}: a volume of {shape[1:]} has more than 2^31 - 1 voxels")
+                    scale, translation = list(position_scale(lpos)), list(_position_translation(lpos))
+                    if not np.allclose(scale[2:], list(position_scale(pos))[2:], rtol=1e-9, atol=0.0):
+                        raise click.ClickException(f"position {k}: the labels' (z, y, x) scale is {scale[2:]}, the intensities' "
+                                                   f"{list(position_scale(pos))[2:]}")
+                    lc = label_names.index(settings.label_channel_name)
+                    info = np.iinfo(la.dtype)
+                    if info.max > 2 ** 31 - 1:             # (a wider type: its values decide)
+                        for t in range(shape[0]):
+                            vol = np.asarray(la.read_volume(t, lc))
+                            if vol.size and (int(vol.max()) > 2 ** 31 - 1 or int(vol.min()) < -2 ** 31):
+                                raise click.ClickException(f"position {k}, t = {t}: a label does not fit int32")
+                    plan[k] = (la, lc, a, [(c, names.index(c)) for c in measured], scale, translation)
+                error = None
+                if rank == 0:
+                    try:
+                        if Path(output_path).exists():
+                            raise FileExistsError(f"{output_path} exists (never overwritten)")
+                        Path(output_path).mkdir(parents=True)
+                    except Exception as exc:  # noqa: BLE001 -- reported on every rank, see _agree
+                        error = f"{type(exc).__name__}: {exc}"
+                _agree(error)
+
+                def columns(table, background, scale_zyx, translation_zyx):
+                    """The values of one channel behind ``MEASURE_COLUMNS``, row by row for the labels with voxels."""
+                    integer = table["sum"].dtype.kind == "u"
+                    number = int if integer else float
+                    out = []
+                    for i in np.flatnonzero(table["count"] > 0):
+                        um = [float(o) + float(v) * float(sc)
+                              for o, v, sc in zip(translation_zyx, table["weighted_centroid"][i], scale_zyx)]
+                        row = [number(table["sum"][i]), float(table["mean"][i]), float(table["std"][i]), number(table["min"][i]),
+                               number(table["max"][i]), *um]
+                        if background is not None:
+                            row += [int(background["count"][i]), float(background["mean"][i]),
+                                    float(table["mean"][i]) - float(background["mean"][i])]
+                        out.append(row)
+                    return out
+
+                entries = {}
+                t0 = time.perf_counter()
+                for k in keys[rank::world]:
+                    la, lc, a, channels, scale, translation = plan[k]
+                    sz, sy, sx = (float(v) for v in scale[2:])
+                    rows = []
+                    for t in range(int(la.shape[0])):
+                        labels = torch.as_tensor(np.ascontiguousarray(la.read_volume(t, lc), dtype=np.int32), device=device)
+                        n = max(int(labels.max().item()), 0)
+                        shell = shell_labels(labels, float(settings.background_distance), float(settings.background_gap),
+                                             scale[2:]) if ring and n > 0 else None
+                        block = None
+                        for _, c in channels:
+                            values = torch.as_tensor(np.ascontiguousarray(a.read_volume(t, c)), device=device)
+                            table = intensity_table(labels, n, values)
+                            background = intensity_table(shell, n, values) if shell is not None else None
+                            if block is None:
+                                live = np.flatnonzero(table["count"] > 0)
+                                block = [[int(t), int(table["label"][i]), int(table["count"][i]), float(table["count"][i]) * sz * sy * sx]
+                                         for i in live]
+                            for row, more in zip(block, columns(table, background, scale[2:], translation[2:])):
+                                row += more
+                        rows += block or []
+                    header = list(MEASURE_COLUMNS)
+                    for name, _ in channels:
+                        header += [f"{name}_{c}" for c in MEASURE_CHANNEL_COLUMNS + (MEASURE_BACKGROUND_COLUMNS if ring else ())]
+                    directory = Path(output_path) / k
+                    directory.mkdir(parents=True, exist_ok=True)
+                    with open(directory / "measurements.csv", "w", newline="") as fh:
+                        w = csv.writer(fh)
+                        w.writerow(header)
+                        w.writerows([[repr(v) if isinstance(v, float) else v for v in row] for row in rows])
+                    entries[k] = len(rows)
+                return {"rank": rank, "world_size": world, "positions": len(keys[rank::world]), "rows": entries,
+                        "seconds": time.perf_counter() - t0, "failed": []}
+            finally:
+                close = getattr(src, "close", None)
+                if close:
+                    close()
+        finally:
+            close = getattr(label_store, "close", None)
+            if close:
+                close()
+    finally:
+        if created:
+            import torch.distributed as dist
+
+            dist.destroy_process_group()
 
 
 @cli.command("pyramid", cls=_eat_all_command("-i", "--input-position-dirpaths"))

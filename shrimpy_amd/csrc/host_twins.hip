@@ -29,6 +29,7 @@
 //                                             <->  the same names without _cpu         (watershed.hip)
 //   lsr_label_overlap_i32_cpu                 <->  lsr_label_overlap_i32               (overlap.hip)
 //   lsr_label_moments_i32_cpu                 <->  lsr_label_moments_i32               (moments.hip)
+//   lsr_label_intensity_f32_cpu / _u16_cpu    <->  lsr_label_intensity_f32 / _u16      (intensity.hip)
 //   lsr_grey_morph_f32_cpu                    <->  lsr_grey_morph_f32                  (morphology.hip)
 //   lsr_rank_filter_f32_cpu                   <->  lsr_rank_filter_f32                 (rank.hip)
 //   lsr_hessian_response_f32_cpu              <->  lsr_hessian_response_f32            (hessian.hip)
@@ -1582,6 +1583,29 @@ extern "C" int lsr_label_moments_i32_cpu(const int32_t* labels, int64_t Z, int64
       }
     }
   }
+  return LSR_OK;
+}
+
+// ---- label intensities (intensity.hip): plain sequential code over intensity.hpp's rule, records and checks, voxel by voxel.
+// uint16 values: the kernel's records byte for byte.  float32 values: count and extremes are the kernel's, the float64 sums are
+// another order of the same terms (both inside intensity.hpp's bound) ----
+#include "intensity.hpp"
+
+extern "C" int lsr_label_intensity_f32_cpu(const int32_t* labels, const float* values, int64_t Z, int64_t Y, int64_t X,
+                                           int64_t n_objects, void* table, int max_blocks, lsr_stream_t) {
+  namespace in = lsr::intensity;
+  if (int rc = in::check_intensity(labels, values, sizeof(float), Z, Y, X, n_objects, table, max_blocks)) return rc;
+  if (n_objects == 0) return LSR_OK;
+  in::accumulate_host<float, in::RecordF32, double>(labels, values, Z, Y, X, n_objects, static_cast<in::RecordF32*>(table));
+  return LSR_OK;
+}
+
+extern "C" int lsr_label_intensity_u16_cpu(const int32_t* labels, const uint16_t* values, int64_t Z, int64_t Y, int64_t X,
+                                           int64_t n_objects, void* table, int max_blocks, lsr_stream_t) {
+  namespace in = lsr::intensity;
+  if (int rc = in::check_intensity(labels, values, sizeof(uint16_t), Z, Y, X, n_objects, table, max_blocks)) return rc;
+  if (n_objects == 0) return LSR_OK;
+  in::accumulate_host<uint16_t, in::RecordU16, uint64_t>(labels, values, Z, Y, X, n_objects, static_cast<in::RecordU16*>(table));
   return LSR_OK;
 }
 

@@ -21,8 +21,14 @@ numbering is a prefix count), ``csrc/host_twins.hip`` on the CPU; both equal ``s
   touching objects by a watershed of their depth map (``shrimpy_amd/watershed.py``), measure, filter, and on request grow the
   labels by a distance and measure each object's inscribed radius (``shrimpy_amd/distance.py``).
 
+* :func:`intensity_table` -- per label what another volume (float32 or uint16) holds: count, sum, sum of squares, mean,
+  standard deviation, extremes and the intensity-weighted first moments (``csrc/intensity.hip``: the moment kernel's form with
+  the run sums reduced inside the wave and float64 LDS adds; PARITY UNPINNED, ``tests/intensity_ref.py``); :func:`shell_labels`
+  -- a ring of local background around every object.  The ``measure`` command applies both to any label store and any channel.
+
 Not built: seeded watersheds, multi-GPU or slab labelling, label pyramids, volumes above ``2^31 - 1`` voxels, ball-shaped or
-rolling-ball background windows (the window is a box), background-subtracted intensity columns in the table.  Labels are
+rolling-ball background windows (the window is a box), cross-channel sums (Pearson / Manders colocalization per object),
+per-object percentiles, :func:`region_table` on the intensity kernel.  Labels are
 numbered from 1 at every timepoint; linking them over time is ``shrimpy_amd/track.py`` (the ``track`` command), where gap
 closing, motion models and a global assignment are not built.
 """
@@ -36,7 +42,8 @@ import numpy as np
 from . import _lib
 
 __all__ = ["REGION_DTYPE", "MOMENTS_DTYPE", "tile_shape", "label_volume", "region_table", "filter_objects", "moments_geometry",
-           "moment_table", "shape_table", "contact_table", "segment_zyx"]
+           "moment_table", "shape_table", "contact_table", "segment_zyx", "INTENSITY_DTYPE_F32", "INTENSITY_DTYPE_U16",
+           "intensity_geometry", "intensity_table", "shell_labels"]
 
 # one record of the object table (csrc/label.hpp ``Region``)
 REGION_DTYPE = np.dtype([("volume", "<i8"), ("sum_zyx", "<i8", (3,)), ("sum_v", "<f8"), ("sum_vzyx", "<f8", (3,)),
@@ -46,6 +53,13 @@ assert REGION_DTYPE.itemsize == 96
 MOMENT_FIELDS = ("volume", "s_z", "s_y", "s_x", "m_zz", "m_yy", "m_xx", "m_zy", "m_zx", "m_yx")
 MOMENTS_DTYPE = np.dtype([(f, "<i8") for f in MOMENT_FIELDS])
 assert MOMENTS_DTYPE.itemsize == 80
+# one record of the intensity table for float32 and for uint16 values (csrc/intensity.hpp ``RecordF32``, ``RecordU16``)
+INTENSITY_SUMS = ("sum_v", "sum_vv", "sum_vz", "sum_vy", "sum_vx")
+INTENSITY_DTYPE_F32 = np.dtype([("count", "<i8")] + [(f, "<f8") for f in INTENSITY_SUMS]
+                               + [("v_min", "<f4"), ("v_max", "<f4"), ("pad", "<u4", (2,))])
+INTENSITY_DTYPE_U16 = np.dtype([("count", "<i8")] + [(f, "<u8") for f in INTENSITY_SUMS]
+                               + [("v_min", "<u4"), ("v_max", "<u4"), ("pad", "<u4", (2,))])
+assert INTENSITY_DTYPE_F32.itemsize == 64 and INTENSITY_DTYPE_U16.itemsize == 64
 
 
 def _tile_shape(entry: str) -> tuple[int, int, int]:
@@ -275,6 +289,88 @@ def moment_table(labels, n: int, _max_blocks: int = 0) -> dict:
     return {f: np.ascontiguousarray(raw[f], dtype=np.int64) for f in MOMENT_FIELDS}
 
 
+def intensity_geometry() -> tuple[int, int]:
+    """``(LDS table slots per workgroup, default cap of the grid)`` of the intensity kernel (``lsr_label_intensity_geometry``)."""
+    out = (ctypes.c_int * 2)()
+    _lib.call("lsr_label_intensity_geometry", out)
+    return int(out[0]), int(out[1])
+
+
+def _raw_intensity(labels, n: int, values, _max_blocks: int = 0) -> np.ndarray:
+    """The ``n`` records of ``lsr_label_intensity_f32`` / ``_u16`` as a host structured array (``INTENSITY_DTYPE_F32`` /
+    ``INTENSITY_DTYPE_U16``, by ``values``' type)."""
+    import torch
+
+    labels = _check_volume(labels, "labels", torch.int32)
+    n = int(n)
+    if n < 0:
+        raise ValueError(f"n must not be negative, got {n}")
+    if not isinstance(values, torch.Tensor) or values.dtype not in (torch.float32, torch.uint16):
+        raise TypeError(f"values must be a float32 or uint16 torch.Tensor, got {getattr(values, 'dtype', type(values).__name__)}")
+    values = _check_volume(values, "values", values.dtype)
+    _same_volume(labels, values, "labels", "values")
+    z, y, x = _shape3(labels, "labels")
+    entry, dtype = (("lsr_label_intensity_f32", INTENSITY_DTYPE_F32) if values.dtype == torch.float32
+                    else ("lsr_label_intensity_u16", INTENSITY_DTYPE_U16))
+    if n == 0:
+        return np.zeros((0,), dtype=dtype)
+    table = torch.zeros((n * dtype.itemsize,), dtype=torch.uint8, device=labels.device)     # the host zeroes it
+    _run(labels.device, entry, labels.data_ptr(), values.data_ptr(), z, y, x, n, table.data_ptr(), int(_max_blocks))
+    return table.cpu().numpy().view(dtype).copy()
+
+
+def intensity_table(labels, n: int, values, _max_blocks: int = 0) -> dict:
+    """What the labels ``1 .. n`` of a (Z, Y, X) int32 tensor hold in ``values``, a float32 or uint16 tensor of the same shape on
+    the same device (CPU or HIP), one row per label, as a dict of numpy arrays of length ``n`` (``csrc/intensity.hip``: one pass
+    over both volumes, runs of equal labels reduced inside the wave, a table in LDS per workgroup; the twins in
+    ``csrc/host_twins.hip``; the rule in ``csrc/intensity.hpp``):
+
+    ``label``, ``count`` (int64), ``sum`` and ``sum_sq`` (float64 for float32 values, uint64 and exact for uint16 values),
+    ``mean``, ``std`` (the population standard deviation in float64: ``sqrt(max(sum_sq / n - mean^2, 0))``), ``min`` and ``max``
+    (``values``' type), ``sum_zyx`` ((n, 3): the sums of ``v z``, ``v y``, ``v x`` in absolute voxel indices) and
+    ``weighted_centroid`` ((n, 3) float64 = ``sum_zyx / sum``, NaN where ``sum`` is 0).
+
+    ``count``, ``min`` and ``max`` are exact; -0.0 sorts below +0.0 and a NaN is an object's ``max`` or ``min`` by its sign bit,
+    as in :func:`region_table`.  A float64 sum is within ``2 n_k 2^-53 sum|terms|`` of the exact sum (atomic adds: not
+    bit-reproducible on the device); uint16 sums are integers.  Labels outside ``1 .. n`` are ignored; a label that no voxel
+    carries has zeros and a NaN ``mean``, ``std`` and ``weighted_centroid``.  ``_max_blocks`` caps the grid (0: the kernel's
+    default)."""
+    raw = _raw_intensity(labels, n, values, _max_blocks)
+    count = raw["count"].astype(np.int64)
+    sum_zyx = np.stack([raw["sum_vz"], raw["sum_vy"], raw["sum_vx"]], axis=1) if len(raw) else np.zeros((0, 3), raw["sum_vz"].dtype)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        total = raw["sum_v"].astype(np.float64)
+        mean = total / count.astype(np.float64)
+        variance = raw["sum_vv"].astype(np.float64) / count.astype(np.float64) - mean * mean
+        # (a NaN variance stays NaN: an object that holds a NaN or an infinity has no standard deviation)
+        std = np.sqrt(np.where(variance < 0.0, 0.0, variance))
+        centroid = sum_zyx.astype(np.float64) / np.where(total == 0.0, np.nan, total)[:, None]
+    return {
+        "label": np.arange(1, len(raw) + 1, dtype=np.int32), "count": count,
+        "sum": np.ascontiguousarray(raw["sum_v"]), "sum_sq": np.ascontiguousarray(raw["sum_vv"]), "mean": mean, "std": std,
+        "min": np.ascontiguousarray(raw["v_min"]).astype(np.float32 if raw.dtype == INTENSITY_DTYPE_F32 else np.uint16),
+        "max": np.ascontiguousarray(raw["v_max"]).astype(np.float32 if raw.dtype == INTENSITY_DTYPE_F32 else np.uint16),
+        "sum_zyx": np.ascontiguousarray(sum_zyx), "weighted_centroid": centroid,
+    }
+
+
+def shell_labels(labels, distance: float, gap: float = 0.0, sampling=(1, 1, 1)):
+    """A ring of local background around every object of ``labels`` ((Z, Y, X) int32): a voxel within ``gap`` of an object (the
+    objects included) is 0, a voxel farther than that and within ``gap + distance`` carries the label of its nearest object, in
+    units of ``sampling`` -- ``expand_labels(labels, gap + distance)`` where ``expand_labels(labels, gap) == 0``, else 0.  A new
+    int32 tensor.  The rings of neighbouring objects do not overlap, because ``distance.expand_labels`` does not."""
+    import torch
+
+    from . import distance as D
+
+    distance, gap = float(distance), float(gap)
+    if not (np.isfinite(distance) and distance >= 0 and np.isfinite(gap) and gap >= 0):
+        raise ValueError(f"distance and gap must be finite and not negative, got {distance!r} and {gap!r}")
+    inner = D.expand_labels(labels, gap, sampling)
+    outer = D.expand_labels(labels, gap + distance, sampling)
+    return torch.where(inner == 0, outer, torch.zeros_like(outer))
+
+
 def _sampling3(sampling) -> tuple[float, float, float]:
     s = tuple(float(v) for v in sampling)
     if len(s) != 3 or not all(np.isfinite(v) and v > 0 for v in s):
@@ -384,9 +480,8 @@ def shape_table(labels, n: int, sampling=(1, 1, 1), bbox=None) -> dict:
 
     A label that no voxel carries has zero counts, NaN lengths and ``touches_border`` False.
 
-    Not built: intensity-weighted moments, a smoothed (Crofton-weight) area estimator and sphericity, a stand-alone ``measure``
-    command for label stores that ``segment`` did not write, ``label_regions_kernel`` on the moment kernel's form, multi-GPU
-    tables."""
+    Not built: a smoothed (Crofton-weight) area estimator and sphericity, ``label_regions_kernel`` on the moment kernel's form
+    (:func:`intensity_table` has it; :func:`region_table` has not been moved), multi-GPU tables."""
     import torch
 
     labels = _check_volume(labels, "labels", torch.int32)

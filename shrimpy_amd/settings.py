@@ -768,6 +768,37 @@ class TrackSettings(_StrictModel):
         return v
 
 
+class MeasureSettings(_StrictModel):
+    """Measuring the objects of a label store in the channels of another store (``segment.intensity_table``, the ``measure``
+    command).
+
+    ``label_channel_name`` is the channel of the label store (``<name>_labels`` from ``segment``, ``<name>_tracks`` from
+    ``track``, or any integer channel).  ``channels`` names the channels of the intensity store that are measured, in the order
+    of the columns; ``None`` takes every channel in store order.  With ``background_distance > 0`` (micrometres, the position's
+    scale) every object is also measured in a ring of local background: the voxels farther than ``background_gap`` from the
+    object and within ``background_gap + background_distance`` of it, nearer to it than to any other object
+    (``segment.shell_labels``)."""
+
+    label_channel_name: str
+    channels: Optional[list[str]] = None
+    background_distance: NonNegativeFloat = 0.0
+    background_gap: NonNegativeFloat = 0.0
+
+    @field_validator("channels")
+    @classmethod
+    def _check_channels(cls, v):
+        if v is not None and (len(v) == 0 or len(set(v)) != len(v)):
+            raise ValueError("channels must name at least one channel, each once (or be null: every channel)")
+        return v
+
+    @field_validator("background_distance", "background_gap")
+    @classmethod
+    def _check_finite(cls, v):
+        if not np.isfinite(v):
+            raise ValueError("must be finite")
+        return v
+
+
 class ReconstructSettings(_StrictModel):
     """Whole per-volume pipeline: (flat-field) -> deskew -> (register) -> (deconvolve)."""
 

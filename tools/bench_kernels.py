@@ -83,6 +83,11 @@ def main():
                     "the three scenes of --label: as shipped, over a sweep of LDS slots and grid caps, and in the plain form without "
                     "an LDS table, beside a device copy, lsr_label_regions_f32 without intensities and the three overlap launches of "
                     "segment.contact_table in the same run; appended to profiles/moments_config2.jsonl")
+    ap.add_argument("--intensity", action="store_true", help="only: ms of the label-intensity kernel (csrc/intensity.hip) on --rl-grid "
+                    "for the three scenes of --label with the scene as the values: as shipped for float32 and uint16 values, over a "
+                    "sweep of LDS slots, grid caps and probe bounds, and in the plain form without an LDS table, beside a device "
+                    "copy of one int32 and one float32 volume and lsr_label_regions_f32 with the intensities in the same run; "
+                    "appended to profiles/intensity_config2.jsonl")
     ap.add_argument("--edt", action="store_true", help="only: ms per launch of the distance transform (csrc/edt.hip: x, y, z; HIP "
                     "events between the launches, median of 5 calls after a warm-up) on --rl-grid, for bench.synthetic_raw at its "
                     "multi-Otsu threshold, Bernoulli noise at p = 0.3 and an all-foreground volume with one background voxel, "
@@ -149,6 +154,9 @@ def main():
         return
     if args.moments:
         _moments(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
+        return
+    if args.intensity:
+        _intensity(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
         return
     if args.watershed:
         _watershed(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
@@ -938,6 +946,31 @@ def _overlap(args, torch, dev, g, bench, oshape):
             f.write(line + "\n")
 
 
+def _label_scenes(torch, dev, g, bench, oshape):
+    """``(name, float32 volume, threshold)`` of the three scenes the label tables are measured on."""
+    from shrimpy_amd import dynatrack
+
+    vol = bench.synthetic_raw(oshape, 1000, dev)
+    yield "bead scene (bench.synthetic_raw) at its multi-Otsu threshold", vol, float(dynatrack._multiotsu_threshold(vol, 0))
+    del vol
+    yield "Bernoulli noise, p = 0.3", torch.rand(oshape, device=dev, generator=g), 0.7
+    yield "all foreground", torch.ones(oshape, dtype=torch.float32, device=dev), 0.5
+
+
+def _timed_cleared(torch, launch, clear, reps):
+    """ms of ``launch`` between HIP events: the median of ``reps`` calls after a warm-up, ``clear()`` outside the timed region."""
+    times = []
+    for _ in range(reps + 1):
+        clear()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        launch()
+        e1.record()
+        torch.cuda.synchronize()
+        times.append(e0.elapsed_time(e1))
+    return float(np.median(times[1:]))
+
+
 MOMENTS_STEP = 1024          # voxels one workgroup takes per stride of its span (csrc/moments.hpp kStep)
 MOMENTS_SLOTS = (64, 128, 256, 512)
 MOMENTS_CAPS = (1024, 4096, 8192, 16384, 65536, 262144)
@@ -952,7 +985,7 @@ def _moments(args, torch, dev, g, bench, oshape):
     without an LDS table (every run head straight to global atomics); lsr_label_regions_f32 without intensities in the same run;
     the three overlap launches of segment.contact_table.  The floor is one volume read, 4 bytes per voxel: the device copy of one
     int32 volume moves twice as much."""
-    from shrimpy_amd import _lib, dynatrack, segment, track
+    from shrimpy_amd import _lib, segment, track
 
     reps = 3
     z, y, x = oshape
@@ -967,23 +1000,10 @@ def _moments(args, torch, dev, g, bench, oshape):
     stream = _lib.stream_ptr(dev)
 
     def scenes():
-        vol = bench.synthetic_raw(oshape, 1000, dev)
-        yield "bead scene (bench.synthetic_raw) at its multi-Otsu threshold", vol, float(dynatrack._multiotsu_threshold(vol, 0))
-        del vol
-        yield "Bernoulli noise, p = 0.3", torch.rand(oshape, device=dev, generator=g), 0.7
-        yield "all foreground", torch.ones(oshape, dtype=torch.float32, device=dev), 0.5
+        return _label_scenes(torch, dev, g, bench, oshape)
 
     def timed(launch, clear):
-        times = []
-        for _ in range(reps + 1):
-            clear()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            launch()
-            e1.record()
-            torch.cuda.synchronize()
-            times.append(e0.elapsed_time(e1))
-        return float(np.median(times[1:]))
+        return _timed_cleared(torch, launch, clear, reps)
 
     def geometry(cap):
         steps = -(-n // MOMENTS_STEP)
@@ -1044,6 +1064,110 @@ def _moments(args, torch, dev, g, bench, oshape):
             line = json.dumps({**r, **stamp})
             print(line, flush=True)
             f.write(line + "\n")
+
+
+INTENSITY_SLOTS = (64, 128, 256, 512)
+INTENSITY_CAPS = (1024, 4096, 16384, 65536, 262144)
+INTENSITY_PROBES = 8         # the LDS probe bound (csrc/intensity.hpp kLdsProbes)
+INTENSITY_PROBE_SWEEP = (1, 2, 4, 16, 32)
+
+
+def _intensity(args, torch, dev, g, bench, oshape):
+    """The label-intensity kernel (csrc/intensity.hip) at the config-2 deskewed shape on the three scenes of --label, labelled
+    under connectivity 6, the scene's own float32 volume as the values (and a uint16 image of it).  Per scene, each the median of
+    3 calls after a warm-up between HIP events (the tables zeroed outside the timed region): the kernel as shipped for float32
+    and for uint16 values; the sweep of LDS slots, grid caps and probe bounds through the measurement entry (float32), and once
+    the plain form without an LDS table; lsr_label_regions_f32 WITH the intensities in the same run.  The floor is one read of
+    both volumes, 8 bytes per voxel: the device copy of one int32 volume plus one float32 volume moves twice as much.  Every
+    form's counts and extremes must equal the shipped form's; the greatest relative difference of a float64 sum is recorded."""
+    from shrimpy_amd import _lib, segment
+
+    reps = 3
+    z, y, x = oshape
+    n = z * y * x
+    lds_slots, default_cap = segment.intensity_geometry()
+    a, fa = torch.empty(oshape, dtype=torch.int32, device=dev), torch.empty(oshape, dtype=torch.float32, device=dev)
+    b, fb = torch.empty_like(a), torch.empty_like(fa)
+
+    def copies():
+        b.copy_(a)
+        fb.copy_(fa)
+
+    copy_ms = _median_ms(copies, reps, torch)
+    records = [{"kernel": "device copy of one int32 volume and one float32 volume (torch copy_)", "grid": list(oshape), "ms": copy_ms,
+                "GBps": 16.0 * n / copy_ms / 1e6}]
+    del a, b, fa, fb
+    stream = _lib.stream_ptr(dev)
+    record = segment.INTENSITY_DTYPE_F32.itemsize
+
+    def geometry(cap):
+        steps = -(-n // MOMENTS_STEP)
+        span = -(-steps // min(steps, cap)) * MOMENTS_STEP
+        return span, -(-n // span)
+
+    def split(table):
+        """(the integer words of every record: count, extremes and pad; the five float64 sums)"""
+        words = table.view(torch.int64).view(-1, record // 8)
+        return torch.cat([words[:, :1], words[:, 6:]], dim=1), words[:, 1:6].contiguous().view(torch.float64)
+
+    for name, vol, threshold in _label_scenes(torch, dev, g, bench, oshape):
+        labels, n_objects = segment.label_volume(vol, threshold, 6)
+        # a uint16 image of the values: scaled into 0 .. 65535, cut to 16 bits through int16 (same bits)
+        scale = 65535.0 / max(float(vol.max().item()), 1e-30)
+        u16 = (vol.clamp(min=0.0) * scale).to(torch.int32).to(torch.int16).view(torch.uint16)
+        torch.cuda.empty_cache()
+        base = {"input": name, "grid": list(oshape), "objects": n_objects, "foreground_fraction": float((labels != 0).sum().item()) / n}
+        print(f"# {name}: {n_objects} objects", flush=True)
+        table = torch.zeros(max(n_objects, 1) * record, dtype=torch.uint8, device=dev)
+        span, blocks = geometry(default_cap)
+        shipped = {"lds_slots": lds_slots, "lds_probes": INTENSITY_PROBES, "max_blocks": default_cap, "default": True,
+                   "workgroups": blocks, "span_voxels": span}
+        ms = _timed_cleared(torch, lambda: _lib.call("lsr_label_intensity_u16", labels.data_ptr(), u16.data_ptr(), z, y, x, n_objects,
+                                                     table.data_ptr(), 0, stream), table.zero_, reps)
+        records.append({**base, "kernel": "lsr_label_intensity_u16", **shipped, "ms": ms, "bytes_per_voxel": 6.0,
+                        "algorithmic_GBps": 6.0 * n / ms / 1e6, "times_the_copy": ms / copy_ms})
+        del u16
+        ms_f32 = _timed_cleared(torch, lambda: _lib.call("lsr_label_intensity_f32", labels.data_ptr(), vol.data_ptr(), z, y, x,
+                                                         n_objects, table.data_ptr(), 0, stream), table.zero_, reps)
+        want_words, want_sums = (t.clone() for t in split(table))
+        forms = [(0, default_cap, 1)] + [(slots, cap, INTENSITY_PROBES) for slots in INTENSITY_SLOTS for cap in INTENSITY_CAPS]
+        forms += [(lds_slots, default_cap, probes) for probes in INTENSITY_PROBE_SWEEP]
+        swept = []
+        for slots, cap, probes in forms:
+            ms = _timed_cleared(torch, lambda: _lib.call("lsr_label_intensity_variant", labels.data_ptr(), vol.data_ptr(), 0, z, y, x,
+                                                         n_objects, table.data_ptr(), cap, slots, probes, stream), table.zero_, reps)
+            words, sums = split(table)
+            assert torch.equal(words, want_words), "a form of the kernel disagrees with the shipped one in a count or an extreme"
+            difference = float(((sums - want_sums).abs() / want_sums.abs().clamp(min=1e-300)).max().item()) if n_objects else 0.0
+            span, blocks = geometry(cap)
+            swept.append({**base, "kernel": "lsr_label_intensity_variant (f32)" + (" (plain form: no LDS table)" if slots == 0 else ""),
+                          "lds_slots": slots, "lds_probes": probes if slots else 0, "max_blocks": cap,
+                          "default": (slots, cap, probes) == (lds_slots, default_cap, INTENSITY_PROBES), "workgroups": blocks,
+                          "span_voxels": span, "ms": ms, "times_the_copy": ms / copy_ms,
+                          "greatest_relative_difference_of_a_sum": difference})
+        del table, want_words, want_sums
+        regions = torch.zeros(max(n_objects, 1) * segment.REGION_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        ms_regions = _timed_cleared(torch, lambda: _lib.call("lsr_label_regions_f32", labels.data_ptr(), vol.data_ptr(), z, y, x,
+                                                             n_objects, regions.data_ptr(), stream), regions.zero_, reps)
+        records.append({**base, "kernel": "lsr_label_intensity_f32", **shipped, "ms": ms_f32, "bytes_per_voxel": 8.0,
+                        "algorithmic_GBps": 8.0 * n / ms_f32 / 1e6, "times_the_copy": ms_f32 / copy_ms,
+                        "times_faster_than_lsr_label_regions_f32": ms_regions / ms_f32})
+        records += swept
+        records.append({**base, "kernel": "lsr_label_regions_f32 (with the intensities)", "ms": ms_regions,
+                        "times_the_copy": ms_regions / copy_ms})
+        del regions, labels, vol
+        torch.cuda.empty_cache()
+    stamp = {"sources": _lib.kernel_source_sha16(), "device": torch.cuda.get_device_name(dev), "reps": reps, "warmups": 1}
+    path = ROOT / "profiles" / "intensity_config2.jsonl"
+    with open(path, "a") as f:
+        for r in records:
+            line = json.dumps({**r, **stamp})
+            print(line, flush=True)
+            f.write(line + "\n")
+    speedup = [r["times_faster_than_lsr_label_regions_f32"] for r in records
+               if r.get("input") == "all foreground" and "times_faster_than_lsr_label_regions_f32" in r][0]
+    print(f"# all foreground: lsr_label_intensity_f32 is {speedup:.1f} times faster than lsr_label_regions_f32 "
+          f"({'meets' if speedup >= 10.0 else 'MISSES'} the condition of 10)", flush=True)
 
 
 def _edt(args, torch, dev, g, bench, oshape):
