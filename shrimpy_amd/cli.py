@@ -35,19 +35,25 @@ Every (position, timepoint, channel) volume is an independent unit.  Launched un
 
 from __future__ import annotations
 
+import contextlib
 import functools
 import logging
 import os
 import time
 
+from dataclasses import dataclass
 from pathlib import Path
+from typing import Callable
 
 import click
 import numpy as np
 
 from .settings import (
+    BackgroundSettings,
     DeconvolveSettings,
     DeskewSettings,
+    DespeckleSettings,
+    EnhanceSettings,
     ReconstructSettings,
     RegisterSettings,
 )
@@ -143,13 +149,13 @@ def resolve_inputs(paths) -> tuple[Path, tuple[str, ...]]:
     return root, tuple(keys)
 
 
-def _common(fn, input_required: bool = True):
+def _common(fn, input_required: bool = True, config_directory: bool = False):
     fn = click.option("-i", "--input-position-dirpaths", "input_path", required=input_required, multiple=True,
                       type=click.UNPROCESSED,
                       help="Input OME-Zarr store (HCS plate or single FOV), or the position directories of one plate "
                            "(a glob such as plate.zarr/*/*/*).")(fn)
     fn = click.option("-c", "--config-filepath", "config", required=True,
-                      type=click.Path(exists=True, dir_okay=False, path_type=Path),
+                      type=click.Path(exists=True, dir_okay=config_directory, path_type=Path),
                       help="YAML settings file.")(fn)
     fn = click.option("-o", "--output-dirpath", "output_path", required=True,
                       type=click.Path(path_type=Path),
@@ -293,6 +299,28 @@ def _open_source(path: Path, io_backend: str):
         raise click.ClickException("--io iohub: iohub is not installed") from exc
     store = iohub_open(str(path), layout="auto", mode="r")
     return store, positions_of(store)
+
+
+@contextlib.contextmanager
+def _closing(store):
+    """``with _closing(store):`` closes the store on the way out, if it is of a kind that has a ``close``."""
+    try:
+        yield store
+    finally:
+        close = getattr(store, "close", None)
+        if close:
+            close()
+
+
+def _selected_keys(src_positions, positions) -> list[str]:
+    """The position keys of the store that ``-p`` selects (none given: all of them), in the store's order."""
+    missing = [p for p in positions if p not in src_positions]
+    if missing:
+        raise click.ClickException(f"positions {missing} not found; available: {list(src_positions)}")
+    keys = [k for k in src_positions if not positions or k in positions]
+    if not keys:
+        raise click.ClickException("no positions to process")
+    return keys
 
 
 def _channel_plan(settings: ReconstructSettings, names: list[str], nc: int) -> list[bool]:
@@ -720,6 +748,25 @@ def cli(verbose: bool):
                         format="%(asctime)s %(levelname)s %(name)s: %(message)s")
 
 
+def _store_command(name: str, help: str, config_directory: bool = False):
+    """Decorator of a ``run_<command>(input_path, config, output_path, positions, zarr_version, resume, io_backend,
+    compression, on_error, levels=, level_factor_z=)``: registers the command ``name`` with the shared options (``_common``;
+    ``config_directory``: ``-c`` may be a directory) and ``help`` as its ``-h`` text, and leaves the function as it is."""
+
+    def register(run):
+        @cli.command(name, cls=_eat_all_command("-i", "--input-position-dirpaths"), help=help)
+        @functools.partial(_common, config_directory=config_directory)
+        def command(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error, levels,
+                    level_factor_z):
+            input_path, positions = _inputs(input_path, positions)
+            _finish(run(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error,
+                        **_pyramid_options(levels, level_factor_z)))
+
+        return run
+
+    return register
+
+
 @cli.command(cls=_eat_all_command("-i", "--input-position-dirpaths"))
 @_common
 def deskew(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error, levels,
@@ -738,13 +785,10 @@ def _target_shape_zyx(target_path) -> tuple[int, int, int]:
 
     root, keys = resolve_inputs(target_path)
     store, positions_of = _open_source(root, "auto")
-    try:
+    with _closing(store):
         for key, pos in positions_of.items():
             if not keys or key in keys:
                 return tuple(int(v) for v in as_volume_array(pos["0"]).shape[-3:])
-    finally:
-        if hasattr(store, "close"):
-            store.close()
     raise click.ClickException(f"-t: no position found in {root}")
 
 
@@ -1066,47 +1110,40 @@ def run_estimate_stabilization(input_path, config, output_path, positions=(), io
     rank, world, device, created = _distributed()
     try:
         src, src_positions = _open_source(Path(input_path), io_backend)
-        keys = [k for k in src_positions if not positions or k in positions]
-        missing = [p for p in positions if p not in src_positions]
-        if missing:
-            raise click.ClickException(f"positions {missing} not found; available: {list(src_positions)}")
-        if not keys:
-            raise click.ClickException("no positions to process")
-        output_path = Path(output_path)
-        output_path.mkdir(parents=True, exist_ok=True)
-        written = []
-        for key in shard_units(keys, rank, world):
-            pos = src_positions[key]
-            names = list(pos.channel_names)
-            wanted = [settings.stabilization_estimation_channel] + list(settings.stabilization_channels)
-            unknown = [n for n in wanted if n not in names]
-            if unknown:
-                raise click.ClickException(f"position {key}: channels {unknown} not in the store (it has {names})")
-            c = names.index(settings.stabilization_estimation_channel)
-            arr = as_volume_array(pos["0"])
-            if len(arr.shape) != 5:
-                raise click.ClickException(f"position {key}: expected 5-D TCZYX data, got shape {tuple(arr.shape)}")
-            pixel_size = float(position_scale(pos)[-1])
+        with _closing(src):
+            keys = _selected_keys(src_positions, positions)
+            output_path = Path(output_path)
+            output_path.mkdir(parents=True, exist_ok=True)
+            written = []
+            for key in shard_units(keys, rank, world):
+                pos = src_positions[key]
+                names = list(pos.channel_names)
+                wanted = [settings.stabilization_estimation_channel] + list(settings.stabilization_channels)
+                unknown = [n for n in wanted if n not in names]
+                if unknown:
+                    raise click.ClickException(f"position {key}: channels {unknown} not in the store (it has {names})")
+                c = names.index(settings.stabilization_estimation_channel)
+                arr = as_volume_array(pos["0"])
+                if len(arr.shape) != 5:
+                    raise click.ClickException(f"position {key}: expected 5-D TCZYX data, got shape {tuple(arr.shape)}")
+                pixel_size = float(position_scale(pos)[-1])
 
-            def series(arr=arr, c=c):
-                for t in range(int(arr.shape[0])):
-                    yield torch.as_tensor(np.ascontiguousarray(arr.read_volume(t, c), dtype=np.float32), device=device)
+                def series(arr=arr, c=c):
+                    for t in range(int(arr.shape[0])):
+                        yield torch.as_tensor(np.ascontiguousarray(arr.read_volume(t, c), dtype=np.float32), device=device)
 
-            try:
-                matrices = estimate_stabilization(series(), settings, pixel_size)
-            except ValueError as exc:
-                raise click.ClickException(f"position {key}: {exc}") from exc
-            doc = StabilizationSettings(stabilization_estimation_channel=settings.stabilization_estimation_channel,
-                                        stabilization_type=settings.stabilization_type,
-                                        stabilization_channels=list(settings.stabilization_channels),
-                                        affine_transform_zyx_list=[m.tolist() for m in matrices])
-            doc.to_yaml(output_path / _position_file(key))
-            written.append(_position_file(key))
-            logger.info("position %s: drift of %d timepoints estimated (last shift %s)", key, len(matrices),
-                        matrices[-1][:3, 3].tolist())
-        close = getattr(src, "close", None)
-        if close:
-            close()
+                try:
+                    matrices = estimate_stabilization(series(), settings, pixel_size)
+                except ValueError as exc:
+                    raise click.ClickException(f"position {key}: {exc}") from exc
+                doc = StabilizationSettings(stabilization_estimation_channel=settings.stabilization_estimation_channel,
+                                            stabilization_type=settings.stabilization_type,
+                                            stabilization_channels=list(settings.stabilization_channels),
+                                            affine_transform_zyx_list=[m.tolist() for m in matrices])
+                doc.to_yaml(output_path / _position_file(key))
+                written.append(_position_file(key))
+                logger.info("position %s: drift of %d timepoints estimated (last shift %s)", key, len(matrices),
+                            matrices[-1][:3, 3].tolist())
         return {"rank": rank, "world_size": world, "output": str(output_path), "written": written}
     finally:
         if created:
@@ -1115,45 +1152,49 @@ def run_estimate_stabilization(input_path, config, output_path, positions=(), io
             dist.destroy_process_group()
 
 
-class _StabilizeStep:
-    """``run_store``'s step of the ``stabilize`` command: ``for_unit`` hands out the translation of the unit's position and
-    timepoint (``warp`` channels) or a plain copy (every other channel); the volume keeps its shape."""
+class _NamedChannelStep:
+    """``run_store``'s step of the commands that filter the channels they name and copy the others: ``for_unit`` hands out
+    ``apply(volume, param_of(unit))`` (``named`` channels) or a plain copy (every other channel); the volume becomes float32
+    and keeps its shape."""
 
-    def __init__(self, matrices_of, warp: bool, raw_shape, _settings, device):
+    def __init__(self, param_of, apply, named: bool, raw_shape, device):
         self.device = device
         self.output_shape = tuple(int(n) for n in raw_shape)
-        self._matrices_of, self._warp = matrices_of, warp
+        self._param_of, self._apply, self._named = param_of, apply, named
 
     def for_unit(self, unit):
         import torch
 
-        from .stabilize import apply_stabilization
-
-        matrix = self._matrices_of(unit.position)[unit.t] if self._warp else None
+        param = self._param_of(unit) if self._named else None
 
         def step(raw):
             vol = torch.as_tensor(raw, device=self.device).to(torch.float32).contiguous()
-            return vol if matrix is None else apply_stabilization(vol, matrix)
+            return self._apply(vol, param) if self._named else vol
 
         return step
 
 
-@cli.command(cls=_eat_all_command("-i", "--input-position-dirpaths"))
-@_common
-def stabilize(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error, levels,
-              level_factor_z):
-    """Apply per-timepoint translations (config: a StabilizationSettings YAML, or the directory estimate-stabilization wrote)."""
-    input_path, positions = _inputs(input_path, positions)
-    _finish(run_stabilize(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error,
-                          **_pyramid_options(levels, level_factor_z)))
+def _run_named_channels(input_path, output_path, channels, keys, positions, zarr_version, param_of, apply, fingerprint_extra,
+                        **store_options) -> dict:
+    """``run_store`` with ``apply(volume, param_of(unit))`` on every volume of the ``channels`` and a copy of the others.
+
+    ``run_store`` has one way to treat some channels differently from the rest, its channel plan for a registration: the
+    channels in ``source_channel_names`` take the step the factory builds from the settings, every other channel the step it
+    builds from the same settings with ``registration=None``.  So the plan handed over is an identity registration of
+    ``channels`` -- nothing is ever warped by it --, and ``registration is not None`` tells the factory that it is building
+    the step of the named channels."""
+    plan = ReconstructSettings(registration=RegisterSettings(source_channel_names=channels,
+                                                             affine_transform_zyx=np.eye(4).tolist()))
+
+    def factory(raw_shape, plan_settings, device):
+        return _NamedChannelStep(param_of, apply, plan_settings.registration is not None, raw_shape, device)
+
+    return run_store(input_path, output_path, plan, tuple(keys) if positions else (), zarr_version,
+                     reconstructor_factory=factory, fingerprint_extra=fingerprint_extra, **store_options)
 
 
-# (`-c` of this command may be a directory)
-for _p in stabilize.params:
-    if _p.name == "config":
-        _p.type = click.Path(exists=True, path_type=Path)
-
-
+@_store_command("stabilize", "Apply per-timepoint translations (config: a StabilizationSettings YAML, or the directory "
+                             "estimate-stabilization wrote).", config_directory=True)
 def run_stabilize(input_path, config, output_path, positions=(), zarr_version: str = "0.5", resume: bool = False,
                   io_backend: str = "auto", compression=None, on_error: str = "raise", levels: int = 1,
                   level_factor_z: int = 2) -> dict:
@@ -1162,13 +1203,12 @@ def run_stabilize(input_path, config, output_path, positions=(), zarr_version: s
     ``<row>_<col>_<fov>.yml`` per position.  Everything is checked before the output store is created."""
     from .io.omezarr import as_volume_array
     from .settings import StabilizationSettings
+    from .stabilize import apply_stabilization
 
     config = Path(config)
     src, src_positions = _open_source(Path(input_path), io_backend)
-    try:
-        keys = [k for k in src_positions if not positions or k in positions]
-        if not keys:
-            raise click.ClickException("no positions to process")
+    with _closing(src):
+        keys = _selected_keys(src_positions, positions)
         per_position = {}
         for key in keys:
             path = config / _position_file(key) if config.is_dir() else config
@@ -1193,63 +1233,85 @@ def run_stabilize(input_path, config, output_path, positions=(), zarr_version: s
         unknown = [n for n in channels if n not in names]
         if unknown:
             raise click.ClickException(f"stabilization_channels {unknown} not in the store (it has {names})")
-    finally:
-        close = getattr(src, "close", None)
-        if close:
-            close()
     matrices = {k: [np.asarray(m, dtype=np.float64) for m in s.affine_transform_zyx_list] for k, s in per_position.items()}
-    # run_store's channel plan: the named channels take the first step, the others the second
-    plan = ReconstructSettings(registration=RegisterSettings(source_channel_names=channels,
-                                                             affine_transform_zyx=np.eye(4).tolist()))
-
-    def factory(raw_shape, settings, device):
-        return _StabilizeStep(matrices.__getitem__, settings.registration is not None, raw_shape, settings, device)
-
-    return run_store(input_path, output_path, plan, tuple(keys) if positions else (), zarr_version,
-                     reconstructor_factory=factory, resume=resume, io_backend=io_backend, compression=compression,
-                     on_error=on_error,
-                     fingerprint_extra={"stabilize": {k: s.model_dump(mode="json") for k, s in per_position.items()}},
-                     levels=levels, level_factor_z=level_factor_z)
+    return _run_named_channels(input_path, output_path, channels, keys, positions, zarr_version,
+                               lambda unit: matrices[unit.position][unit.t], apply_stabilization,
+                               {"stabilize": {k: s.model_dump(mode="json") for k, s in per_position.items()}},
+                               resume=resume, io_backend=io_backend, compression=compression, on_error=on_error,
+                               levels=levels, level_factor_z=level_factor_z)
 
 
-class _BackgroundStep:
-    """``run_store``'s step of the ``subtract-background`` command: ``for_unit`` hands out the top-hat at the half-widths of
-    the unit's position (``named`` channels) or a plain copy (every other channel); the volume keeps its shape."""
+@dataclass(frozen=True)
+class _ChannelFilter:
+    """A command that filters the channels its settings name, as ``_run_channel_filter`` runs it."""
 
-    def __init__(self, half_widths_of, op: str, named: bool, raw_shape, _settings, device):
-        self.device = device
-        self.output_shape = tuple(int(n) for n in raw_shape)
-        self._half_widths_of, self._op, self._named = half_widths_of, op, named
-
-    def for_unit(self, unit):
-        import torch
-
-        from . import morphology
-
-        half_widths = self._half_widths_of(unit.position) if self._named else None
-        tophat = getattr(morphology, self._op)
-
-        def step(raw):
-            vol = torch.as_tensor(raw, device=self.device).to(torch.float32).contiguous()
-            return vol if half_widths is None else tophat(vol, half_widths)
-
-        return step
+    settings: type              # the settings model the YAML is loaded into
+    channels: str               # its field that lists the channels to filter, under the name the messages use
+    prepare: Callable           # (settings, scale_zyx) -> the filter's parameter for one position; ValueError: the run is refused
+    apply: Callable             # (float32 volume, settings, that parameter) -> the filtered volume
+    extra: Callable             # (settings, {position key: parameter}) -> the command's ``fingerprint_extra``
 
 
-@cli.command("subtract-background", cls=_eat_all_command("-i", "--input-position-dirpaths"))
-@_common
-def subtract_background(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error,
-                        levels, level_factor_z):
-    """Subtract a slowly varying background: the top-hat of whole channels (config: a BackgroundSettings YAML).
+def _run_channel_filter(command: _ChannelFilter, input_path, config, output_path, positions, zarr_version, io_backend,
+                        **store_options) -> dict:
+    """Load and check the settings, find the parameter of every selected position at its scale -- all of it before the output
+    store is created --, then ``_run_named_channels``."""
+    from .io.omezarr import position_scale
+
+    try:
+        settings = command.settings.from_yaml(config)
+    except (ValueError, TypeError) as exc:
+        raise click.ClickException(f"{config}: {exc}") from exc
+    channels = list(getattr(settings, command.channels))
+    if not channels:          # (EnhanceSettings allows it, for segment; the other models have refused it already)
+        raise click.ClickException(f"{config}: {command.channels} is empty: nothing to filter")
+    src, src_positions = _open_source(Path(input_path), io_backend)
+    with _closing(src):
+        keys = _selected_keys(src_positions, positions)
+        names = list(src_positions[keys[0]].channel_names)
+        unknown = [n for n in channels if n not in names]
+        if unknown:
+            raise click.ClickException(f"{command.channels} {unknown} not in the store (it has {names})")
+        parameters = {}
+        for key in keys:
+            scale = tuple(float(v) for v in position_scale(src_positions[key])[-3:])
+            try:
+                parameters[key] = command.prepare(settings, scale)
+            except ValueError as exc:
+                raise click.ClickException(f"position {key}: {exc}") from exc
+    return _run_named_channels(input_path, output_path, channels, keys, positions, zarr_version,
+                               lambda unit: parameters[unit.position], lambda vol, p: command.apply(vol, settings, p),
+                               command.extra(settings, parameters), io_backend=io_backend, **store_options)
+
+
+def _half_widths_extra(name: str):
+    """``_ChannelFilter.extra`` of a command whose parameter is a position's half-widths: the document under ``name``."""
+    return lambda settings, half_widths: {name: {"settings": settings.model_dump(mode="json"),
+                                                 "half_widths": {k: list(v) for k, v in half_widths.items()}}}
+
+
+def _background_half_widths(settings, scale):
+    from .morphology import half_widths_of
+
+    return half_widths_of(settings.radius, scale)
+
+
+def _background_apply(vol, settings, half_widths):
+    from . import morphology
+
+    return getattr(morphology, settings.op)(vol, half_widths)
+
+
+_BACKGROUND = _ChannelFilter(BackgroundSettings, "channel_names", _background_half_widths, _background_apply,
+                             _half_widths_extra("subtract_background"))
+
+
+@_store_command("subtract-background", """Subtract a slowly varying background: the top-hat of whole channels (config: a
+    BackgroundSettings YAML).
 
     Every volume of the channels channel_names is replaced by its white top-hat (v - opening(v); op: black_tophat gives
     closing(v) - v) under a box of `radius` micrometres (a number or [z, y, x]; 0 on an axis: no window there) at the
-    position's scale; the other channels are copied.  The window has to be wider than the objects that are to stay."""
-    input_path, positions = _inputs(input_path, positions)
-    _finish(run_subtract_background(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression,
-                                    on_error, **_pyramid_options(levels, level_factor_z)))
-
-
+    position's scale; the other channels are copied.  The window has to be wider than the objects that are to stay.""")
 def run_subtract_background(input_path, config, output_path, positions=(), zarr_version: str = "0.5", resume: bool = False,
                             io_backend: str = "auto", compression=None, on_error: str = "raise", levels: int = 1,
                             level_factor_z: int = 2) -> dict:
@@ -1257,100 +1319,44 @@ def run_subtract_background(input_path, config, output_path, positions=(), zarr_
     (``shrimpy_amd/morphology.py``) at the half-widths ``radius`` comes to at the position's ``(z, y, x)`` scale, the other
     channels are copied.  Everything is checked before the output store is created: the settings, the channels, and the
     half-widths of every position against the kernels' cap."""
-    from .io.omezarr import position_scale
-    from .morphology import half_widths_of
-    from .settings import BackgroundSettings
-
-    try:
-        settings = BackgroundSettings.from_yaml(config)
-    except (ValueError, TypeError) as exc:
-        raise click.ClickException(f"{config}: {exc}") from exc
-    channels = list(settings.channel_names)
-    src, src_positions = _open_source(Path(input_path), io_backend)
-    try:
-        missing = [p for p in positions if p not in src_positions]
-        if missing:
-            raise click.ClickException(f"positions {missing} not found; available: {list(src_positions)}")
-        keys = [k for k in src_positions if not positions or k in positions]
-        if not keys:
-            raise click.ClickException("no positions to process")
-        names = list(src_positions[keys[0]].channel_names)
-        unknown = [n for n in channels if n not in names]
-        if unknown:
-            raise click.ClickException(f"channel_names {unknown} not in the store (it has {names})")
-        half_widths = {}
-        for key in keys:
-            scale = tuple(float(v) for v in position_scale(src_positions[key])[-3:])
-            try:
-                half_widths[key] = half_widths_of(settings.radius, scale)
-            except ValueError as exc:
-                raise click.ClickException(f"position {key}: {exc}") from exc
-    finally:
-        close = getattr(src, "close", None)
-        if close:
-            close()
-    # run_store's channel plan: the named channels take the first step, the others the second
-    plan = ReconstructSettings(registration=RegisterSettings(source_channel_names=channels,
-                                                             affine_transform_zyx=np.eye(4).tolist()))
-
-    def factory(raw_shape, plan_settings, device):
-        return _BackgroundStep(half_widths.__getitem__, settings.op, plan_settings.registration is not None, raw_shape,
-                               plan_settings, device)
-
-    return run_store(input_path, output_path, plan, tuple(keys) if positions else (), zarr_version,
-                     reconstructor_factory=factory, resume=resume, io_backend=io_backend, compression=compression,
-                     on_error=on_error,
-                     fingerprint_extra={"subtract_background": {"settings": settings.model_dump(mode="json"),
-                                                                "half_widths": {k: list(v) for k, v in half_widths.items()}}},
-                     levels=levels, level_factor_z=level_factor_z)
+    return _run_channel_filter(_BACKGROUND, input_path, config, output_path, positions, zarr_version, io_backend, resume=resume,
+                               compression=compression, on_error=on_error, levels=levels, level_factor_z=level_factor_z)
 
 
-class _DespeckleStep:
-    """``run_store``'s step of the ``despeckle`` command: ``for_unit`` hands out the rank filter at the half-widths of the
-    unit's position (``named`` channels) or a plain copy (every other channel); the volume keeps its shape."""
+def _despeckle_half_widths(settings, scale):
+    from . import rank
 
-    def __init__(self, half_widths_of, settings, named: bool, raw_shape, _settings, device):
-        self.device = device
-        self.output_shape = tuple(int(n) for n in raw_shape)
-        self._half_widths_of, self._despeckle, self._named = half_widths_of, settings, named
-
-    def for_unit(self, unit):
-        import torch
-
-        from . import rank
-
-        half_widths = self._half_widths_of(unit.position) if self._named else None
-        s = self._despeckle
-
-        def step(raw):
-            vol = torch.as_tensor(raw, device=self.device).to(torch.float32).contiguous()
-            if half_widths is None:
-                return vol
-            if s.percentile is not None:
-                return rank.percentile_filter(vol, s.percentile, half_widths)
-            if s.op == "median":
-                return rank.median_filter(vol, half_widths)
-            return rank.remove_outliers(vol, half_widths, s.threshold, s.op[len("remove_"):])
-
-        return step
+    if settings.half_widths is not None:
+        half_widths = rank._half_widths(settings.half_widths)
+    else:
+        half_widths = rank.half_widths_of(settings.radius, scale)
+    if settings.percentile is not None:
+        rank.rank_of_percentile(settings.percentile, rank.window_size(half_widths))
+    return half_widths
 
 
-@cli.command("despeckle", cls=_eat_all_command("-i", "--input-position-dirpaths"))
-@_common
-def despeckle(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error, levels,
-              level_factor_z):
-    """Remove hot pixels and speckle: a median / outlier-removal filter of whole channels (config: a DespeckleSettings YAML).
+def _despeckle_apply(vol, s, half_widths):
+    from . import rank
+
+    if s.percentile is not None:
+        return rank.percentile_filter(vol, s.percentile, half_widths)
+    if s.op == "median":
+        return rank.median_filter(vol, half_widths)
+    return rank.remove_outliers(vol, half_widths, s.threshold, s.op[len("remove_"):])
+
+
+_DESPECKLE = _ChannelFilter(DespeckleSettings, "channel_names", _despeckle_half_widths, _despeckle_apply,
+                            _half_widths_extra("despeckle"))
+
+
+@_store_command("despeckle", """Remove hot pixels and speckle: a median / outlier-removal filter of whole channels (config: a
+    DespeckleSettings YAML).
 
     Every volume of the channels channel_names is filtered under a box of `radius` micrometres (a number or [z, y, x]) at the
     position's scale, or of `half_widths` voxels ([z, y, x]; hot pixels of a raw stack: [0, 1, 1]); at most 3 voxels to each
     side.  op: median replaces every voxel by the median of its box (or, with `percentile`, by that percentile);
     remove_bright (the default), remove_dark and remove_both replace only the voxels that differ from the median by more than
-    `threshold` and leave the others as they are.  The other channels are copied."""
-    input_path, positions = _inputs(input_path, positions)
-    _finish(run_despeckle(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error,
-                          **_pyramid_options(levels, level_factor_z)))
-
-
+    `threshold` and leave the others as they are.  The other channels are copied.""")
 def run_despeckle(input_path, config, output_path, positions=(), zarr_version: str = "0.5", resume: bool = False,
                   io_backend: str = "auto", compression=None, on_error: str = "raise", levels: int = 1,
                   level_factor_z: int = 2) -> dict:
@@ -1358,100 +1364,36 @@ def run_despeckle(input_path, config, output_path, positions=(), zarr_version: s
     (``shrimpy_amd/rank.py``) at ``half_widths``, or at the half-widths ``radius`` comes to at the position's ``(z, y, x)``
     scale; the other channels are copied.  Everything is checked before the output store is created: the settings, the
     channels, and the half-widths of every position against the kernel's cap."""
-    from . import rank
-    from .io.omezarr import position_scale
-    from .settings import DespeckleSettings
-
-    try:
-        settings = DespeckleSettings.from_yaml(config)
-    except (ValueError, TypeError) as exc:
-        raise click.ClickException(f"{config}: {exc}") from exc
-    channels = list(settings.channel_names)
-    src, src_positions = _open_source(Path(input_path), io_backend)
-    try:
-        missing = [p for p in positions if p not in src_positions]
-        if missing:
-            raise click.ClickException(f"positions {missing} not found; available: {list(src_positions)}")
-        keys = [k for k in src_positions if not positions or k in positions]
-        if not keys:
-            raise click.ClickException("no positions to process")
-        names = list(src_positions[keys[0]].channel_names)
-        unknown = [n for n in channels if n not in names]
-        if unknown:
-            raise click.ClickException(f"channel_names {unknown} not in the store (it has {names})")
-        half_widths = {}
-        for key in keys:
-            scale = tuple(float(v) for v in position_scale(src_positions[key])[-3:])
-            try:
-                if settings.half_widths is not None:
-                    half_widths[key] = rank._half_widths(settings.half_widths)
-                else:
-                    half_widths[key] = rank.half_widths_of(settings.radius, scale)
-                if settings.percentile is not None:
-                    rank.rank_of_percentile(settings.percentile, rank.window_size(half_widths[key]))
-            except ValueError as exc:
-                raise click.ClickException(f"position {key}: {exc}") from exc
-    finally:
-        close = getattr(src, "close", None)
-        if close:
-            close()
-    # run_store's channel plan: the named channels take the first step, the others the second
-    plan = ReconstructSettings(registration=RegisterSettings(source_channel_names=channels,
-                                                             affine_transform_zyx=np.eye(4).tolist()))
-
-    def factory(raw_shape, plan_settings, device):
-        return _DespeckleStep(half_widths.__getitem__, settings, plan_settings.registration is not None, raw_shape,
-                              plan_settings, device)
-
-    return run_store(input_path, output_path, plan, tuple(keys) if positions else (), zarr_version,
-                     reconstructor_factory=factory, resume=resume, io_backend=io_backend, compression=compression,
-                     on_error=on_error,
-                     fingerprint_extra={"despeckle": {"settings": settings.model_dump(mode="json"),
-                                                      "half_widths": {k: list(v) for k, v in half_widths.items()}}},
-                     levels=levels, level_factor_z=level_factor_z)
+    return _run_channel_filter(_DESPECKLE, input_path, config, output_path, positions, zarr_version, io_backend, resume=resume,
+                               compression=compression, on_error=on_error, levels=levels, level_factor_z=level_factor_z)
 
 
-class _EnhanceStep:
-    """``run_store``'s step of the ``enhance`` command: ``for_unit`` hands out the multi-scale Hessian response at the scales
-    of the unit's position (``named`` channels) or a plain copy (every other channel); the volume keeps its shape."""
+def _enhance_scales(settings, scale):
+    from . import hessian
 
-    def __init__(self, scales_of, settings, named: bool, raw_shape, _settings, device):
-        self.device = device
-        self.output_shape = tuple(int(n) for n in raw_shape)
-        self._scales_of, self._enhance, self._named = scales_of, settings, named
-
-    def for_unit(self, unit):
-        import torch
-
-        from . import hessian
-
-        scales = self._scales_of(unit.position) if self._named else None
-        s = self._enhance
-
-        def step(raw):
-            vol = torch.as_tensor(raw, device=self.device).to(torch.float32).contiguous()
-            if scales is None:
-                return vol
-            return hessian.enhance(vol, s.measure, scales[0], scales[1], s.dark)
-
-        return step
+    sigmas, sampling = settings.scales(scale)
+    for sigma in sigmas:
+        hessian.blur_radii(sigma, sampling)
+    return sigmas, sampling
 
 
-@cli.command("enhance", cls=_eat_all_command("-i", "--input-position-dirpaths"))
-@_common
-def enhance(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error, levels,
-            level_factor_z):
-    """Enhance tubes, sheets or blobs: a filter on the eigenvalues of the smoothed Hessian (config: an EnhanceSettings YAML).
+def _enhance_apply(vol, s, scales):
+    from . import hessian
+
+    return hessian.enhance(vol, s.measure, scales[0], scales[1], s.dark)
+
+
+_ENHANCE = _ChannelFilter(EnhanceSettings, "channels", _enhance_scales, _enhance_apply, lambda settings, scales: {
+    "enhance": {"settings": settings.model_dump(mode="json"), "scales": {k: [list(v[0]), list(v[1])] for k, v in scales.items()}}})
+
+
+@_store_command("enhance", """Enhance tubes, sheets or blobs: a filter on the eigenvalues of the smoothed Hessian (config: an
+    EnhanceSettings YAML).
 
     Every volume of the channels `channels` is replaced by its `measure` -- ridge, tube (Sato's tubeness), sheet, blob, log
     (the scale-normalised Laplacian) or an eigenvalue e1 <= e2 <= e3 --, the maximum over the scales `sigmas_um`
     (micrometres, at the position's scale) or `sigmas` (voxels); dark: true looks for dark structures.  The other channels
-    are copied."""
-    input_path, positions = _inputs(input_path, positions)
-    _finish(run_enhance(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error,
-                        **_pyramid_options(levels, level_factor_z)))
-
-
+    are copied.""")
 def run_enhance(input_path, config, output_path, positions=(), zarr_version: str = "0.5", resume: bool = False,
                 io_backend: str = "auto", compression=None, on_error: str = "raise", levels: int = 1,
                 level_factor_z: int = 2) -> dict:
@@ -1459,56 +1401,8 @@ def run_enhance(input_path, config, output_path, positions=(), zarr_version: str
     scales -- ``sigmas_um`` at the position's ``(z, y, x)`` scale, ``sigmas`` on the voxel grid --; the other channels are
     copied.  Everything is checked before the output store is created: the settings, the channels, and the blur radius of
     every scale of every position against the blur's cap."""
-    from . import hessian
-    from .io.omezarr import position_scale
-    from .settings import EnhanceSettings
-
-    try:
-        settings = EnhanceSettings.from_yaml(config)
-    except (ValueError, TypeError) as exc:
-        raise click.ClickException(f"{config}: {exc}") from exc
-    channels = list(settings.channels)
-    if not channels:
-        raise click.ClickException(f"{config}: channels is empty: nothing to filter")
-    src, src_positions = _open_source(Path(input_path), io_backend)
-    try:
-        missing = [p for p in positions if p not in src_positions]
-        if missing:
-            raise click.ClickException(f"positions {missing} not found; available: {list(src_positions)}")
-        keys = [k for k in src_positions if not positions or k in positions]
-        if not keys:
-            raise click.ClickException("no positions to process")
-        names = list(src_positions[keys[0]].channel_names)
-        unknown = [n for n in channels if n not in names]
-        if unknown:
-            raise click.ClickException(f"channels {unknown} not in the store (it has {names})")
-        scales = {}
-        for key in keys:
-            scale = tuple(float(v) for v in position_scale(src_positions[key])[-3:])
-            try:
-                scales[key] = settings.scales(scale)
-                for sigma in scales[key][0]:
-                    hessian.blur_radii(sigma, scales[key][1])
-            except ValueError as exc:
-                raise click.ClickException(f"position {key}: {exc}") from exc
-    finally:
-        close = getattr(src, "close", None)
-        if close:
-            close()
-    # run_store's channel plan: the named channels take the first step, the others the second
-    plan = ReconstructSettings(registration=RegisterSettings(source_channel_names=channels,
-                                                             affine_transform_zyx=np.eye(4).tolist()))
-
-    def factory(raw_shape, plan_settings, device):
-        return _EnhanceStep(scales.__getitem__, settings, plan_settings.registration is not None, raw_shape, plan_settings,
-                            device)
-
-    return run_store(input_path, output_path, plan, tuple(keys) if positions else (), zarr_version,
-                     reconstructor_factory=factory, resume=resume, io_backend=io_backend, compression=compression,
-                     on_error=on_error,
-                     fingerprint_extra={"enhance": {"settings": settings.model_dump(mode="json"),
-                                                    "scales": {k: [list(v[0]), list(v[1])] for k, v in scales.items()}}},
-                     levels=levels, level_factor_z=level_factor_z)
+    return _run_channel_filter(_ENHANCE, input_path, config, output_path, positions, zarr_version, io_backend, resume=resume,
+                               compression=compression, on_error=on_error, levels=levels, level_factor_z=level_factor_z)
 
 
 def _position_translation(position) -> tuple[float, ...]:
@@ -1562,43 +1456,37 @@ def run_estimate_stitch(input_path, config, output_path, positions=(), io_backen
     rank, world, device, created = _distributed()
     try:
         src, src_positions = _open_source(Path(input_path), io_backend)
-        keys = [k for k in src_positions if not positions or k in positions]
-        missing = [p for p in positions if p not in src_positions]
-        if missing:
-            raise click.ClickException(f"positions {missing} not found; available: {list(src_positions)}")
-        if not keys:
-            raise click.ClickException("no positions to process")
-        total: dict = {}
-        for well, names in _wells(keys).items():
-            arrays = {k: as_volume_array(src_positions[k]["0"]) for k in names}
-            for k, a in arrays.items():
-                if len(a.shape) != 5:
-                    raise click.ClickException(f"position {k}: expected 5-D TCZYX data, got shape {tuple(a.shape)}")
-            channel_names = list(src_positions[names[0]].channel_names)
-            if settings.channel not in channel_names:
-                raise click.ClickException(f"well {well}: channel {settings.channel!r} not in the store (it has {channel_names})")
-            c = channel_names.index(settings.channel)
-            shapes = {k: tuple(int(n) for n in a.shape[2:]) for k, a in arrays.items()}
-            if settings.initial_placement == "grid":
-                initial = dict(zip(names, grid_placement([shapes[k] for k in names], settings.grid_columns,
-                                                         settings.percent_overlap)))
-            else:
-                initial = {k: tuple(t / sc for t, sc in zip(_position_translation(src_positions[k])[2:],
-                                                            position_scale(src_positions[k])[2:])) for k in names}
+        with _closing(src):
+            keys = _selected_keys(src_positions, positions)
+            total: dict = {}
+            for well, names in _wells(keys).items():
+                arrays = {k: as_volume_array(src_positions[k]["0"]) for k in names}
+                for k, a in arrays.items():
+                    if len(a.shape) != 5:
+                        raise click.ClickException(f"position {k}: expected 5-D TCZYX data, got shape {tuple(a.shape)}")
+                channel_names = list(src_positions[names[0]].channel_names)
+                if settings.channel not in channel_names:
+                    raise click.ClickException(f"well {well}: channel {settings.channel!r} not in the store "
+                                               f"(it has {channel_names})")
+                c = channel_names.index(settings.channel)
+                shapes = {k: tuple(int(n) for n in a.shape[2:]) for k, a in arrays.items()}
+                if settings.initial_placement == "grid":
+                    initial = dict(zip(names, grid_placement([shapes[k] for k in names], settings.grid_columns,
+                                                             settings.percent_overlap)))
+                else:
+                    initial = {k: tuple(t / sc for t, sc in zip(_position_translation(src_positions[k])[2:],
+                                                                position_scale(src_positions[k])[2:])) for k in names}
 
-            @functools.lru_cache(maxsize=1)
-            def volume(k, arrays=arrays, c=c):
-                return arrays[k].read_volume(0, c)
+                @functools.lru_cache(maxsize=1)
+                def volume(k, arrays=arrays, c=c):
+                    return arrays[k].read_volume(0, c)
 
-            def crop(k, sl):
-                return torch.as_tensor(np.ascontiguousarray(volume(k)[sl], dtype=np.float32), device=device)
+                def crop(k, sl):
+                    return torch.as_tensor(np.ascontiguousarray(volume(k)[sl], dtype=np.float32), device=device)
 
-            placed = estimate_translations(crop, shapes, initial, settings)
-            total.update({k: [float(v) for v in t] for k, t in placed.items()})
-            logger.info("well %s: %d tiles placed", well, len(names))
-        close = getattr(src, "close", None)
-        if close:
-            close()
+                placed = estimate_translations(crop, shapes, initial, settings)
+                total.update({k: [float(v) for v in t] for k, t in placed.items()})
+                logger.info("well %s: %d tiles placed", well, len(names))
         if rank == 0:
             Path(output_path).parent.mkdir(parents=True, exist_ok=True)
             StitchSettings(total_translation=total).to_yaml(output_path)
@@ -1614,16 +1502,8 @@ def run_estimate_stitch(input_path, config, output_path, positions=(), io_backen
 STITCH_RESIDENT_SHARE = 0.8
 
 
-@cli.command(cls=_eat_all_command("-i", "--input-position-dirpaths"))
-@_common
-def stitch(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error, levels,
-           level_factor_z):
-    """Compose the fields of view of every well into one position per well (config: the StitchSettings YAML of estimate-stitch)."""
-    input_path, positions = _inputs(input_path, positions)
-    _finish(run_stitch(input_path, config, output_path, positions, zarr_version, resume, io_backend, compression, on_error,
-                       **_pyramid_options(levels, level_factor_z)))
-
-
+@_store_command("stitch", "Compose the fields of view of every well into one position per well (config: the StitchSettings YAML "
+                          "of estimate-stitch).")
 def run_stitch(input_path, config, output_path, positions=(), zarr_version: str = "0.5", resume: bool = False,
                io_backend: str = "auto", compression=None, on_error: str = "raise", levels: int = 1,
                level_factor_z: int = 2) -> dict:
@@ -1787,13 +1667,8 @@ def _run_object_store(input_path, output_path, positions, zarr_version, io_backe
     rank, world, device, created = _distributed()
     try:
         src, src_positions = _open_source(Path(input_path), io_backend)
-        try:
-            missing = [p for p in positions if p not in src_positions]
-            if missing:
-                raise click.ClickException(f"positions {missing} not found; available: {list(src_positions)}")
-            keys = [k for k in src_positions if not positions or k in positions]
-            if not keys:
-                raise click.ClickException("no positions to process")
+        with _closing(src):
+            keys = _selected_keys(src_positions, positions)
             arrays, channel, geometry = {}, {}, {}
             for k in keys:
                 pos = src_positions[k]
@@ -1835,20 +1710,12 @@ def _run_object_store(input_path, output_path, positions, zarr_version, io_backe
             dst_positions = dict(dst.positions())
             entries = {}
             t0 = time.perf_counter()
-            try:
+            with _closing(dst):
                 for k in keys[rank::world]:
                     out = as_volume_array(dst_positions[k]["0"])
                     entries[k] = process(k, arrays[k], channel[k], out, geometry[k], device, Path(output_path) / k)
-            finally:
-                close = getattr(dst, "close", None)
-                if close:
-                    close()
             return {"rank": rank, "world_size": world, "positions": len(keys[rank::world]), result_key: entries,
                     "seconds": time.perf_counter() - t0, "failed": []}
-        finally:
-            close = getattr(src, "close", None)
-            if close:
-                close()
     finally:
         if created:
             import torch.distributed as dist
@@ -2148,9 +2015,9 @@ def run_measure(labels_path, input_path, config, output_path, positions=(), io_b
     rank, world, device, created = _distributed()
     try:
         label_store, label_positions = _open_source(Path(labels_path), io_backend)
-        try:
+        with _closing(label_store):
             src, src_positions = _open_source(Path(input_path), io_backend)
-            try:
+            with _closing(src):
                 missing = [p for p in positions if p not in src_positions]
                 if missing:
                     raise click.ClickException(f"positions {missing} not found in {input_path}; available: {list(src_positions)}")
@@ -2257,14 +2124,6 @@ def run_measure(labels_path, input_path, config, output_path, positions=(), io_b
                     entries[k] = len(rows)
                 return {"rank": rank, "world_size": world, "positions": len(keys[rank::world]), "rows": entries,
                         "seconds": time.perf_counter() - t0, "failed": []}
-            finally:
-                close = getattr(src, "close", None)
-                if close:
-                    close()
-        finally:
-            close = getattr(label_store, "close", None)
-            if close:
-                close()
     finally:
         if created:
             import torch.distributed as dist
