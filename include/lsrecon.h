@@ -141,6 +141,12 @@ int lsr_minmax_u16(const uint16_t* in, int64_t n, float* out2, void* scratch, ls
  * General order-1 (trilinear) affine resample; any 3x4 matrix.
  * mode/cval as scipy.ndimage.affine_transform. fp64 coordinates and weights, same operation
  * order as scipy: bit-identical to the CPU oracle for finite inputs.
+ * Non-finite inputs: the three kernels and the host twin apply the rule of csrc/resample.hpp literally -- every corner is
+ * multiplied, also by a weight of exactly 0 (inf * 0 is a NaN), so a NaN or an infinity reaches exactly the voxels one of whose
+ * eight taps holds it -- and agree bit for bit (a NaN by position) at every voxel none of whose coordinates is exactly n - 1 on
+ * its axis.  There the upper neighbour, of weight 0, is voxel n - 1 itself in the gather kernel and the twin and a staged
+ * duplicate of in-volume data (in a padded source: the padding column) in the LDS-staged kernels: the same bits on finite data
+ * only.  (tests/affine_ref.py restates the rule; tests/test_affine_edges_gpu.py holds all four to it.)
  */
 int lsr_affine_f32(const float* in, int64_t Zi, int64_t Yi, int64_t Xi, float* out, int64_t Zo,
                    int64_t Yo, int64_t Xo, const double M[12], float cval, int mode,
@@ -162,6 +168,22 @@ int lsr_affine_pitched_f32(const float* in, int64_t Zi, int64_t Yi, int64_t Xi, 
                            lsr_stream_t stream);
 int lsr_affine_path_pitched(int64_t Zi, int64_t Yi, int64_t Xi, int64_t in_pitch, int64_t in_plane,
                             const double M[12], int mode); /* lsr_affine_path for such a source */
+/* The launch lsr_affine_pitched_f32 makes for these shapes, strides, matrix and mode (lsr_affine_f32: in_pitch = Xi,
+ * in_plane = Yi * Xi, out_pitch = Xo) -- host code, no device call; the status is the one that entry returns for the
+ * same arguments with valid buffers.  out[0] = the path as lsr_affine_path_pitched numbers it, then
+ *   1 (csrc/affine_planar.hip): out[1..13] = waves per workgroup, tile rows, tile columns, box_y, box_x (the staged box of a
+ *     source plane), ring slots, LDS bytes, z_chunk (output planes per workgroup), tiles_y, tiles_x, patch h, patch w
+ *     (tiles per patch, exact mode), workgroups launched;
+ *   2 (csrc/affine_box.hip): out[1..13] = block tz, ty, tx, box bz, by, bx, LDS bytes, blocks along z, y, x, `linear`
+ *     (1: patch-major order as numbered, 0: a contiguous run of it per XCD), 0, workgroups launched;
+ *   0 (csrc/affine.hip): out[2], out[3] = rows and columns of a workgroup, out[9], out[10] = tiles_y, tiles_x, out[13] =
+ *     workgroups launched; the rest 0.
+ * out[14], out[15] are 0.  LSR_PLANAR_WAVES, LSR_PLANAR_PATCH and LSR_BOX_LINEAR (measurement switches, read per
+ * launch) are honoured as the launchers honour them: those launch from the same functions, so what the tests count from a
+ * plan is what runs.  Only what the call itself knows can still send it to the gather kernel: `in` not 16-byte aligned,
+ * in == out, or a device that refuses the LDS budget. */
+int lsr_affine_plan(int64_t Zi, int64_t Yi, int64_t Xi, int64_t in_pitch, int64_t in_plane, int64_t Zo, int64_t Yo,
+                    int64_t Xo, int64_t out_pitch, const double M[12], int mode, int64_t out[16]);
 /* Which kernel lsr_affine_f32 runs for this matrix on a (.., Yi, Xi) moving volume: 1 = the
  * LDS-staged z-marching kernel (csrc/affine_planar.hip: constant mode, z decoupled from the plane,
  * |M[0]| <= 1.5, Xi a multiple of 4, source box of a 32 x 128 tile within LDS), 0 = the general

@@ -6,7 +6,7 @@ draws are used as they are; this file holds the tables only.
 
 The device entries (lsr_affine_f32, lsr_affine_pitched_f32): the negative code, or "ok".  The pure host functions: the
 value (lsr_affine_path, lsr_affine_path_pitched, lsr_affine_kernel_choice), the value and the six ints
-(lsr_affine_box_shape), the status and the output bytes (lsr_affine_f32_cpu, which really resamples: its extents are
+(lsr_affine_box_shape), the status and the sixteen numbers (lsr_affine_plan), the status and the output bytes (lsr_affine_f32_cpu, which really resamples: its extents are
 of kind "s", a volume of at most 6 x 10 x 12 in the rows and 6 x 6 x 6 in the draws).  NEVER run this where a device is
 visible.
 """
@@ -50,8 +50,11 @@ ENTRIES = {
                                 ("in_plane", "l", Y * PITCH), ("M", "p", PLANAR), ("mode", "i", 0)],
     "lsr_affine_kernel_choice": [("Yi", "l", Y), ("Xi", "l", X), ("M", "p", PLANAR), ("mode", "i", 0)],
     "lsr_affine_box_shape": [("Zi", "l", Z), ("Yi", "l", Y), ("Xi", "l", X), ("M", "p", TILTED), ("out6", "p", 11)],
+    "lsr_affine_plan": [("Zi", "l", Z), ("Yi", "l", Y), ("Xi", "l", X), ("in_pitch", "l", PITCH), ("in_plane", "l", Y * PITCH),
+                        ("Zo", "l", Z), ("Yo", "l", Y), ("Xo", "l", X), ("out_pitch", "l", OPITCH), ("M", "p", PLANAR),
+                        ("mode", "i", 0), ("out16", "p", 11)],
 }
-OUTPUT = {"lsr_affine_f32_cpu": 6 * 10 * 12 * 4, "lsr_affine_box_shape": 6 * 4}
+OUTPUT = {"lsr_affine_f32_cpu": 6 * 10 * 12 * 4, "lsr_affine_box_shape": 6 * 4, "lsr_affine_plan": 16 * 8}
 HOST_ONLY = set(ENTRIES) - {"lsr_affine_f32", "lsr_affine_pitched_f32"}
 
 # ---- one row per check group: the baseline with exactly that condition broken ---------------------------------------
@@ -95,11 +98,21 @@ BREAKS = {
                                                               ({"Xi": 1 << 30}, None)],
     "lsr_affine_box_shape": [({"M": None}, 0), ({"out6": None}, 0), ({"Zi": 0}, 0), ({"Xi": 1 << 30}, 0), ({"M": STEEP}, 0),
                              ({"M": PLANAR}, 1), ({"Zi": 1}, 0), ({"Xi": 7}, 0), ({"M": NAN}, None)],
+    # (the pitched entry's statuses in its order, the buffers apart; the 16 numbers where the call passes)
+    "lsr_affine_plan": [({"out16": None}, E_NULL), ({"M": None}, E_NULL), ({"Zi": 0}, E_UNSUPPORTED), ({"Yo": -1}, E_UNSUPPORTED),
+                        ({"Xi": 1 << 30}, E_UNSUPPORTED), ({"in_pitch": -4}, E_UNSUPPORTED), ({"in_plane": 1 << 32}, E_UNSUPPORTED),
+                        ({"out_pitch": 1 << 31}, E_UNSUPPORTED), ({"in_pitch": X - 1}, E_SHAPE), ({"in_plane": Y * PITCH - 1}, E_SHAPE),
+                        ({"out_pitch": X - 1}, E_SHAPE), ({"in_pitch": X - 1, "M": None}, E_SHAPE), ({"mode": 2, "M": None}, E_NULL),
+                        ({"mode": 2}, E_ARG), ({"mode": 2, "M": NAN}, E_ARG), ({"M": NAN}, E_ARG), ({"M": INF}, E_ARG),
+                        ({"mode": 1}, 0), ({"mode": 256}, 0), ({"mode": 257}, 0), ({"M": TILTED}, 0), ({"M": STEEP}, 0),
+                        ({"in_pitch": X + 1, "in_plane": Y * (X + 1)}, 0), ({"in_plane": Y * PITCH + 2}, 0),
+                        ({"in_pitch": X, "in_plane": Y * X, "out_pitch": X}, 0), ({"Zi": 1, "M": TILTED}, 0)],
 }
 CODES = {n: set() for n in ENTRIES}
 CODES["lsr_affine_f32"] = CODES["lsr_affine_pitched_f32"] = CODES["lsr_affine_f32_cpu"] = {E_NULL, E_SHAPE, E_UNSUPPORTED, E_ARG}
+CODES["lsr_affine_plan"] = {E_NULL, E_SHAPE, E_UNSUPPORTED, E_ARG}
 
-TABLES = base.Tables(FIXTURE, ENTRIES, BREAKS, OUTPUT, HOST_ONLY, CODES, output_args=("out", "out6"),
+TABLES = base.Tables(FIXTURE, ENTRIES, BREAKS, OUTPUT, HOST_ONLY, CODES, output_args=("out", "out6", "out16"),
                      baseline={"lsr_affine_box_shape": 1})
 
 

@@ -106,6 +106,7 @@ SIGNATURES: dict[str, list] = {
                                _int, _stream],
     "lsr_affine_path_pitched": [_i64, _i64, _i64, _i64, _i64, _f64p, _int],
     "lsr_affine_path": [_i64, _i64, _i64, _f64p, _int],
+    "lsr_affine_plan": [_i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f64p, _int, ctypes.POINTER(ctypes.c_int64)],
     "lsr_affine_box_shape": [_i64, _i64, _i64, _f64p, ctypes.POINTER(ctypes.c_int)],
     "lsr_affine_normal_size": [],
     "lsr_affine_normal_blocks": [],

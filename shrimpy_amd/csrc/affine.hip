@@ -165,6 +165,20 @@ __global__ __launch_bounds__(kThreads) void affine_kernel(AffineArgs p) {
   }
 }
 
+// The gather kernel's launch for a call neither LDS-staged kernel took: its limits and its grid (affine_impl launches from
+// it, lsr_affine_plan reports it).
+int gather_plan(int64_t Zi, int64_t plane, int64_t Zo, int64_t Yo, int64_t Xo, int* tiles_x, int* tiles_y, int64_t* grid) {
+  // (the LDS-staged kernels address a volume plane by plane with 64-bit bases; the gather kernel does not)
+  LSR_REQUIRE(Zi * plane <= (int64_t(1) << 32), LSR_E_UNSUPPORTED,
+              "the moving volume spans more than 2^32 elements and this map does not fit the LDS-staged kernels "
+              "(the gather kernel indexes elements in 32 bits): resample it in z slabs");
+  *tiles_x = static_cast<int>(lsr::ceil_div(Xo, kTileX));
+  *tiles_y = static_cast<int>(lsr::ceil_div(Yo, kRows));
+  *grid = int64_t(*tiles_x) * *tiles_y * Zo;
+  LSR_REQUIRE(*grid < (int64_t(1) << 31), LSR_E_SHAPE, "grid of %lld workgroups is too large", (long long)*grid);
+  return LSR_OK;
+}
+
 // a call that met its entry's requirements: pick the kernel, launch (blend: grid-constant)
 int affine_impl(const char* what, const float* in, int64_t Zi, int64_t Yi, int64_t Xi, int64_t pitch, int64_t plane,
                 float* out, int64_t Zo, int64_t Yo, int64_t Xo, int64_t opitch, int64_t oplane, const double M[12],
@@ -177,11 +191,9 @@ int affine_impl(const char* what, const float* in, int64_t Zi, int64_t Yi, int64
                               lsr::as_stream(stream))))
     return lsr::launch_status(what);
 
-  // (the LDS-staged kernels address a volume plane by plane with 64-bit bases; the gather kernel below does not)
-  LSR_REQUIRE(Zi * plane <= (int64_t(1) << 32), LSR_E_UNSUPPORTED,
-              "the moving volume spans more than 2^32 elements and this map does not fit the LDS-staged kernels "
-              "(the gather kernel indexes elements in 32 bits): resample it in z slabs");
   AffineArgs p;
+  int64_t blocks;
+  if (int rc = gather_plan(Zi, plane, Zo, Yo, Xo, &p.tiles_x, &p.tiles_y, &blocks)) return rc;
   p.in = in;
   p.out = out;
   p.Zi = static_cast<int>(Zi); p.Yi = static_cast<int>(Yi); p.Xi = static_cast<int>(Xi);
@@ -191,11 +203,6 @@ int affine_impl(const char* what, const float* in, int64_t Zi, int64_t Yi, int64
   for (int i = 0; i < 12; ++i) p.m[i] = M[i];
   p.cval = cval;
   p.mode = blend ? LSR_MODE_GRID_CONSTANT : LSR_MODE_CONSTANT;
-  p.tiles_x = static_cast<int>(lsr::ceil_div(Xo, kTileX));
-  p.tiles_y = static_cast<int>(lsr::ceil_div(Yo, kRows));
-  const int64_t blocks = int64_t(p.tiles_x) * p.tiles_y * Zo;
-  LSR_REQUIRE(blocks < (int64_t(1) << 31), LSR_E_SHAPE, "grid of %lld workgroups is too large",
-              (long long)blocks);
   const dim3 grid(static_cast<unsigned>(blocks)), block(kThreads);
   hipStream_t s = lsr::as_stream(stream);
   if (blend) {
@@ -257,20 +264,60 @@ extern "C" int lsr_affine_f32(const float* in, int64_t Zi, int64_t Yi, int64_t X
   return affine_impl("lsr_affine_f32", in, Zi, Yi, Xi, Xi, Yi * Xi, out, Zo, Yo, Xo, Xo, Yo * Xo, M, cval, f32, blend, stream);
 }
 
+// the requirements of lsr_affine_pitched_f32 on everything but its two buffers, in its order
+static int pitched_requirements(int64_t Zi, int64_t Yi, int64_t Xi, int64_t in_pitch, int64_t in_plane, int64_t Zo, int64_t Yo,
+                                int64_t Xo, int64_t out_pitch, int64_t out_plane) {
+  int rc;
+  // (no require_positive: an extent <= 0 of a padded volume is LSR_E_UNSUPPORTED, as it always was)
+  if ((rc = lsr::require_volumes(Zi, Yi, Xi, Zo, Yo, Xo)) || (rc = lsr::require_stride_range("source", in_pitch, in_plane)) ||
+      (rc = lsr::require_stride_range("output", out_pitch, out_plane)) ||
+      (rc = lsr::require_stride_fit("source", in_pitch, in_plane, Yi, Xi)) ||
+      (rc = lsr::require_stride_fit("output", out_pitch, out_plane, Yo, Xo)))
+    return rc;
+  return LSR_OK;
+}
+
 extern "C" int lsr_affine_pitched_f32(const float* in, int64_t Zi, int64_t Yi, int64_t Xi, int64_t in_pitch,
                                       int64_t in_plane, float* out, int64_t Zo, int64_t Yo, int64_t Xo,
                                       int64_t out_pitch, int64_t out_plane, const double M[12], float cval, int mode,
                                       lsr_stream_t stream) {
   int rc;
   bool blend, f32;
-  // (no require_positive: an extent <= 0 of a padded volume is LSR_E_UNSUPPORTED, as it always was)
-  if ((rc = lsr::require_volumes(Zi, Yi, Xi, Zo, Yo, Xo)) || (rc = lsr::require_stride_range("source", in_pitch, in_plane)) ||
-      (rc = lsr::require_stride_range("output", out_pitch, out_plane)) ||
-      (rc = lsr::require_stride_fit("source", in_pitch, in_plane, Yi, Xi)) ||
-      (rc = lsr::require_stride_fit("output", out_pitch, out_plane, Yo, Xo)) || (rc = lsr::require_buffers(in, out, M)))
+  if ((rc = pitched_requirements(Zi, Yi, Xi, in_pitch, in_plane, Zo, Yo, Xo, out_pitch, out_plane)) ||
+      (rc = lsr::require_buffers(in, out, M)))
     return rc;
   LSR_REQUIRE(in_pitch < lsr::kMaxExtent, LSR_E_UNSUPPORTED, "a source row of %lld floats exceeds 2^30", (long long)in_pitch);
   if ((rc = lsr::require_border(mode, &blend, &f32)) || (rc = lsr::check_matrix(M))) return rc;
   return affine_impl("lsr_affine_pitched_f32", in, Zi, Yi, Xi, in_pitch, in_plane, out, Zo, Yo, Xo, out_pitch, out_plane, M,
                      cval, f32, blend, stream);
+}
+
+extern "C" int lsr_affine_plan(int64_t Zi, int64_t Yi, int64_t Xi, int64_t in_pitch, int64_t in_plane, int64_t Zo, int64_t Yo,
+                               int64_t Xo, int64_t out_pitch, const double M[12], int mode, int64_t out[16]) {
+  int rc;
+  bool blend, f32;
+  // (the smallest out_plane the entry takes for this out_pitch: no decision depends on a larger one)
+  if ((rc = pitched_requirements(Zi, Yi, Xi, in_pitch, in_plane, Zo, Yo, Xo, out_pitch, Yo * out_pitch))) return rc;
+  LSR_REQUIRE_PTR(out);
+  LSR_REQUIRE_PTR(M);
+  LSR_REQUIRE(in_pitch < lsr::kMaxExtent, LSR_E_UNSUPPORTED, "a source row of %lld floats exceeds 2^30", (long long)in_pitch);
+  if ((rc = lsr::require_border(mode, &blend, &f32)) || (rc = lsr::check_matrix(M))) return rc;
+  for (int i = 0; i < 16; ++i) out[i] = 0;
+  lsr::AffinePlanarPlan pl;
+  lsr::AffineBoxPlan bx;
+  if (lsr::affine_planar_plan(Yi, Xi, in_pitch, in_plane, Zo, Yo, Xo, M, f32, &pl)) {
+    const int64_t v[14] = {1, pl.waves, pl.tile_y, pl.tile_x, pl.box_y, pl.box_x, pl.slots, pl.lds_bytes, pl.z_chunk,
+                           pl.tiles_y, pl.tiles_x, pl.patch_h, pl.patch_w, pl.grid};
+    for (int i = 0; i < 14; ++i) out[i] = v[i];
+  } else if (lsr::affine_box_plan(Zi, Yi, Xi, in_pitch, in_plane, Zo, Yo, Xo, out_pitch, M, f32, &bx)) {
+    const int64_t v[14] = {2, bx.tz, bx.ty, bx.tx, bx.bz, bx.by, bx.bx, bx.lds_bytes, bx.tz_n, bx.ty_n, bx.tx_n, bx.linear, 0,
+                           bx.grid};
+    for (int i = 0; i < 14; ++i) out[i] = v[i];
+  } else {
+    int tiles_x, tiles_y;
+    int64_t grid;
+    if ((rc = gather_plan(Zi, in_plane, Zo, Yo, Xo, &tiles_x, &tiles_y, &grid))) return rc;
+    out[2] = kRows; out[3] = kTileX; out[9] = tiles_y; out[10] = tiles_x; out[13] = grid;
+  }
+  return LSR_OK;
 }

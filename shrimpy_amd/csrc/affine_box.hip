@@ -487,12 +487,42 @@ bool affine_box_shape(int64_t Zi, int64_t Yi, int64_t Xi, const double M[12], in
   return true;
 }
 
+// The launch of the box path for this call (resample.hpp); false = not applicable.
+bool affine_box_plan(int64_t Zi, int64_t Yi, int64_t Xi, int64_t pitch, int64_t plane, int64_t Zo, int64_t Yo, int64_t Xo,
+                     int64_t opitch, const double M[12], bool f32, AffineBoxPlan* plan) {
+  BoxShape sh;
+  if (Yo * opitch >= (int64_t(1) << 31)) return false;   // 32-bit output offsets inside a plane
+  if (!pick_shape(Zi, Yi, Xi, pitch, plane, M, &sh)) return false;
+  AffineBoxPlan& q = *plan;
+  q.tz = sh.tz; q.ty = sh.ty; q.tx = sh.tx;
+  q.bz = sh.bz; q.by = sh.by; q.bx = sh.bx;
+  q.lds_bytes = sh.lds_bytes;
+  q.tz_n = static_cast<int>(ceil_div(Zo, sh.tz));
+  q.ty_n = static_cast<int>(ceil_div(Yo, sh.ty));
+  q.tx_n = static_cast<int>(ceil_div(Xo, sh.tx));
+  q.pz_n = static_cast<int>(ceil_div(q.tz_n, kPatch));
+  q.py_n = static_cast<int>(ceil_div(q.ty_n, kPatch));
+  q.px_n = static_cast<int>(ceil_div(q.tx_n, kPatch));
+  const int64_t padded = int64_t(q.pz_n) * q.py_n * q.px_n * (kPatch * kPatch * kPatch);
+  const int64_t per_xcd = ceil_div(padded, 8);
+  if (per_xcd * 8 >= (int64_t(1) << 31)) return false;
+  q.per_xcd = static_cast<int>(per_xcd);
+  // f32 mode (HBM / LDS-DMA bound): the plain patch-major order, whose consecutive blocks go to the eight
+  // XCDs in turn, is as fast or faster (2.52 against 2.71 ms on config 3 o tilt 3 deg); the exact mode keeps
+  // the per-XCD runs (their L2 hits: 1.10x the source fetched).  LSR_BOX_LINEAR=1 / 0 forces either.
+  q.linear = f32 ? 1 : 0;
+  if (const char* e = std::getenv("LSR_BOX_LINEAR")) q.linear = e[0] != '0';
+  // (blocks past `padded` decode to a patch index >= the patch count: px >= px_n -> bx >= tx_n -> exit)
+  q.grid = per_xcd * 8;
+  return true;
+}
+
 bool launch_affine_box(const float* in, int64_t Zi, int64_t Yi, int64_t Xi, int64_t pitch, int64_t plane, float* out,
                        int64_t Zo, int64_t Yo, int64_t Xo, int64_t opitch, int64_t oplane, const double M[12], float cval,
                        bool f32, bool grid, hipStream_t s) {
-  BoxShape sh;
-  if ((reinterpret_cast<uintptr_t>(in) & 15) != 0 || Yo * opitch >= (int64_t(1) << 31)) return false;
-  if (!pick_shape(Zi, Yi, Xi, pitch, plane, M, &sh)) return false;
+  AffineBoxPlan sh;
+  if ((reinterpret_cast<uintptr_t>(in) & 15) != 0) return false;
+  if (!affine_box_plan(Zi, Yi, Xi, pitch, plane, Zo, Yo, Xo, opitch, M, f32, &sh)) return false;
   BoxArgs p;
   p.in = in; p.out = out;
   p.Zi = static_cast<int>(Zi); p.Yi = static_cast<int>(Yi); p.Xi = static_cast<int>(Xi);
@@ -506,22 +536,10 @@ bool launch_affine_box(const float* in, int64_t Zi, int64_t Yi, int64_t Xi, int6
   p.box_z = sh.bz; p.box_y = sh.by; p.box_x = sh.bx;
   p.inv_cx = 1.0f / static_cast<float>(sh.bx / 4);
   p.inv_by = 1.0f / static_cast<float>(sh.by);
-  p.tz_n = static_cast<int>(ceil_div(Zo, sh.tz));
-  p.ty_n = static_cast<int>(ceil_div(Yo, sh.ty));
-  p.tx_n = static_cast<int>(ceil_div(Xo, sh.tx));
-  p.pz_n = static_cast<int>(ceil_div(p.tz_n, kPatch));
-  p.py_n = static_cast<int>(ceil_div(p.ty_n, kPatch));
-  p.px_n = static_cast<int>(ceil_div(p.tx_n, kPatch));
-  const int64_t padded = int64_t(p.pz_n) * p.py_n * p.px_n * (kPatch * kPatch * kPatch);
-  const int64_t per_xcd = ceil_div(padded, 8);
-  if (per_xcd * 8 >= (int64_t(1) << 31)) return false;
-  p.per_xcd = static_cast<int>(per_xcd);
-  // f32 mode (HBM / LDS-DMA bound): the plain patch-major order, whose consecutive blocks go to the eight
-  // XCDs in turn, is as fast or faster (2.52 against 2.71 ms on config 3 o tilt 3 deg); the exact mode keeps
-  // the per-XCD runs (their L2 hits: 1.10x the source fetched).  LSR_BOX_LINEAR=1 / 0 forces either.
-  p.linear = f32 ? 1 : 0;
-  if (const char* e = std::getenv("LSR_BOX_LINEAR")) p.linear = e[0] != '0';
-  // (blocks past `padded` decode to a patch index >= the patch count: px >= px_n -> bx >= tx_n -> exit)
+  p.tz_n = sh.tz_n; p.ty_n = sh.ty_n; p.tx_n = sh.tx_n;
+  p.pz_n = sh.pz_n; p.py_n = sh.py_n; p.px_n = sh.px_n;
+  p.per_xcd = sh.per_xcd;
+  p.linear = sh.linear;
   p.probe = 0;
 #ifdef LSR_BOX_PROBES
   {
@@ -532,9 +550,8 @@ bool launch_affine_box(const float* in, int64_t Zi, int64_t Yi, int64_t Xi, int6
               sh.bx, (long long)sh.lds_bytes);
   }
 #endif
-  const unsigned blocks = static_cast<unsigned>(per_xcd * 8);
+  const unsigned blocks = static_cast<unsigned>(sh.grid);
   const size_t lds = static_cast<size_t>(sh.lds_bytes);
-  if (Yo * opitch >= (int64_t(1) << 31)) return false;   // 32-bit output offsets inside a plane
   switch (sh.tz * 2 + (f32 ? 1 : 0)) {
     case 8 * 2 + 1: return launch_shape<true, 8>(p, blocks, lds, grid, s);
     case 8 * 2 + 0: return launch_shape<false, 8>(p, blocks, lds, grid, s);

@@ -380,7 +380,6 @@ __global__ __launch_bounds__(64 * NW, 4) void affine_planar_kernel(PlanarArgs p)
 
 namespace lsr {
 
-// Returns true if the planar kernel took the launch; false = not applicable, use the general one.
 // Geometry of the planar path for this matrix and moving volume; false = not applicable.
 bool affine_planar_geometry(int64_t Yi, int64_t Xi, int64_t pitch, const double M[12], int* box_y_out, int* box_x_out,
                             int* slots_out, int64_t* lds_bytes_out, int* tile_out, int waves) {
@@ -406,12 +405,12 @@ bool affine_planar_geometry(int64_t Yi, int64_t Xi, int64_t pitch, const double 
   return false;
 }
 
-bool launch_affine_planar(const float* in, int64_t Zi, int64_t Yi, int64_t Xi, int64_t pitch, int64_t plane,
-                          float* out, int64_t Zo, int64_t Yo, int64_t Xo, int64_t opitch, int64_t oplane,
-                          const double M[12], float cval, bool f32, bool grid, hipStream_t s) {
+// The launch of the planar path for this call (resample.hpp); false = not applicable.
+bool affine_planar_plan(int64_t Yi, int64_t Xi, int64_t pitch, int64_t plane, int64_t Zo, int64_t Yo, int64_t Xo,
+                        const double M[12], bool f32, AffinePlanarPlan* plan) {
   int box_y, box_x, slots, tile = 0;
   int64_t lds_bytes;
-  if (plane % 4 != 0 || (reinterpret_cast<uintptr_t>(in) & 15) != 0) return false;
+  if (plane % 4 != 0) return false;
   int waves = kWaves;
   if (!affine_planar_geometry(Yi, Xi, pitch, M, &box_y, &box_x, &slots, &lds_bytes, &tile, waves)) return false;
   // Maps whose source box is much larger than the tile because they ROTATE in the plane (10 degrees and more) run 3-16 %
@@ -432,6 +431,41 @@ bool launch_affine_planar(const float* in, int64_t Zi, int64_t Yi, int64_t Xi, i
     }
   }
   const int kTY = waves * kTiles[tile].nr, kTX = 64 * kTiles[tile].nc;
+  AffinePlanarPlan& q = *plan;
+  q.waves = waves; q.tile = tile; q.tile_y = kTY; q.tile_x = kTX;
+  q.box_y = box_y; q.box_x = box_x; q.slots = slots; q.lds_bytes = lds_bytes;
+  q.tiles_x = static_cast<int>(ceil_div(Xo, kTX));
+  q.tiles_y = static_cast<int>(ceil_div(Yo, kTY));
+  // z split: enough workgroups for ~4 per CU, chunks of at least 16 planes (each chunk refetches
+  // one source plane)
+  const int64_t tiles = int64_t(q.tiles_x) * q.tiles_y;
+  int64_t chunks = ceil_div(256 * 4, tiles);
+  if (chunks < 1) chunks = 1;
+  int64_t chunk = ceil_div(Zo, chunks);
+  if (chunk < 16) chunk = 16;
+  if (chunk > Zo) chunk = Zo;
+  q.z_chunk = static_cast<int>(chunk);
+  q.patch_h = 8; q.patch_w = 8;
+  if (const char* e = std::getenv("LSR_PLANAR_PATCH")) {   // measurement override: "h,w" with h * w = 64
+    int h = 0, w = 0;
+    if (std::sscanf(e, "%d,%d", &h, &w) == 2 && h > 0 && w > 0 && h * w == kPatchSize) { q.patch_h = h; q.patch_w = w; }
+  }
+  q.py_n = static_cast<int>(ceil_div(q.tiles_y, q.patch_h));
+  q.px_n = static_cast<int>(ceil_div(q.tiles_x, q.patch_w));
+  const int64_t padded = int64_t(q.py_n) * q.px_n * ceil_div(Zo, chunk) * kPatchSize;
+  if (padded >= (int64_t(1) << 30)) return false;
+  q.per_xcd = static_cast<int>(ceil_div(padded, 8));
+  q.grid = f32 ? tiles * ceil_div(Zo, chunk) : int64_t(q.per_xcd) * 8;
+  return true;
+}
+
+// Returns true if the planar kernel took the launch; false = not applicable, use the general one.
+bool launch_affine_planar(const float* in, int64_t Zi, int64_t Yi, int64_t Xi, int64_t pitch, int64_t plane,
+                          float* out, int64_t Zo, int64_t Yo, int64_t Xo, int64_t opitch, int64_t oplane,
+                          const double M[12], float cval, bool f32, bool grid, hipStream_t s) {
+  AffinePlanarPlan q;
+  if ((reinterpret_cast<uintptr_t>(in) & 15) != 0) return false;
+  if (!affine_planar_plan(Yi, Xi, pitch, plane, Zo, Yo, Xo, M, f32, &q)) return false;
 
   PlanarArgs p;
   p.in = in; p.out = out;
@@ -443,29 +477,12 @@ bool launch_affine_planar(const float* in, int64_t Zi, int64_t Yi, int64_t Xi, i
   p.b = M[5]; p.c = M[6]; p.ty = M[7];
   p.d = M[9]; p.e = M[10]; p.tx = M[11];
   p.cval = cval;
-  p.box_y = box_y; p.box_x = box_x; p.slots = slots;
-  p.tiles_x = static_cast<int>(ceil_div(Xo, kTX));
-  p.tiles_y = static_cast<int>(ceil_div(Yo, kTY));
-  // z split: enough workgroups for ~4 per CU, chunks of at least 16 planes (each chunk refetches
-  // one source plane)
-  const int64_t tiles = int64_t(p.tiles_x) * p.tiles_y;
-  int64_t chunks = ceil_div(256 * 4, tiles);
-  if (chunks < 1) chunks = 1;
-  int64_t chunk = ceil_div(Zo, chunks);
-  if (chunk < 16) chunk = 16;
-  if (chunk > Zo) chunk = Zo;
-  p.z_chunk = static_cast<int>(chunk);
-  p.patch_h = 8; p.patch_w = 8;
-  if (const char* e = std::getenv("LSR_PLANAR_PATCH")) {   // measurement override: "h,w" with h * w = 64
-    int h = 0, w = 0;
-    if (std::sscanf(e, "%d,%d", &h, &w) == 2 && h > 0 && w > 0 && h * w == kPatchSize) { p.patch_h = h; p.patch_w = w; }
-  }
-  p.py_n = static_cast<int>(ceil_div(p.tiles_y, p.patch_h));
-  p.px_n = static_cast<int>(ceil_div(p.tiles_x, p.patch_w));
-  const int64_t padded = int64_t(p.py_n) * p.px_n * ceil_div(Zo, chunk) * kPatchSize;
-  if (padded >= (int64_t(1) << 30)) return false;
-  p.per_xcd = static_cast<int>(ceil_div(padded, 8));
-  const int64_t blocks = f32 ? tiles * ceil_div(Zo, chunk) : int64_t(p.per_xcd) * 8;
+  p.box_y = q.box_y; p.box_x = q.box_x; p.slots = q.slots;
+  p.tiles_x = q.tiles_x; p.tiles_y = q.tiles_y;
+  p.z_chunk = q.z_chunk;
+  p.patch_h = q.patch_h; p.patch_w = q.patch_w;
+  p.py_n = q.py_n; p.px_n = q.px_n;
+  p.per_xcd = q.per_xcd;
   static std::atomic<uint64_t> lds_allowed[32] = {};
   using Kernel = void (*)(PlanarArgs);
 #define LSR_PLANAR_TILE(NR, NC, NW)                                                                            \
@@ -475,13 +492,13 @@ bool launch_affine_planar(const float* in, int64_t Zi, int64_t Yi, int64_t Xi, i
       {LSR_PLANAR_TILE(4, 2, 8), LSR_PLANAR_TILE(4, 1, 8), LSR_PLANAR_TILE(2, 2, 8), LSR_PLANAR_TILE(2, 1, 8)},
       {LSR_PLANAR_TILE(4, 2, 4), LSR_PLANAR_TILE(4, 1, 4), LSR_PLANAR_TILE(2, 2, 4), LSR_PLANAR_TILE(2, 1, 4)}};
 #undef LSR_PLANAR_TILE                                          // [waves == 4][tile][2 * grid + f32], tiles as kTiles
-  const int w4 = waves == 4 ? 1 : 0;
-  const Kernel kernel = kernels[w4][tile][2 * grid + f32];
+  const int w4 = q.waves == 4 ? 1 : 0;
+  const Kernel kernel = kernels[w4][q.tile][2 * grid + f32];
   if (lsr::allow_dynamic_lds(reinterpret_cast<const void*>(kernel), 150 * 1024,
-                             lds_allowed[16 * w4 + 4 * tile + 2 * grid + f32], "affine_planar_kernel") != LSR_OK)
+                             lds_allowed[16 * w4 + 4 * q.tile + 2 * grid + f32], "affine_planar_kernel") != LSR_OK)
     return false;   // the caller runs the gather kernel
-  hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(blocks)), dim3(64 * waves),
-                     static_cast<size_t>(lds_bytes), s, p);
+  hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(q.grid)), dim3(64 * q.waves),
+                     static_cast<size_t>(q.lds_bytes), s, p);
   return true;
 }
 

@@ -168,6 +168,35 @@ bool affine_box_geometry(int64_t Zi, int64_t Yi, int64_t Xi, int64_t pitch, int6
                          int* box_z, int* box_y, int* box_x, int64_t* lds_bytes);
 bool affine_box_shape(int64_t Zi, int64_t Yi, int64_t Xi, const double M[12], int out6[6]);
 
+// The launch of one LDS-staged affine call: everything the host decides from the shapes, the strides, the matrix and the
+// measurement switches.  launch_affine_planar / launch_affine_box launch from these and lsr_affine_plan reports them, so what
+// the tests count is what runs.  (What only the call itself knows -- the alignment of `in`, in == out, a device that refuses
+// the LDS budget -- is not part of a plan: each of them sends the call to the gather kernel.)
+struct AffinePlanarPlan {
+  int waves, tile;             // 8 or 4 waves per workgroup; index into the tile table
+  int tile_y, tile_x;          // output pixels per tile
+  int box_y, box_x, slots;     // staged source box of a plane (rows, floats per row), ring depth
+  int64_t lds_bytes;
+  int z_chunk;                 // output planes per workgroup
+  int tiles_y, tiles_x;
+  int patch_h, patch_w;        // exact mode: tiles per patch
+  int py_n, px_n, per_xcd;
+  int64_t grid;                // workgroups launched
+};
+bool affine_planar_plan(int64_t Yi, int64_t Xi, int64_t pitch, int64_t plane, int64_t Zo, int64_t Yo, int64_t Xo,
+                        const double M[12], bool f32, AffinePlanarPlan* plan);
+struct AffineBoxPlan {
+  int tz, ty, tx;              // block of output voxels
+  int bz, by, bx;              // staged source box (planes, rows, floats per row)
+  int64_t lds_bytes;
+  int tz_n, ty_n, tx_n;        // blocks per axis
+  int pz_n, py_n, px_n;        // 4 x 4 x 4 patches per axis
+  int per_xcd, linear;
+  int64_t grid;                // workgroups launched
+};
+bool affine_box_plan(int64_t Zi, int64_t Yi, int64_t Xi, int64_t pitch, int64_t plane, int64_t Zo, int64_t Yo, int64_t Xo,
+                     int64_t opitch, const double M[12], bool f32, AffineBoxPlan* plan);
+
 // ---- device only -------------------------------------------------------------------------------------------------------
 #if defined(__HIPCC__)
 
