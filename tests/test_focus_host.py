@@ -5,6 +5,10 @@ waveorder is not installed: PARITY IS UNPINNED and ``focus_ref`` (float64 NumPy)
 5902 bins of the full spectrum (5904 with ``r`` from ``np.fft.fftfreq``, whose products round two boundary bins the other
 way); every case peaks at its ``z0`` with a gap to the second-largest power of at least 0.36 of the peak, and a complex64
 pocketfft evaluation of the rule differs from float64 by at most 4e-8 of the peak.
+
+The twin is also swept over every window length the kernels accept, with the tables, planes and bounds of the device sweep
+(``tests/transform_cases.py``, ``tests/test_focus_lengths_gpu.py``), and that sweep's float64 references are recomputed in
+single precision under the same bounds.
 """
 
 import numpy as np
@@ -13,6 +17,7 @@ import torch
 
 from shrimpy_amd import focus as F
 from tests import focus_ref as R
+from tests import transform_cases as T
 
 
 def _all_cases():
@@ -70,6 +75,54 @@ def test_host_twin_against_the_model(name, data):
     print(f"{name}: worst |P - P_ref| / bound = {ratio.max():.3g}")
     assert np.all(ratio <= 1.0)
     assert np.array_equal(F.midband_power(vol, **R.OPTICS, **kw), got.numpy())      # arrays take the same route
+
+
+LENGTH_CASES = T.slices(T.FOCUS_ROW_CASES) + T.slices(T.FOCUS_COL_CASES)
+
+
+def test_the_length_sweep_covers_every_length_the_kernels_accept():
+    from shrimpy_amd import _lib
+
+    assert len(T.ROW_X) == 86 and len(T.COL_Y) == 109
+    assert [x for x in range(0, 4101) if _lib.call_value("lsr_rfft_rows_supported", x)] == T.ROW_X
+    assert [y for y in range(0, 2100) if _lib.call_value("lsr_band_power_supported", y, 8)] == T.COL_Y
+    assert sorted({c[1] for c in T.FOCUS_ROW_CASES}) == T.ROW_X and sorted({c[0] for c in T.FOCUS_COL_CASES}) == T.COL_Y
+    assert all(_lib.call_value("lsr_band_power_supported", yc, xc) for yc, xc, _ in T.FOCUS_ROW_CASES + T.FOCUS_COL_CASES)
+    assert T.longest_pair(lambda y, x: _lib.call_value("lsr_band_power_supported", y, x)) == (2048, 4096)
+
+
+@pytest.mark.parametrize("part", LENGTH_CASES, ids=T.slice_id)
+def test_host_twin_at_every_length(part):
+    """``lsr_band_power_f32_cpu`` with the tables of the device sweep (``tests/test_focus_lengths_gpu.py``): "full" and the
+    one-bin tables at both self-paired columns, both self-mirrored rows, their crossings, (1, 1) and a pseudo-random bin, on
+    a normal plane, a tone at one of those bins and an impulse, against float64 ``fft2`` under the device's bound.  The twin
+    transforms in float64: worst |P - P_ref| / bound 4.3e-10 (full), 2.4e-9 (one bin)."""
+    for yc, xc, index in part:
+        with T.at(f"(Yc, Xc) = ({yc}, {xc})"):
+            case = T.FocusCase(yc, xc, index)
+            case.check_reference()
+            for kind, b, table, weighted, ref, bound in case.tables:
+                case.check_power("twin power", T.host_twin_power(case, table), kind, b, weighted, ref, bound)
+
+
+@pytest.mark.parametrize("part", LENGTH_CASES, ids=T.slice_id)
+def test_length_references_hold_in_single_precision(part):
+    """No bound of the length sweep can hide a failure of its float64 reference: pocketfft in single precision on the same
+    windows sits inside the same bounds, x leg and power, at every length and table.  Worst ratios: x leg l2 0.704, max 4.24
+    (of 2.5 and 32); power 5.7e-3 (full), 0.540 (one bin: the tone on its own self-paired bin at (1500, 12), P = 18000 one
+    float32 ulp high; below 0.1 on the normal and impulse planes)."""
+    import scipy.fft as sf
+
+    for yc, xc, index in part:
+        with T.at(f"(Yc, Xc) = ({yc}, {xc})"):
+            case = T.FocusCase(yc, xc, index)
+            rows = sf.rfft(case.win, axis=2)
+            assert rows.dtype == np.complex64
+            T.check_x_leg("single x leg", rows, case.rows, xc)
+            mag = np.abs(sf.fft2(case.win)).astype(np.float64)
+            for kind, b, table, weighted, ref, bound in case.tables:
+                case.check_power("single power", T.power_from_mask(mag, T.table_mask(table, yc, xc)), kind, b, weighted, ref,
+                                 bound)
 
 
 def test_uint16_is_widened():

@@ -6,6 +6,10 @@ waveorder is not installed: PARITY IS UNPINNED and ``phase_ref`` (float64 NumPy,
 ``HOST_TOL``: the host route is ``torch.fft`` in complex64 with a complex64 filter; its error, ``max|got - ref| / max|ref|``
 over the cases of ``phase_ref.CASES``, was measured at 3.6e-7 (worst: (24, 40, 72), z_padding 5; the others 1.5e-7 ..
 2.5e-7) and is pinned at four times that.
+
+The per-length sweep of the row kernels (``tests/test_phase_lengths_gpu.py``) rests on ``phase_ref.extend`` and on float64
+``rfft`` / ``irfft``: the first is held here to the mirror rule index by index, the second recomputed in single precision
+under the sweep's own bounds.
 """
 import numpy as np
 import pytest
@@ -15,6 +19,7 @@ import yaml
 from shrimpy_amd import phase as P
 from shrimpy_amd.settings import PhaseSettings
 from tests import phase_ref as R
+from tests import transform_cases as T
 
 HOST_TOL = 1.45e-6     # 4 x 3.6e-7 (measured, see above)
 
@@ -68,6 +73,48 @@ def test_settings_reject(block, message):
 ])
 def test_mirror_extension_tables(n, g, table):
     assert P.mirror_indices(n, g).tolist() == table == R.mirror_table(n, g)
+
+
+def test_extend_is_the_mirror_rule_index_by_index():
+    """``phase_ref.extend`` is the only witness of the kernel's ``mirror_index`` in the per-length sweep
+    (``tests/test_phase_lengths_gpu.py``): here it is held, on every geometry of that sweep, against the rule as the header of
+    ``csrc/phase.hip`` words it, index by index, and against the same extension built from ``np.pad``."""
+    seen = set()
+    for i, x in enumerate(T.ROW_X):
+        shape, grid = T.phase_geometry(i, x)
+        assert all(0 < n <= g for n, g in zip(shape, grid))
+        vol = np.arange(1, 1 + int(np.prod(shape)), dtype=np.float64).reshape(shape)        # every voxel its own value
+        ext = R.extend(vol, grid)
+        assert ext.shape == grid
+        iz, iy, ix = ([T.mirror_literal(j, n, g) for j in range(g)] for n, g in zip(shape, grid))
+        assert np.array_equal(ext, vol[np.ix_(iz, iy, ix)]), (shape, grid)
+        for (n, g), literal in zip(zip(shape, grid), (iz, iy, ix)):
+            assert P.mirror_indices(n, g).tolist() == literal == T.mirror_by_padding(np.arange(n), g).tolist(), (n, g)
+            seen.add((n == g, g - n > n, g - n > 2 * n, (g - n) % 2))
+    # no padding, padding longer than the volume, the clamp on both sides, odd and even padding: all were met
+    assert {s[0] for s in seen} == {True, False} and any(s[1] for s in seen) and any(s[2] for s in seen)
+    assert {s[3] for s in seen if not s[0]} == {0, 1}
+
+
+@pytest.mark.parametrize("part", T.slices(list(enumerate(T.ROW_X))), ids=lambda p: f"{p[0][1]}..{p[-1][1]}")
+def test_row_references_hold_in_single_precision(part):
+    """No bound of the per-length sweep can hide a failure of its float64 reference: pocketfft in single precision on the
+    same rows (forward: the mirror-extended volumes; inverse: the complex64 spectra) sits inside the same bounds at every
+    length.  Worst ratios over all lengths: forward l2 0.387, max 6.72; inverse l2 0.492, max 8.79 (of 2.5 and 32)."""
+    import scipy.fft as sf
+
+    for i, x in part:
+        with T.at(f"X = {x}"):
+            vols, shape, grid = T.phase_volumes(i, x)
+            for vol in vols:
+                single = sf.rfft(R.extend(vol, grid).astype(np.float32), axis=2)
+                assert single.dtype == np.complex64
+                T.check_rows("single forward", single, T.forward_reference(vol, grid), x)
+            rows, specs, shape, grid = T.phase_grid_rows(i, x)
+            for spec in specs:
+                single = sf.irfft(np.ascontiguousarray(spec.transpose(0, 2, 1)), n=x, axis=2) / np.float32(grid[0] * grid[1] * 2.5)
+                assert single.dtype == np.float32
+                T.check_rows("single inverse", single, T.inverse_reference(spec, grid, 2.5), x)
 
 
 def test_grid_rule():
