@@ -1242,6 +1242,44 @@ int lsr_label_intensity_variant(const int32_t* labels, const void* v, int value_
                                 lsr_stream_t stream);
 
 /*
+ * Per-object sums over two channels at once (csrc/coloc.hip; the rule is stated in csrc/coloc.hpp): what
+ * shrimpy_amd/colocalize.py: pair_table, coefficients, costes_thresholds and the `colocalize` command read.  No upstream is
+ * pinned; tests/coloc_ref.py restates the rule in numpy.
+ *
+ * lsr_label_coloc_f32 / _u16: labels is an int32 (Z, Y, X) volume or NULL, a and b two float32 / uint16 volumes of that shape
+ * (device memory), ta and tb two thresholds.  With labels == NULL, n_objects must be 1 and every voxel belongs to object 1.
+ * Let A = (float(a) > ta), B = (float(b) > tb) (a NaN value compares false).  For every voxel with 1 <= label <= n_objects,
+ * record label - 1 of `table` gains: word 0 count 1; words 1..5 sum_a, sum_b, sum_aa, sum_bb, sum_ab the terms a, b, a^2, b^2,
+ * a b; word 6 count_both 1 where A and B; words 7..11 both_a .. both_ab the same five terms where A and B; words 12, 13 count_A,
+ * count_B; words 14, 15 a_where_B, b_where_A.  `table` (device memory, WHICH THE CALLER HAS ZEROED) is n_objects records of 16
+ * words of 8 bytes: counts int64, sums float64 for float32 values and uint64 for uint16 values.  Labels outside 1 .. n_objects
+ * are ignored; a label that no voxel carries keeps a zero record.
+ * uint16: pure integer arithmetic, independent of the order of execution (65535^2 * 2^31 < 2^63: no sum can wrap).  float32:
+ * the counts are exact; every sum is within m 2^-53 sum|terms| of the exact sum of its exact terms (m: the number of terms of
+ * that sum), in atomic adds whose order is not fixed; a non-finite voxel follows IEEE arithmetic into its own object's sums only.
+ * max_blocks caps the grid (0: the default of lsr_label_coloc_geometry); only the order of the float64 adds depends on it.
+ * Refused before any launch and with nothing read or written: LSR_E_ARG for a NULL a, b or table, a non-positive extent,
+ * n_objects < 0, labels == NULL with n_objects != 1, a NaN threshold, max_blocks < 0 or a table that overlaps an input;
+ * LSR_E_UNSUPPORTED for more than 2^31 - 1 voxels.  n_objects == 0 returns at once.
+ * One launch: each workgroup walks one contiguous span of the three volumes; while whole wave steps hold one label every lane
+ * keeps the sixteen quantities in registers and the wave reduces them once; wave steps with more than one run find the runs by
+ * one ballot and reduce them by shuffles restricted to the run; a table in LDS (64-bit LDS atomic adds) is flushed once.  Without
+ * labels there is no label stream and no table.  Shared words are touched by atomics only, nothing waits for anything.
+ * lsr_label_coloc_geometry: out[0] = the slots of one workgroup's LDS table, out[1] = the default cap of the grid.
+ */
+int lsr_label_coloc_geometry(int out[2]);
+int lsr_label_coloc_f32(const int32_t* labels, const float* a, const float* b, int64_t Z, int64_t Y, int64_t X, int64_t n_objects,
+                        float ta, float tb, void* table, int max_blocks, lsr_stream_t stream);
+int lsr_label_coloc_u16(const int32_t* labels, const uint16_t* a, const uint16_t* b, int64_t Z, int64_t Y, int64_t X,
+                        int64_t n_objects, float ta, float tb, void* table, int max_blocks, lsr_stream_t stream);
+/* measurement only (tools/bench_kernels.py --coloc): the same kernel (a and b are uint16 where value_is_u16 != 0, float32
+ * otherwise) with lds_slots slots in the LDS table (a power of two up to 256) probed over at most lds_probes (1 .. 256) slots,
+ * or with lds_slots == 0 the plain form in which every part goes to the global record directly */
+int lsr_label_coloc_variant(const int32_t* labels, const void* a, const void* b, int value_is_u16, int64_t Z, int64_t Y, int64_t X,
+                            int64_t n_objects, float ta, float tb, void* table, int max_blocks, int lds_slots, int lds_probes,
+                            lsr_stream_t stream);
+
+/*
  * Host twins (csrc/host_twins.hip): the same signatures with HOST pointers, the same argument checks and the
  * same arithmetic in the same order, so the results equal the device entry points' bit for bit.  They serve
  * the boxes where the reference itself resolves to the CPU (shrimpy/preprocessing.py:78-82 -- its CI has no
@@ -1402,6 +1440,14 @@ int lsr_label_intensity_f32_cpu(const int32_t* labels, const float* v, int64_t Z
                                 void* table, int max_blocks, lsr_stream_t stream);
 int lsr_label_intensity_u16_cpu(const int32_t* labels, const uint16_t* v, int64_t Z, int64_t Y, int64_t X, int64_t n_objects,
                                 void* table, int max_blocks, lsr_stream_t stream);
+
+/* ... of the two-channel sums (csrc/coloc.hip): plain sequential code over the same rule, records and checks (csrc/coloc.hpp),
+ * voxel by voxel.  uint16: the kernel's records byte for byte.  float32: the kernel's counts; the float64 sums add the same
+ * terms in raster order, inside the same bound.  Every pointer HOST memory; max_blocks is checked and otherwise unused. */
+int lsr_label_coloc_f32_cpu(const int32_t* labels, const float* a, const float* b, int64_t Z, int64_t Y, int64_t X,
+                            int64_t n_objects, float ta, float tb, void* table, int max_blocks, lsr_stream_t stream);
+int lsr_label_coloc_u16_cpu(const int32_t* labels, const uint16_t* a, const uint16_t* b, int64_t Z, int64_t Y, int64_t X,
+                            int64_t n_objects, float ta, float tb, void* table, int max_blocks, lsr_stream_t stream);
 
 /* ... of the grey morphology (csrc/morphology.hip): the same plan of passes and the same walk along a line
  * (csrc/morphology.hpp), so `out` is the kernels' bits.  Every pointer HOST memory; `scratch` holds the results between the

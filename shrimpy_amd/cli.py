@@ -23,10 +23,13 @@ CPU path (biahub's; the reference's own CLI has only ``acquire`` and ``gui``,
     python -m shrimpy_amd.cli segment     -i store.zarr -c segment.yml   -o labels.zarr
     python -m shrimpy_amd.cli track       -i labels.zarr -c track.yml    -o tracks.zarr
     python -m shrimpy_amd.cli measure     -l tracks.zarr -i store.zarr -c measure.yml -o measurements/
+    python -m shrimpy_amd.cli colocalize  -i store.zarr [-l labels.zarr] -c colocalize.yml -o colocalization/
 
 ``measure`` reads two stores and writes tables only: per position ``measurements.csv``, one row per timepoint and label (or
 track id) with its volume and, per channel of the intensity store, the sum, mean, standard deviation, extremes and weighted
-centroid -- on request beside the mean of a ring of local background around each object.
+centroid -- on request beside the mean of a ring of local background around each object.  ``colocalize`` relates pairs of
+channels: per position ``colocalization_summary.csv`` (Pearson, Manders, overlap coefficients of the whole volume, with fixed or
+Costes' automatic thresholds) and, with a label store, ``colocalization.csv`` with the same per object.
 
 Every (position, timepoint, channel) volume is an independent unit.  Launched under
 ``python -m torch.distributed.run --nproc-per-node N`` each rank takes the units
@@ -2124,6 +2127,223 @@ def run_measure(labels_path, input_path, config, output_path, positions=(), io_b
                     entries[k] = len(rows)
                 return {"rank": rank, "world_size": world, "positions": len(keys[rank::world]), "rows": entries,
                         "seconds": time.perf_counter() - t0, "failed": []}
+    finally:
+        if created:
+            import torch.distributed as dist
+
+            dist.destroy_process_group()
+
+
+# colocalization.csv: COLOCALIZE_COLUMNS, then per pair `A__B_<column>` for COLOCALIZE_PAIR_COLUMNS
+COLOCALIZE_COLUMNS = ("t", "label", "volume_voxels")
+COLOCALIZE_COUNT_COLUMNS = ("count_both", "count_A", "count_B")
+COLOCALIZE_PAIR_COLUMNS = ("pearson", "pearson_above", "manders_m1", "manders_m2", "overlap", "k1", "k2", "fraction_both", "a_in_b",
+                           "b_in_a") + COLOCALIZE_COUNT_COLUMNS
+# the columns that mean nothing without thresholds (Costes' search found the channels uncorrelated): NaN, counts 0
+COLOCALIZE_THRESHOLD_COLUMNS = ("pearson_above", "manders_m1", "manders_m2", "fraction_both", "a_in_b", "b_in_a")
+COLOCALIZE_SUMMARY_COLUMNS = ("t", "channel_a", "channel_b", "region", "voxels", "threshold_a", "threshold_b",
+                              "thresholds_from") + COLOCALIZE_PAIR_COLUMNS
+
+
+@cli.command(cls=_eat_all_command("-i", "--input-position-dirpaths"))
+@click.option("-i", "--input-position-dirpaths", "input_path", required=True, multiple=True, type=click.UNPROCESSED,
+              help="The OME-Zarr store whose channels are related (HCS plate or single FOV), or the position directories of one plate.")
+@click.option("-l", "--labels-dirpath", "labels_path", default=None, type=click.Path(exists=True, file_okay=False, path_type=Path),
+              help="Optional OME-Zarr store of integer labels (the output of segment or track): adds the per-object table.")
+@click.option("-c", "--config-filepath", "config", required=True, type=click.Path(exists=True, dir_okay=False, path_type=Path),
+              help="ColocalizeSettings YAML.")
+@click.option("-o", "--output-dirpath", "output_path", required=True, type=click.Path(path_type=Path),
+              help="Output directory (must not exist); the tables are written into <output>/<position>/.")
+@click.option("-p", "--position", "positions", multiple=True, help='Restrict to these position keys ("row/col/fov"); repeatable.')
+@click.option("--io", "io_backend", type=click.Choice(["auto", "native", "iohub"]), default="auto", show_default=True,
+              help="Store access for the inputs: this package's reader, iohub, or native with iohub as the fallback.")
+def colocalize(input_path, labels_path, config, output_path, positions, io_backend):
+    """Colocalization of pairs of channels, per volume and per labelled object (config: a ColocalizeSettings YAML).
+
+    Writes <output>/<position>/colocalization_summary.csv: per timepoint and pair of channels Pearson's r (over all voxels and
+    over the voxels above both thresholds), Manders' M1 and M2, the overlap coefficient with k1 and k2 and the fractions of
+    voxels above the thresholds, for the whole volume and -- with -l -- for the labelled voxels, with the thresholds used.
+    With -l it also writes <output>/<position>/colocalization.csv: the same per label that has voxels.
+
+    thresholds: [ta, tb] counts a voxel as signal where it is strictly above; thresholds: costes searches Costes' automatic
+    thresholds per timepoint and pair over costes_region (volume, or labelled).  uint16 and float32 channels are taken as they
+    are stored; the two channels of a pair must have one type."""
+    input_path, positions = _inputs(input_path, positions)
+    _finish(run_colocalize(input_path, labels_path, config, output_path, positions, io_backend))
+
+
+def run_colocalize(input_path, labels_path, config, output_path, positions=(), io_backend: str = "auto") -> dict:
+    """``colocalize``: per (position, t) the label volume (with ``labels_path``) and every channel that a pair names are uploaded
+    once; per pair the thresholds are the settings' or come from ``colocalize.costes_thresholds``, then one launch of
+    ``colocalize.pair_table`` (``csrc/coloc.hip``, or its host twin on a CPU-only machine) without labels gives the whole
+    volume's record and, with labels, one more gives the records per object, whose sum over the objects is the labelled
+    region's.  ``colocalize.coefficients`` turns the records into the columns.  ``<output>/<position>/colocalization.csv``
+    (only with labels): ``COLOCALIZE_COLUMNS``, then per pair ``A__B_<column>`` of ``COLOCALIZE_PAIR_COLUMNS``, one row per
+    ``(t, label)`` with voxels.  ``<output>/<position>/colocalization_summary.csv``: ``COLOCALIZE_SUMMARY_COLUMNS``, one row per
+    ``t``, pair and region (``volume``, and with labels ``labelled``); ``thresholds_from`` is ``settings``, ``costes`` or
+    ``costes:uncorrelated`` -- then the thresholds are NaN and so are the columns that need them.  Everything is checked before
+    the output directory is created: the positions exist in both stores, the channels exist, a pair's channels have one type,
+    uint16 or float32, the label data is integer and fits int32, ``(T, Z, Y, X)`` and the ``(z, y, x)`` scale of the two stores
+    agree per position.  With several ranks the positions are dealt out in turn."""
+    import csv
+
+    import torch
+
+    from . import colocalize as K
+    from .io.omezarr import as_volume_array, position_scale
+    from .settings import ColocalizeSettings
+
+    try:
+        settings = ColocalizeSettings.from_yaml(config)
+    except (ValueError, TypeError) as exc:
+        raise click.ClickException(f"{config}: {exc}") from exc
+    with_labels = labels_path is not None
+    costes = settings.thresholds == "costes"
+    if with_labels and settings.label_channel_name is None:
+        raise click.ClickException(f"{config}: label_channel_name is needed with a label store (-l)")
+    if not with_labels and costes and settings.costes_region == "labelled":
+        raise click.ClickException(f"{config}: costes_region 'labelled' needs a label store (-l)")
+    pairs = [tuple(pair) for pair in settings.pairs]
+    used = list(dict.fromkeys(name for pair in pairs for name in pair))
+
+    rank, world, device, created = _distributed()
+    try:
+        with contextlib.ExitStack() as stack:
+            label_positions = {}
+            if with_labels:
+                label_store, label_positions = _open_source(Path(labels_path), io_backend)
+                stack.enter_context(_closing(label_store))
+            src, src_positions = _open_source(Path(input_path), io_backend)
+            stack.enter_context(_closing(src))
+            missing = [p for p in positions if p not in src_positions]
+            if missing:
+                raise click.ClickException(f"positions {missing} not found in {input_path}; available: {list(src_positions)}")
+            keys = [k for k in src_positions if not positions or k in positions]
+            if not keys:
+                raise click.ClickException("no positions to process")
+            plan = {}
+            for k in keys:
+                pos = src_positions[k]
+                names = list(pos.channel_names)
+                absent = [c for c in used if c not in names]
+                if absent:
+                    raise click.ClickException(f"channels {absent} not in position {k} of {input_path} (it has {names})")
+                a = as_volume_array(pos["0"])
+                if len(a.shape) != 5:
+                    raise click.ClickException(f"position {k}: expected 5-D TCZYX data, got shape {tuple(a.shape)}")
+                if np.dtype(a.dtype) not in (np.dtype(np.uint16), np.dtype(np.float32)):
+                    raise click.ClickException(f"position {k}: data type {a.dtype}; uint16 or float32 channels are related")
+                shape = (int(a.shape[0]),) + tuple(int(v) for v in a.shape[2:])
+                if int(np.prod(shape[1:], dtype=np.int64)) > 2 ** 31 - 1:
+                    raise click.ClickException(f"position {k}: a volume of {shape[1:]} has more than 2^31 - 1 voxels")
+                la = lc = None
+                if with_labels:
+                    if k not in label_positions:
+                        raise click.ClickException(f"position {k} not found in {labels_path}; available: {list(label_positions)}")
+                    lpos = label_positions[k]
+                    label_names = list(lpos.channel_names)
+                    if settings.label_channel_name not in label_names:
+                        raise click.ClickException(f"label_channel_name {settings.label_channel_name!r} not in position {k} of "
+                                                   f"{labels_path} (it has {label_names})")
+                    la = as_volume_array(lpos["0"])
+                    if len(la.shape) != 5:
+                        raise click.ClickException(f"position {k}: expected 5-D TCZYX labels, got shape {tuple(la.shape)}")
+                    if np.dtype(la.dtype).kind not in "iu":
+                        raise click.ClickException(f"position {k}: label data type {la.dtype}; labels are integer data")
+                    other = (int(la.shape[0]),) + tuple(int(v) for v in la.shape[2:])
+                    if shape != other:
+                        raise click.ClickException(f"position {k}: the labels are (T, Z, Y, X) = {other}, the channels {shape}")
+                    scale = list(position_scale(lpos))
+                    if not np.allclose(scale[2:], list(position_scale(pos))[2:], rtol=1e-9, atol=0.0):
+                        raise click.ClickException(f"position {k}: the labels' (z, y, x) scale is {scale[2:]}, the channels' "
+                                                   f"{list(position_scale(pos))[2:]}")
+                    lc = label_names.index(settings.label_channel_name)
+                    if np.iinfo(la.dtype).max > 2 ** 31 - 1:             # (a wider type: its values decide)
+                        for t in range(shape[0]):
+                            vol = np.asarray(la.read_volume(t, lc))
+                            if vol.size and (int(vol.max()) > 2 ** 31 - 1 or int(vol.min()) < -2 ** 31):
+                                raise click.ClickException(f"position {k}, t = {t}: a label does not fit int32")
+                plan[k] = (a, {c: names.index(c) for c in used}, la, lc)
+            error = None
+            if rank == 0:
+                try:
+                    if Path(output_path).exists():
+                        raise FileExistsError(f"{output_path} exists (never overwritten)")
+                    Path(output_path).mkdir(parents=True)
+                except Exception as exc:  # noqa: BLE001 -- reported on every rank, see _agree
+                    error = f"{type(exc).__name__}: {exc}"
+            _agree(error)
+
+            def values_of(table, known: bool):
+                """Per record the values behind ``COLOCALIZE_PAIR_COLUMNS``."""
+                columns = K.coefficients(table)
+                out = []
+                for i in range(len(table)):
+                    row = [float(columns[c][i]) if known or c not in COLOCALIZE_THRESHOLD_COLUMNS else float("nan")
+                           for c in K.COEFFICIENTS]
+                    out.append(row + [int(table[c][i]) if known else 0 for c in COLOCALIZE_COUNT_COLUMNS])
+                return out
+
+            def total_of(table):
+                """One record: the sum of the records of ``table``."""
+                one = np.zeros((1,), dtype=table.dtype)
+                for f, v in K._totals(table).items():
+                    one[f] = v
+                return one
+
+            def write(path, header, rows):
+                with open(path, "w", newline="") as fh:
+                    w = csv.writer(fh)
+                    w.writerow(header)
+                    w.writerows([[repr(v) if isinstance(v, float) else v for v in row] for row in rows])
+
+            entries = {}
+            t0 = time.perf_counter()
+            for k in keys[rank::world]:
+                a, index, la, lc = plan[k]
+                rows, summary = [], []
+                for t in range(int(a.shape[0])):
+                    labels, n = None, 1
+                    if with_labels:
+                        labels = torch.as_tensor(np.ascontiguousarray(la.read_volume(t, lc), dtype=np.int32), device=device)
+                        n = max(int(labels.max().item()), 0)
+                    volumes = {c: torch.as_tensor(np.ascontiguousarray(a.read_volume(t, index[c])), device=device) for c in used}
+                    block = None
+                    for ca, cb in pairs:
+                        va, vb = volumes[ca], volumes[cb]
+                        source, known = "settings", True
+                        if costes:
+                            found = K.costes_thresholds(labels, n, va, vb, region=settings.costes_region)
+                            known = found["status"] == "ok"
+                            source = "costes" if known else f"costes:{found['status']}"
+                            thresholds = (found["ta"], found["tb"])
+                        else:
+                            thresholds = tuple(float(np.float32(v)) for v in settings.thresholds)
+                        launch = thresholds if known else (float("inf"), float("inf"))
+                        regions = [("volume", K.pair_table(None, 1, va, vb, launch))]
+                        if with_labels:
+                            table = K.pair_table(labels, n, va, vb, launch)
+                            regions.append(("labelled", total_of(table)))
+                            live = np.flatnonzero(table["count"] > 0)
+                            if block is None:
+                                block = [[int(t), int(i) + 1, int(table["count"][i])] for i in live]
+                            for row, more in zip(block, values_of(table[live], known)):
+                                row += more
+                        for region, record in regions:
+                            summary.append([int(t), ca, cb, region, int(record["count"][0]), float(thresholds[0]),
+                                            float(thresholds[1]), source] + values_of(record, known)[0])
+                    rows += block or []
+                directory = Path(output_path) / k
+                directory.mkdir(parents=True, exist_ok=True)
+                write(directory / "colocalization_summary.csv", list(COLOCALIZE_SUMMARY_COLUMNS), summary)
+                if with_labels:
+                    header = list(COLOCALIZE_COLUMNS)
+                    for ca, cb in pairs:
+                        header += [f"{ca}__{cb}_{c}" for c in COLOCALIZE_PAIR_COLUMNS]
+                    write(directory / "colocalization.csv", header, rows)
+                entries[k] = {"objects": len(rows), "summary": len(summary)}
+            return {"rank": rank, "world_size": world, "positions": len(keys[rank::world]), "rows": entries,
+                    "seconds": time.perf_counter() - t0, "failed": []}
     finally:
         if created:
             import torch.distributed as dist

@@ -30,6 +30,7 @@
 //   lsr_label_overlap_i32_cpu                 <->  lsr_label_overlap_i32               (overlap.hip)
 //   lsr_label_moments_i32_cpu                 <->  lsr_label_moments_i32               (moments.hip)
 //   lsr_label_intensity_f32_cpu / _u16_cpu    <->  lsr_label_intensity_f32 / _u16      (intensity.hip)
+//   lsr_label_coloc_f32_cpu / _u16_cpu        <->  lsr_label_coloc_f32 / _u16          (coloc.hip)
 //   lsr_grey_morph_f32_cpu                    <->  lsr_grey_morph_f32                  (morphology.hip)
 //   lsr_rank_filter_f32_cpu                   <->  lsr_rank_filter_f32                 (rank.hip)
 //   lsr_hessian_response_f32_cpu              <->  lsr_hessian_response_f32            (hessian.hip)
@@ -1606,6 +1607,30 @@ extern "C" int lsr_label_intensity_u16_cpu(const int32_t* labels, const uint16_t
   if (int rc = in::check_intensity(labels, values, sizeof(uint16_t), Z, Y, X, n_objects, table, max_blocks)) return rc;
   if (n_objects == 0) return LSR_OK;
   in::accumulate_host<uint16_t, in::RecordU16, uint64_t>(labels, values, Z, Y, X, n_objects, static_cast<in::RecordU16*>(table));
+  return LSR_OK;
+}
+
+// ---- per-object sums over two channels (coloc.hip): plain sequential code over coloc.hpp's rule, records and checks, voxel by
+// voxel in raster order.  uint16 values: the kernel's records byte for byte.  float32 values: the counts are the kernel's, the
+// float64 sums are another order of the same terms (both inside coloc.hpp's bound) ----
+#include "coloc.hpp"
+
+extern "C" int lsr_label_coloc_f32_cpu(const int32_t* labels, const float* a, const float* b, int64_t Z, int64_t Y, int64_t X,
+                                       int64_t n_objects, float ta, float tb, void* table, int max_blocks, lsr_stream_t) {
+  namespace co = lsr::coloc;
+  if (int rc = co::check_coloc(labels, a, b, sizeof(float), Z, Y, X, n_objects, ta, tb, table, max_blocks)) return rc;
+  if (n_objects == 0) return LSR_OK;
+  co::accumulate_host<float, co::RecordF32, double>(labels, a, b, Z * Y * X, n_objects, ta, tb, static_cast<co::RecordF32*>(table));
+  return LSR_OK;
+}
+
+extern "C" int lsr_label_coloc_u16_cpu(const int32_t* labels, const uint16_t* a, const uint16_t* b, int64_t Z, int64_t Y, int64_t X,
+                                       int64_t n_objects, float ta, float tb, void* table, int max_blocks, lsr_stream_t) {
+  namespace co = lsr::coloc;
+  if (int rc = co::check_coloc(labels, a, b, sizeof(uint16_t), Z, Y, X, n_objects, ta, tb, table, max_blocks)) return rc;
+  if (n_objects == 0) return LSR_OK;
+  co::accumulate_host<uint16_t, co::RecordU16, uint64_t>(labels, a, b, Z * Y * X, n_objects, ta, tb,
+                                                         static_cast<co::RecordU16*>(table));
   return LSR_OK;
 }
 

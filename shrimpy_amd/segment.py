@@ -27,8 +27,8 @@ numbering is a prefix count), ``csrc/host_twins.hip`` on the CPU; both equal ``s
   -- a ring of local background around every object.  The ``measure`` command applies both to any label store and any channel.
 
 Not built: seeded watersheds, multi-GPU or slab labelling, label pyramids, volumes above ``2^31 - 1`` voxels, ball-shaped or
-rolling-ball background windows (the window is a box), cross-channel sums (Pearson / Manders colocalization per object),
-per-object percentiles, :func:`region_table` on the intensity kernel.  Labels are
+rolling-ball background windows (the window is a box), per-object percentiles, :func:`region_table` on the intensity kernel
+(sums over two channels -- Pearson / Manders colocalization per object -- are ``shrimpy_amd/colocalize.py``).  Labels are
 numbered from 1 at every timepoint; linking them over time is ``shrimpy_amd/track.py`` (the ``track`` command), where gap
 closing, motion models and a global assignment are not built.
 """

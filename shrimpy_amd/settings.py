@@ -799,6 +799,41 @@ class MeasureSettings(_StrictModel):
         return v
 
 
+class ColocalizeSettings(_StrictModel):
+    """Colocalization of pairs of channels, per labelled object and per volume (``colocalize.pair_table``, the ``colocalize``
+    command).
+
+    ``pairs`` names the pairs ``[a, b]`` of channels of the intensity store, in the order of the columns: at least one, the two
+    names of a pair differ, each pair once.  ``label_channel_name`` is the channel of the label store (needed when the command
+    is given one).  ``thresholds`` is ``[ta, tb]`` -- a voxel counts as signal in a channel where it is strictly above -- or
+    ``"costes"``: Costes' automatic thresholds (``colocalize.costes_thresholds``) per (position, t, pair), over
+    ``costes_region``: the whole ``volume`` or the ``labelled`` voxels."""
+
+    pairs: list[list[str]]
+    label_channel_name: Optional[str] = None
+    thresholds: Union[list[float], Literal["costes"]] = [0.0, 0.0]
+    costes_region: Literal["volume", "labelled"] = "volume"
+
+    @field_validator("pairs")
+    @classmethod
+    def _check_pairs(cls, v):
+        if len(v) == 0:
+            raise ValueError("pairs must name at least one pair of channels")
+        for pair in v:
+            if len(pair) != 2 or pair[0] == pair[1]:
+                raise ValueError(f"a pair is two different channel names, got {pair!r}")
+        if len({tuple(pair) for pair in v}) != len(v):
+            raise ValueError("each pair must be named once")
+        return v
+
+    @field_validator("thresholds")
+    @classmethod
+    def _check_thresholds(cls, v):
+        if v != "costes" and (len(v) != 2 or any(np.isnan(t) for t in v)):
+            raise ValueError("thresholds must be [ta, tb] (two numbers, not NaN) or \"costes\"")
+        return v
+
+
 class ReconstructSettings(_StrictModel):
     """Whole per-volume pipeline: (flat-field) -> deskew -> (register) -> (deconvolve)."""
 

@@ -88,6 +88,11 @@ def main():
                     "sweep of LDS slots, grid caps and probe bounds, and in the plain form without an LDS table, beside a device "
                     "copy of one int32 and one float32 volume and lsr_label_regions_f32 with the intensities in the same run; "
                     "appended to profiles/intensity_config2.jsonl")
+    ap.add_argument("--coloc", action="store_true", help="only: ms of the colocalization kernel (csrc/coloc.hip) on --rl-grid for the "
+                    "three scenes of --label, float32 and uint16 channels, with and without labels; the sweep of LDS slots, grid "
+                    "caps and probe bounds and the plain form; beside a device copy of the three volumes and two launches of the "
+                    "label-intensity kernel; lines appended to profiles/coloc_config2.jsonl")
+    ap.add_argument("--coloc-crop", default="1,1024,1024", help="Z,Y,X of the small crop --coloc also times the kernel on")
     ap.add_argument("--edt", action="store_true", help="only: ms per launch of the distance transform (csrc/edt.hip: x, y, z; HIP "
                     "events between the launches, median of 5 calls after a warm-up) on --rl-grid, for bench.synthetic_raw at its "
                     "multi-Otsu threshold, Bernoulli noise at p = 0.3 and an all-foreground volume with one background voxel, "
@@ -157,6 +162,9 @@ def main():
         return
     if args.intensity:
         _intensity(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
+        return
+    if args.coloc:
+        _coloc(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
         return
     if args.watershed:
         _watershed(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
@@ -1168,6 +1176,152 @@ def _intensity(args, torch, dev, g, bench, oshape):
                if r.get("input") == "all foreground" and "times_faster_than_lsr_label_regions_f32" in r][0]
     print(f"# all foreground: lsr_label_intensity_f32 is {speedup:.1f} times faster than lsr_label_regions_f32 "
           f"({'meets' if speedup >= 10.0 else 'MISSES'} the condition of 10)", flush=True)
+
+
+COLOC_SLOTS = (64, 128, 256)
+COLOC_CAPS = (4096, 16384, 65536, 262144)
+COLOC_PROBES = 8             # the LDS probe bound (csrc/coloc.hpp kLdsProbes)
+COLOC_PROBE_SWEEP = (1, 32)
+
+
+def _coloc(args, torch, dev, g, bench, oshape):
+    """The colocalization kernel (csrc/coloc.hip) at the config-2 deskewed shape on the three scenes of --label, labelled under
+    connectivity 6: channel a is the scene's own float32 volume, channel b = 0.5 a + uniform noise, the thresholds their means
+    (and uint16 images of both).  Per scene, each the median of 3 calls after a warm-up between HIP events (the tables zeroed
+    outside the timed region): the kernel as shipped for float32 and uint16 channels, with the labels and without; the sweep of
+    LDS slots, grid caps and probe bounds through the measurement entry (float32) and the plain form without an LDS table; two
+    launches of lsr_label_intensity_f32 on the same labels (the nearest existing kernel: 16 bytes per voxel where this one reads
+    12); and the kernel on the crop --coloc-crop.  torch's own formulation (index_add_ of the fifteen float64 terms) is NOT timed
+    here: on the bead scene it did not finish within 7 minutes, neither on 8 planes nor on a (1, 1024, 1024) crop, where the
+    kernel takes a fraction of a millisecond -- index_add_ sends every background voxel to one and the same float64 word.  The floor is a device copy of one int32 and two float32 volumes, which moves twice the bytes.
+    Every form's counts must equal the shipped form's; the greatest relative difference of a float64 sum is recorded."""
+    from shrimpy_amd import _lib, colocalize, segment
+
+    reps = 3
+    z, y, x = oshape
+    n = z * y * x
+    lds_slots, default_cap = colocalize.coloc_geometry()
+    a, fa = torch.empty(oshape, dtype=torch.int32, device=dev), torch.empty(oshape, dtype=torch.float32, device=dev)
+    b, fb, fc, fd = torch.empty_like(a), torch.empty_like(fa), torch.empty_like(fa), torch.empty_like(fa)
+
+    def copies():
+        b.copy_(a)
+        fb.copy_(fa)
+        fd.copy_(fc)
+
+    class Records(list):
+        """Every record is printed when it is made: a long run is never silent, and a stall shows where it is."""
+
+        def append(self, r):
+            print(json.dumps(r), flush=True)
+            super().append(r)
+
+    copy_ms = _median_ms(copies, reps, torch)
+    records = Records()
+    records.append({"kernel": "device copy of one int32 volume and two float32 volumes (torch copy_)", "grid": list(oshape), "ms": copy_ms,
+                    "GBps": 24.0 * n / copy_ms / 1e6})
+    del a, b, fa, fb, fc, fd
+    torch.cuda.empty_cache()
+    stream = _lib.stream_ptr(dev)
+    record = colocalize.COLOC_DTYPE_F32.itemsize
+    counts = [colocalize.COLOC_FIELDS.index(f) for f in colocalize.COLOC_COUNTS]
+    sums = [i for i in range(16) if i not in counts]
+
+    def geometry(cap, voxels=n):
+        steps = -(-voxels // MOMENTS_STEP)
+        span = -(-steps // min(steps, cap)) * MOMENTS_STEP
+        return span, -(-voxels // span)
+
+    def split(table):
+        """(the four counts of every record, its twelve float64 sums)"""
+        words = table.view(torch.int64).view(-1, record // 8)
+        return words[:, counts].contiguous(), words[:, sums].contiguous().view(torch.float64)
+
+    def timed(launch, table):
+        return _timed_cleared(torch, launch, table.zero_, reps)
+
+    def u16_of(vol):
+        # scaled into 0 .. 65535, cut to 16 bits through int16 (same bits)
+        scale = 65535.0 / max(float(vol.max().item()), 1e-30)
+        return (vol.clamp(min=0.0) * scale).to(torch.int32).to(torch.int16).view(torch.uint16)
+
+    for name, vol, threshold in _label_scenes(torch, dev, g, bench, oshape):
+        labels, n_objects = segment.label_volume(vol, threshold, 6)
+        vb = 0.5 * vol + torch.rand(oshape, device=dev, generator=g) * float(vol.mean().item())
+        ta, tb = float(vol.mean().item()), float(vb.mean().item())
+        ua, ub = u16_of(vol), u16_of(vb)
+        uta, utb = float(ua.to(torch.float32).mean().item()), float(ub.to(torch.float32).mean().item())
+        torch.cuda.empty_cache()
+        base = {"input": name, "grid": list(oshape), "objects": n_objects, "foreground_fraction": float((labels != 0).sum().item()) / n,
+                "thresholds": [ta, tb]}
+        print(f"# {name}: {n_objects} objects", flush=True)
+        table = torch.zeros(max(n_objects, 1) * record, dtype=torch.uint8, device=dev)
+        span, blocks = geometry(default_cap)
+        shipped = {"lds_slots": lds_slots, "lds_probes": COLOC_PROBES, "max_blocks": default_cap, "default": True,
+                   "workgroups": blocks, "span_voxels": span}
+        ms = timed(lambda: _lib.call("lsr_label_coloc_u16", labels.data_ptr(), ua.data_ptr(), ub.data_ptr(), z, y, x, n_objects, uta, utb,
+                                     table.data_ptr(), 0, stream), table)
+        records.append({**base, "kernel": "lsr_label_coloc_u16", **shipped, "thresholds": [uta, utb], "ms": ms, "bytes_per_voxel": 8.0,
+                        "algorithmic_GBps": 8.0 * n / ms / 1e6, "times_the_copy": ms / copy_ms})
+        ms_f32 = timed(lambda: _lib.call("lsr_label_coloc_f32", labels.data_ptr(), vol.data_ptr(), vb.data_ptr(), z, y, x, n_objects, ta,
+                                         tb, table.data_ptr(), 0, stream), table)
+        want_counts, want_sums = (t.clone() for t in split(table))
+        records.append({**base, "kernel": "lsr_label_coloc_f32", **shipped, "ms": ms_f32, "bytes_per_voxel": 12.0,
+                        "algorithmic_GBps": 12.0 * n / ms_f32 / 1e6, "times_the_copy": ms_f32 / copy_ms})
+        forms = [(0, default_cap, 1)] + [(slots, cap, COLOC_PROBES) for slots in COLOC_SLOTS for cap in COLOC_CAPS]
+        forms += [(lds_slots, default_cap, probes) for probes in COLOC_PROBE_SWEEP]
+        for slots, cap, probes in forms:
+            ms = timed(lambda: _lib.call("lsr_label_coloc_variant", labels.data_ptr(), vol.data_ptr(), vb.data_ptr(), 0, z, y, x,
+                                         n_objects, ta, tb, table.data_ptr(), cap, slots, probes, stream), table)
+            got_counts, got_sums = split(table)
+            assert torch.equal(got_counts, want_counts), "a form of the kernel disagrees with the shipped one in a count"
+            difference = float(((got_sums - want_sums).abs() / want_sums.abs().clamp(min=1e-300)).max().item()) if n_objects else 0.0
+            span, blocks = geometry(cap)
+            records.append({**base, "kernel": "lsr_label_coloc_variant (f32)" + (" (plain form: no LDS table)" if slots == 0 else ""),
+                            "lds_slots": slots, "lds_probes": probes if slots else 0, "max_blocks": cap,
+                            "default": (slots, cap, probes) == (lds_slots, default_cap, COLOC_PROBES), "workgroups": blocks,
+                            "span_voxels": span, "ms": ms, "times_the_copy": ms / copy_ms,
+                            "greatest_relative_difference_of_a_sum": difference})
+        del want_counts, want_sums
+        # without labels: the whole volume is one object
+        one = torch.zeros(record, dtype=torch.uint8, device=dev)
+        for cap in (0,) + COLOC_CAPS:
+            span, blocks = geometry(cap or default_cap)
+            ms = timed(lambda: _lib.call("lsr_label_coloc_f32", None, vol.data_ptr(), vb.data_ptr(), z, y, x, 1, ta, tb, one.data_ptr(),
+                                         cap, stream), one)
+            records.append({**base, "kernel": "lsr_label_coloc_f32 (labels = NULL)", "max_blocks": cap or default_cap, "default": cap == 0,
+                            "workgroups": blocks, "span_voxels": span, "ms": ms, "bytes_per_voxel": 8.0,
+                            "algorithmic_GBps": 8.0 * n / ms / 1e6, "times_the_copy": ms / copy_ms})
+        ms = timed(lambda: _lib.call("lsr_label_coloc_u16", None, ua.data_ptr(), ub.data_ptr(), z, y, x, 1, uta, utb, one.data_ptr(), 0,
+                                     stream), one)
+        records.append({**base, "kernel": "lsr_label_coloc_u16 (labels = NULL)", "max_blocks": default_cap, "default": True, "ms": ms,
+                        "bytes_per_voxel": 4.0, "algorithmic_GBps": 4.0 * n / ms / 1e6, "times_the_copy": ms / copy_ms})
+        del ua, ub, one
+        # the nearest existing kernel: one launch per channel
+        tables = torch.zeros(2 * max(n_objects, 1) * segment.INTENSITY_DTYPE_F32.itemsize, dtype=torch.uint8, device=dev)
+        half = tables.numel() // 2
+
+        def two_launches():
+            _lib.call("lsr_label_intensity_f32", labels.data_ptr(), vol.data_ptr(), z, y, x, n_objects, tables.data_ptr(), 0, stream)
+            _lib.call("lsr_label_intensity_f32", labels.data_ptr(), vb.data_ptr(), z, y, x, n_objects, tables[half:].data_ptr(), 0, stream)
+
+        ms = timed(two_launches, tables)
+        records.append({**base, "kernel": "two launches of lsr_label_intensity_f32 (one per channel)", "ms": ms, "bytes_per_voxel": 16.0,
+                        "times_the_copy": ms / copy_ms, "times_lsr_label_coloc_f32": ms / ms_f32})
+        del tables
+        # a crop: the size on which a formulation in torch's own operators would be tried
+        cz, cy, cx = (min(int(v), full) for v, full in zip(args.coloc_crop.split(","), oshape))
+        c_labels, c_a, c_b = (t[z // 2:z // 2 + cz, :cy, :cx].contiguous() for t in (labels, vol, vb))
+        ms_crop = timed(lambda: _lib.call("lsr_label_coloc_f32", c_labels.data_ptr(), c_a.data_ptr(), c_b.data_ptr(), cz, cy, cx,
+                                          n_objects, ta, tb, table.data_ptr(), 0, stream), table)
+        records.append({**base, "grid": [cz, cy, cx], "kernel": "lsr_label_coloc_f32 on the crop", "ms": ms_crop})
+        del c_labels, c_a, c_b, table, labels, vol, vb
+        torch.cuda.empty_cache()
+    stamp = {"sources": _lib.kernel_source_sha16(), "device": torch.cuda.get_device_name(dev), "reps": reps, "warmups": 1}
+    path = ROOT / "profiles" / "coloc_config2.jsonl"
+    with open(path, "a") as f:
+        for r in records:
+            f.write(json.dumps({**r, **stamp}) + "\n")
 
 
 def _edt(args, torch, dev, g, bench, oshape):
