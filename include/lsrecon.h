@@ -230,7 +230,12 @@ int lsr_affine_normal_equations_f32(const float* moving, int64_t Zi, int64_t Yi,
  * counter) are DEVICE memory, zeroed by the entry on `stream` before the launch.  The sums are integer: the same bits on
  * every run and from the host twin.  bins in [4, 64], t_hi > t_lo, m_hi > m_lo.  Size limit: the volumes every entry
  * accepts (extents below 2^30, fewer than 2^48 voxels): 65536 * n stays below 2^64, and the kernel's 32-bit LDS
- * counters are flushed before 65536 full-weight samples per lane could wrap them.
+ * counters are flushed before 65536 full-weight samples per lane could wrap them.  The launch has
+ * lsr_affine_joint_histogram_blocks() workgroups of 256 threads; grid sample s is visited by workgroup
+ * (s / 256) % blocks, in both kernels.
+ * Values that are not finite (the lerp is IEEE arithmetic as written, so one NaN or infinite tap can make m NaN): a NaN
+ * or -inf target value goes to target bin 0, +inf to the last; a NaN u is clamped to 0 -- all weight in column 0, w1 = 0
+ * -- and adds nothing to the gradient; a u of +inf is clamped to bins - 1, of -inf to 0.
  * lsr_affine_mi_gradient_f32: for every sample whose unclamped u lies strictly inside (0, bins - 1) -- a u of exactly 0
  * or bins - 1 counts as clamped and adds nothing -- adds dL[a][b0] * (bins - 1) / (m_hi - m_lo) * (dm/dz, dm/dy, dm/dx)
  * (x) ((x - centre) / scale, 1) to 12 fp64 sums.  `dL` ([bins][bins - 1], DEVICE memory) is the caller's
@@ -242,6 +247,7 @@ int lsr_affine_joint_histogram_f32(const float* moving, int64_t Zi, int64_t Yi, 
                                    int64_t Zo, int64_t Yo, int64_t Xo, const double M[12], const int stride[3],
                                    int bins, double t_lo, double t_hi, double m_lo, double m_hi,
                                    unsigned long long* hist, unsigned long long* n_samples, lsr_stream_t stream);
+int lsr_affine_joint_histogram_blocks(void);
 int lsr_affine_mi_gradient_size(void);
 int lsr_affine_mi_gradient_blocks(void);
 int lsr_affine_mi_gradient_f32(const float* moving, int64_t Zi, int64_t Yi, int64_t Xi, const float* target,

@@ -116,6 +116,7 @@ SIGNATURES: dict[str, list] = {
     "lsr_affine_joint_histogram_f32": [_c_f32p, _i64, _i64, _i64, _c_f32p, _i64, _i64, _i64, _f64p,
                                        ctypes.POINTER(ctypes.c_int), _int, ctypes.c_double, ctypes.c_double,
                                        ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, _stream],
+    "lsr_affine_joint_histogram_blocks": [],
     "lsr_affine_mi_gradient_size": [],
     "lsr_affine_mi_gradient_blocks": [],
     "lsr_affine_mi_gradient_f32": [_c_f32p, _i64, _i64, _i64, _c_f32p, _i64, _i64, _i64, _f64p,

@@ -177,6 +177,7 @@ __global__ __launch_bounds__(kThreads) void mi_gradient_kernel(Geometry p, Binni
 
 }  // namespace
 
+extern "C" int lsr_affine_joint_histogram_blocks(void) { return kHistBlocks; }
 extern "C" int lsr_affine_mi_gradient_size(void) { return kGradParams; }
 extern "C" int lsr_affine_mi_gradient_blocks(void) { return kGradBlocks; }
 

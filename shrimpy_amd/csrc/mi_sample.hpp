@@ -16,6 +16,13 @@
 //
 // Gradient: a sample contributes when its unclamped u lies strictly inside (0, bins - 1); a sample whose u is exactly 0
 // or exactly bins - 1 counts as clamped and contributes nothing (tests/mi_ref.py states the same rule).
+//
+// Values that are not finite.  The lerp is IEEE arithmetic as written: a NaN tap makes m NaN, and so does an infinite
+// tap, whatever its fraction (0 * inf, inf - inf).  The clamps are written as comparisons that a NaN fails:
+//     target:  NaN -> bin 0,  -inf -> bin 0,  +inf -> bin bins - 1
+//     moving:  u NaN -> u = 0 (b0 = 0, w1 = 0: the whole weight in column 0; no gradient term),
+//              u = -inf -> 0,  u = +inf -> bins - 1 (b0 = bins - 2, w1 = 65536; no gradient term either)
+// A sample with such a value is still counted: the count depends on the coordinates alone.
 #pragma once
 
 #include <cmath>
@@ -103,7 +110,7 @@ __host__ __device__ __forceinline__ double moving_position(const Binning& q, dou
 __host__ __device__ __forceinline__ void parzen(const Binning& q, double u_raw, int& b0, unsigned& w1) {
 #pragma clang fp contract(off)
   const double top = q.bins - 1;
-  const double u = u_raw >= top ? top : (u_raw > 0.0 ? u_raw : 0.0);
+  const double u = u_raw >= top ? top : (u_raw > 0.0 ? u_raw : 0.0);   // (a NaN fails both: 0)
   const int fl = static_cast<int>(floor(u));
   b0 = fl < q.bins - 2 ? fl : q.bins - 2;
   const double f = u - b0;

@@ -1,7 +1,8 @@
 """Mutual-information metric of the registration estimate on the device: the joint-histogram kernel against its host
 twin bit for bit (integer sums), the sizes at which a 32-bit LDS counter would wrap, the gradient kernel against its twin,
 the recovery of a known transform under a non-monotone intensity map, and ``estimate-registration --metric mi`` followed
-by ``register`` store to store.  The twins are pinned to ``tests/mi_ref.py`` by ``test_mi_host.py``."""
+by ``register`` store to store.  The twins are pinned to ``tests/mi_ref.py`` by ``test_mi_host.py``; the kernels meet
+``mi_ref`` directly, at every dispatch edge, in ``test_mi_fp64_gpu.py``."""
 
 import numpy as np
 import pytest
