@@ -1057,8 +1057,14 @@ int lsr_edt_profile_f32(const float* in, int64_t Z, int64_t Y, int64_t X, float 
  * not matter) holds the results between the passes; `in` is never written and `out` exactly once.
  * lsr_grey_morph_tiling: {the greatest half-width per axis, columns per workgroup of the y and z passes, outputs per staged
  * row segment of the x pass, threads per workgroup of the x pass}.
+ * lsr_grey_morph_dispatch: the edges at which the launches choose their code, from the constants they branch on: {the greatest
+ * half-width of the narrow instantiation of the strided walk, the greatest half-width whose strip still fits static LDS (above
+ * it the widest instantiation asks for dynamic LDS), the workgroups of the x pass at most (with more rows a workgroup strides
+ * over them), the rows read ahead of the walk by the narrow, the static-LDS and the dynamic-LDS instantiation}.  For tests
+ * that aim at those edges; it changes nothing.
  */
 int lsr_grey_morph_tiling(int tiling[4]);
+int lsr_grey_morph_dispatch(int dispatch[6]);
 int64_t lsr_grey_morph_scratch_bytes(int64_t Z, int64_t Y, int64_t X);
 int lsr_grey_morph_f32(const float* in, float* out, int64_t Z, int64_t Y, int64_t X, int rz, int ry, int rx, int op,
                        void* scratch, lsr_stream_t stream);

@@ -184,6 +184,7 @@ SIGNATURES: dict[str, list] = {
                             ctypes.POINTER(ctypes.c_float), _stream],
     "lsr_label_expand_i32": [ctypes.c_void_p, ctypes.c_void_p, _i64, _i64, _i64, _f64p, ctypes.c_double, ctypes.c_void_p, _stream],
     "lsr_grey_morph_tiling": [ctypes.POINTER(ctypes.c_int)],
+    "lsr_grey_morph_dispatch": [ctypes.POINTER(ctypes.c_int)],
     "lsr_grey_morph_scratch_bytes": [_i64, _i64, _i64],
     "lsr_grey_morph_f32": [_c_f32p, _c_f32p, _i64, _i64, _i64, _int, _int, _int, _int, ctypes.c_void_p, _stream],
     "lsr_rank_filter_tiling": [ctypes.POINTER(ctypes.c_int)],

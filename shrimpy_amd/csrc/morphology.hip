@@ -33,7 +33,6 @@ using mo::encode;
 using mo::umax;
 
 constexpr int kRowBuf = mo::kRowSegment + 2 * mo::kMaxHalfWidth;
-constexpr int64_t kMaxRowBlocks = 256 * 16;      // x pass: workgroups at most (they stride over the rows, reading ahead)
 
 constexpr int kRowRegs = (kRowBuf + mo::kRowThreads - 1) / mo::kRowThreads;   // values of one segment per thread
 
@@ -131,7 +130,7 @@ int mo::launch_pass(const float* src, const mo::StoreSink& sink, int64_t Z, int6
   // segments of equal length (a multiple of the wavefront), at most kRowSegment outputs each
   const int64_t want = lsr::ceil_div(X, mo::kRowSegment);
   const int seg = static_cast<int>(lsr::ceil_div(lsr::ceil_div(X, want), lsr::kWave) * lsr::kWave);
-  hipLaunchKernelGGL(morph_rows_kernel, dim3(static_cast<unsigned>(std::min(Z * Y, kMaxRowBlocks))), dim3(mo::kRowThreads), 0, st,
+  hipLaunchKernelGGL(morph_rows_kernel, dim3(static_cast<unsigned>(std::min(Z * Y, mo::kMaxRowBlocks))), dim3(mo::kRowThreads), 0, st,
                      src, sink, Z * Y, X, ps.r, ps.least ? 1 : 0, seg, static_cast<int>(lsr::ceil_div(X, seg)));
   return LSR_OK;
 }
@@ -142,6 +141,17 @@ extern "C" int lsr_grey_morph_tiling(int tiling[4]) {
   tiling[1] = mo::kColumns;
   tiling[2] = mo::kRowSegment;
   tiling[3] = mo::kRowThreads;
+  return LSR_OK;
+}
+
+extern "C" int lsr_grey_morph_dispatch(int dispatch[6]) {
+  LSR_REQUIRE_PTR(dispatch);
+  dispatch[0] = mo::kNarrow;
+  dispatch[1] = mo::kMaxStaticHalfWidth;
+  dispatch[2] = static_cast<int>(mo::kMaxRowBlocks);
+  dispatch[3] = mo::kAheadNarrow;
+  dispatch[4] = mo::kAheadStatic;
+  dispatch[5] = mo::kAheadDynamic;
   return LSR_OK;
 }
 

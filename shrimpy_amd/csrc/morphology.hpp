@@ -37,6 +37,15 @@ constexpr int kColumns = 64;                // strided passes: columns per workg
 constexpr int kRowSegment = 2048;           // x pass: outputs per staged segment of a row at most (>= 4 * kMaxHalfWidth)
 constexpr int kRowThreads = 256;
 constexpr int kMaxPasses = 6;
+constexpr int64_t kMaxRowBlocks = 256 * 16;  // x pass: workgroups at most (they stride over the rows, reading ahead)
+// The strided walk's instantiations, by the rows they read ahead: up to kNarrow registers, not LDS, limit the waves; up to
+// kStaticLdsBytes of strip the launch needs no opt-in; above it the kernel is allowed dynamic LDS first (launch_strided).
+constexpr int kNarrow = 12;
+constexpr int kStaticLdsBytes = 64 * 1024;
+constexpr int kAheadNarrow = 8, kAheadStatic = 16, kAheadDynamic = 32;
+// the greatest half-width whose strip, (2r + 1) * kColumns codes, fits kStaticLdsBytes
+constexpr int kMaxStaticHalfWidth = (kStaticLdsBytes / (kColumns * static_cast<int>(sizeof(uint32_t))) - 1) / 2;
+static_assert(kNarrow < kMaxStaticHalfWidth && kMaxStaticHalfWidth < kMaxHalfWidth, "three instantiations, in this order");
 static_assert(kRowSegment >= 4 * kMaxHalfWidth, "the carried halo of the x pass must not overlap its source: half a segment >= 2r");
 
 enum Op { kErode = 0, kDilate = 1, kOpen = 2, kClose = 3, kWhiteTophat = 4, kBlackTophat = 5 };
@@ -228,8 +237,7 @@ __global__ __launch_bounds__(kColumns) void morph_strided_kernel(const float* __
 
 // Launches the walk over `lines` on `st`, sink by sink.  Rows in flight per lane: the wider the window, the fewer wavefronts
 // its LDS strip (w * kColumns codes) leaves on a compute unit, the more each has in flight; up to kNarrow registers, not LDS,
-// limit the waves.
-constexpr int kNarrow = 12;
+// limit the waves (kNarrow, kStaticLdsBytes and the depths: above).
 constexpr int64_t kMaxBlocks = int64_t(1) << 20;
 template <typename Sink>
 inline int launch_strided(const float* src, const Lines& lines, int r, bool least, const Sink& sink, const char* who,
@@ -240,13 +248,17 @@ inline int launch_strided(const float* src, const Lines& lines, int r, bool leas
   const size_t lds = sizeof(uint32_t) * (2 * r + 1) * kColumns;
   const dim3 grid(static_cast<unsigned>(tiles < kMaxBlocks ? tiles : kMaxBlocks));
   if (r <= kNarrow) {
-    hipLaunchKernelGGL((morph_strided_kernel<8, Sink>), grid, dim3(kColumns), lds, st, src, lines, r, least ? 1 : 0, sink);
-  } else if (lds <= 64 * 1024) {
-    hipLaunchKernelGGL((morph_strided_kernel<16, Sink>), grid, dim3(kColumns), lds, st, src, lines, r, least ? 1 : 0, sink);
+    hipLaunchKernelGGL((morph_strided_kernel<kAheadNarrow, Sink>), grid, dim3(kColumns), lds, st, src, lines, r, least ? 1 : 0,
+                       sink);
+  } else if (lds <= static_cast<size_t>(kStaticLdsBytes)) {
+    hipLaunchKernelGGL((morph_strided_kernel<kAheadStatic, Sink>), grid, dim3(kColumns), lds, st, src, lines, r, least ? 1 : 0,
+                       sink);
   } else {
-    if (int rc = allow_dynamic_lds(reinterpret_cast<const void*>(morph_strided_kernel<32, Sink>), kMaxLds, lds_allowed, who))
+    if (int rc = allow_dynamic_lds(reinterpret_cast<const void*>(morph_strided_kernel<kAheadDynamic, Sink>), kMaxLds,
+                                   lds_allowed, who))
       return rc;
-    hipLaunchKernelGGL((morph_strided_kernel<32, Sink>), grid, dim3(kColumns), lds, st, src, lines, r, least ? 1 : 0, sink);
+    hipLaunchKernelGGL((morph_strided_kernel<kAheadDynamic, Sink>), grid, dim3(kColumns), lds, st, src, lines, r,
+                       least ? 1 : 0, sink);
   }
   return LSR_OK;
 }

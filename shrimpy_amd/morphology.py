@@ -30,7 +30,7 @@ import math
 from . import _lib
 from .segment import _check_volume, _run, _scratch, _shape3
 
-__all__ = ["tiling", "max_half_width", "grey_erosion", "grey_dilation", "grey_opening", "grey_closing", "white_tophat",
+__all__ = ["tiling", "dispatch", "max_half_width", "grey_erosion", "grey_dilation", "grey_opening", "grey_closing", "white_tophat",
            "black_tophat", "half_widths_of", "subtract_background", "fill_holes"]
 
 OPS = {"grey_erosion": 0, "grey_dilation": 1, "grey_opening": 2, "grey_closing": 3, "white_tophat": 4, "black_tophat": 5}
@@ -41,6 +41,15 @@ def tiling() -> tuple[int, int, int, int]:
     pass, threads per workgroup of the x pass)`` (``lsr_grey_morph_tiling``)."""
     out = (ctypes.c_int * 4)()
     _lib.call("lsr_grey_morph_tiling", out)
+    return tuple(out)
+
+
+def dispatch() -> tuple[int, int, int, int, int, int]:
+    """The edges at which the launches choose their code (``lsr_grey_morph_dispatch``): ``(greatest half-width of the narrow
+    instantiation of the y and z walk, greatest half-width whose strip fits static LDS, workgroups of the x pass at most, rows
+    read ahead by the narrow, the static-LDS and the dynamic-LDS instantiation)``.  For tests that aim at those edges."""
+    out = (ctypes.c_int * 6)()
+    _lib.call("lsr_grey_morph_dispatch", out)
     return tuple(out)
 
 

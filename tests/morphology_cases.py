@@ -54,7 +54,11 @@ PARAM_IDS = ["x".join(map(str, s)) + "-r" + "_".join(map(str, r)) for s, r in PA
 @functools.lru_cache(maxsize=None)
 def volume(shape, content):
     """The float32 volume of a case (read-only)."""
-    rng = np.random.default_rng([SHAPES.index(shape), CONTENTS.index(content)])
+    return filled(shape, content, np.random.default_rng([SHAPES.index(shape), CONTENTS.index(content)]))
+
+
+def filled(shape, content, rng):
+    """``content`` at ``shape`` from ``rng`` (read-only): what ``volume`` caches, for case files with shapes of their own."""
     n = int(np.prod(shape))
     if content == "noise":
         v = rng.normal(size=shape)

@@ -127,6 +127,9 @@ def test_entry_statuses():
     four = (ctypes.c_int * 4)()
     assert lib.lsr_grey_morph_tiling(four) == 0 and tuple(four) == M.tiling() and lib.lsr_grey_morph_tiling(None) == -1
     assert four[0] >= 128
+    six = (ctypes.c_int * 6)()
+    assert lib.lsr_grey_morph_dispatch(six) == 0 and tuple(six) == M.dispatch() and lib.lsr_grey_morph_dispatch(None) == -1
+    assert 0 < six[0] < six[1] < four[0] and six[2] > 0 and 0 < six[3] < six[4] < six[5]
     assert lib.lsr_grey_morph_scratch_bytes(4, 5, 6) == 2 * 4 * 120
     assert lib.lsr_grey_morph_scratch_bytes(0, 5, 6) == -2 and lib.lsr_grey_morph_scratch_bytes(2 ** 30, 5, 6) == -3
     assert lib.lsr_grey_morph_scratch_bytes(171, 2048, 2270) == 8 * 171 * 2048 * 2270 > 2 ** 31     # the config-2 deskewed grid
