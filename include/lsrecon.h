@@ -969,6 +969,10 @@ int lsr_stitch_f32(const void* table, int n_tiles, float* out, const int64_t box
  *   2^31 - 1 voxels (LSR_E_UNSUPPORTED beyond); a NULL pointer is LSR_E_NULL, a non-positive extent LSR_E_SHAPE.
  * lsr_label_tile_shape: the (z, y, x) tile one workgroup labels in LDS.  lsr_label_scratch_bytes: the size of `scratch`
  * (device memory; its contents on entry do not matter), or a negative status for a shape out of range.
+ * lsr_label_launch_geometry: {threads per workgroup, voxels per workgroup of the numbering launches, threads of the one
+ * workgroup that scans their counts, the cap of the grid-stride launches' grids, the cap of the local launch's grid}: a
+ * volume with more work than a cap is walked with a grid stride, a volume of more numbering workgroups than scan threads
+ * gives every scan thread several counts.
  * lsr_label_f32 runs seven launches on `stream` -- local (one tile per workgroup, the threshold fused into the load),
  * merge (unions across tile faces, atomicMin on the parent words), flatten, count, scan, rank, final -- with the
  * union-find kept in `labels` itself; no workgroup ever waits for another (csrc/label.hip states the two rules).
@@ -986,6 +990,7 @@ int lsr_stitch_f32(const void* table, int n_tiles, float* out, const int64_t box
  * and must be 0; a label outside 0 .. n_map - 1 becomes 0).  One launch.
  */
 int lsr_label_tile_shape(int zyx[3]);
+int lsr_label_launch_geometry(int64_t out[5]);
 int lsr_label_scratch_bytes(int64_t Z, int64_t Y, int64_t X);
 int lsr_label_f32(const float* in, int64_t Z, int64_t Y, int64_t X, float threshold, int connectivity, int32_t* labels,
                   int32_t* n_objects, void* scratch, lsr_stream_t stream);
@@ -1133,6 +1138,8 @@ int lsr_hessian_response_f32(const float* g, float* out, int64_t Z, int64_t Y, i
  *   receives B, the number of summits up(v) == v.  basins must not alias objects or surface (LSR_E_ARG).  A volume holds at
  *   most 2^31 - 1 voxels (LSR_E_UNSUPPORTED beyond); a NULL pointer is LSR_E_NULL, a non-positive extent LSR_E_SHAPE.
  * lsr_watershed_tile_shape: the (z, y, x) tile one workgroup stages in LDS with a one-voxel halo.
+ * lsr_watershed_launch_geometry: lsr_label_launch_geometry's five numbers as this translation unit compiled them (it holds its
+ * own copy of the numbering launches); the second cap is that of this local launch's grid.
  * lsr_watershed_scratch_bytes: the size of `scratch` (device memory; its contents on entry do not matter) -- the block counts
  * of the numbering and one direction byte per voxel -- or a negative status for a shape out of range.
  * lsr_watershed_f32 runs seven launches on `stream` -- local (up(v) of every voxel of a tile, unions inside the tile), merge
@@ -1151,6 +1158,7 @@ int lsr_hessian_response_f32(const float* g, float* out, int64_t Z, int64_t Y, i
  * launch (and the clearing of counts); the table's words are touched by atomics only, nothing waits for anything.
  */
 int lsr_watershed_tile_shape(int zyx[3]);
+int lsr_watershed_launch_geometry(int64_t out[5]);
 int64_t lsr_watershed_scratch_bytes(int64_t Z, int64_t Y, int64_t X);
 int lsr_watershed_f32(const int32_t* objects, const float* surface, int64_t Z, int64_t Y, int64_t X, int connectivity,
                       int32_t* basins, int32_t* n_basins, void* scratch, lsr_stream_t stream);

@@ -170,6 +170,7 @@ SIGNATURES: dict[str, list] = {
     "lsr_stitch_f32": [ctypes.c_void_p, _int, _c_f32p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _int, _f32,
                        _stream],
     "lsr_label_tile_shape": [ctypes.POINTER(ctypes.c_int)],
+    "lsr_label_launch_geometry": [ctypes.POINTER(ctypes.c_int64)],
     "lsr_label_scratch_bytes": [_i64, _i64, _i64],
     "lsr_label_f32": [_c_f32p, _i64, _i64, _i64, _f32, _int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _stream],
     "lsr_label_profile_f32": [_c_f32p, _i64, _i64, _i64, _f32, _int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -193,6 +194,7 @@ SIGNATURES: dict[str, list] = {
     "lsr_hessian_response_f32": [_c_f32p, _c_f32p, _i64, _i64, _i64, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                  ctypes.c_double, _int, _int, _int, _stream],
     "lsr_watershed_tile_shape": [ctypes.POINTER(ctypes.c_int)],
+    "lsr_watershed_launch_geometry": [ctypes.POINTER(ctypes.c_int64)],
     "lsr_watershed_scratch_bytes": [_i64, _i64, _i64],
     "lsr_watershed_f32": [ctypes.c_void_p, _c_f32p, _i64, _i64, _i64, _int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _stream],
     "lsr_watershed_profile_f32": [ctypes.c_void_p, _c_f32p, _i64, _i64, _i64, _int, ctypes.c_void_p, ctypes.c_void_p,

@@ -273,6 +273,16 @@ extern "C" int lsr_label_tile_shape(int zyx[3]) {
   return LSR_OK;
 }
 
+extern "C" int lsr_label_launch_geometry(int64_t out[5]) {
+  LSR_REQUIRE_PTR(out);
+  out[0] = kThreads;
+  out[1] = lb::kChunk;
+  out[2] = kScanThreads;
+  out[3] = kMaxBlocks;
+  out[4] = kMaxTileBlocks;
+  return LSR_OK;
+}
+
 extern "C" int lsr_label_scratch_bytes(int64_t Z, int64_t Y, int64_t X) {
   if (int rc = lb::check_volume(Z, Y, X)) return rc;
   return static_cast<int>(lb::number_blocks(Z * Y * X) * sizeof(int));       // (at most 2 MiB)

@@ -270,6 +270,16 @@ extern "C" int lsr_watershed_tile_shape(int zyx[3]) {
   return LSR_OK;
 }
 
+extern "C" int lsr_watershed_launch_geometry(int64_t out[5]) {
+  LSR_REQUIRE_PTR(out);
+  out[0] = kThreads;
+  out[1] = lb::kChunk;
+  out[2] = kScanThreads;
+  out[3] = kMaxBlocks;
+  out[4] = kMaxTileBlocks;
+  return LSR_OK;
+}
+
 extern "C" int64_t lsr_watershed_scratch_bytes(int64_t Z, int64_t Y, int64_t X) {
   if (int rc = lb::check_volume(Z, Y, X)) return rc;
   return ws::scratch_bytes(Z * Y * X);       // (a byte per voxel: up to 2 GiB)

@@ -41,7 +41,7 @@ import numpy as np
 
 from . import _lib
 
-__all__ = ["REGION_DTYPE", "MOMENTS_DTYPE", "tile_shape", "label_volume", "region_table", "filter_objects", "moments_geometry",
+__all__ = ["REGION_DTYPE", "MOMENTS_DTYPE", "tile_shape", "launch_geometry", "label_volume", "region_table", "filter_objects", "moments_geometry",
            "moment_table", "shape_table", "contact_table", "segment_zyx", "INTENSITY_DTYPE_F32", "INTENSITY_DTYPE_U16",
            "intensity_geometry", "intensity_table", "shell_labels"]
 
@@ -71,6 +71,18 @@ def _tile_shape(entry: str) -> tuple[int, int, int]:
 def tile_shape() -> tuple[int, int, int]:
     """The ``(z, y, x)`` tile one workgroup labels in LDS (``lsr_label_tile_shape``)."""
     return _tile_shape("lsr_label_tile_shape")
+
+
+def _launch_geometry(entry: str) -> tuple[int, int, int, int, int]:
+    out = (ctypes.c_int64 * 5)()
+    _lib.call(entry, out)
+    return tuple(int(v) for v in out)
+
+
+def launch_geometry() -> tuple[int, int, int, int, int]:
+    """``(threads per workgroup, voxels per workgroup of the numbering launches, threads of the scan's one workgroup, cap of
+    the grid-stride launches' grids, cap of the local launch's grid)`` of ``csrc/label.hip`` (``lsr_label_launch_geometry``)."""
+    return _launch_geometry("lsr_label_launch_geometry")
 
 
 def _run(device, entry: str, *args) -> None:

@@ -39,10 +39,10 @@ from __future__ import annotations
 import numpy as np
 
 from . import _lib
-from .segment import (_check_volume, _connectivity, _fill_pair_table, _run, _same_volume, _scratch, _shape3, _tile_shape,
-                      region_table)
+from .segment import (_check_volume, _connectivity, _fill_pair_table, _launch_geometry, _run, _same_volume, _scratch, _shape3,
+                      _tile_shape, region_table)
 
-__all__ = ["SADDLE_DTYPE", "MAX_CAPACITY", "tile_shape", "watershed_basins", "basin_saddles", "merge_map", "split_labels",
+__all__ = ["SADDLE_DTYPE", "MAX_CAPACITY", "tile_shape", "launch_geometry", "watershed_basins", "basin_saddles", "merge_map", "split_labels",
            "split_touching"]
 
 # one slot of the saddle table (csrc/watershed.hpp ``Saddle``)
@@ -55,6 +55,12 @@ MAX_CAPACITY = 1 << 28
 def tile_shape() -> tuple[int, int, int]:
     """The ``(z, y, x)`` tile one workgroup stages in LDS (``lsr_watershed_tile_shape``)."""
     return _tile_shape("lsr_watershed_tile_shape")
+
+
+def launch_geometry() -> tuple[int, int, int, int, int]:
+    """:func:`shrimpy_amd.segment.launch_geometry` of ``csrc/watershed.hip``, which compiles its own copy of the numbering
+    launches (``lsr_watershed_launch_geometry``)."""
+    return _launch_geometry("lsr_watershed_launch_geometry")
 
 
 def _key_to_float(keys: np.ndarray) -> np.ndarray:

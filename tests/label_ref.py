@@ -7,7 +7,9 @@ union-find is rooted at the smallest linear index), so the comparison is exact e
 
 The float64 sums of the table are compared within the a-priori bound ``n_k * 2^-53 * sum|terms|`` per label (``n_k`` voxels;
 any order of ``n_k - 1`` float64 additions of exactly representable terms stays inside it -- the products ``v * coordinate``
-are exact in float64 at the sizes tested: 24 significant bits times fewer than 2^11).
+are exact in float64 at the sizes tested: 24 significant bits times fewer than 2^11.  That holds at scale too: the greatest
+extent a table is measured over in ``tests/label_scale_cases.py`` is 2000 < 2^11, which ``tests/test_label_scale_host.py``
+asserts; 35 bits of a product leave 18 to spare).
 """
 
 import functools

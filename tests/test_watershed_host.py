@@ -231,6 +231,9 @@ def test_entry_statuses():
     lib = _lib.load()
     zyx = (ctypes.c_int * 3)()
     assert lib.lsr_watershed_tile_shape(zyx) == 0 and tuple(zyx) == C.T and lib.lsr_watershed_tile_shape(None) == -1
+    five = (ctypes.c_int64 * 5)()
+    assert lib.lsr_watershed_launch_geometry(five) == 0 and tuple(five) == W.launch_geometry() and min(five) >= 1
+    assert lib.lsr_watershed_launch_geometry(None) == -1 and b"NULL" in lib.lsr_last_error()
     assert lib.lsr_watershed_scratch_bytes(4, 5, 6) >= 4 * 5 * 6 + 4
     assert lib.lsr_watershed_scratch_bytes(0, 5, 6) == -2 and lib.lsr_watershed_scratch_bytes(2 ** 11, 2 ** 10, 2 ** 10) == -3
     big = lib.lsr_watershed_scratch_bytes(2 ** 11, 2 ** 10, 2 ** 10 - 1)       # a byte per voxel: past int32 territory
