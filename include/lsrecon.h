@@ -1300,6 +1300,58 @@ int lsr_label_coloc_variant(const int32_t* labels, const void* a, const void* b,
                             lsr_stream_t stream);
 
 /*
+ * Whole-volume statistics (csrc/stats.hip; the rule is stated in csrc/stats.hpp): what shrimpy_amd/stats.py: order_statistics,
+ * quantiles, summary and rescale read.  tests/stats_ref.py restates the rule in numpy.
+ *
+ * Keys: a float32 value is ordered by its order-preserving 32-bit key (the sign bit flipped for a value with the sign bit
+ * clear, every bit flipped otherwise: -0.0 below +0.0, the infinities ordinary values); a uint16 value is its own 16-bit key.
+ * A NaN is counted in the moment record and takes part in nothing else.  A key is `passes` digits of out[0] bits of
+ * lsr_volume_stats_geometry, the most significant first.
+ *
+ * lsr_digit_histogram_f32 / _u16: one pass of a radix select over the n voxels of `in` (device memory, aligned to 16 / 8
+ * bytes) for k ranks (1 .. K).  prefixes[r] (HOST memory) is the integer made of the `pass` digits rank r has fixed so far
+ * (0 in pass 0), table_of_rank[r] (HOST memory, 0 .. k - 1) the table it reads; ranks share a table exactly where they share
+ * a prefix.  For every non-NaN voxel whose key carries the prefix of table t, word t * bins + (digit `pass` of the key) of
+ * `tables` (device memory, k * bins counters of 64 bits) gains 1.  THE ENTRY DOES NOT ZERO `tables`: calls on several volumes
+ * pool into one multiset.  In pass 0 `moments` may be a record of 5 words of 8 bytes (device memory, not zeroed by the entry
+ * either), which gains: word 0 the number of non-NaN voxels, word 1 the number of NaNs, words 2 and 3 the sums of v and v^2
+ * (float64 for float32 values, uint64 for uint16 values); word 4 holds ~key(min) in its low and key(max) in its high 32 bits,
+ * each raised to the maximum of what it held and the volume's (zero is neutral; with word 0 == 0 there are no extremes).
+ * Otherwise `moments` is NULL.  Tables, counts and extremes are exact and independent of the order of execution; a float64
+ * sum is within n 2^-53 sum|terms| of the exact sum of its exact terms, in atomic adds whose order is not fixed, and follows
+ * IEEE addition where infinities are present; uint16 sums are integers.
+ * grid_cap caps the grid (0: the default).  form: low byte 0 = lanes of a wave whose table and bin equal the lane before them
+ * are counted by the head of their run in one LDS add, 1 = one LDS add per voxel (the same tables; kept for the bench); the
+ * bits above the low byte, where not 0, are the number of strides after which a workgroup flushes its LDS tables (the default
+ * is 2^31 voxels' worth: a 32-bit LDS counter cannot wrap), which the tests use to reach that flush.
+ * Refused before any launch and with nothing read or written: LSR_E_ARG for n <= 0, k outside 1 .. K, a pass the key does not
+ * have, a NULL or misaligned pointer, a prefix the pass cannot have, a table index outside 0 .. k - 1, ranks that share a
+ * table without sharing a prefix or the reverse, moments outside pass 0, grid_cap < 0, an unknown form, or buffers that
+ * overlap; LSR_E_UNSUPPORTED for n >= 2^48 and, for uint16 values with a record, for 65535^2 n >= 2^64.
+ * One launch: each workgroup walks one contiguous span in strides, every load of a stride issued before the first is used,
+ * counts in up to K tables of 32-bit counters in LDS and flushes them by 64-bit global adds.  Shared words are touched by
+ * atomics only, nothing waits for anything.
+ *
+ * lsr_rescale_f32 / _u16: out[i] = (float(in[i]) - sub) / div, then with clip != 0 max(., lo) and min(., hi); a NaN stays a
+ * NaN.  One float32 rounding per step: bit for bit numpy's np.clip((v.astype(f32) - f32(sub)) / f32(div), lo, hi).  in and
+ * out device memory aligned to 16 bytes; a float32 volume may be rescaled in place (out == in), any other overlap is refused.
+ * LSR_E_ARG for n <= 0, a NULL or misaligned pointer, clip outside {0, 1}, or with a clip lo > hi or a NaN bound;
+ * LSR_E_UNSUPPORTED for n >= 2^48.
+ *
+ * lsr_volume_stats_geometry: out[0] = the digit's bits, out[1] = bins, out[2] = K, out[3] = threads of a workgroup, out[4] =
+ * voxels one wave takes per stride (a workgroup takes out[3] / 64 times as many), out[5] = the default grid cap, out[6] = the
+ * LDS bytes of a workgroup, out[7] = the passes of a float32 volume; a uint16 volume takes ceil(16 / out[0]).
+ */
+int lsr_volume_stats_geometry(int64_t out[8]);
+int lsr_digit_histogram_f32(const float* in, int64_t n, int pass, const uint32_t* prefixes, const int32_t* table_of_rank, int k,
+                            void* tables, void* moments, int grid_cap, int form, lsr_stream_t stream);
+int lsr_digit_histogram_u16(const uint16_t* in, int64_t n, int pass, const uint32_t* prefixes, const int32_t* table_of_rank, int k,
+                            void* tables, void* moments, int grid_cap, int form, lsr_stream_t stream);
+int lsr_rescale_f32(const float* in, int64_t n, float sub, float div, int clip, float lo, float hi, float* out, lsr_stream_t stream);
+int lsr_rescale_u16(const uint16_t* in, int64_t n, float sub, float div, int clip, float lo, float hi, float* out,
+                    lsr_stream_t stream);
+
+/*
  * Host twins (csrc/host_twins.hip): the same signatures with HOST pointers, the same argument checks and the
  * same arithmetic in the same order, so the results equal the device entry points' bit for bit.  They serve
  * the boxes where the reference itself resolves to the CPU (shrimpy/preprocessing.py:78-82 -- its CI has no
@@ -1484,6 +1536,19 @@ int lsr_rank_filter_f32_cpu(const float* in, float* out, int64_t Z, int64_t Y, i
  * store (csrc/hessian.hpp), so `out` is the kernel's bits.  Every pointer HOST memory. */
 int lsr_hessian_response_f32_cpu(const float* g, float* out, int64_t Z, int64_t Y, int64_t X, double sz, double sy, double sx,
                                  double scale, int measure, int dark, int accumulate, lsr_stream_t stream);
+
+/* ... of the whole-volume statistics (csrc/stats.hip): plain sequential code over the same rule, record and checks
+ * (csrc/stats.hpp), voxel by voxel.  Tables, counts and the codes of the extremes are the kernel's words, and so are uint16
+ * sums; float32 sums add the same terms in raster order, inside the same bound.  The rescale is the kernel's expression: the
+ * kernel's bits.  Every pointer HOST memory; grid_cap and form are checked and otherwise unused. */
+int lsr_digit_histogram_f32_cpu(const float* in, int64_t n, int pass, const uint32_t* prefixes, const int32_t* table_of_rank, int k,
+                                void* tables, void* moments, int grid_cap, int form, lsr_stream_t stream);
+int lsr_digit_histogram_u16_cpu(const uint16_t* in, int64_t n, int pass, const uint32_t* prefixes, const int32_t* table_of_rank,
+                                int k, void* tables, void* moments, int grid_cap, int form, lsr_stream_t stream);
+int lsr_rescale_f32_cpu(const float* in, int64_t n, float sub, float div, int clip, float lo, float hi, float* out,
+                        lsr_stream_t stream);
+int lsr_rescale_u16_cpu(const uint16_t* in, int64_t n, float sub, float div, int clip, float lo, float hi, float* out,
+                        lsr_stream_t stream);
 
 /* ... of the mutual-information metric (csrc/estimate_mi.hip): the per-sample rule of csrc/mi_sample.hpp on both sides.
  * The histogram and the count are the kernel's bits; the gradient rows are sums over lsr_affine_mi_gradient_blocks()

@@ -219,6 +219,13 @@ SIGNATURES: dict[str, list] = {
                             _int, _stream],
     "lsr_label_coloc_variant": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, _int, _i64, _i64, _i64, _i64, _f32, _f32,
                                 ctypes.c_void_p, _int, _int, _int, _stream],
+    "lsr_volume_stats_geometry": [ctypes.POINTER(ctypes.c_int64)],
+    "lsr_digit_histogram_f32": [ctypes.c_void_p, _i64, _int, ctypes.c_void_p, ctypes.c_void_p, _int, ctypes.c_void_p, ctypes.c_void_p,
+                                _int, _int, _stream],
+    "lsr_digit_histogram_u16": [ctypes.c_void_p, _i64, _int, ctypes.c_void_p, ctypes.c_void_p, _int, ctypes.c_void_p, ctypes.c_void_p,
+                                _int, _int, _stream],
+    "lsr_rescale_f32": [ctypes.c_void_p, _i64, _f32, _f32, _int, _f32, _f32, ctypes.c_void_p, _stream],
+    "lsr_rescale_u16": [ctypes.c_void_p, _i64, _f32, _f32, _int, _f32, _f32, ctypes.c_void_p, _stream],
     "lsr_crc32c_host": [ctypes.c_void_p, _i64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)],
     "lsr_crc32c_host_portable": [ctypes.c_void_p, _i64, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)],
     "lsr_average_slices_f32": [_c_f32p, _i64, _i64, _i64, _c_f32p, _i64, _int, _stream],
@@ -317,6 +324,8 @@ for _name in ("lsr_deskew_f32", "lsr_deskew_u16", "lsr_deskew_cval", "lsr_affine
               "lsr_label_intensity_f32", "lsr_label_intensity_u16",
               # ... and of the two-channel sums (csrc/coloc.hip)
               "lsr_label_coloc_f32", "lsr_label_coloc_u16",
+              # ... and of the whole-volume statistics (csrc/stats.hip)
+              "lsr_digit_histogram_f32", "lsr_digit_histogram_u16", "lsr_rescale_f32", "lsr_rescale_u16",
               # ... and of the grey morphology (csrc/morphology.hip)
               "lsr_grey_morph_f32",
               # ... and of the rank filters (csrc/rank.hip)

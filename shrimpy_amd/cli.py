@@ -2442,6 +2442,281 @@ def run_pyramid(store_path, positions=(), levels: int = 2, level_factor_z: int =
             dist.destroy_process_group()
 
 
+STATISTICS_COLUMNS = ("count", "nan_count", "min", "max", "mean", "std")
+
+
+def _quantile_name(q: float) -> str:
+    return f"q_{q!r}"
+
+
+def _statistics_document(summary: dict) -> dict:
+    """One ``stats.summary`` as ``statistics.json`` holds it: the moments, ``quantiles`` under ``q_<q>``, ``median``, ``iqr``."""
+    out = {k: summary[k] for k in STATISTICS_COLUMNS}
+    out["quantiles"] = {_quantile_name(q): v for q, v in summary["quantiles"].items()}
+    out["median"], out["iqr"] = summary["median"], summary["iqr"]
+    return out
+
+
+class _StoreVolumes:
+    """The volumes of one channel over a list of ``(array, t, c)`` as a re-iterable of device tensors: every walk reads the
+    store again and holds one volume at a time (what ``stats`` pools over)."""
+
+    def __init__(self, sources, device):
+        self._sources, self._device = list(sources), device
+
+    def __iter__(self):
+        import torch
+
+        for array, t, c in self._sources:
+            yield torch.as_tensor(np.ascontiguousarray(array.read_volume(t, c)), device=self._device)
+
+
+@cli.command(cls=_eat_all_command("-i", "--input-position-dirpaths"))
+@click.option("-i", "--input-position-dirpaths", "input_path", required=True, multiple=True, type=click.UNPROCESSED,
+              help="The OME-Zarr store whose channels are measured (HCS plate or single FOV), or the position directories of one plate.")
+@click.option("-c", "--config-filepath", "config", default=None, type=click.Path(exists=True, dir_okay=False, path_type=Path),
+              help="StatisticsSettings YAML (default: every channel, the default quantiles, level volume).")
+@click.option("-o", "--output-dirpath", "output_path", required=True, type=click.Path(path_type=Path),
+              help="Output directory (must not exist): statistics.json, and <position>/statistics.csv for the volume level.")
+@click.option("-p", "--position", "positions", multiple=True, help='Restrict to these position keys ("row/col/fov"); repeatable.')
+@click.option("--io", "io_backend", type=click.Choice(["auto", "native", "iohub"]), default="auto", show_default=True,
+              help="Store access for the input: this package's reader, iohub, or native with iohub as the fallback.")
+@click.option("--write-metadata", "write_metadata", is_flag=True,
+              help="Also patch the INPUT store's position groups: `normalization` (per channel fov_statistics and "
+                   "dataset_statistics: mean, std, median, iqr) and omero.channels[i].window (min, max, start = q_0.001, "
+                   "end = q_0.999).  Needs the levels position and dataset and the quantiles 0.001 and 0.999.")
+def statistics(input_path, config, output_path, positions, io_backend, write_metadata):
+    """Exact whole-volume statistics of every channel: count, NaN count, min, max, mean, std, quantiles, median and IQR.
+
+    uint16 and float32 data are measured as stored.  Level `volume` uploads each (position, t, channel) volume once and runs
+    every pass on the resident volume; levels `position` (pooled over t) and `dataset` (pooled over every selected position)
+    each cost one more read of the store per pass of the select (4 for float32, 2 for uint16, times the groups of 8 ranks)."""
+    input_path, positions = _inputs(input_path, positions)
+    _finish(run_statistics(input_path, config, output_path, positions, io_backend, write_metadata))
+
+
+def run_statistics(input_path, config, output_path, positions=(), io_backend: str = "auto", write_metadata: bool = False) -> dict:
+    """``statistics``: ``stats.summary`` of every selected channel per (position, t) volume, per position and over the dataset,
+    as the settings' ``levels`` ask.  ``<output>/<position>/statistics.csv`` (level ``volume``): ``t, channel``,
+    ``STATISTICS_COLUMNS``, ``q_<q>`` per quantile, ``median, iqr``.  ``<output>/statistics.json``: ``settings``, ``quantiles``,
+    ``positions: {key: {channel: {...}}}`` and ``dataset: {channel: {...}}`` for the levels asked.  Everything is checked before
+    the output directory is created: the positions and channels exist, the data is uint16 or float32, one type per channel
+    across the positions when the dataset is pooled.  Runs on a CPU-only machine (the host twins).
+
+    ``write_metadata`` patches, through ``Position._patch_zattrs`` and touching nothing else, the INPUT store's position groups
+    with ``normalization: {channel: {fov_statistics: {mean, std, median, iqr}, dataset_statistics: {...}}}`` and
+    ``omero.channels[i].window = {min, max, start: q_0.001, end: q_0.999}`` (the position's figures).  The ``normalization``
+    layout is recalled from VisCy's preprocessing, not checked against it: PARITY UNPINNED."""
+    import csv
+    import json
+
+    import torch
+
+    from . import stats
+    from .io.omezarr import as_volume_array, open_ome_zarr
+    from .settings import StatisticsSettings
+
+    try:
+        settings = StatisticsSettings.from_yaml(config) if config is not None else StatisticsSettings()
+    except (ValueError, TypeError) as exc:
+        raise click.ClickException(f"{config}: {exc}") from exc
+    levels, qs = set(settings.levels), settings.all_quantiles()
+    if write_metadata:
+        if not {"position", "dataset"} <= levels:
+            raise click.ClickException("--write-metadata needs the levels position and dataset")
+        if not {0.001, 0.999} <= set(qs):
+            raise click.ClickException("--write-metadata needs the quantiles 0.001 and 0.999 (the contrast window)")
+    rank, world, device, created = _distributed()
+    try:
+        if world > 1 and levels != {"volume"}:
+            raise click.ClickException("the levels position and dataset pool on one device: run them with one rank")
+        src, src_positions = _open_source(Path(input_path), io_backend)
+        with _closing(src):
+            keys = _selected_keys(src_positions, positions)
+            plan, dtypes = {}, {}
+            for k in keys:
+                pos = src_positions[k]
+                names = list(pos.channel_names)
+                measured = list(settings.channel_names) or names
+                absent = [c for c in measured if c not in names]
+                if absent:
+                    raise click.ClickException(f"channel_names {absent} not in position {k} of {input_path} (it has {names})")
+                a = as_volume_array(pos["0"])
+                if len(a.shape) != 5:
+                    raise click.ClickException(f"position {k}: expected 5-D TCZYX data, got shape {tuple(a.shape)}")
+                if np.dtype(a.dtype) not in (np.dtype(np.uint16), np.dtype(np.float32)):
+                    raise click.ClickException(f"position {k}: data type {a.dtype}; uint16 or float32 is measured")
+                for c in measured:
+                    if "dataset" in levels and dtypes.setdefault(c, np.dtype(a.dtype)) != np.dtype(a.dtype):
+                        raise click.ClickException(f"channel {c}: {dtypes[c]} and {a.dtype} cannot be pooled into one dataset")
+                plan[k] = (a, [(c, names.index(c)) for c in measured])
+            writable = None
+            if write_metadata:
+                try:
+                    writable = open_ome_zarr(Path(input_path), layout="auto", mode="a", prefer_iohub=False)
+                except Exception as exc:  # noqa: BLE001
+                    raise click.ClickException(f"--write-metadata: {input_path} cannot be opened for writing: {exc}") from exc
+            error = None
+            if rank == 0:
+                try:
+                    if Path(output_path).exists():
+                        raise FileExistsError(f"{output_path} exists (never overwritten)")
+                    Path(output_path).mkdir(parents=True)
+                except Exception as exc:  # noqa: BLE001 -- reported on every rank, see _agree
+                    error = f"{type(exc).__name__}: {exc}"
+            _agree(error)
+            t0 = time.perf_counter()
+            document = {"settings": settings.model_dump(mode="json"), "quantiles": qs}
+            rows_written = {}
+            if "volume" in levels:
+                for k in keys[rank::world]:
+                    a, channels = plan[k]
+                    rows = []
+                    for t in range(int(a.shape[0])):
+                        for name, c in channels:
+                            vol = torch.as_tensor(np.ascontiguousarray(a.read_volume(t, c)), device=device)
+                            s = stats.summary(vol, qs)
+                            rows.append([t, name] + [s[f] for f in STATISTICS_COLUMNS] + [s["quantiles"][q] for q in qs]
+                                        + [s["median"], s["iqr"]])
+                    directory = Path(output_path) / k
+                    directory.mkdir(parents=True, exist_ok=True)
+                    with open(directory / "statistics.csv", "w", newline="") as fh:
+                        w = csv.writer(fh)
+                        w.writerow(["t", "channel", *STATISTICS_COLUMNS, *[_quantile_name(q) for q in qs], "median", "iqr"])
+                        w.writerows([[repr(v) if isinstance(v, float) else v for v in row] for row in rows])
+                    rows_written[k] = len(rows)
+            if "position" in levels:
+                document["positions"] = {
+                    k: {name: _statistics_document(stats.summary(
+                        _StoreVolumes([(plan[k][0], t, c) for t in range(int(plan[k][0].shape[0]))], device), qs))
+                        for name, c in plan[k][1]} for k in keys}
+            if "dataset" in levels:
+                document["dataset"] = {
+                    name: _statistics_document(stats.summary(
+                        _StoreVolumes([(plan[k][0], t, dict(plan[k][1])[name]) for k in keys for t in range(int(plan[k][0].shape[0]))],
+                                      device), qs))
+                    for name in [c for c, _ in plan[keys[0]][1]]}
+            if rank == 0:
+                with open(Path(output_path) / "statistics.json", "w") as fh:
+                    json.dump(document, fh, indent=1)
+            if writable is not None:
+                available = dict(writable.positions()) if hasattr(writable, "positions") else {keys[0]: writable}
+                for k in keys:
+                    per_channel = document["positions"][k]
+
+                    def mutate(attrs, per_channel=per_channel, names=list(src_positions[k].channel_names)):
+                        four = ("mean", "std", "median", "iqr")
+                        attrs["normalization"] = {
+                            name: {"fov_statistics": {f: figures[f] for f in four},
+                                   "dataset_statistics": {f: document["dataset"][name][f] for f in four}}
+                            for name, figures in per_channel.items()}
+                        channels = attrs.setdefault("omero", {}).setdefault("channels", [{"label": n} for n in names])
+                        for name, figures in per_channel.items():
+                            channels[names.index(name)]["window"] = {
+                                "min": figures["min"], "max": figures["max"],
+                                "start": figures["quantiles"][_quantile_name(0.001)], "end": figures["quantiles"][_quantile_name(0.999)]}
+
+                    available[k]._patch_zattrs(mutate)
+            return {"rank": rank, "world_size": world, "positions": len(keys), "rows": rows_written, "levels": sorted(levels),
+                    "metadata_written": bool(write_metadata), "seconds": time.perf_counter() - t0, "failed": []}
+    finally:
+        if created:
+            import torch.distributed as dist
+
+            dist.destroy_process_group()
+
+
+def _statistics_figures(document: dict, where: str, settings) -> tuple[float, float]:
+    """``(sub, div)`` of a method from one channel's entry of ``statistics.json``; ``KeyError``: a figure it needs is absent."""
+    if settings.method == "zscore":
+        return float(document["mean"]), float(document["std"])
+    if settings.method == "robust":
+        return float(document["median"]), float(document["iqr"])
+    found = []
+    for p in (settings.lower_percentile, settings.upper_percentile):
+        near = [v for name, v in document["quantiles"].items() if abs(float(name[2:]) - p / 100.0) <= 1e-9]
+        if not near:
+            raise KeyError(f"{where}: no quantile {p / 100.0!r} (percentile {p})")
+        found.append(float(near[0]))
+    return found[0], found[1] - found[0]
+
+
+@_store_command("normalize", """Normalize the intensities of whole channels (config: a NormalizeSettings YAML).
+
+    Every volume of the channels channel_names becomes (v - sub) / div in float32; the other channels are copied.  method:
+    percentile (sub = the lower_percentile-th percentile, div = the upper_percentile-th minus it; clip: true clamps to
+    [0, 1]), zscore (mean and standard deviation) or robust (median and interquartile range).  level: volume computes each
+    volume's own statistics in the step -- per timepoint this is the bleach correction --; position and dataset read
+    statistics.json from statistics_dirpath (the output of the statistics command at those levels).  A divisor that is 0 or
+    not finite becomes 1 and the unit is listed under `degenerate` in the result.""")
+def run_normalize(input_path, config, output_path, positions=(), zarr_version: str = "0.5", resume: bool = False,
+                  io_backend: str = "auto", compression=None, on_error: str = "raise", levels: int = 1,
+                  level_factor_z: int = 2) -> dict:
+    """``normalize``: ``stats.rescale`` of every ``(position, t, c)`` volume of a named channel by the figures of its level, the
+    other channels copied (``_run_named_channels``).  Everything is checked before the output store is created: the settings,
+    the channels, and -- for the levels ``position`` and ``dataset`` -- that ``statistics.json`` holds the position, the channel
+    and the figures the method needs.  The result's ``degenerate`` lists the units whose divisor was replaced by 1."""
+    import json
+    import math
+
+    from . import stats
+    from .settings import NormalizeSettings
+
+    try:
+        settings = NormalizeSettings.from_yaml(config)
+    except (ValueError, TypeError) as exc:
+        raise click.ClickException(f"{config}: {exc}") from exc
+    channels = list(settings.channel_names)
+    src, src_positions = _open_source(Path(input_path), io_backend)
+    with _closing(src):
+        keys = _selected_keys(src_positions, positions)
+        names = list(src_positions[keys[0]].channel_names)
+        unknown = [n for n in channels if n not in names]
+        if unknown:
+            raise click.ClickException(f"channel_names {unknown} not in the store (it has {names})")
+    figures = {}
+    if settings.level != "volume":
+        path = Path(settings.statistics_dirpath) / "statistics.json"
+        try:
+            document = json.loads(path.read_text())
+        except (OSError, ValueError) as exc:
+            raise click.ClickException(f"{path}: {exc}") from exc
+        for key in keys:
+            for name in channels:
+                where = f"{path}: " + ("dataset" if settings.level == "dataset" else f"position {key}") + f", channel {name}"
+                try:
+                    entry = document["dataset"][name] if settings.level == "dataset" else document["positions"][key][name]
+                    figures[(key, names.index(name))] = _statistics_figures(entry, where, settings)
+                except KeyError as exc:
+                    raise click.ClickException(f"{where}: statistics.json lacks {exc.args[0]!r}; run `statistics` with the level "
+                                               f"{settings.level} and the quantiles the method needs") from exc
+    degenerate = []
+    clip = (0.0, 1.0) if settings.clip else None
+
+    def safe(unit, sub, div):
+        bad = not (math.isfinite(div) and div != 0.0 and math.isfinite(sub))
+        if bad:
+            degenerate.append({"position": unit.position, "t": int(unit.t), "c": int(unit.c)})
+        return (sub if math.isfinite(sub) else 0.0), (div if math.isfinite(div) and div != 0.0 else 1.0)
+
+    def apply(vol, unit):
+        if settings.level == "volume":
+            sub, div, bad = stats.normalization(vol, settings.method, settings.lower_percentile, settings.upper_percentile)
+            if bad:
+                degenerate.append({"position": unit.position, "t": int(unit.t), "c": int(unit.c)})
+        else:
+            sub, div = safe(unit, *figures[(unit.position, int(unit.c))])
+        return stats.rescale(vol, sub, div, clip)
+
+    result = _run_named_channels(input_path, output_path, channels, keys, positions, zarr_version, lambda unit: unit, apply,
+                                 {"normalize": {"settings": settings.model_dump(mode="json"),
+                                                "figures": {f"{k}:{c}": list(v) for (k, c), v in sorted(figures.items())}}},
+                                 resume=resume, io_backend=io_backend, compression=compression, on_error=on_error,
+                                 levels=levels, level_factor_z=level_factor_z)
+    result["degenerate"] = degenerate
+    return result
+
+
 def main():
     cli()
 

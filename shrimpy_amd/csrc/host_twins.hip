@@ -1698,3 +1698,53 @@ extern "C" int lsr_hessian_response_f32_cpu(const float* g, float* out, int64_t 
   });
   return LSR_OK;
 }
+
+// ---- whole-volume statistics (stats.hip): plain sequential code over stats.hpp's rule, record and checks, voxel by voxel.  The
+// tables, the counts and the codes of the extremes are the kernel's words; uint16 sums too; float32 sums are another order of the
+// same terms (both inside stats.hpp's bound).  The rescale is the kernel's expression: the kernel's bits ----
+#include "stats.hpp"
+
+namespace {
+
+template <typename V, typename Sum>
+int digit_histogram_host(const V* in, int64_t n, int pass, const uint32_t* prefixes, const int32_t* table_of_rank, int k, void* tables,
+                         void* moments, int grid_cap, int form) {
+  namespace st = lsr::stats;
+  st::Plan plan;
+  if (int rc = st::check_histogram(in, sizeof(V), n, pass, prefixes, table_of_rank, k, tables, moments, grid_cap, form, &plan)) return rc;
+  st::histogram_host<V, Sum>(in, n, plan, static_cast<uint64_t*>(tables), static_cast<uint64_t*>(moments));
+  return LSR_OK;
+}
+
+template <typename V>
+int rescale_host(const V* in, int64_t n, float sub, float div, int clip, float lo, float hi, float* out) {
+  namespace st = lsr::stats;
+  if (int rc = st::check_rescale(in, sizeof(V), n, clip, lo, hi, out)) return rc;
+  lsr::parallel_ranges(n, [&](int64_t first, int64_t last) {
+    for (int64_t i = first; i < last; ++i) out[i] = st::rescale_one(in[i], sub, div, clip != 0, lo, hi);
+  });
+  return LSR_OK;
+}
+
+}  // namespace
+
+extern "C" int lsr_digit_histogram_f32_cpu(const float* in, int64_t n, int pass, const uint32_t* prefixes, const int32_t* table_of_rank,
+                                           int k, void* tables, void* moments, int grid_cap, int form, lsr_stream_t) {
+  return digit_histogram_host<float, double>(in, n, pass, prefixes, table_of_rank, k, tables, moments, grid_cap, form);
+}
+
+extern "C" int lsr_digit_histogram_u16_cpu(const uint16_t* in, int64_t n, int pass, const uint32_t* prefixes,
+                                           const int32_t* table_of_rank, int k, void* tables, void* moments, int grid_cap, int form,
+                                           lsr_stream_t) {
+  return digit_histogram_host<uint16_t, uint64_t>(in, n, pass, prefixes, table_of_rank, k, tables, moments, grid_cap, form);
+}
+
+extern "C" int lsr_rescale_f32_cpu(const float* in, int64_t n, float sub, float div, int clip, float lo, float hi, float* out,
+                                   lsr_stream_t) {
+  return rescale_host(in, n, sub, div, clip, lo, hi, out);
+}
+
+extern "C" int lsr_rescale_u16_cpu(const uint16_t* in, int64_t n, float sub, float div, int clip, float lo, float hi, float* out,
+                                   lsr_stream_t) {
+  return rescale_host(in, n, sub, div, clip, lo, hi, out);
+}

@@ -547,7 +547,8 @@ SHAPE_COLUMNS = ("axis_lengths", "major_axis", "surface_area", "contact_area", "
 def segment_zyx(vol, settings, sampling=(1, 1, 1)):
     """Threshold, label, measure and filter one (Z, Y, X) float32 volume by a :class:`~shrimpy_amd.settings.SegmentSettings`:
     ``(labels, table, n)``.  With ``sigma > 0`` the blurred volume is thresholded; with ``threshold: otsu`` the threshold is
-    the multi-Otsu one of what is thresholded (a constant volume has no objects).  The table's intensities are ``vol``'s.
+    the multi-Otsu one of what is thresholded (a constant volume has no objects), with ``threshold: {percentile: p}`` its
+    ``p``-th percentile (``stats.quantiles``).  The table's intensities are ``vol``'s.
     With ``background_radius > 0`` the white top-hat of ``vol`` under a box of that radius (in the units of ``sampling``,
     ``shrimpy_amd/morphology.py``) is what is blurred and thresholded; with ``fill_holes`` the mask ``work > threshold`` is
     filled (``scipy.ndimage.binary_fill_holes``) before it is labelled, for every ``connectivity``.  With ``median_radius > 0``
@@ -589,6 +590,10 @@ def segment_zyx(vol, settings, sampling=(1, 1, 1)):
     work = D._gaussian_blur_3d(work, float(settings.sigma)) if settings.sigma > 0 else work
     if settings.threshold == "otsu":
         threshold = D._multiotsu_threshold(work, int(settings.otsu_component))
+    elif hasattr(settings.threshold, "percentile"):
+        from . import stats
+
+        threshold = stats.quantiles(work, [float(settings.threshold.percentile) / 100.0])[0]
     else:
         threshold = float(settings.threshold)
     if settings.fill_holes:

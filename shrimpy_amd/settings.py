@@ -579,6 +579,21 @@ class EnhanceSettings(_StrictModel):
         return [float(v) for v in self.sigmas], (1.0, 1.0, 1.0)
 
 
+class PercentileThreshold(_StrictModel):
+    """``threshold: {percentile: p}`` of :class:`SegmentSettings`: the ``p``-th percentile (numpy's ``linear`` rule, exact order
+    statistics: ``shrimpy_amd/stats.py``) of what is thresholded, taken where ``otsu`` is taken.  ``99.5`` keeps the brightest
+    0.5 %."""
+
+    percentile: float
+
+    @field_validator("percentile")
+    @classmethod
+    def _check_percentile(cls, v):
+        if not 0.0 <= v <= 100.0:
+            raise ValueError("percentile must lie in [0, 100]")
+        return v
+
+
 class SegmentSettings(_StrictModel):
     """Connected-component segmentation of one channel (``shrimpy_amd/segment.py``, the ``segment`` command).
 
@@ -630,7 +645,7 @@ class SegmentSettings(_StrictModel):
     face; split (``split``) and grown (``expand_distance``) labels do."""
 
     channel_name: str
-    threshold: Union[float, Literal["otsu"]]
+    threshold: Union[float, Literal["otsu"], PercentileThreshold]
     median_radius: Union[NonNegativeFloat, tuple[NonNegativeFloat, NonNegativeFloat, NonNegativeFloat]] = 0.0
     background_radius: Union[NonNegativeFloat, tuple[NonNegativeFloat, NonNegativeFloat, NonNegativeFloat]] = 0.0
     enhance: Optional[EnhanceSettings] = None
@@ -651,8 +666,8 @@ class SegmentSettings(_StrictModel):
     @field_validator("threshold")
     @classmethod
     def _check_threshold(cls, v):
-        if not isinstance(v, str) and not np.isfinite(float(v)):
-            raise ValueError("threshold must be a finite number or \"otsu\"")
+        if not isinstance(v, (str, PercentileThreshold)) and not np.isfinite(float(v)):
+            raise ValueError("threshold must be a finite number, \"otsu\" or {percentile: p}")
         return v
 
     @field_validator("background_radius")
@@ -832,6 +847,72 @@ class ColocalizeSettings(_StrictModel):
         if v != "costes" and (len(v) != 2 or any(np.isnan(t) for t in v)):
             raise ValueError("thresholds must be [ta, tb] (two numbers, not NaN) or \"costes\"")
         return v
+
+
+class StatisticsSettings(_StrictModel):
+    """Whole-volume statistics of a store (``shrimpy_amd/stats.py``, the ``statistics`` command).
+
+    ``channel_names``: the channels measured, empty for all.  ``quantiles``: in [0, 1]; 0.25, 0.5 and 0.75 are always added
+    (``median`` and ``iqr`` need them).  ``levels``: ``volume`` (one row per (t, channel) in ``statistics.csv``), ``position``
+    (pooled over t) and ``dataset`` (pooled over every selected position and t); the last two read the store once more per
+    pass."""
+
+    channel_names: list[str] = []
+    quantiles: list[float] = [0.001, 0.01, 0.25, 0.5, 0.75, 0.99, 0.999]
+    levels: list[Literal["volume", "position", "dataset"]] = ["volume"]
+
+    @field_validator("quantiles")
+    @classmethod
+    def _check_quantiles(cls, v):
+        if any(not 0.0 <= q <= 1.0 for q in v):
+            raise ValueError("quantiles must lie in [0, 1]")
+        return v
+
+    @field_validator("levels")
+    @classmethod
+    def _check_levels(cls, v):
+        if not v or len(set(v)) != len(v):
+            raise ValueError("levels must name at least one of volume, position, dataset, each once")
+        return v
+
+    def all_quantiles(self) -> list[float]:
+        return sorted({float(q) for q in self.quantiles} | {0.25, 0.5, 0.75})
+
+
+class NormalizeSettings(_StrictModel):
+    """Intensity normalization of whole channels (``shrimpy_amd/stats.py``, the ``normalize`` command): every volume of the
+    channels ``channel_names`` becomes ``(v - sub) / div`` in float32, the other channels are copied.
+
+    ``method``: ``percentile`` (``sub`` = the ``lower_percentile``-th percentile, ``div`` = the ``upper_percentile``-th minus
+    it; with ``clip`` the result is clamped to [0, 1]), ``zscore`` (mean and standard deviation) or ``robust`` (median and
+    interquartile range).  ``level``: ``volume`` takes each volume's own statistics -- per timepoint this is the bleach
+    correction --; ``position`` and ``dataset`` read them from the ``statistics.json`` the ``statistics`` command wrote into
+    ``statistics_dirpath``.  A divisor that is 0 or not finite becomes 1 and the unit is reported as degenerate."""
+
+    channel_names: list[str]
+    method: Literal["percentile", "zscore", "robust"] = "percentile"
+    lower_percentile: float = 1.0
+    upper_percentile: float = 99.9
+    clip: bool = False
+    level: Literal["volume", "position", "dataset"] = "volume"
+    statistics_dirpath: Optional[str] = None
+
+    @field_validator("channel_names")
+    @classmethod
+    def _check_channels(cls, v):
+        if not v or len(set(v)) != len(v):
+            raise ValueError("channel_names must name at least one channel, each once")
+        return v
+
+    @model_validator(mode="after")
+    def _check(self):
+        if not 0.0 <= self.lower_percentile < self.upper_percentile <= 100.0:
+            raise ValueError("0 <= lower_percentile < upper_percentile <= 100")
+        if self.clip and self.method != "percentile":
+            raise ValueError("clip goes with method: percentile (it clamps to [0, 1])")
+        if self.level != "volume" and not self.statistics_dirpath:
+            raise ValueError(f"level: {self.level} reads statistics.json: statistics_dirpath is required")
+        return self
 
 
 class ReconstructSettings(_StrictModel):

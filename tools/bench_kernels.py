@@ -92,6 +92,12 @@ def main():
                     "three scenes of --label, float32 and uint16 channels, with and without labels; the sweep of LDS slots, grid "
                     "caps and probe bounds and the plain form; beside a device copy of the three volumes and two launches of the "
                     "label-intensity kernel; lines appended to profiles/coloc_config2.jsonl")
+    ap.add_argument("--stats", action="store_true", help="only: ms of one digit pass of the whole-volume select (csrc/stats.hip) on "
+                    "--rl-grid in both forms (runs reduced inside the wave, one LDS add per voxel), passes 0 and 1, over a sweep of "
+                    "the grid cap, float32 and uint16, and of stats.summary end to end, on the bench's bead scene, Bernoulli noise, "
+                    "an all-zero volume and the bead scene with its outer quarter set to 0 (HIP events, median of 3 calls after a "
+                    "warm-up), beside a device copy of the volume, the rescale kernel, and what torch.quantile and torch.sort do "
+                    "on the full volume and on the largest crop they accept; appended to profiles/stats_config2.jsonl")
     ap.add_argument("--coloc-crop", default="1,1024,1024", help="Z,Y,X of the small crop --coloc also times the kernel on")
     ap.add_argument("--edt", action="store_true", help="only: ms per launch of the distance transform (csrc/edt.hip: x, y, z; HIP "
                     "events between the launches, median of 5 calls after a warm-up) on --rl-grid, for bench.synthetic_raw at its "
@@ -162,6 +168,9 @@ def main():
         return
     if args.intensity:
         _intensity(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
+        return
+    if args.stats:
+        _stats(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
         return
     if args.coloc:
         _coloc(args, torch, dev, g, bench, tuple(int(v) for v in args.rl_grid.split(",")))
@@ -1320,6 +1329,120 @@ def _coloc(args, torch, dev, g, bench, oshape):
     stamp = {"sources": _lib.kernel_source_sha16(), "device": torch.cuda.get_device_name(dev), "reps": reps, "warmups": 1}
     path = ROOT / "profiles" / "coloc_config2.jsonl"
     with open(path, "a") as f:
+        for r in records:
+            f.write(json.dumps({**r, **stamp}) + "\n")
+
+
+STATS_CAPS = (2048, 8192, 32768, 131072)
+STATS_QUANTILES = (0.001, 0.01, 0.25, 0.5, 0.75, 0.99, 0.999)
+
+
+def _stats(args, torch, dev, g, bench, oshape):
+    """One digit pass of the whole-volume select (csrc/stats.hip) at the config-2 deskewed shape, float32 and uint16, on four
+    scenes: the bench's bead scene, Bernoulli noise (p = 0.3, values 0 and 1), an all-zero volume and the bead scene with its
+    outer quarter (an eighth of x on either side) set to exact 0.  Per scene and type, each the median of 3 calls after a warm-up
+    between HIP events: pass 0 with the moment record and pass 1 with the prefixes the seven default quantiles reach, in both
+    forms, the kept form over a sweep of the grid cap; stats.summary end to end (wall clock, its synchronisations included) and
+    the rescale.  The floor is a device copy of the volume, which moves twice the bytes a pass reads.  Every form and cap must
+    give the tables of the first.  Then what torch.quantile and torch.sort do on the full float32 volume and on a 16e6-voxel
+    crop."""
+    import time
+
+    from shrimpy_amd import _lib
+    from shrimpy_amd import stats as ST
+
+    reps = 3
+    n = oshape[0] * oshape[1] * oshape[2]
+    geo = ST.geometry()
+
+    class Records(list):
+        def append(self, r):
+            print(json.dumps(r), flush=True)
+            super().append(r)
+
+    records = Records()
+    src = torch.empty(oshape, dtype=torch.float32, device=dev)
+    dst = torch.empty_like(src)
+    copy_ms = {4: _median_ms(lambda: dst.copy_(src), reps, torch)}
+    hsrc = torch.zeros(oshape, dtype=torch.int16, device=dev)
+    hdst = torch.empty_like(hsrc)
+    copy_ms[2] = _median_ms(lambda: hdst.copy_(hsrc), reps, torch)
+    for size, ms in copy_ms.items():
+        records.append({"kernel": f"device copy of one volume of {size}-byte voxels (torch copy_)", "grid": list(oshape), "ms": ms,
+                        "GBps": 2.0 * size * n / ms / 1e6})
+    del src, dst, hdst, hsrc
+    torch.cuda.empty_cache()
+
+    def scenes():
+        vol = bench.synthetic_raw(oshape, 1000, dev)
+        yield "bead scene (bench.synthetic_raw)", vol
+        eighth = oshape[2] // 8
+        vol[:, :, :eighth] = 0.0
+        vol[:, :, oshape[2] - eighth:] = 0.0
+        yield "bead scene, outer quarter exact 0", vol
+        del vol
+        yield "Bernoulli noise, p = 0.3", (torch.rand(oshape, device=dev, generator=g) < 0.3).to(torch.float32)
+        yield "all zero", torch.zeros(oshape, dtype=torch.float32, device=dev)
+
+    def u16_of(vol):
+        scale = 65535.0 / max(float(vol.max().item()), 1e-30)
+        return (vol.clamp(min=0.0) * scale).to(torch.int32).to(torch.int16).view(torch.uint16)
+
+    for name, vol in scenes():
+        for flat in (vol.reshape(-1), u16_of(vol).reshape(-1)):
+            size = flat.element_size()
+            kind = "f32" if size == 4 else "u16"
+            base = {"input": name, "grid": list(oshape), "dtype": kind}
+            table0, _ = ST._pass0(ST._Pool(flat))
+            total = int(table0.astype(object).sum())
+            state = sorted({ST._walk(table0, r)[0] for q in STATS_QUANTILES for r in ST._bracket(q, total)[:2]})[:geo["K"]]
+            plans = {0: ([0], [0]), 1: (state, list(range(len(state))))}
+            record = torch.zeros(ST.RECORD_WORDS, dtype=torch.int64, device=dev)
+            first = {}
+            for p, (prefixes, table_of) in plans.items():
+                tables = torch.zeros(len(prefixes) * geo["bins"], dtype=torch.int64, device=dev)
+                for form, form_name in ((ST.FORM_RUNS, "runs"), (ST.FORM_PLAIN, "plain")):
+                    for cap in (0,) + (STATS_CAPS if form == ST.FORM_RUNS and kind == "f32" else ()):
+                        def launch():
+                            ST.digit_histogram(flat, p, prefixes, table_of, tables, record if p == 0 else None, cap, form)
+
+                        def clear():
+                            tables.zero_()
+                            record.zero_()
+
+                        ms = _timed_cleared(torch, launch, clear, reps)
+                        got = tables.cpu().numpy().copy()
+                        same = bool(np.array_equal(got, first.setdefault(p, got)))
+                        records.append({**base, "kernel": f"lsr_digit_histogram_{kind}", "pass": p, "tables": len(prefixes), "form": form_name,
+                                        "grid_cap": cap or geo["default_grid_cap"], "default": cap == 0, "ms": ms,
+                                        "algorithmic_GBps": size * n / ms / 1e6, "times_the_copy": ms / copy_ms[size],
+                                        "tables_equal_the_first": same})
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            s = ST.summary(flat, STATS_QUANTILES)
+            torch.cuda.synchronize()
+            records.append({**base, "kernel": "stats.summary (7 quantiles + quartiles, moments), wall clock", "ms": (time.perf_counter() - t0) * 1e3,
+                            "median": s["median"], "iqr": s["iqr"], "count": s["count"], "zero_fraction": float(((flat if size == 4 else flat.view(torch.int16)) == 0).sum().item()) / n})
+            out = torch.empty(flat.shape, dtype=torch.float32, device=dev)
+            ms = _median_ms(lambda: ST.rescale(flat, 1.0, 3.0, (0.0, 1.0), out), reps, torch)
+            records.append({**base, "kernel": f"lsr_rescale_{kind}", "ms": ms, "algorithmic_GBps": (size + 4.0) * n / ms / 1e6})
+            del out, tables, record
+            torch.cuda.empty_cache()
+        del flat
+    # torch's own operators on the last scene's shape (values do not matter for what they accept)
+    vol = torch.rand(oshape, device=dev, generator=g).reshape(-1)
+    for what, count in (("the full volume", n), ("a crop of 16 000 000 voxels", 16_000_000)):
+        part = vol[:count]
+        for op_name, op in (("torch.quantile(v, 0.5)", lambda: torch.quantile(part, 0.5)), ("torch.sort(v)", lambda: torch.sort(part))):
+            try:
+                ms = _median_ms(op, reps, torch)
+                records.append({"kernel": f"{op_name} on {what}", "voxels": count, "ms": ms})
+            except Exception as e:       # (recorded: what torch does is the finding)
+                records.append({"kernel": f"{op_name} on {what}", "voxels": count, "error": f"{type(e).__name__}: {str(e)[:300]}"})
+            torch.cuda.empty_cache()
+    stamp = {"sources": _lib.kernel_source_sha16(), "device": torch.cuda.get_device_name(dev), "reps": reps, "warmups": 1,
+             "digit_bits": geo["digit_bits"], "K": geo["K"]}
+    with open(ROOT / "profiles" / "stats_config2.jsonl", "a") as f:
         for r in records:
             f.write(json.dumps({**r, **stamp}) + "\n")
 
